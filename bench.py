@@ -15,6 +15,14 @@ GPU; rank r binds device r, RCCL for the barrier / max-over-ranks); under an ext
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`) RANK / LOCAL_RANK / WORLD_SIZE come from
 the environment and `--gpus` must agree with WORLD_SIZE (it fails loudly otherwise).
 
+A plain run (`--gpus N --steps K --warmup W`) measures the headline only: it sets up, runs W warm-up steps (and captures the
+pipeline's graphs), times ONE region of exactly K steps and prints the line (`ms_per_step` = that region / K). Every secondary
+measurement -- the repeated regions (10, median), per-batch latency, the kernel roofline objects, bf16 mode, host results, the
+einsum sweep, the CPU baseline, the training step and the other configs -- runs only with `--full`, as described below.
+`--dump-outputs DIR` writes the results of the last timed step (device results of `simple_test`; the loss terms of a training
+step) as DIR/<name>.npy after the timed region (`output_arrays`): same arguments, same inputs and weights, so two builds can be
+compared output for output.
+
 Prints ONE JSON line (rank 0) as the LAST line of stdout: the compact record (`compact_record` / `emit`: < 4 KB of strict JSON -- the
 contract keys, `roofline`, `cpu_baseline` and one short object per secondary measurement); the full record with every note goes to
 gpurun_out/bench_full.json (`--full-line` prints it instead: what a parent bench.py run parses from its children). `value` is PARITY
@@ -263,6 +271,63 @@ def emit(res, full_path=None, stream=None):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
+DUMP_SAMPLE = 1 << 20           # elements kept of a larger array: a fixed, seeded sample (plus its per-row sums)
+_RESULT_FIELDS = ('labels', 'bboxes', 'masks')      # an instance result (maskformer_fusion_head.simple_test)
+
+
+def _output_leaves(obj, name):
+    """(name, tensor | ndarray | number) of every leaf of a result structure, walked in order"""
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _output_leaves(v, f'{name}.{k}' if name else str(k))
+    elif isinstance(obj, (list, tuple)):
+        fields = _RESULT_FIELDS if (len(obj) == 3 and name.endswith('_results')) else None
+        for i, v in enumerate(obj):
+            yield from _output_leaves(v, f'{name}.{fields[i] if fields else i}' if name else f'img{i}')
+    elif obj is not None and not isinstance(obj, str):
+        yield name, obj
+
+
+def output_arrays(results):
+    """name -> float32 / float64 numpy array of what the timed path returned: floating tensors in f32 (f64 stays f64),
+    integer tensors in f64, bool in f32. An array of more than DUMP_SAMPLE elements is replaced by a sample of DUMP_SAMPLE
+    elements at sorted indices drawn from a generator seeded by its name (`<name>.sample`), and, if it has rows, by the f64
+    sum of each row (`<name>.rowsum`, e.g. the area of every mask); the sample shrinks if the whole would pass DUMP_LIMIT_BYTES."""
+    import zlib
+    import numpy as np
+    leaves = []
+    for name, v in _output_leaves(results, ''):
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+        leaves.append((name, t.detach()))
+    big = [t for _, t in leaves if t.numel() > DUMP_SAMPLE]
+    fixed = sum(8 * t.numel() for _, t in leaves if t.numel() <= DUMP_SAMPLE) + sum(8 * t.shape[0] for t in big if t.dim() > 1)
+    per = max(0, min(DUMP_SAMPLE, (DUMP_LIMIT_BYTES - fixed) // (8 * len(big)))) if big else DUMP_SAMPLE
+    out = {}
+    for name, t in leaves:
+        wide = torch.float64 if (t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)) else torch.float32
+        if t.numel() > DUMP_SAMPLE:
+            if t.dim() > 1:
+                out[name + '.rowsum'] = t.reshape(t.shape[0], -1).sum(1, dtype=torch.float64).cpu().numpy()
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (per,), generator=g).sort().values
+            out[name + '.sample'] = t.reshape(-1)[idx.to(t.device)].to(wide).cpu().numpy()
+        else:
+            out[name] = t.to(wide).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})')
+    return out
+
+
+def write_outputs(arrays, dirname):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, re.sub(r'[^A-Za-z0-9_.-]', '_', name) + '.npy'), a)
+    print(f'bench.py: wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values())} bytes) to {dirname}', file=sys.stderr)
+
+
 def workload_config(args):
     """model dict of the selected BASELINE config (reference files: configs/instance/coco_b48n17.py, configs/openset_panoptic/
     coco_panoptic_p20.py; Swin-B = the Mask2Former Swin-B backbone settings)."""
@@ -499,11 +564,12 @@ def host_results_rate(args, model, img, metas, dev):
                 how=f'{nstage}-stage pipeline, bit-packed masks, pinned async D2H, C++ RLE on a persistent pool of host threads overlapped with the next batch')
 
 
-def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
+def time_mode(args, model, img, metas, dev, precision, barrier, collect_events, latency=True, dump=False):
     """images/sec of the step in one precision mode: the staged pipeline (one HIP stream + hipGraph per stage) or one graph
     per step / eager launches; the K-step region is repeated `args.repeats` times back to back (each bracketed by the barrier)
-    and the MEDIAN region is reported, so that the timed span is >= 0.5 s while `steps` stays what the driver passed.
-    Then: per-batch latency (one step alone) and, if `collect_events`, the same K steps once more eagerly with HIP events
+    and the MEDIAN region is reported (a plain run: one region of exactly K steps).
+    If `dump`: the results of the last timed step as host arrays (`outputs`, see output_arrays). Then, if `latency`:
+    per-batch latency (one step alone) and, if `collect_events`, the same K steps once more eagerly with HIP events
     around the hot launches on the launch stream (events cannot be recorded inside a graph replay)."""
     import statistics
     from cgg_amd import ops, runtime
@@ -516,6 +582,7 @@ def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
             step()
         torch.cuda.synchronize()
         graph = pipe = None
+        last = [None]              # the last timed step's results (a pipeline: its slot)
         how = 'eager launches'
         if args.graph and args.pipeline:
             try:
@@ -542,7 +609,7 @@ def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
                     step()
                 torch.cuda.current_stream().wait_stream(side)
                 with torch.cuda.graph(graph):
-                    step()
+                    last[0] = step()
                 graph.replay()
                 torch.cuda.synchronize()
                 how = 'one hipGraph per step, replayed back to back'
@@ -556,11 +623,11 @@ def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
             t0 = time.perf_counter()
             for _ in range(args.steps):
                 if pipe is not None:
-                    pipe.submit(img)
+                    last[0] = pipe.submit(img)
                 elif graph is not None:
                     graph.replay()
                 else:
-                    step()
+                    last[0] = step()
             if pipe is not None:
                 pipe.flush()          # every submitted step is complete before the closing barrier + synchronize
             barrier()
@@ -571,9 +638,13 @@ def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
         out['how'] = how
         out['hip_graph'] = graph is not None or pipe is not None
         out['pipelined'] = pipe is not None
+        if dump:
+            results = pipe.wait(last[0]) if pipe is not None else last[0]
+            torch.cuda.synchronize()
+            out['outputs'] = output_arrays(results)
         # ---- per-batch latency: ONE step alone (no cross-step overlap), submit -> results complete ----
         lat = []
-        for _ in range(5):
+        for _ in range(5 if latency else 0):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             if pipe is not None:
@@ -585,7 +656,7 @@ def time_mode(args, model, img, metas, dev, precision, barrier, collect_events):
                 step()
             torch.cuda.synchronize()
             lat.append((time.perf_counter() - t1) * 1e3)
-        out['latency_ms'] = sorted(lat)[len(lat) // 2]
+        out['latency_ms'] = sorted(lat)[len(lat) // 2] if lat else None
         pipe = graph = None
         if collect_events:
             ops.KERNEL_EVENTS, ops.KERNEL_META = {}, {}
@@ -652,6 +723,8 @@ def train_run(args, cfg, model, img, metas, dev, rank, world, steps=None, warmup
         logs = train_step(model, optimizer, reducer, data, clip)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(output_arrays(dict(logs)), args.dump_outputs)      # the last step's loss terms
     tmax = torch.tensor([dt], dtype=torch.float64, device='cpu' if args.shared_devices else dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -659,7 +732,7 @@ def train_run(args, cfg, model, img, metas, dev, rank, world, steps=None, warmup
     # ---- roofline of the step's hand-written kernel families: ONE more step, eagerly, with HIP events around the launches on the
     #      launch stream (the timed region above carries no events) ----
     roofline, kernels = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         from cgg_amd import ops
         ops.KERNEL_EVENTS, ops.KERNEL_META = {}, {}
         train_step(model, optimizer, reducer, data, clip)
@@ -948,7 +1021,7 @@ def workload_child(workload, extra_args, timeout=900):
     """Another BASELINE config measured by THIS script in a child process (started after the parent has finished its GPU work,
     never an exec from a GPU-initialised process) -> its parsed JSON line or an error record."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--full-line'] + list(extra_args)
+    cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--full', '--full-line'] + list(extra_args)
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
         line = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -967,7 +1040,7 @@ def train_step_child(args, precision='fp32', workload='cfg2'):
     training arithmetic, open_set/apis/train.py:182-189) / `train_step.bf16_mode` (bf16 autocast: narrower, secondary)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--steps', str(args.train_steps), '--warmup', '3',
-           '--precision', precision, '--full-line']
+           '--precision', precision, '--full', '--full-line']
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         line = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -1011,8 +1084,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=10,
-                    help='the K-step timed region is repeated this many times back to back; the median region is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='the K-step timed region is repeated this many times back to back; the median region is reported '
+                         '(default: 1, with --full 10)')
+    ap.add_argument('--full', action='store_true',
+                    help='also take every secondary measurement of the record: repeated timed regions, per-batch latency, '
+                         'per-kernel roofline figures, the bf16 mode, host results, the einsum sweep, the CPU baseline, the '
+                         'training step and the other BASELINE configs (the switches below choose among them). Default: set up, '
+                         'warm up, time --steps steps once, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the results of the last timed step as DIR/<name>.npy (f32 / f64; '
+                         'arrays over 1 Mi elements as a fixed seeded sample + per-row sums; <= 64 MB in all)')
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS),
                     help="BASELINE.json config: cfg1 (default: the metric's config, forward-only), cfg2 (R50 training step), cfg3 "
                          '(Swin-B + 200 queries training step, one GPU\'s share of the DDP batch), cfg4 (COCO-panoptic 1333x800 forward)')
@@ -1037,15 +1119,15 @@ def main():
                          'merged, 0 = one graph per step replayed back to back')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--host-results', type=int, default=1,
-                    help='1 (default): also time the step with results delivered to the host as COCO RLE (reported as '
+                    help='1 (default; --full only): also time the step with results delivered to the host as COCO RLE (reported as '
                          '`host_results`, never `value`)')
     ap.add_argument('--no-bf16-mode', action='store_true', help='skip the secondary bf16 (throughput-mode) timing')
     ap.add_argument('--train-step', type=int, default=1,
-                    help="1 (default, rank 0 of a 1-GPU run): also run configs[2]'s training step in a child process -> `train_step`")
+                    help="1 (default, rank 0 of a 1-GPU --full run): also run configs[2]'s training step in a child process -> `train_step`")
     ap.add_argument('--train-steps', type=int, default=5)
     ap.add_argument('--no-einsum-sweep', action='store_true', help='skip the Q = 100 / 200 mask-logit einsum launches (profile runs)')
     ap.add_argument('--extra-workloads', type=int, default=1,
-                    help='1 (default, rank 0 of a 1-GPU cfg1 run): also measure configs[3] and configs[4] in child processes -> `extra`')
+                    help='1 (default, rank 0 of a 1-GPU cfg1 --full run): also measure configs[3] and configs[4] in child processes -> `extra`')
     ap.add_argument('--full-line', action='store_true',
                     help='print the FULL record as the stdout line (what a parent bench.py run parses from its children); default: '
                          'the compact line, full record in gpurun_out/bench_full*.json')
@@ -1060,6 +1142,12 @@ def main():
         args.queries = wl['queries']
     if args.batch is None:
         args.batch = wl['batch']
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
+    if not args.full:
+        # a plain run measures the headline only: every secondary measurement is --full's
+        args.no_cpu_baseline = args.no_bf16_mode = args.no_einsum_sweep = True
+        args.host_results = args.train_step = args.extra_workloads = 0
     primary = args.workload == 'cfg1'       # the driver's default line: carries the secondary objects (bf16, host results, CPU, ...)
 
     if args.gpus < 1:
@@ -1107,7 +1195,10 @@ def main():
         torch.cuda.synchronize()
 
     Q = args.queries
-    main_mode = time_mode(args, model, img, metas, dev, args.precision, barrier, collect_events=(args.precision == 'fp32'))
+    main_mode = time_mode(args, model, img, metas, dev, args.precision, barrier, collect_events=(args.precision == 'fp32' and args.full),
+                          latency=args.full, dump=bool(args.dump_outputs) and rank == 0)
+    if 'outputs' in main_mode:
+        write_outputs(main_mode.pop('outputs'), args.dump_outputs)
     dt = main_mode['dt']
     tmax = torch.tensor([dt], dtype=torch.float64, device='cpu' if args.shared_devices else dev)
     if world > 1:
@@ -1115,7 +1206,7 @@ def main():
     dt = float(tmax.item())
 
     kernels = {}
-    if args.precision == 'fp32' and rank == 0:
+    if args.precision == 'fp32' and rank == 0 and args.full:
         kernels = kernel_summaries(args, main_mode.get('events', {}), main_mode.get('meta', {}), B, H, W, Q)
     roofline = kernels.pop('gemm_x3', None)
 
@@ -1125,7 +1216,7 @@ def main():
     agree_all, agree_src = agreement_records()
     agree_key = {'cfg1': 'configs1_bf16', 'cfg4': 'configs4_bf16'}.get(args.workload)
     need = ([agree_key] if (agree_key and not args.no_bf16_mode and args.precision == 'fp32') else []) + \
-        (['configs1_fp32_no_injection'] if primary else [])
+        (['configs1_fp32_no_injection'] if primary and args.full else [])
     missing = [k for k in need if not isinstance(agree_all.get(k), dict)]
     if missing:
         raise SystemExit(f'bench.py: {agree_src} lacks the agreement record(s) {missing} this line publishes -- regenerate it with '
@@ -1181,14 +1272,14 @@ def main():
                                parity_mode_agreement_without_injection=dict(
                                    record=agree_all.get('configs1_fp32_no_injection'),
                                    source=f'committed profile: {agree_src} (tests/test_fullsize_gpu.py::'
-                                          'test_configs1_fp32_mode_end_to_end_without_injection, fp32 = parity mode)') if primary else None,
+                                          'test_configs1_fp32_mode_end_to_end_without_injection, fp32 = parity mode)') if primary and args.full else None,
                                x3_overflow=overflow, library_fallbacks=dict(count=runtime.library_fallbacks(), sites=dict(runtime.FALLBACKS)),
                                hip_graph=main_mode['hip_graph'], ranks_share_devices=bool(args.shared_devices),
                                pipeline=main_mode['how'],
                                timed_region=f'{args.steps} steps, repeated {args.repeats}x back to back; median region '
                                             f'{dt * 1e3:.1f} ms (min {min(main_mode["regions_s"]) * 1e3:.1f}, max '
                                             f'{max(main_mode["regions_s"]) * 1e3:.1f})'),
-                   latency_ms_per_batch=main_mode['latency_ms'], bf16_mode=other, host_results=host, roofline=roofline,
+                   latency_ms_per_batch=main_mode.get('latency_ms'), bf16_mode=other, host_results=host, roofline=roofline,
                    kernels=kernels, einsum_mfma_target=sweep)
         if not args.no_cpu_baseline and world == 1 and primary:
             res['cpu_baseline'] = cpu_baseline(args, cfg, model, img_cpu)
@@ -1220,6 +1311,7 @@ def main():
         torch.cuda.empty_cache()
         targs = copy.copy(args)
         targs.workload, targs.mode, targs.batch = 'cfg2', 'train', WORKLOADS['cfg2']['batch']
+        targs.dump_outputs = None           # the dump holds the inference step's results
         tcfg, tmodel = build_model(targs, dev)
         timg = torch.randn(targs.batch, 3, H, W, generator=torch.Generator().manual_seed(99 + rank)).to(dev)
         ts = train_run(targs, tcfg, tmodel, timg, synthetic.img_metas(targs.batch, H, W), dev, rank, world, steps=args.train_steps,

@@ -9,7 +9,7 @@ R=/root/repo
 O=$R/gpurun_out/r6/prof
 mkdir -p $O
 WHAT="${@:-line cfg1 cfg4 train msda}"
-LEAN="--no-cpu-baseline --no-bf16-mode --host-results 0 --train-step 0 --extra-workloads 0 --no-einsum-sweep"
+LEAN="--full --no-cpu-baseline --no-bf16-mode --host-results 0 --train-step 0 --extra-workloads 0 --no-einsum-sweep"
 infer() {   # $1 = workload tag, $2 = delimiter kernel of the eager step table
   W=$1
   BENCH="$R/bench.py --workload $W --steps 20 --warmup 5 $LEAN --repeats 3"
@@ -36,7 +36,7 @@ for what in $WHAT; do
 case $what in
 line)
   cd $R
-  python bench.py > $O/bench_line.json 2> $O/bench_line.err
+  python bench.py --full > $O/bench_line.json 2> $O/bench_line.err
   cp $R/gpurun_out/bench_full.json $O/bench_full.json
   tail -c 600 $O/bench_line.json
   cd /tmp ;;
@@ -45,7 +45,7 @@ cfg4) infer cfg4 cgg_panoptic_paint ;;
 train)
   for w in cfg2 cfg3; do for p in fp32 bf16; do
     rm -rf /tmp/trainprof_${w}_$p
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/trainprof_${w}_$p -- python3 $R/bench.py --workload $w --steps 4 --warmup 2 --precision $p > $O/${w}_train_under_rocprof_$p.log 2>&1
+    rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/trainprof_${w}_$p -- python3 $R/bench.py --workload $w --steps 4 --warmup 2 --precision $p --full > $O/${w}_train_under_rocprof_$p.log 2>&1
     # (bench.py runs 2 warm-up + 4 timed + 1 event-timed step = 7 steps; the clip's NormTwoOps launches per step depend on the bucket count)
     python3 $R/scratch/step_kernels2.py /tmp/trainprof_${w}_$p NormTwoOps 3 auto:7 > $O/${w}_train_step_kernels_$p.txt 2>&1
   done; done

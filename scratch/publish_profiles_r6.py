@@ -58,7 +58,7 @@ def workload(tag, name):
         hot = json.load(open(p))
     fetch = per_kernel(os.path.join(src, f'{tag}_pmc_FETCH_SIZE.csv'), 'FETCH_SIZE')
     write = per_kernel(os.path.join(src, f'{tag}_pmc_WRITE_SIZE.csv'), 'WRITE_SIZE')
-    cmd = (f'rocprofv3 --pmc <counter> -- python3 bench.py --workload {tag} --graph 0 --pipeline 0 --steps 4 --warmup 3 --repeats 1 (lean flags; '
+    cmd = (f'rocprofv3 --pmc <counter> -- python3 bench.py --workload {tag} --graph 0 --pipeline 0 --steps 4 --warmup 3 --repeats 1 --full (lean flags; '
            'separate passes for FETCH_SIZE and WRITE_SIZE; KB units; FETCH_SIZE x2: gfx950 tallies 128-B requests of wide coalesced reads at '
            '64 B, MI355X_MICROARCH.md "HBM")')
     steps_traced = 3 + 4 + 5 + 4      # warm-up + timed + latency + event re-run steps of the eager PMC command
@@ -99,7 +99,7 @@ def workload(tag, name):
         rows = list(csv.DictReader(open(p)))
         rows.sort(key=lambda r: -int(r['TotalDurationNs']))
         with open(os.path.join(dst, f'r6_{name}_bench_kernel_stats_top.txt'), 'w') as f:
-            f.write(f'rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {tag} --steps 20 --warmup 5 --no-cpu-baseline --no-bf16-mode '
+            f.write(f'rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {tag} --steps 20 --warmup 5 --full --no-cpu-baseline --no-bf16-mode '
                     '--host-results 0 --train-step 0 --extra-workloads 0 --no-einsum-sweep --repeats 3   (parity mode fp32 = f16 x 3 MFMA, hipGraph, staged pipeline, 1x MI355X)\n')
             f.write('whole process: eager warm-up + graph captures + 3 x 20 timed pipelined steps + 20 eager event-timed steps\n')
             f.write('%-100s %8s %12s %10s %7s\n' % ('kernel', 'calls', 'total_us', 'avg_us', 'pct'))

@@ -13,7 +13,7 @@ for r in csv.DictReader(open(f)):
                 continue
             inst = n[n.index(key):].split('(')[0]
             agg[(inst, r['Grid_Size_X'], r['Grid_Size_Y'])].append(d)
-cmd = 'rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bf16-mode --host-results 0 --train-step 0 --no-einsum-sweep --repeats 3'
+cmd = 'rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-bf16-mode --host-results 0 --train-step 0 --no-einsum-sweep --repeats 3'
 print('Per-launch durations from the kernel trace of `%s`\n' % cmd)
 print('%-46s %10s %8s %8s %10s %10s %10s' % ('kernel', 'grid_x', 'grid_y', 'calls', 'avg_us', 'min_us', 'max_us'))
 for k, v in sorted(agg.items(), key=lambda kv: (kv[0][0], int(kv[0][1]))):

@@ -350,9 +350,14 @@ def main():
         cls_l, emb_l, mask_l = ref_head.forward(feats, metas)
         # G3: one forward_head call in isolation (einsum + attention-mask rule)
         c3, e3, m3, a3 = ref_head.forward_head(qf, mf, (4, 6))
+        # the same call in float64: the f32 results of two CPUs' BLAS kernels differ by a few ulps (summation order), the
+        # float64 ones agree far below the bounds the oracle is held to
+        ref64 = m2f.Mask2FormerHeadOpen(**hc).eval()
+        ref64.load_state_dict(ref_head.state_dict())
+        c6, e6, m6, a6 = ref64.double().forward_head(qf.double(), mf.double(), (4, 6))
     # inputs are regenerated by tests/util.g4_inputs(); only expected outputs are stored
     npz('g4_head_forward.npz', seed=0, cls=torch.stack(cls_l), emb=torch.stack(emb_l), mask=torch.stack(mask_l),
-        fh_cls=c3, fh_emb=e3, fh_mask=m3, fh_attn=a3)
+        fh_cls=c3, fh_emb=e3, fh_mask=m3, fh_attn=a3, fh64_cls=c6, fh64_emb=e6, fh64_mask=m6, fh64_attn=a6)
 
     # ---- G5/G6: targets + losses of one decoder layer, with captured random points ----
     ref_head.train()

@@ -87,3 +87,25 @@ def test_committed_agreement_profile_has_every_record_the_line_publishes():
     recs, src = bench.agreement_records()
     missing = [k for k in bench.AGREEMENT_KEYS if not isinstance(recs.get(k), dict)]
     assert not missing, f'{src} lacks {missing}: tools/collect_agreement.sh'
+
+
+def test_dump_outputs_arrays_are_wide_bounded_and_reproducible(tmp_path):
+    """`--dump-outputs`: every leaf of the results in f32 / f64, a large array as a seeded sample + per-row sums, <= 64 MB."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    res = [dict(all_results=(torch.randint(0, 65, (100,), generator=g), torch.rand(100, 5, generator=g),
+                             torch.rand(100, 512, 512, generator=g) > 0.5)) for _ in range(8)]
+    a = bench.output_arrays(res)
+    assert set(a) >= {'img0.all_results.labels', 'img7.all_results.bboxes', 'img3.all_results.masks.sample',
+                      'img3.all_results.masks.rowsum'}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a['img0.all_results.labels'].dtype == np.float64 and a['img0.all_results.bboxes'].dtype == np.float32
+    assert np.array_equal(a['img2.all_results.masks.rowsum'], res[2]['all_results'][2].reshape(100, -1).sum(1).double().numpy())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    b = bench.output_arrays(res)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    bench.write_outputs(a, str(tmp_path / 'out'))
+    assert np.array_equal(np.load(tmp_path / 'out' / 'img5.all_results.masks.sample.npy'), a['img5.all_results.masks.sample'])
+    loss = bench.output_arrays(dict(loss=1.5, loss_cls=torch.tensor(0.25)))
+    assert loss['loss'].dtype == np.float64 and float(loss['loss_cls']) == 0.25
