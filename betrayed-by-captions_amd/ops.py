@@ -630,6 +630,110 @@ def masked_xattn_backward(q, kv, bits, out, lse, grad_out, num_heads, scale=None
 
 
 # ------------------------------------------------------------------------------------------------
+# K6w  fused (shifted-)window self-attention of the Swin blocks (csrc/window_attn.hip)
+# ------------------------------------------------------------------------------------------------
+WINDOW_ATTN_HEAD_DIM = 32
+WINDOW_ATTN_MAX_TOKENS = 144
+
+
+def window_attention_shape_ok(channels, ws, num_heads, hw=None, shift=0):
+    """The shapes `window_attention` is built for: head dim 32, ws^2 <= 144, 0 <= shift < ws and (when given) a padded map that is
+    a window multiple. No stage shape of BASELINE configs[3] is gated off: the fused forward + backward beat the SDPA path at all
+    four (profiles/window_attn_ab.txt)."""
+    H, ws, shift = int(num_heads), int(ws), int(shift)
+    if H <= 0 or channels != H * WINDOW_ATTN_HEAD_DIM or ws <= 0 or ws * ws > WINDOW_ATTN_MAX_TOKENS or not 0 <= shift < ws:
+        return False
+    return hw is None or (hw[0] > 0 and hw[1] > 0 and hw[0] % ws == 0 and hw[1] % ws == 0)
+
+
+def window_attention_ok(qkv, ws, num_heads, hw=None, shift=0):
+    """The supported set of `window_attention`, in one place: f32 contiguous (B, Hp*Wp, 3C) ROCm rows of a supported shape."""
+    if not (torch.is_tensor(qkv) and qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.is_contiguous()):
+        return False
+    if qkv.shape[2] % 3 or (hw is not None and qkv.shape[1] != hw[0] * hw[1]):
+        return False
+    return window_attention_shape_ok(qkv.shape[2] // 3, ws, num_heads, hw, shift)
+
+
+def _window_attn_args(qkv, table, hw, ws, shift, num_heads, scale, who):
+    dev_ptr(qkv, 'qkv', torch.float32)          # refuses CPU tensors before any torch.cuda call
+    dev_ptr(table, 'table', torch.float32)
+    if qkv.dim() != 3:
+        raise CggError(f'{who}: qkv must be (B, Hp*Wp, 3C), got {tuple(qkv.shape)}')
+    Hp, Wp = int(hw[0]), int(hw[1])
+    ws, shift, H = int(ws), int(shift), int(num_heads)
+    B, L, C3 = qkv.shape
+    if L != Hp * Wp:
+        raise CggError(f'{who}: qkv has {L} rows, the map {Hp} x {Wp} has {Hp * Wp}')
+    if C3 % 3 or H <= 0 or C3 // 3 != H * WINDOW_ATTN_HEAD_DIM:
+        raise CggError(f'{who}: qkv last dim {C3} is not 3 x {H} heads x {WINDOW_ATTN_HEAD_DIM}')
+    if ws <= 0 or tuple(table.shape) != ((2 * ws - 1) ** 2, H):
+        raise CggError(f'{who}: table must be ({(2 * ws - 1) ** 2}, {H}) for window {ws}, got {tuple(table.shape)}')
+    if table.device != qkv.device:
+        raise CggError(f'{who}: qkv and table live on different devices')
+    if scale is None:
+        scale = 1.0 / math.sqrt(WINDOW_ATTN_HEAD_DIM)
+    return B, Hp, Wp, C3 // 3, H, ws, shift, float(scale)
+
+
+def window_attention(qkv, table, hw, ws, shift, num_heads, scale=None, return_lse=False):
+    """qkv (B, Hp*Wp, 3C) f32 rows of the qkv linear over the padded, un-rolled map ([q | k | v], each heads x 32); table
+    ((2 ws - 1)^2, heads) the relative-position bias parameter; hw = (Hp, Wp), both window multiples -> (B, Hp*Wp, C) f32, the
+    (shifted-)window attention of every token in the same token order (cyclic shift, window partition / reverse, bias lookup and the
+    additive -100 shifted-window mask are address arithmetic inside the kernel).
+    return_lse: also the (B, heads, Hp*Wp) log-sum-exp rows that `window_attention_backward` consumes."""
+    B, Hp, Wp, C, H, ws, shift, scale = _window_attn_args(qkv, table, hw, ws, shift, num_heads, scale, 'window_attention')
+    out = torch.empty((B, Hp * Wp, C), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, H, Hp * Wp), dtype=torch.float32, device=qkv.device)
+    with _timed('window_attn_fwd'):
+        rc = _lib_().cgg_window_attn_forward(dev_ptr(qkv), dev_ptr(table), dev_ptr(out), dev_ptr(lse), B, Hp, Wp, C, H, ws, shift,
+                                             scale, stream_ptr(qkv.device))
+    check(rc, 'cgg_window_attn_forward')
+    return (out, lse) if return_lse else out
+
+
+def window_attention_backward(qkv, table, lse, grad_out, hw, ws, shift, num_heads, scale=None):
+    """Gradients of `window_attention` w.r.t. qkv (B, Hp*Wp, 3C) and table ((2 ws - 1)^2, heads) from the saved log-sum-exp rows: the
+    probabilities are recomputed per window, grad_table is summed in a fixed order (no atomics: two calls give identical bits)."""
+    B, Hp, Wp, C, H, ws, shift, scale = _window_attn_args(qkv, table, hw, ws, shift, num_heads, scale, 'window_attention_backward')
+    dev_ptr(lse, 'lse', torch.float32)
+    grad_out = grad_out.contiguous()
+    dev_ptr(grad_out, 'grad_out', torch.float32)
+    if tuple(lse.shape) != (B, H, Hp * Wp) or tuple(grad_out.shape) != (B, Hp * Wp, C):
+        raise CggError(f'window_attention_backward: lse {tuple(lse.shape)} / grad_out {tuple(grad_out.shape)} do not match '
+                       f'qkv {tuple(qkv.shape)}')
+    lib = _lib_()
+    wsb = _workspace(lib.cgg_window_attn_backward_workspace_bytes(B, Hp, Wp, H, ws), qkv.device)
+    gqkv = torch.empty_like(qkv)
+    gtab = torch.empty_like(table)
+    with _timed('window_attn_bwd'):
+        rc = lib.cgg_window_attn_backward(dev_ptr(qkv), dev_ptr(table), dev_ptr(lse), dev_ptr(grad_out), dev_ptr(gqkv), dev_ptr(gtab),
+                                          dev_ptr(wsb), B, Hp, Wp, C, H, ws, shift, scale, stream_ptr(qkv.device))
+    check(rc, 'cgg_window_attn_backward')
+    return gqkv, gtab
+
+
+class WindowAttentionFn(torch.autograd.Function):
+    """`window_attention` with gradients for qkv and table (saves qkv, table and the log-sum-exp rows; not the output)."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, hw, ws, shift, num_heads, scale):
+        qkv = qkv.contiguous()
+        table = table.contiguous()
+        out, lse = window_attention(qkv, table, hw, ws, shift, num_heads, scale, return_lse=True)
+        ctx.save_for_backward(qkv, table, lse)
+        ctx.args = (tuple(hw), ws, shift, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, table, lse = ctx.saved_tensors
+        hw, ws, shift, num_heads, scale = ctx.args
+        gqkv, gtab = window_attention_backward(qkv, table, lse, grad_out, hw, ws, shift, num_heads, scale)
+        return gqkv, gtab, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
 # K16  caption grounding pair costs
 # ------------------------------------------------------------------------------------------------
 def grounding_supported(pred, cap):

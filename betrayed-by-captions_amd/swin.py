@@ -3,15 +3,23 @@ contract is the upstream one ([3P] mmdet 2.28 `mmdet/models/backbones/swin.py`, 
 (`embed_dims, depths, num_heads, window_size, mlp_ratio, out_indices, patch_norm, drop_path_rate, ...`), parameter
 names (`patch_embed.projection`, `stages.N.blocks.M.attn.w_msa.{qkv,proj,relative_position_bias_table}`,
 `ffn.layers.0.0 / 1`, `stages.N.downsample.{norm,reduction}`, `normN`) and the unfold-ordered patch merging, so an
-mmdet Swin checkpoint loads unchanged. Plain PyTorch (scaled_dot_product_attention for the window attention, bf16
-autocast in throughput mode): the backbone is outside the hand-written-kernel scope of the hot path.
+mmdet Swin checkpoint loads unchanged. In parity (fp32) mode on the device the window attention of every block -- cyclic shift,
+window partition, relative-position bias, shifted-window mask, softmax, window reverse -- is one fused HIP kernel forward and one
+backward (`ops.WindowAttentionFn`, csrc/window_attn.hip); CGG_SWIN_WINATTN=0 restores the PyTorch path below for A/B. Everything
+else (CPU, throughput / bf16 mode under autocast, attention dropout, unsupported shapes) is plain PyTorch
+(scaled_dot_product_attention for the window attention).
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import runtime
+from . import ops, runtime
 from .registry import BACKBONES
+
+# read once at import; 0: the roll / partition / SDPA path everywhere (A/B against the fused window-attention kernels)
+WINATTN = os.environ.get('CGG_SWIN_WINATTN', '1') != '0'
 
 
 def _double_step_seq(step1, len1, step2, len2):
@@ -78,10 +86,44 @@ class ShiftWindowMSA(nn.Module):
         x = windows.view(B, H // ws, W // ws, ws, ws, -1)
         return x.permute(0, 1, 3, 2, 4, 5).contiguous().view(B, H, W, -1)
 
+    def _native_ok(self, query):
+        """The fused kernels apply: parity mode on the device, f32 without autocast, a supported shape, no attention dropout."""
+        m = self.w_msa
+        return (WINATTN and query.is_cuda and query.dtype == torch.float32 and runtime.precision() == 'fp32'
+                and not torch.is_autocast_enabled() and not (self.training and m.attn_drop.p > 0)
+                and m.qkv.weight.dtype == torch.float32 and m.relative_position_bias_table.dtype == torch.float32
+                and ops.window_attention_shape_ok(query.shape[-1], self.window_size, m.num_heads, shift=self.shift_size))
+
+    def _forward_native(self, query, hw_shape):
+        """qkv over the padded map's rows -> fused window attention -> proj -> crop. The padding rows are zero AFTER norm1 as in
+        the reference (their q / k / v equal the qkv bias and they take part as keys); autograd routes their gradient into
+        qkv.bias through the linear."""
+        B, L, C = query.shape
+        H, W = hw_shape
+        ws, m = self.window_size, self.w_msa
+        pad_r, pad_b = (ws - W % ws) % ws, (ws - H % ws) % ws
+        x = query.view(B, H, W, C)
+        if pad_r > 0 or pad_b > 0:
+            x = F.pad(x, (0, 0, 0, pad_r, 0, pad_b))
+        Hp, Wp = H + pad_b, W + pad_r
+        qkv = m.qkv(x.reshape(B, Hp * Wp, C))
+        x = ops.WindowAttentionFn.apply(qkv, m.relative_position_bias_table, (Hp, Wp), ws, self.shift_size, m.num_heads,
+                                        float(m.scale))
+        x = m.proj_drop(m.proj(x))
+        if pad_r > 0 or pad_b > 0:
+            x = x.view(B, Hp, Wp, C)[:, :H, :W, :].contiguous()
+        return x.view(B, H * W, C)
+
     def forward(self, query, hw_shape):
         B, L, C = query.shape
         H, W = hw_shape
         assert L == H * W, 'input feature has wrong size'
+        if self._native_ok(query):
+            x = self._forward_native(query, hw_shape)
+            if self.training and self.drop_path_rate > 0:          # stochastic depth, per sample
+                keep = 1 - self.drop_path_rate
+                x = x * (torch.rand((B, 1, 1), device=x.device, dtype=x.dtype) < keep).to(x.dtype) / keep
+            return x
         ws = self.window_size
         query = query.view(B, H, W, C)
         pad_r, pad_b = (ws - W % ws) % ws, (ws - H % ws) % ws

@@ -312,8 +312,42 @@ int cgg_masked_xattn_backward_x3(const float* q, const void* kv, const uint32_t*
                                  const float* grad_out, const float* grad_out_amax, float* grad_q, void* grad_kv, void* ws, int B,
                                  int Q, int H, int D, int S, float scale, cgg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K6w  Fused (shifted-)window multi-head self-attention of the Swin blocks, forward and backward (csrc/window_attn.hip).
+ *
+ * Replaces, per SwinBlock of [3P] mmdet 2.28 mmdet/models/backbones/swin.py (ShiftWindowMSA.forward -> WindowMSA.forward):
+ * torch.roll, window partition, the (3, B_, heads, N, D) permute of qkv, the materialised (B_, heads, N, N) relative-position
+ * bias + shifted-window mask, softmax(q k^T * scale + bias + mask) v, the transpose back, window reverse and the reverse roll.
+ * All of the re-ordering is addressing: token (y, x) of the rolled map is token ((y + shift) % Hp, (x + shift) % Wp) of the
+ * input, windows are ws x ws tiles of the rolled map, and every result goes back to the row its query came from.
+ *
+ *   qkv    [B, Hp*Wp, 3*C] f32  rows of the qkv linear over the PADDED, un-rolled, un-partitioned map, token-major (y * Wp + x);
+ *                               columns [q | k | v], each heads x D
+ *   table  [(2 ws - 1)^2, heads] f32  relative_position_bias_table; pair (i, j) of a window reads row
+ *                               (yi - yj + ws - 1) * (2 ws - 1) + (xi - xj + ws - 1)
+ *   out    [B, Hp*Wp, C] f32    softmax rows applied to v, heads concatenated, same token order as qkv
+ *   lse    [B, heads, Hp*Wp] f32  max + log(sum exp) of each query's scores (natural log), consumed by the backward
+ *   shift > 0: pairs whose rolled coordinates lie in different regions of the three-slice labelling [0, n - ws), [n - ws, n - shift),
+ *   [n - shift, n) (per axis) get the reference's ADDITIVE -100 (not -inf).
+ * Backward (recomputes the probabilities from qkv and lse; delta = rowsum(P o dP)):
+ *   grad_out   [B, Hp*Wp, C] f32
+ *   grad_qkv   [B, Hp*Wp, 3*C] f32  written, not accumulated: every token belongs to exactly one window
+ *   grad_table [(2 ws - 1)^2, heads] f32  written; dS summed over batch, windows and index-equal pairs in a fixed order
+ *                               (per-(window chunk, head) N x N partials in ws, folded by a second kernel): no floating-point
+ *                               atomics, bit-reproducible
+ *   ws         cgg_window_attn_backward_workspace_bytes(...) bytes
+ * f32 MFMA (v_mfma_f32_16x16x4_f32: exact products, f32 accumulation); nothing of size N x N is read, and only the grad_table
+ * partials are written. Requires D == 32 (C == heads * 32), ws * ws <= 144, Hp % ws == Wp % ws == 0, 0 <= shift < ws;
+ * anything else returns CGG_EUNSUPPORTED, null pointers CGG_EINVAL, both before touching the device.             */
+int cgg_window_attn_forward(const float* qkv, const float* table, float* out, float* lse, int B, int Hp, int Wp, int C,
+                            int heads, int ws, int shift, float scale, cgg_stream_t stream);
+int64_t cgg_window_attn_backward_workspace_bytes(int B, int Hp, int Wp, int heads, int ws);
+int cgg_window_attn_backward(const float* qkv, const float* table, const float* lse, const float* grad_out, float* grad_qkv,
+                             float* grad_table, void* ws_buf, int B, int Hp, int Wp, int C, int heads, int ws, int shift,
+                             float scale, cgg_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
- * K16  Caption-grounding pair costs and their backward.
+ * K16 Caption-grounding pair costs and their backward.
  *
  * Replaces the body of open_set/models/losses/grounding_loss.py:32-58 (`grounding_loss`, evaluated for each of the 10
  * decoder outputs at open_set/models/mask2former_head.py:542-548): for every (caption i, image j) pair
