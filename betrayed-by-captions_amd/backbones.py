@@ -13,12 +13,10 @@ import torch.nn as nn
 from . import ops, runtime
 from .registry import BACKBONES
 
-# throughput mode: ResNet layer1 identity Bottlenecks as one HIP launch (ops.bottleneck64); CGG_FUSED_BOTTLENECK=0 = three library calls
-FUSED_BOTTLENECK = os.environ.get('CGG_FUSED_BOTTLENECK', '1') != '0'
-# training: frozen stem + stages on the BN-folded inference path under no_grad (CGG_FROZEN_FOLDED=0 = autograd-recorded torch path)
+# training: frozen stem + stages on the BN-folded inference path under no_grad (CGG_FROZEN_FOLDED=0 = autograd-recorded torch path,
+# the comparison side of tests/test_train_gpu.py)
 FROZEN_FOLDED = os.environ.get('CGG_FROZEN_FOLDED', '1') != '0'
-FROZEN_NHWC_BF16 = os.environ.get('CGG_FROZEN_NHWC_BF16', '1') != '0'   # throughput mode: frozen stages' maps through the transpose kernel
-# parity mode: the 7x7 stem on the x3 MFMA kernel (CGG_X3_STEM=0 = MIOpen f32 convolution, A/B)
+# parity mode: the 7x7 stem on the x3 MFMA kernel (CGG_X3_STEM=0 = MIOpen f32 convolution; tests/test_env_switches_gpu.py)
 X3_STEM = os.environ.get('CGG_X3_STEM', '1') != '0'
 
 
@@ -275,7 +273,7 @@ class ResNet(nn.Module):
                 identity = x
                 if blk.downsample is not None:
                     identity = self._conv_nhwc(x, blk.downsample[0], next(seq), False)
-                if (FUSED_BOTTLENECK and isinstance(blk, Bottleneck) and blk.downsample is None and blk.conv1.in_channels == 256
+                if (isinstance(blk, Bottleneck) and blk.downsample is None and blk.conv1.in_channels == 256
                         and blk.conv1.out_channels == 64 and tuple(blk.conv2.stride) == (1, 1) and blk.conv2.groups == 1
                         and tuple(blk.conv2.dilation) == (1, 1) and tuple(blk.conv2.padding) == (1, 1) and ops.bottleneck64_ok(x)):
                     # layer1 identity block: conv1 -> conv2 -> conv3 + residual in ONE launch (the 64-channel intermediates stay in LDS)
@@ -477,7 +475,7 @@ class ResNet(nn.Module):
         res = []
         for k, o in enumerate(outs):
             src = frozen_nhwc[k] if k < len(frozen_nhwc) else None
-            if (src is not None and (src.dtype == torch.float32 or (src.dtype == torch.bfloat16 and FROZEN_NHWC_BF16))
+            if (src is not None and src.dtype in (torch.float32, torch.bfloat16)
                     and src.is_cuda and src.is_contiguous() and not src.requires_grad):
                 # a frozen stage's channel-last map (f32 in parity mode, bf16 in throughput mode: one contiguous cast pass first): NCHW
                 # by the tiled transpose kernel (ATen's strided clone of the 1-GB stride-4 map took 1.1 ms, this 0.35), and the

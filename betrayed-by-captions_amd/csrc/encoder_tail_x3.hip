@@ -433,8 +433,8 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
 
 int* cgg_x3_overflow_flag_ptr();       // x3s_gemm.hip
 
-// CGG_TAIL_WAVES=4: round 3-5's four-wavefront form (A/B); read once, when the library is loaded
-static const bool e3_waves8 = !(getenv("CGG_TAIL_WAVES") && atoi(getenv("CGG_TAIL_WAVES")) == 4);
+// eight wavefronts per workgroup, two per SIMD (four, one per SIMD, measured 2-5 % slower on five of six shapes: profiles/r6_tail_waves_ab.txt)
+constexpr int E3_NWV = 8;
 
 static int e3_launch(const float* a32, const float* x32, const void* wo_x3, const float* bo, const float* gamma0,
                      const float* beta0, float eps0, const void* w1_x3, const float* b1, const void* w2_x3,
@@ -455,20 +455,15 @@ static int e3_launch(const float* a32, const float* x32, const void* wo_x3, cons
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)cgg_encoder_tail_x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)cgg_encoder_tail_x3_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e =
+        hipFuncSetAttribute((const void*)cgg_encoder_tail_x3_kernel<E3_NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu", who, lds);
     if (dev >= 0 && dev < 16) attr_set[dev] = true;
   }
-#define E3_GO(NWV)                                                                                                               \
-  hipLaunchKernelGGL(cgg_encoder_tail_x3_kernel<NWV>, dim3((M + E3_RB - 1) / E3_RB), dim3(64 * NWV), lds, (hipStream_t)stream, a32, x32, \
-                     cgg_x3_view(wo_x3, E3_C, E3_C), bo, gamma0, beta0, eps0, cgg_x3_view(w1_x3, F, E3_C), b1,                  \
-                     cgg_x3_view(w2_x3, E3_C, F), b2, gamma1, beta1, eps1, pos, pos_rows, y32, yp32, M, F, x3a,                 \
-                     cgg_x3_overflow_flag_ptr())
-  if (e3_waves8) E3_GO(8);
-  else E3_GO(4);
-#undef E3_GO
+  hipLaunchKernelGGL(cgg_encoder_tail_x3_kernel<E3_NWV>, dim3((M + E3_RB - 1) / E3_RB), dim3(64 * E3_NWV), lds, (hipStream_t)stream, a32,
+                     x32, cgg_x3_view(wo_x3, E3_C, E3_C), bo, gamma0, beta0, eps0, cgg_x3_view(w1_x3, F, E3_C), b1,
+                     cgg_x3_view(w2_x3, E3_C, F), b2, gamma1, beta1, eps1, pos, pos_rows, y32, yp32, M, F, x3a,
+                     cgg_x3_overflow_flag_ptr());
   CGG_CHECK_LAUNCH(who);
   return CGG_OK;
 }

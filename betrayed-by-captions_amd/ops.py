@@ -126,14 +126,17 @@ def msda_forward_fused(value, level_hw, level_start, offs_logits, ref_points, nu
     return out
 
 
-MSDA_VALUE_PAD = 0 if os.environ.get('CGG_MSDA_VALUE_PAD', '1') == '0' else 32
+MSDA_VALUE_PAD = 32      # floats appended to a 256-float value row by `padded_value_rows`
 
 
 def padded_value_rows(B, Nv, H, D, device):
-    """(buffer (B, Nv, H D + pad) f32, value view (B, Nv, H, D) into it): MSDeformAttn value rows with a padded row stride. A stride
+    """A probe / test helper for the strided-value forms of the MSDeformAttn kernels (`cgg_msda_forward_fused_vld`, the backward's
+    strided grad_value): NO production path allocates its value projection through it (tests/test_kernels_gpu.py and
+    scratch/msda_vld_probe.py do; profiles/r6_msda_value_row_stride.txt). Returns
+    (buffer (B, Nv, H D + pad) f32, value view (B, Nv, H, D) into it): MSDeformAttn value rows with a padded row stride. A stride
     that is a multiple of 512 bytes (H D = 256 floats = 1 KiB) sends the four corner lines of a tap, and neighbouring pixels' lines,
     to the same L2 channels; 288 floats per row instead of 256 made the forward gather 20 % faster at configs[1] / [2] shapes
-    (scratch/msda_vld_probe.py: 256 -> 115 us, 288 -> 92, 320 -> 98, 384 -> 110, 512 -> 112, 544 -> 93). CGG_MSDA_VALUE_PAD=0: packed."""
+    (scratch/msda_vld_probe.py: 256 -> 115 us, 288 -> 92, 320 -> 98, 384 -> 110, 512 -> 112, 544 -> 93) in that probe."""
     C = H * D
     buf = torch.empty((B, Nv, C + MSDA_VALUE_PAD), dtype=torch.float32, device=device)
     return buf, buf[..., :C].unflatten(-1, (H, D))
@@ -569,7 +572,6 @@ def masked_xattn(q, kv, bits, num_heads, scale=None, return_lse=False):
 
 CGG_F32_BF16MFMA = 2                 # include/cgg_hip.h: f32 rows in memory, bf16 MFMA operands (training kernels of throughput mode)
 CGG_F32_X3 = 3                       # cgg_masked_xattn_forward_lse only: the forward on the f32-class f16 x 3 contraction
-XATTN_BF16_TRAIN = os.environ.get('CGG_XATTN_BF16_TRAIN', '1') != '0'
 XATTN_X3_TRAIN = os.environ.get('CGG_XATTN_X3_TRAIN', '1') != '0'
 XATTN_X3_BWD = os.environ.get('CGG_XATTN_X3_BWD', '1') != '0'       # parity-mode training: the cross-attention backward on f16 x 3 (0: f32 MFMA)
 
@@ -580,7 +582,7 @@ def _xattn_train_dtype(forward=False):
     which also writes the log-sum-exp rows) and the backward on the exact f32 MFMA."""
     from . import runtime
     if runtime.is_bf16():
-        return CGG_F32_BF16MFMA if XATTN_BF16_TRAIN else CGG_F32
+        return CGG_F32_BF16MFMA
     return CGG_F32_X3 if (forward and XATTN_X3_TRAIN and XATTN_X3 and runtime.x3_enabled()) else CGG_F32
 
 

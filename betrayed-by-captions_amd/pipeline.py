@@ -41,7 +41,7 @@ class StagePipeline:
     example  -- an example input batch (shape / dtype / device are frozen into the graphs)
     """
 
-    def __init__(self, stages, example, slots=None, warmup=2, priorities=None, streams=None, tail=None):
+    def __init__(self, stages, example, slots=None, warmup=2, streams=None, tail=None):
         """tail -- optional callable applied EAGERLY (not captured) to the last graph stage's output: post-processing with
                    data-dependent host reads (the panoptic fusion head reads segment counts: no hipGraph can hold that). It runs
                    on its own stream ONE BATCH BEHIND the graph stages -- `submit(k + 1)` first enqueues batch k + 1's graphs, then
@@ -56,11 +56,7 @@ class StagePipeline:
             raise ValueError('StagePipeline: a tail needs slots >= 2')
         dev = example.device
         self.dev = dev
-        import os
-        if priorities is None and os.environ.get('CGG_PIPE_PRIO'):
-            priorities = [int(v) for v in os.environ['CGG_PIPE_PRIO'].split(',')]
-        self.streams = list(streams) if streams is not None else \
-            [torch.cuda.Stream(dev, priority=(priorities[i] if priorities else 0)) for i in range(n)]
+        self.streams = list(streams) if streams is not None else [torch.cuda.Stream(dev, priority=0) for _ in range(n)]
         self.inputs = [torch.empty_like(example) for _ in range(self.slots)]
         self.done = [[torch.cuda.Event() for _ in range(self.slots)] for _ in range(n)]
         self.graphs = [[None] * self.slots for _ in range(n)]

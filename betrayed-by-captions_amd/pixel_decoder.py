@@ -25,18 +25,16 @@ from .registry import (ATTENTION, FEEDFORWARD_NETWORK, PLUGIN_LAYERS, POSITIONAL
                        build_feedforward_network, build_positional_encoding,
                        build_transformer_layer, build_transformer_layer_sequence)
 
-# throughput mode: encoder FFN + residual LayerNorm as one HIP launch (ops.encoder_ffn_ln); CGG_FUSED_FFN=0 restores the
-# two library GEMMs + LayerNorm pass for A/B measurements
-FUSED_FFN = os.environ.get('CGG_FUSED_FFN', '1') != '0'
-FUSED_TAIL = os.environ.get('CGG_FUSED_TAIL', '1') != '0'   # ... preceded by output_proj + its residual LayerNorm
-FUSED_PROJ = os.environ.get('CGG_FUSED_PROJ', '1') != '0'
+# The switches of this module (README.md, "Environment switches"): each is the only handle by which
+# tests/test_env_switches_gpu.py drives a fallback that shapes outside the kernels' rules take as well. The fused
+# throughput-mode stages (ops.encoder_proj / encoder_ffn_ln / encoder_layer_tail) are selected by shape alone.
+# encoder layer: output_proj + residual LayerNorm + FFN + residual LayerNorm as one launch (0: the per-GEMM tier)
+FUSED_TAIL = os.environ.get('CGG_FUSED_TAIL', '1') != '0'
 FUSED_TRAIN_MSDA = os.environ.get('CGG_FUSED_TRAIN_MSDA', '1') != '0'   # training: MSDeformAttn prologue inside the kernels (fwd + bwd)
 FUSED_TRAIN_LN = os.environ.get('CGG_FUSED_TRAIN_LN', '1') != '0'   # training: residual + LayerNorm as one-pass HIP fwd / bwd
-VALUE_HEAD_MAJOR = os.environ.get('CGG_VALUE_HEAD_MAJOR', '1') != '0'   # value written (B, 8, N, 32) for the MSDeformAttn gather
 # x3a encoder stream: value / offsets / logits of a layer from ONE GEMM (needs the strided-value sampling kernel: not with the
 # generic MSDeformAttn kernels forced)
 MERGED_PROJ = os.environ.get('CGG_MERGED_PROJ', '1') != '0' and not os.environ.get('CGG_MSDA_GENERIC')
-POS_IN_PROJ = os.environ.get('CGG_POS_IN_PROJ', '1') != '0'   # the projection kernel forms x + pos from a bf16 pos table   # value_proj + offsets/weights GEMMs as one HIP launch
 
 
 # ------------------------------------------------------------------------------------------------
@@ -537,10 +535,6 @@ class MSDeformAttnPixelDecoder(nn.Module):
                                                 act_cfg=act_cfg))
         self.mask_feature = nn.Conv2d(feat_channels, out_channels, kernel_size=1, stride=1, padding=0)
         self.num_outs = num_outs
-        # throughput-mode (bf16) encoder stream: keep the residual between LayerNorms in bf16 (the rows the GEMMs read
-        # anyway) instead of a separate f32 copy; False restores the f32 residual stream
-        import os
-        self.stream_residual_bf16 = not os.environ.get('CGG_STREAM_RES_F32')
         self._ref_cache = {}
 
     def init_weights(self):
@@ -586,7 +580,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         def nc(layer):
             a = layer.attentions[0]
             return a.sampling_offsets.out_features + a.attention_weights.out_features
-        return FUSED_PROJ and C == 256 and all(nc(l) % 32 == 0 and 256 <= nc(l) <= 384 for l in self.encoder.layers)
+        return C == 256 and all(nc(l) % 32 == 0 and 256 <= nc(l) <= 384 for l in self.encoder.layers)
 
     def _encoder_stream_bf16(self, src, pos, ref, level_hw, level_start, x16=None, xp16=None, kv_tables=None):
         """Throughput-mode encoder over the (B, 21504, 256) bf16 stream, THREE launches per layer (round 2):
@@ -594,8 +588,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
         `ops.msda_forward_fused_bf16` (softmax / sampling locations in the prologue) and `ops.encoder_layer_tail`
         (output_proj + residual LayerNorm + FFN + residual LayerNorm; the last layer also emits the query decoder's
         K / V operands). Each stage falls back to its library-GEMM form (4 GEMMs + 2 fused residual-LayerNorm passes, the
-        round-1 path) when its shape is not built or its CGG_FUSED_* switch is off. `src` (f32 stream) is only read
-        with the f32 residual option (CGG_STREAM_RES_F32)."""
+        round-1 path) when its shape is not built (or CGG_FUSED_TAIL=0). The residual between the LayerNorms stays bf16 -- the rows
+        the GEMMs read anyway; `src` (f32) is only read to make them when the caller passes no `x16`."""
         bf = torch.bfloat16
         cc = runtime.cast_cached
         if x16 is None:
@@ -605,7 +599,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         n_layers = len(self.encoder.layers)
         proj_ok = self._proj_fused(C)
         # with the projection kernel forming `x + pos` itself (bf16 pos table), the layer tails stop writing those rows
-        pos16 = runtime.derived_cached('enc_pos16', (pos,), lambda: pos.to(bf).contiguous()) if proj_ok and POS_IN_PROJ else None
+        pos16 = runtime.derived_cached('enc_pos16', (pos,), lambda: pos.to(bf).contiguous()) if proj_ok else None
         for li, layer in enumerate(self.encoder.layers):
             attn = layer.attentions[0]
             H, D = attn.num_heads, C // attn.num_heads
@@ -622,7 +616,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                                              lambda: ops.pack_encoder_proj_weight(torch.cat([so.weight, aw.weight], 0)))
                 bcf = runtime.derived_cached('msda_bcf', (so.bias, aw.bias),
                                              lambda: torch.cat([so.bias, aw.bias], 0).float().contiguous())
-                hm = VALUE_HEAD_MAJOR and H == 8 and D == 32 and len(level_hw) == 3 and attn.num_points == 4
+                hm = H == 8 and D == 32 and len(level_hw) == 3 and attn.num_points == 4
                 value, offs = ops.encoder_proj(x16, xp16, wvp, vp.bias, wcp, bcf, pos16=pos16 if xp16 is None else None,
                                                value_head_major=hm)
                 if not hm:
@@ -635,8 +629,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
             n0, n1 = layer.norms
             ffn = layer.ffns[0]
             last = li == n_layers - 1
-            fused_ffn = (self.stream_residual_bf16 and FUSED_FFN and ffn.layers[0][0].out_features % 256 == 0
-                         and (not last or kv_tables is not None))
+            fused_ffn = ffn.layers[0][0].out_features % 256 == 0 and (not last or kv_tables is not None)
             if fused_ffn and FUSED_TAIL and C == 256:
                 # output_proj + residual LayerNorm + FFN + residual LayerNorm as ONE launch: neither the projection output, nor
                 # the first LayerNorm's rows, nor the (B, N, 1024) hidden activation reach memory
@@ -654,12 +647,9 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 src = x16
                 continue
             o16 = F.linear(a16, cc(attn.output_proj.weight), cc(attn.output_proj.bias))
-            if self.stream_residual_bf16:
-                # residual stream in bf16: the LayerNorm reads the same bf16 rows the GEMMs read (66 instead of 132 MB)
-                _, x16, _ = ops.add_layernorm_stream(x16, o16, n0.weight, n0.bias, n0.eps, want_f32=False)
-                src = x16
-            else:
-                src, x16, _ = ops.add_layernorm_stream(src, o16, n0.weight, n0.bias, n0.eps)
+            # residual stream in bf16: the LayerNorm reads the same bf16 rows the GEMMs read (66 instead of 132 MB)
+            _, x16, _ = ops.add_layernorm_stream(x16, o16, n0.weight, n0.bias, n0.eps, want_f32=False)
+            src = x16
             if fused_ffn:
                 # FFN + residual LayerNorm as one launch: the (B, N, 1024) hidden activation stays on chip
                 fc1, fc2 = ffn.layers[0][0], ffn.layers[1]
@@ -684,8 +674,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                                                       level_start)
                 return src, (m16, mp16)
             src, x16, xp16 = ops.add_layernorm_stream(src, f16, n1.weight, n1.bias, n1.eps, pos=pos,
-                                                      want_f32=last or not self.stream_residual_bf16,
-                                                      want_bf16=not last, want_pos=not last)
+                                                      want_f32=last, want_bf16=not last, want_pos=not last)
         return src if kv_tables is None else (src, None)
 
     # ---- throughput-mode inference stream: channel-last bf16 from the backbone to the packed mask feature ----
@@ -699,6 +688,20 @@ class MSDeformAttnPixelDecoder(nn.Module):
             hit = (key, pos)
             self.__dict__['_pos_cache'] = hit
         return runtime.keepalive(hit[1])
+
+    def _stream_levels(self, feats):
+        """(level_hw, level_start, N, pos, ref) of the encoder's pyramid, levels low -> high resolution: the (h, w) of each level, its
+        first row in the (B, N, C) stream, the row count N, the cached (N, C) positional table and (N, 2) reference points."""
+        dev = feats[0].device
+        level_hw = []
+        for i in range(self.num_encoder_levels):
+            f = feats[self.num_input_levels - i - 1]
+            level_hw.append((int(f.shape[2]), int(f.shape[3])))
+        level_start, N = [], 0
+        for h, w in level_hw:
+            level_start.append(N)
+            N += h * w
+        return level_hw, level_start, N, self._pos_cached(level_hw, dev), self._reference_points(level_hw, dev)
 
     def stream_ready(self, feats):
         """True when `forward_stream` applies: throughput mode, no autograd, channel-last bf16 features (what the
@@ -739,21 +742,10 @@ class MSDeformAttnPixelDecoder(nn.Module):
         B = feats[0].shape[0]
         dev = feats[0].device
         C = 256
-        level_hw = []
-        for i in range(self.num_encoder_levels):
-            f = feats[self.num_input_levels - i - 1]
-            level_hw.append((int(f.shape[2]), int(f.shape[3])))
-        level_start, N = [], 0
-        for h, w in level_hw:
-            level_start.append(N)
-            N += h * w
-        pos = self._pos_cached(level_hw, dev)
-        ref = self._reference_points(level_hw, dev)
-        # bf16 residual stream: the f32 copy of the encoder input is never read; projection kernel with the bf16 pos table:
-        # neither are the `x + pos` rows
-        need32 = not self.stream_residual_bf16
-        needp = not (self._proj_fused(C) and POS_IN_PROJ)
-        src = torch.empty((B, N, C), dtype=torch.float32, device=dev) if need32 else None
+        level_hw, level_start, N, pos, ref = self._stream_levels(feats)
+        # bf16 residual stream: no f32 copy of the encoder input exists; projection kernel with the bf16 pos table: neither do
+        # the `x + pos` rows
+        needp = not self._proj_fused(C)
         x16 = torch.empty((B, N, C), dtype=torch.bfloat16, device=dev)
         xp16 = torch.empty((B, N, C), dtype=torch.bfloat16, device=dev) if needp else None
         ws = ops.group_norm_nhwc_workspace(B, int(feats[0].shape[2]) * int(feats[0].shape[3]), 32, dev)   # largest map
@@ -764,18 +756,16 @@ class MSDeformAttnPixelDecoder(nn.Module):
             y = self._gemm1x1(f.permute(0, 2, 3, 1).reshape(B * h * w, f.shape[1]), cm.conv).view(B, h * w, C)
             gn = getattr(cm, cm.norm_name)
             off = level_start[i] * C
-            ops.group_norm_nhwc(y, gn.weight, gn.bias, 32, gn.eps, ws, out32=(src, off, N * C) if need32 else None,
-                                out16=(x16, off, N * C), pos=(pos, off) if needp else None,
+            ops.group_norm_nhwc(y, gn.weight, gn.bias, 32, gn.eps, ws, out16=(x16, off, N * C), pos=(pos, off) if needp else None,
                                 outp16=(xp16, off, N * C) if needp else None)
         kv16 = None
         if kv_tables is not None:
-            src, kv = self._encoder_stream_bf16(src, pos, ref, level_hw, level_start, x16, xp16,
-                                                kv_tables(level_hw, dev))
+            src, kv = self._encoder_stream_bf16(None, pos, ref, level_hw, level_start, x16, xp16, kv_tables(level_hw, dev))
             if kv is not None:
                 kv16 = [(kv[0][B * s0:B * (s0 + h * w)].view(B, h * w, C), kv[1][B * s0:B * (s0 + h * w)].view(B, h * w, C))
                         for s0, (h, w) in zip(level_start, level_hw)]
         else:
-            src = self._encoder_stream_bf16(src, pos, ref, level_hw, level_start, x16, xp16)
+            src = self._encoder_stream_bf16(None, pos, ref, level_hw, level_start, x16, xp16)
         mems = [src[:, s0:s0 + h * w, :] for s0, (h, w) in zip(level_start, level_hw)]
         if defer_fpn:        # the caller runs `stream_fpn(*fpn_args)` later (pipeline stage balancing)
             fpn_args = (feats[0], src, level_hw[-1], level_start[-1], N)
@@ -971,16 +961,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         C = 256
         rows = lambda f: (f if ops.is_x3a(f) else ops.x3a_encode(ops.nchw_to_nhwc(f).contiguous()).permute(0, 3, 1, 2)) \
             .as_subclass(torch.Tensor).permute(0, 2, 3, 1).reshape(-1, f.shape[1])
-        level_hw = []
-        for i in range(self.num_encoder_levels):
-            f = feats[self.num_input_levels - i - 1]
-            level_hw.append((int(f.shape[2]), int(f.shape[3])))
-        level_start, N = [], 0
-        for h, w in level_hw:
-            level_start.append(N)
-            N += h * w
-        pos = self._pos_cached(level_hw, dev)
-        ref = self._reference_points(level_hw, dev)
+        level_hw, level_start, N, pos, ref = self._stream_levels(feats)
         src = torch.empty((B, N, C), dtype=torch.float32, device=dev)      # x3a rows
         # src + pos, x3a rows (the first layer's offsets input) -- not needed when every layer takes the merged projection
         need_srcp = not all(self._merged_proj_ok(l) for l in self.encoder.layers)
@@ -1007,20 +988,19 @@ class MSDeformAttnPixelDecoder(nn.Module):
         ReLU, mask_feature -> (B, H4, W4, C) f32."""
         C = 256
         B = src.shape[0]
-        if True:
-            lat, outc = self.lateral_convs[0], self.output_convs[0]
-            hl, wl = fine_hw
-            level_start = [fine_start]
-            y = runtime.linear_x3s(frows, lat.conv.weight.flatten(1), lat.conv.bias).view(B, H4 * W4, C)
-            gn = getattr(lat, lat.norm_name)
-            ops.group_norm_nhwc_x3a(y, gn.weight, gn.bias, 32, gn.eps, ws, out=(y, 0, H4 * W4 * C),
-                                    up=(src, level_start[-1] * C, N * C, hl, wl), W=W4)                # y: f32 -> x3a in place
-            w3 = runtime.derived_cached('x3_conv_image', (outc.conv.weight,), lambda: ops.pack_conv_weight_x3(outc.conv.weight))
-            z = ops.conv_x3s_nhwc(y.view(B, H4, W4, C), w3, C, 3, 1, 1, outc.conv.bias, out_split=False).view(B, H4 * W4, C)
-            gn = getattr(outc, outc.norm_name)
-            ops.group_norm_nhwc_x3a(z, gn.weight, gn.bias, 32, gn.eps, ws, out=(z, 0, H4 * W4 * C), relu=True)
-            mf = runtime.linear_x3s(z.view(B * H4 * W4, C), self.mask_feature.weight.flatten(1), self.mask_feature.bias)
-            return mf.view(B, H4, W4, -1)
+        lat, outc = self.lateral_convs[0], self.output_convs[0]
+        hl, wl = fine_hw
+        level_start = [fine_start]
+        y = runtime.linear_x3s(frows, lat.conv.weight.flatten(1), lat.conv.bias).view(B, H4 * W4, C)
+        gn = getattr(lat, lat.norm_name)
+        ops.group_norm_nhwc_x3a(y, gn.weight, gn.bias, 32, gn.eps, ws, out=(y, 0, H4 * W4 * C),
+                                up=(src, level_start[-1] * C, N * C, hl, wl), W=W4)                # y: f32 -> x3a in place
+        w3 = runtime.derived_cached('x3_conv_image', (outc.conv.weight,), lambda: ops.pack_conv_weight_x3(outc.conv.weight))
+        z = ops.conv_x3s_nhwc(y.view(B, H4, W4, C), w3, C, 3, 1, 1, outc.conv.bias, out_split=False).view(B, H4 * W4, C)
+        gn = getattr(outc, outc.norm_name)
+        ops.group_norm_nhwc_x3a(z, gn.weight, gn.bias, 32, gn.eps, ws, out=(z, 0, H4 * W4 * C), relu=True)
+        mf = runtime.linear_x3s(z.view(B * H4 * W4, C), self.mask_feature.weight.flatten(1), self.mask_feature.bias)
+        return mf.view(B, H4, W4, -1)
 
     def forward_stream_x3(self, feats, defer_fpn=False):
         """-> (mask_feature (B, H4, W4, C) f32 channel-last, [memories (B, hw_l, C) f32 low->high res], level sizes). 1x1
@@ -1033,16 +1013,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
         B = feats[0].shape[0]
         dev = feats[0].device
         C = 256
-        level_hw = []
-        for i in range(self.num_encoder_levels):
-            f = feats[self.num_input_levels - i - 1]
-            level_hw.append((int(f.shape[2]), int(f.shape[3])))
-        level_start, N = [], 0
-        for h, w in level_hw:
-            level_start.append(N)
-            N += h * w
-        pos = self._pos_cached(level_hw, dev)
-        ref = self._reference_points(level_hw, dev)
+        level_hw, level_start, N, pos, ref = self._stream_levels(feats)
         src = torch.empty((B, N, C), dtype=torch.float32, device=dev)
         ws = ops.group_norm_nhwc_workspace(B, int(feats[0].shape[2]) * int(feats[0].shape[3]), 32, dev)   # largest map
         for i in range(self.num_encoder_levels):

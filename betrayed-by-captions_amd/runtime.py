@@ -7,7 +7,8 @@ precision:
             (csrc/x3s_gemm.hip), the one-launch encoder tail, the x3 query-decoder chains, the x3 mask-logit einsum; f32
             MSDeformAttn values / norms / softmax; f32-MFMA attention. Under autograd (training): f32 library GEMMs /
             convolutions (hipBLASLt / MIOpen) with the HIP kernels for attention, MSDeformAttn, losses.
-            CGG_X3=0 restores round 2's f32-library parity path, CGG_X3A=0 round 3's f32-row x3 stream (A/B only).
+            CGG_X3=0 restores round 2's f32-library parity path, CGG_X3A=0 round 3's f32-row x3 stream: the two documented
+            escapes from the default arithmetic.
   'bf16' -- throughput mode named by BASELINE.json's north_star: bf16 MFMA contractions
             (mask logits 1x bf16 MFMA, bf16 values for the MSDeformAttn gather, torch GEMMs/convs
             under bf16 autocast); softmax / normalisation / accumulation stay f32.
@@ -45,7 +46,11 @@ def is_bf16():
 
 import os as _os
 
-# read once at import (the hot path called os.environ.get per linear)
+# The switches of this module, each read once at import (the hot path called os.environ.get per linear). README.md
+# ("Environment switches") is the full table with the reason each one exists; a path that lost its A/B is deleted, not kept "off".
+#   escapes:                       CGG_X3, CGG_X3A
+#   handles on live fallbacks:     CGG_X3_TRAIN, CGG_X3_LAYER_NODES, CGG_X3_FPN_ROWS   (rows of tests/test_env_switches_gpu.py)
+#   comparison sides of tests:     CGG_X3_RESNET_TRAIN, CGG_X3_INPUT_ROWS              (flipped in-process as module attributes)
 _X3 = _os.environ.get('CGG_X3', '1') != '0'
 _X3A = _os.environ.get('CGG_X3A', '1') != '0'
 
@@ -179,7 +184,7 @@ class _X3LinearFn(torch.autograd.Function):
     per product, as accurate as an f32 GEMM -- tests/test_x3_gpu.py); the x3 images of W and W^T are re-packed when the optimiser
     changes the weight (cached against its version). The weight gradient dW = dy^T x reduces over ALL rows into a tiny output:
     `ops.wgrad_x3` (csrc/wgrad_x3.hip: both row-major operands through `ds_read_b64_tr_b16` transpose reads, row ranges split over
-    the grid, partial tiles summed in fixed order); CGG_X3_WGRAD=0 = one batched f32 library GEMM over S row slabs (round 3)."""
+    the grid, partial tiles summed in fixed order)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -204,27 +209,22 @@ class _X3LinearFn(torch.autograd.Function):
         g2 = gy.reshape(-1, N)
         if g2.stride(1) != 1 or g2.stride(0) % 4 or g2.data_ptr() % 16:
             g2 = g2.contiguous()
-        M = x2.shape[0]
         gx = gw = gb = None
         # grad_output is not unit scale (|g| ~ 1e-4 .. 1e-8 behind a normalised loss): its f16 pieces are taken after a per-tensor
         # power-of-two pre-scale from max |g| (ONE exact streaming pass, shared by the grad-input GEMM and the weight-gradient kernel;
         # a SAMPLED maximum was tried and is unsafe: encoder gradients are sparse -- most rows ~0, a few boundary rows 10^6 x larger --
         # so every 8th row can miss all of them and the true maximum then overflows f16: NaN weight gradients at configs[2] shapes)
-        # instead of the activations' fixed 2^4 (with 2^4 a gradient of 1e-6 kept ~10 of its 22 bits); CGG_X3_GSCALE=0
-        # restores the fixed scale for A/B
-        amax = ops.absmax(g2) if _X3_GSCALE and N % 4 == 0 else None
+        # instead of the activations' fixed 2^4 (with 2^4 a gradient of 1e-6 kept ~10 of its 22 bits)
+        amax = ops.absmax(g2) if N % 4 == 0 else None
         if ctx.needs_input_grad[0]:
             wtk = derived_cached('x3_image_t', (weight,), lambda: ops.pack_linear_weight_x3(weight.detach().t().contiguous()))
             gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=g2.device)
             ops.gemm_x3(g2, wtk, K, out=gx.view(-1, K), amax=amax)
         if ctx.needs_input_grad[1]:
-            if _X3_WGRAD and ctx.has_bias and ctx.needs_input_grad[2] and N % 4 == 0:
+            if ctx.has_bias and ctx.needs_input_grad[2] and N % 4 == 0:
                 gw, gb = ops.wgrad_x3(g2, x2, want_bias=True, amax=amax)      # the bias gradient from the same pass over grad_output
-            elif _X3_WGRAD:
-                gw = ops.wgrad_x3(g2, x2, amax=amax)   # transpose-read x3 kernel (csrc/wgrad_x3.hip), partial tiles summed in fixed order
             else:
-                S = next((s for s in (32, 16, 8, 4, 2) if M % s == 0 and M // s >= 4096), 1)
-                gw = torch.bmm(g2.view(S, M // S, N).transpose(1, 2), x2.view(S, M // S, K)).sum(0)
+                gw = ops.wgrad_x3(g2, x2, amax=amax)   # transpose-read x3 kernel (csrc/wgrad_x3.hip), partial tiles summed in fixed order
         if gb is None and ctx.has_bias and ctx.needs_input_grad[2]:
             gb = g2.sum(0)
         return gx, gw, gb
@@ -258,7 +258,7 @@ class _X3LinearTableFn(torch.autograd.Function):
         N, K = weight.shape
         g2 = _rows(gy, N)
         gx = gw = gt = None
-        amax = ops.absmax(g2) if _X3_GSCALE else None
+        amax = ops.absmax(g2)
         if ctx.needs_input_grad[0]:
             wtk = derived_cached('x3_image_t', (weight,), lambda: ops.pack_linear_weight_x3(weight.detach().t().contiguous()))
             gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=g2.device)
@@ -302,10 +302,10 @@ class _X3FfnFn(torch.autograd.Function):
         g2 = gy.reshape(-1, N)
         if g2.stride(1) != 1 or g2.stride(0) % 4 or g2.data_ptr() % 16:
             g2 = g2.contiguous()
-        amax = ops.absmax(g2) if _X3_GSCALE else None
+        amax = ops.absmax(g2)
         gw2, gb2 = ops.wgrad_x3(g2, h, want_bias=True, amax=amax)
         w2t = derived_cached('x3_image_t', (w2,), lambda: ops.pack_linear_weight_x3(w2.detach().t().contiguous()))
-        gh, amax_h = ops.gemm_x3_bwd(g2, w2t, F_, amax=amax, mask=h, want_amax=_X3_GSCALE)       # d / d(pre-activation)
+        gh, amax_h = ops.gemm_x3_bwd(g2, w2t, F_, amax=amax, mask=h, want_amax=True)       # d / d(pre-activation)
         gw1, gb1 = ops.wgrad_x3(gh, x2, want_bias=True, amax=amax_h)
         gx = None
         if ctx.needs_input_grad[0]:
@@ -434,7 +434,7 @@ def x3_layer_nodes_ok(layer, src):
     lin1, lin2 = ffn.layers[0][0], ffn.layers[1]
     C = src.shape[-1]
     w_cat_rows = attn.sampling_offsets.weight.shape[0] + attn.attention_weights.weight.shape[0]
-    return (_X3_LAYER_NODES and _X3_GSCALE and _X3_WGRAD and src.dim() == 3 and C == 256
+    return (_X3_LAYER_NODES and src.dim() == 3 and C == 256
             and x3_train_linear_ok(src, attn.value_proj.weight) and x3_train_linear_ok(src, attn.output_proj.weight)
             and x3_train_ffn_ok(src, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
             and attn.sampling_offsets.weight.shape[1] == C and w_cat_rows % 32 == 0
@@ -496,17 +496,14 @@ class _X3Conv3x3Fn(torch.autograd.Function):
         gp = ops.nchw_to_nhwc_pad1(gy)                    # (B, H + 2, W + 2, N), zero border
         gx = gw = None
         # per-tensor pre-scale of grad_output (see _X3LinearFn); the zero border does not change the maximum
-        amax = ops.absmax(gp.view(-1, N)) if _X3_GSCALE else None
+        amax = ops.absmax(gp.view(-1, N))
         if ctx.needs_input_grad[0]:
             wt = derived_cached('x3_conv_image_dgrad', (weight,),
                                 lambda: ops.pack_conv_weight_x3(weight.detach().flip(2, 3).transpose(0, 1).contiguous()))
-            if amax is not None:
-                # f32 rows split in the kernel with the per-tensor scale (the x3a form bakes the fixed 2^4 into the stored pieces)
-                gx = ops.nhwc_to_nchw(ops.conv_x3_nhwc(gp, wt, C, 3, 1, 0, amax=amax))
-            else:
-                # (contiguous NCHW: a channel-last-strided gradient sent the producer's backward -- the FPN's bilinear up-sample -- down
-                # torch's NHWC kernel, 4.3 ms instead of 1.4)
-                gx = ops.nhwc_to_nchw(ops.conv_x3s_nhwc(ops.x3a_encode(gp), wt, C, 3, 1, 0, None, out_split=False))
+            # f32 rows split in the kernel with the per-tensor scale (the x3a form bakes the fixed 2^4 into the stored pieces).
+            # (contiguous NCHW: a channel-last-strided gradient sent the producer's backward -- the FPN's bilinear up-sample -- down
+            # torch's NHWC kernel, 4.3 ms instead of 1.4)
+            gx = ops.nhwc_to_nchw(ops.conv_x3_nhwc(gp, wt, C, 3, 1, 0, amax=amax))
         if ctx.needs_input_grad[1]:
             xr, gr = xp.view(-1, C), gp.view(-1, N)       # rows of the (B, H + 2, W + 2) grid
             Mp = xr.shape[0]
@@ -532,12 +529,8 @@ class _X3ConvBnFn(torch.autograd.Function):
     add launches and their backward kernels: forward = the x3 implicit GEMM with s folded into the packed filter and (t, res, ReLU) in
     its epilogue; backward = one ReLU-mask pass, one max |g| pass (per-tensor pre-scale, see `_X3LinearFn`), grad-input as the x3
     GEMM / convolution with the transposed (flipped) filter, grad-weight as `ops.wgrad_x3` (nine taps over zero-padded maps for
-    3 x 3, see `_X3Conv3x3Fn`), scaled by s.
-    3 x 3 / STRIDE 2 / pad 1 (even H, W; the first block's convolution): x[iy] reaches out[oy] through tap ky = iy + 1 - 2 oy, so the
-    input pixels of one parity class (iy & 1, ix & 1) see a fixed 1 x 1, 1 x 2, 2 x 1 or 2 x 2 sub-filter of grad_output -- grad-input is
-    FOUR small stride-1 convolutions over grad_output (zero row / column appended: the 2-tap reach to oy + 1) whose results interleave,
-    nine taps' worth of MFMA work like the forward (a zero-dilated grad_output would cost four times that); grad-weight pairs
-    grad_output with the four parity-class sub-maps of the zero-padded input, in which a tap is again a constant row offset."""
+    3 x 3, see `_X3Conv3x3Fn`), scaled by s. A 3 x 3 / stride-2 convolution (the first block's) is not this node's: it stays a
+    library call on the channel-last view (`resnet_stage_x3_train`)."""
 
     @staticmethod
     def forward(ctx, x, weight, scale, shift, res, stride, relu):
@@ -565,15 +558,12 @@ class _X3ConvBnFn(torch.autograd.Function):
         N, C, k, _ = weight.shape
         B, H, W, _ = x.shape
         g = gy.contiguous()
-        amax = None
-        if relu and _X3_GSCALE and g.numel() % 4 == 0:
+        if relu:
             g, amax = ops.relu_backward_absmax(g, y)          # ReLU mask and max |g| in one pass
-        elif relu:
-            g = torch.ops.aten.threshold_backward(g, y, 0.0)
+        else:
+            amax = ops.absmax(g.view(-1, N))
         OH, OW = g.shape[1], g.shape[2]
         g2 = g.view(-1, N)
-        if amax is None and _X3_GSCALE:
-            amax = ops.absmax(g2)
         gx = gw = None
         if ctx.needs_input_grad[0]:
             if k == 1:
@@ -585,39 +575,14 @@ class _X3ConvBnFn(torch.autograd.Function):
                 else:       # the pixels a stride-s 1 x 1 filter never read get no gradient
                     gx = torch.zeros_like(x)
                     gx[:, ::stride, ::stride] = gs
-            elif stride == 1:
+            else:
                 wt = derived_cached('x3_convbn_image_t', (weight, scale), lambda: ops.pack_conv_weight_x3(
                     (weight.detach() * scale.view(-1, 1, 1, 1)).flip(2, 3).transpose(0, 1).contiguous()))
                 gx = ops.conv_x3_nhwc(g, wt, C, k, 1, k // 2, amax=amax)
-            else:
-                taps = ([1], [2, 0])                      # filter taps seen by even / odd input coordinates, at offsets 0 (, + 1)
-
-                def sub_images():
-                    ws = weight.detach() * scale.view(-1, 1, 1, 1)
-                    return [ops.pack_conv_weight_x3(ws[:, :, taps[py]][:, :, :, taps[px]].transpose(0, 1).contiguous())
-                            for py in (0, 1) for px in (0, 1)]
-                imgs = derived_cached('x3_convbn_image_t_s2', (weight, scale), sub_images)
-                gp = F.pad(g, (0, 0, 0, 1, 0, 1))          # (B, OH + 1, OW + 1, N): zero last row / column
-                gx = torch.empty_like(x)
-                for py in (0, 1):
-                    for px in (0, 1):
-                        o = ops.conv_x3_nhwc(gp, imgs[2 * py + px], C, (len(taps[py]), len(taps[px])), 1, 0, amax=amax)
-                        gx[:, py::2, px::2] = o[:, :OH, :OW]
         if ctx.needs_input_grad[1]:
             if k == 1:
                 xs = x if stride == 1 else x[:, ::stride, ::stride].contiguous()
                 gw = ops.wgrad_x3(g2, xs.view(-1, C), amax=amax).view(N, C, 1, 1)
-            elif stride == 2:
-                xp = F.pad(x, (0, 0, 1, 1, 1, 1))
-                gr = F.pad(g, (0, 0, 0, 1, 0, 1)).view(-1, N)      # rows of the (B, OH + 1, OW + 1) grid the sub-maps share
-                Mp = gr.shape[0]
-                ph = [[xp[:, py::2, px::2].contiguous().view(-1, C) for px in (0, 1)] for py in (0, 1)]
-                gw = torch.empty((N, k, k, C), dtype=torch.float32, device=x.device)
-                for ky in range(3):
-                    for kx in range(3):
-                        off = (ky >> 1) * (OW + 1) + (kx >> 1)
-                        gw[:, ky, kx, :] = ops.wgrad_x3(gr[:Mp - off], ph[ky & 1][kx & 1][off:], amax=amax)
-                gw = gw.permute(0, 3, 1, 2)
             else:
                 # both maps zero-padded by one pixel: a filter tap is a constant row offset between two row-major matrices
                 xr = F.pad(x, (0, 0, 1, 1, 1, 1)).view(-1, C)
@@ -649,26 +614,16 @@ def _x3_convbn_ok(conv, bn):
             and conv.groups == 1 and tuple(conv.dilation) == (1, 1) and getattr(conv, 'padding_mode', 'zeros') == 'zeros'
             and conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0 and conv.weight.requires_grad
             and ((k == (1, 1) and s in ((1, 1), (2, 2)) and tuple(conv.padding) == (0, 0))
-                 or (k == (3, 3) and s in ((1, 1), (2, 2)) and tuple(conv.padding) == (1, 1))))
-
-
-# the first block's 3 x 3 / stride-2 convolution on `_X3ConvBnFn` too (four sub-filter convolutions for grad-input, parity-class
-# sub-maps for grad-weight). OFF by default: correct (tests/test_x3s_gpu.py) but 2 % SLOWER per configs[2] step than MIOpen's kernels
-# on the channel-last views (85.0 vs 86.8 images/s) -- the padding / parity-class copies and 13 small launches cost more than the one
-# convolution saves (profiles/r6_resnet_stage_train_ab.txt)
-_X3_RESNET_S2 = _os.environ.get('CGG_X3_RESNET_S2', '0') == '1'
-
-
-def _conv2_s2_on_x3(blk, H, W):
-    return _X3_RESNET_S2 and tuple(blk.conv2.stride) == (2, 2) and H % 2 == 0 and W % 2 == 0
+                 or (k == (3, 3) and s == (1, 1) and tuple(conv.padding) == (1, 1))))
 
 
 def x3_resnet_stage_ok(stage, x):
     """PARITY-mode training of a ResNet stage of Bottlenecks with frozen BatchNorm on channel-last maps and own kernels
-    (`_X3ConvBnFn`; a 3 x 3 / stride-2 convolution -- the first block's -- needs even H, W, else it stays a library call on the
-    channel-last view -- which is also the default, CGG_X3_RESNET_S2=1 moves it). x: the stage's channel-last f32 input (B, H, W, C)."""
+    (`_X3ConvBnFn`; a 3 x 3 / stride-2 convolution -- the first block's -- stays a library call on the channel-last view: moving it
+    to four sub-filter x3 convolutions measured 2 % slower per configs[2] step, profiles/r6_resnet_stage_train_ab.txt).
+    x: the stage's channel-last f32 input (B, H, W, C)."""
     from .backbones import Bottleneck
-    if not (_X3_RESNET_TRAIN and _X3_TRAIN and _X3_WGRAD and x3_enabled() and torch.is_grad_enabled() and x.is_cuda
+    if not (_X3_RESNET_TRAIN and _X3_TRAIN and x3_enabled() and torch.is_grad_enabled() and x.is_cuda
             and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
         return False
     B, H, W, C = x.shape
@@ -681,7 +636,7 @@ def x3_resnet_stage_ok(stage, x):
                 return False
             pairs.append((blk.downsample[0], blk.downsample[1]))
         s2 = tuple(blk.conv2.stride)
-        if s2 == (1, 1) or _conv2_s2_on_x3(blk, H, W):
+        if s2 == (1, 1):
             pairs.append((blk.conv2, blk.bn2))
         elif not (isinstance(blk.bn2, torch.nn.BatchNorm2d) and not blk.bn2.training):
             return False
@@ -713,18 +668,19 @@ def resnet_stage_x3_train(stage, x, tap=None):
     for blk in stage:
         identity = x if blk.downsample is None else cb(x, blk.downsample[0], blk.downsample[1], False)
         y = cb(x, blk.conv1, blk.bn1, True)
-        if tuple(blk.conv2.stride) == (1, 1) or _conv2_s2_on_x3(blk, y.shape[1], y.shape[2]):
+        if tuple(blk.conv2.stride) == (1, 1):
             y = cb(y, blk.conv2, blk.bn2, True)
         else:
-            # (3 x 3 / stride 2: grad-input would be four sub-filter convolutions; the library's channel-last kernels on the views)
+            # (3 x 3 / stride 2: the library's channel-last kernels on the views)
             y = torch.relu(blk.bn2(blk.conv2(y.permute(0, 3, 1, 2)))).permute(0, 2, 3, 1).contiguous()
             tap(y)
         x = cb(y, blk.conv3, blk.bn3, True, identity)
     return x
 
 
-_X3_FPN_ROWS_BF16 = _os.environ.get('CGG_X3_FPN_ROWS_BF16', '1') != '0'      # ... also in throughput (bf16) mode: 170.4 -> 166.0 ms per configs[2] step
-_X3_FPN_ROWS = _os.environ.get('CGG_X3_FPN_ROWS', '1') != '0'      # parity-mode training: the finest FPN level channel-last on own kernels (A/B)
+# parity-mode training: the finest FPN level channel-last on own kernels (0: the module path; tests/test_env_switches_gpu.py).
+# Throughput (bf16) mode takes the same level: 170.4 -> 166.0 ms per configs[2] step.
+_X3_FPN_ROWS = _os.environ.get('CGG_X3_FPN_ROWS', '1') != '0'
 
 
 class _NchwToRowsFn(torch.autograd.Function):
@@ -800,13 +756,10 @@ class _X3FpnLevelFn(torch.autograd.Function):
         N = wc.shape[0]
         gp = ops.zero_border_map(B, H, W, N, cur.device)
         _, dg2, db2, _ = ops.group_norm_nhwc_backward(y2, y3, g3.contiguous(), stats2, g2, groups, eps2, True, (H, W), dx_padded=gp)
-        amax = ops.absmax(gp.view(-1, N)) if _X3_GSCALE else None
+        amax = ops.absmax(gp.view(-1, N))
         wt = derived_cached('x3_conv_image_dgrad', (wc,),
                             lambda: ops.pack_conv_weight_x3(wc.detach().flip(2, 3).transpose(0, 1).contiguous()))
-        if amax is not None:
-            gy1 = ops.conv_x3_nhwc(gp, wt, C, 3, 1, 0, amax=amax)
-        else:
-            gy1 = ops.conv_x3s_nhwc(ops.x3a_encode(gp), wt, C, 3, 1, 0, None, out_split=False)
+        gy1 = ops.conv_x3_nhwc(gp, wt, C, 3, 1, 0, amax=amax)
         xr, gr = y1p.view(-1, C), gp.view(-1, N)
         Mp = xr.shape[0]
         lo_, hi_ = W + 3, Mp - (W + 3)                    # rows outside are border rows: grad_output is zero there
@@ -844,7 +797,7 @@ def input_level_x3_train(cm, feat):
     from . import ops
     conv = cm.conv
     gn = getattr(cm, cm.norm_name, None) if cm.norm_name else None
-    if not (_X3_INPUT_ROWS and _X3_TRAIN and _X3_WGRAD and x3_enabled() and torch.is_grad_enabled() and feat.is_cuda
+    if not (_X3_INPUT_ROWS and _X3_TRAIN and x3_enabled() and torch.is_grad_enabled() and feat.is_cuda
             and feat.dim() == 4 and feat.dtype == torch.float32 and cm.activate is None and isinstance(gn, nn.GroupNorm)
             and gn.num_groups * 8 == conv.out_channels == gn.num_channels and gn.affine
             and tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0)
@@ -867,8 +820,8 @@ def x3_fpn_level_ok(pd, x, lo_hw):
     """PARITY-mode training of the pixel decoder's single FPN level (lateral 1 x 1 + GN, + up-sample, 3 x 3 + GN + ReLU, mask-feature
     1 x 1) on channel-last rows and own kernels: `_X3FpnLevelFn` + `_X3LinearFn`s."""
     import torch.nn as nn
-    bf = is_bf16() and _X3 and _X3_FPN_ROWS_BF16      # throughput mode may take the (more accurate) f32-class level too
-    if not (_X3_FPN_ROWS and _X3_TRAIN and _X3A and _X3_WGRAD and (x3_enabled() or bf) and torch.is_grad_enabled() and x.is_cuda
+    bf = is_bf16() and _X3      # throughput mode may take the (more accurate) f32-class level too
+    if not (_X3_FPN_ROWS and _X3_TRAIN and _X3A and (x3_enabled() or bf) and torch.is_grad_enabled() and x.is_cuda
             and x.dtype in ((torch.float32, torch.bfloat16) if bf else (torch.float32,)) and x.dim() == 4 and len(pd.lateral_convs) == 1):
         return False
     lat, outc, mf = pd.lateral_convs[0], pd.output_convs[0], pd.mask_feature
@@ -962,8 +915,6 @@ def conv3x3_x3_train(x, conv):
 _X3_MAX_BYTES = 0xFFFFFF00          # operand span the x3 kernels can address (32-bit buffer descriptors); larger -> library path
 X3_TRAIN_ROWS = 8192               # rows from which parity-mode training linears run on the x3 GEMM (CGG_X3_TRAIN=0 disables)
 _X3_TRAIN = _os.environ.get('CGG_X3_TRAIN', '1') != '0'
-_X3_WGRAD = _os.environ.get('CGG_X3_WGRAD', '1') != '0'
-_X3_GSCALE = _os.environ.get('CGG_X3_GSCALE', '1') != '0'          # per-tensor pre-scale of grad_output in the x3 training kernels
 
 
 def x3_train_linear_ok(x, weight):
@@ -994,15 +945,14 @@ class ParityLinear(torch.nn.Linear):
         return F.linear(x, w, self.bias)
 
 
-SPLITK_WGRAD_ROWS = 32768          # rows from which the training linears use `_SplitKLinearFn` (CGG_SPLITK_WGRAD=0 disables)
-_SPLITK_WGRAD = _os.environ.get('CGG_SPLITK_WGRAD', '1') != '0'      # read once, like every switch of this module
+SPLITK_WGRAD_ROWS = 32768          # rows from which the training linears use `_SplitKLinearFn`
 
 
 def linear_bf16_train(x, weight, bias=None):
     """bf16 `F.linear` for the training step (returns bf16): split-K weight gradient for huge row counts, autocast otherwise."""
     import torch.nn.functional as F
     rows = x.numel() // x.shape[-1]
-    if rows >= SPLITK_WGRAD_ROWS and weight.requires_grad and _SPLITK_WGRAD:
+    if rows >= SPLITK_WGRAD_ROWS and weight.requires_grad:
         return _SplitKLinearFn.apply(x, weight, bias)
     with torch.autocast(device_type='cuda', dtype=torch.bfloat16):
         return F.linear(x, weight, bias)

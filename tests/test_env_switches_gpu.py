@@ -10,8 +10,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-SWITCHES = ['', 'CGG_X3=0', 'CGG_X3A=0', 'CGG_X3_STEM=0', 'CGG_FUSED_TAIL=0', 'CGG_MSDA_GENERIC=1', 'CGG_MERGED_PROJ=0', 'CGG_TAIL_WAVES=4',
-            'CGG_EXACT_F32_LOGITS=0', 'CGG_XATTN_X3=0', 'CGG_X3_GSCALE=0']
+SWITCHES = ['', 'CGG_X3=0', 'CGG_X3A=0', 'CGG_X3_STEM=0', 'CGG_FUSED_TAIL=0', 'CGG_MSDA_GENERIC=1', 'CGG_MERGED_PROJ=0',
+            'CGG_EXACT_F32_LOGITS=0', 'CGG_XATTN_X3=0']
 
 
 @pytest.mark.parametrize('switch', SWITCHES)
@@ -27,7 +27,7 @@ def test_parity_mode_switch(dev, switch):
 
 # the training-side switches (none was ever exercised off-default): each alternative path must give the oracle's
 # losses and gradients too. One parity-mode forward_train + backward at batch 4 x 512^2 per switch (tests/env_switch_train_worker.py).
-TRAIN_SWITCHES = ['', 'CGG_X3_TRAIN=0', 'CGG_X3_WGRAD=0', 'CGG_X3_LAYER_NODES=0', 'CGG_X3_FPN_ROWS=0', 'CGG_MSDA_BWD_2S=0',
+TRAIN_SWITCHES = ['', 'CGG_X3_TRAIN=0', 'CGG_X3_LAYER_NODES=0', 'CGG_X3_FPN_ROWS=0', 'CGG_MSDA_BWD_2S=0',
                   'CGG_X3_GENERATOR=0', 'CGG_XATTN_X3_TRAIN=0', 'CGG_FUSED_TRAIN_LN=0', 'CGG_FUSED_TRAIN_MSDA=0', 'CGG_X3A=0', 'CGG_POINT_LOGITS_X3=0', 'CGG_XATTN_X3_BWD=0']
 
 
