@@ -227,14 +227,16 @@ def stream_ptr(device=None):
 
 
 def dev_ptr(t, name='tensor', dtype=None):
-    """data_ptr of a contiguous ROCm tensor (None passes through as NULL)."""
+    """data_ptr of a contiguous ROCm tensor (None passes through as NULL). `dtype` is one torch dtype or a tuple of them; it is
+    tested BEFORE the device, so a tensor of a type the callee cannot read is refused by that name wherever it lives."""
     if t is None:
         return None
+    if dtype is not None and t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+        want = ' | '.join(str(d) for d in dtype) if isinstance(dtype, tuple) else str(dtype)
+        raise CggError(f'{name} must be {want} (got {t.dtype})')
     if not t.is_cuda:
         raise CggError(f'{name} must live on a ROCm device (got {t.device}); the CGG hot path has '
                        'no CPU implementation outside /oracle')
     if not t.is_contiguous():
         raise CggError(f'{name} must be contiguous')
-    if dtype is not None and t.dtype != dtype:
-        raise CggError(f'{name} must be {dtype} (got {t.dtype})')
     return ctypes.c_void_p(t.data_ptr())

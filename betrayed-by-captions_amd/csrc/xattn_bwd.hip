@@ -41,8 +41,17 @@ __device__ __forceinline__ xb_s16x4 xb_cvt4(float a, float b, float c, float d) 
 // split into two f16 pieces of (power-of-two scale) x value and the group becomes THREE v_mfma_f32_32x32x8_f16 (al bh + ah bl + ah bh):
 // 60 MFMAs of 32 cycles per (32 queries x 32 keys) instead of 80 f32 MFMAs of 64. Pre-scales: 2^4 for scale q, K, V (unit-scale
 // rows, like every x3 activation operand); s_g = 2^(9 - floor(log2 max |dO|)) for dO (a gradient: per-tensor scale from a device
-// scalar, x3.h "per-tensor pre-scale"); 2^14 for P (<= 1); s_g / 64 for dS = P (dP - delta) (|dS| <= 4000 max |dO| keeps it inside
-// f16). All are powers of two: the accumulators are un-scaled exactly (scores before the exponential, gradients when stored).
+// scalar, x3.h "per-tensor pre-scale"); 2^14 for P (<= 1). dS = P (dP - delta) has no a-priori magnitude: |dP| reaches max |dO| times
+// the L1 norm of a key's V row over the head's 32 channels, so a scale tied to max |dO| alone (s_g / 64, round 6) sent V entries of a
+// few hundred to inf with no flag. Its scale s_s is therefore taken from a bound the kernel computes itself:
+//     |dS[q][key]| <= max |dO| * max_key ||V_key||_1 + max_q |delta_q|
+// with the first maximum over the 32 keys a wave holds of the current 128-key tile (one add-reduction over the V registers it has
+// loaded anyway) and the second over the <= 128 queries (delta is in LDS). s_s = 2^(14 - floor(log2 bound)) puts the bound in
+// [2^14, 2^15), a factor two inside f16. dK / dV accumulate per key tile and are un-scaled per tile; the dQ accumulators live across
+// key tiles, so s_s only ever DECREASES along a wave's tiles and the accumulators are multiplied by the (power-of-two) ratio when it
+// does. All scales are powers of two: the accumulators are un-scaled exactly (scores before the exponential, gradients when stored).
+// GUARANTEE: for scale q, K, V inside the x3 operand range |a| < 4094 (x3.h) and finite grad_out, no f16 piece overflows; the
+// gradients are finite and f32-class (tests/test_gates_gpu.py drives V and grad_out across that range).
 typedef __attribute__((ext_vector_type(4))) _Float16 xb_h4;
 struct XbX3 {
   xb_h4 h, l;
@@ -56,6 +65,20 @@ __device__ __forceinline__ XbX3 xb_split4(float a, float b, float c, float d, fl
   r.h = __builtin_convertvector(v, xb_h4);                                  // RNE
   r.l = __builtin_convertvector(v - __builtin_convertvector(r.h, f32x4), xb_h4);   // the residual is exact in f32
   return r;
+}
+__device__ __forceinline__ float xb_wave_max(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+// the dS pre-scale for a bound on |dS|: 2^(14 - floor(log2 bound)); a zero / denormal / non-finite bound keeps 1
+__device__ __forceinline__ float xb_ds_scale(float bound) {
+  const uint32_t b = __builtin_bit_cast(uint32_t, bound);
+  const int e = (int)((b >> 23) & 0xffu);
+  if (e == 0 || e == 255) return 1.f;
+  int se = 14 - (e - 127);
+  se = se > 100 ? 100 : (se < -100 ? -100 : se);
+  return __builtin_bit_cast(float, (uint32_t)(se + 127) << 23);
 }
 __device__ __forceinline__ f32x16 xb_mfma3(const XbX3& a, const XbX3& b, f32x16 acc) {
   acc = __builtin_amdgcn_mfma_f32_32x32x8f16(a.l, b.h, acc, 0, 0, 0);
@@ -72,10 +95,11 @@ __global__ __launch_bounds__(256) void cgg_xattn_bwd_kernel(
     float scale, const float* __restrict__ gout_amax) {
   constexpr int D = 32;
   constexpr bool BF = MODE == 1, X3 = MODE == 2;
-  // x3 pre-scales (see above); sg from the device scalar max |dO|
-  const float sg = X3 ? cgg_x3_scale_from_amax(*gout_amax) : 1.f;
+  // x3 pre-scales (see above); sg from the device scalar max |dO|, ss (dS) per key tile from the kernel's own bound
+  const float gmax = X3 ? *gout_amax : 0.f;
+  const float sg = X3 ? cgg_x3_scale_from_amax(gmax) : 1.f;
   constexpr float SA = CGG_X3_ASCALE, SP = 16384.f;
-  const float ss = sg * (1.f / 64.f);
+  float ss = 0x1p100f;                                  // scale of the dQ accumulators: only ever lowered (they start at zero)
   const int chunk = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi = lane >> 5;
@@ -120,6 +144,8 @@ __global__ __launch_bounds__(256) void cgg_xattn_bwd_kernel(
     Ds[tid] = dl;
   }
   __syncthreads();
+  float dmax = 0.f;                                    // x3: max_q |delta_q|, the second term of the dS bound
+  if constexpr (X3) dmax = xb_wave_max(fmaxf(fabsf(Ds[lane]), fabsf(Ds[lane + 64])));
 
   f32x16 dq[4];
 #pragma unroll
@@ -158,6 +184,18 @@ __global__ __launch_bounds__(256) void cgg_xattn_bwd_kernel(
     // x3: the key tile's operands split once for the <= 4 query tiles (K / V rows as B operands, K columns for the dQ contraction)
     XbX3 kx3[4], vx3[4], kc3[4];
     if constexpr (X3) {
+      // the dS scale of this key tile: ||V_key||_1 over the head (the two half rows of a key sit in lanes j and j + 32)
+      float l1 = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) l1 += fabsf(vf[e]);
+      l1 += __shfl_xor(l1, 32);
+      const float st = xb_ds_scale(gmax * xb_wave_max(l1) + dmax);
+      if (st < ss) {                                    // wave-uniform
+        const float down = st / ss;                     // a power of two <= 1/2
+#pragma unroll
+        for (int t = 0; t < 4; ++t) dq[t] = dq[t] * down;
+        ss = st;
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         kx3[t] = xb_split4(kf[4 * t], kf[4 * t + 1], kf[4 * t + 2], kf[4 * t + 3], SA);

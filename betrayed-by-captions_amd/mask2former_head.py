@@ -180,13 +180,16 @@ class LazyMasks:
 
 class _MaskLogitsFn(torch.autograd.Function):
     """einsum('bqc,bchw->bqhw') on the HIP MFMA kernels, forward (`cgg_mask_logits` on the packed feature) and backward
-    (`cgg_mask_logits_backward`: the two transposed contractions; shapes outside the kernels' limits keep torch.einsum)."""
+    (`cgg_mask_logits_backward`: the two transposed contractions; shapes outside the kernels' limits keep torch.einsum, in either
+    direction -- `ops.mask_logits_ok` / `ops.mask_logits_backward_ok`)."""
 
     @staticmethod
     def forward(ctx, embed, feat, packed):
         embed = embed.contiguous()
         ctx.save_for_backward(embed, feat)
         ctx.split = packed.lo is not None
+        if not ops.mask_logits_ok(embed, packed):
+            return torch.einsum('bqc,bchw->bqhw', embed, feat.to(embed.dtype))
         out = torch.cat([ops.mask_logits(embed[:, s:s + 256].contiguous(), packed, want_logits=True)[0]
                          for s in range(0, embed.shape[1], 256)], 1) if embed.shape[1] > 256 else \
             ops.mask_logits(embed, packed, want_logits=True)[0]
@@ -997,7 +1000,7 @@ class Mask2FormerHeadOpen(nn.Module):
                 all_pts = pts.permute(1, 0, 2, 3).reshape(B, n * P, 2)
                 pred_pts = torch.empty((n, B, Q, P), dtype=torch.float32, device=dev)     # (no stack: each product lands in its slab)
                 if POINT_LOGITS_X3 and runtime.x3_enabled() and ops.point_sample_nhwc_x3_ok(nhwc, all_pts, n) \
-                        and all(m.mask_embed.shape[-1] == nhwc.shape[-1] for m in all_mask_preds):
+                        and all(m.mask_embed.shape[-1] == nhwc.shape[-1] and m.mask_embed.shape[1] <= 256 for m in all_mask_preds):
                     # parity mode: the sampler writes the samples as x3 images (no (B, n P, C) f32 tensor: 2 GB at configs[2]) and
                     # each layer's (Q x C) x (C x P) product is the f32-class MFMA einsum kernel on them (the f32 library bmm ran
                     # these at 44 TF/s: 2.3 ms per step)

@@ -52,6 +52,19 @@ def _int_array(vals):
     return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+_F32_BF16 = (torch.float32, torch.bfloat16)
+
+
+def _f32_bf16_tag(t, name):
+    """CGG_F32 / CGG_BF16 for an operand whose element type crosses the C ABI as a tag (None: CGG_F32 beside a NULL pointer). Any
+    other dtype raises, naming the argument, before a pointer is taken: the callee would read the buffer as one of the two."""
+    if t is None or t.dtype == torch.float32:
+        return CGG_F32
+    if t.dtype == torch.bfloat16:
+        return CGG_BF16
+    raise CggError(f'{name} must be torch.float32 | torch.bfloat16 (got {t.dtype})')
+
+
 # ------------------------------------------------------------------------------------------------
 # K1/K2  MSDeformAttn core   ([3P] mmcv MultiScaleDeformableAttnFunction)
 # ------------------------------------------------------------------------------------------------
@@ -68,12 +81,10 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, a
     """value (B,Nv,H,D) f32|bf16; spatial_shapes (L,2) int64; level_start_index (L,) int64;
     sampling_locations (B,Nq,H,L,P,2) f32; attention_weights (B,Nq,H,L,P) f32 -> (B,Nq,H*D) f32."""
     B, Nv, H, D, L, Nq, P = _msda_dims(value, sampling_locations)
-    vdt = CGG_BF16 if value.dtype == torch.bfloat16 else CGG_F32
-    if value.dtype not in (torch.float32, torch.bfloat16):
-        raise CggError(f'msda_forward: value dtype {value.dtype}')
+    vdt = _f32_bf16_tag(value, 'msda_forward: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
     rc = _lib_().cgg_msda_forward(
-        dev_ptr(value, 'value'), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
+        dev_ptr(value, 'value', _F32_BF16), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
         dev_ptr(level_start_index, 'level_start_index', torch.int64),
         dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
         dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(out), B, Nv, H, D, L,
@@ -85,12 +96,12 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, a
 def msda_forward_hostlevels(value, level_hw, level_start, sampling_locations, attention_weights):
     """Same op, level table as python lists (no D2H; legal under hipGraph capture)."""
     B, Nv, H, D, L, Nq, P = _msda_dims(value, sampling_locations)
-    vdt = CGG_BF16 if value.dtype == torch.bfloat16 else CGG_F32
+    vdt = _f32_bf16_tag(value, 'msda_forward_hostlevels: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
     hw = _int_array([v for pair in level_hw for v in pair])
     st = _int_array(level_start)
     rc = _lib_().cgg_msda_forward_hostlevels(
-        dev_ptr(value, 'value'), hw, st, dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
+        dev_ptr(value, 'value', _F32_BF16), hw, st, dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
         dev_ptr(attention_weights, 'attention_weights', torch.float32), None, 0, dev_ptr(out), B, Nv,
         H, D, L, Nq, P, vdt, 0, stream_ptr(value.device))
     check(rc, 'cgg_msda_forward_hostlevels')
@@ -104,7 +115,7 @@ def msda_forward_fused(value, level_hw, level_start, offs_logits, ref_points, nu
     Bq, Nq, ld = offs_logits.shape
     L = len(level_start)
     P = int(num_points)
-    vdt = CGG_BF16 if value.dtype == torch.bfloat16 else CGG_F32
+    vdt = _f32_bf16_tag(value, 'msda_forward_fused: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
     hw = _int_array([v for pair in level_hw for v in pair])
     st = _int_array(level_start)
@@ -119,7 +130,7 @@ def msda_forward_fused(value, level_hw, level_start, offs_logits, ref_points, nu
         return out
     with _timed('msda_fused'):
         rc = _lib_().cgg_msda_forward_hostlevels(
-            dev_ptr(value, 'value'), hw, st, dev_ptr(offs_logits, 'offs_logits', torch.float32), None,
+            dev_ptr(value, 'value', _F32_BF16), hw, st, dev_ptr(offs_logits, 'offs_logits', torch.float32), None,
             dev_ptr(ref_points, 'ref_points', torch.float32), ld, dev_ptr(out), B, Nv, H, D, L, Nq, P, vdt,
             1, stream_ptr(value.device))
     check(rc, 'cgg_msda_forward_hostlevels(fused)')
@@ -280,14 +291,18 @@ class MultiScaleDeformableAttnFunction(torch.autograd.Function):
                 attention_weights, im2col_step=64):
         ctx.save_for_backward(value, sampling_locations, attention_weights)
         ctx.levels = msda_read_levels(value_spatial_shapes, value_level_start_index, value.shape[1])
-        return msda_forward_hostlevels(value.contiguous(), ctx.levels[0], ctx.levels[1], sampling_locations.contiguous(),
-                                       attention_weights.contiguous())
+        # mmcv's op takes half and double values too; the kernels read f32 | bf16 only, so any other float type is computed on an
+        # f32 copy and the output returned in value's own type (backward upcasts likewise and casts grad_value back)
+        v = value if value.dtype in _F32_BF16 else value.float()
+        out = msda_forward_hostlevels(v.contiguous(), ctx.levels[0], ctx.levels[1], sampling_locations.contiguous(),
+                                      attention_weights.contiguous())
+        return out if v is value else out.to(value.dtype)
 
     @staticmethod
     def backward(ctx, grad_output):
         value, loc, attw = ctx.saved_tensors
         gv, gl, gw = msda_backward_hostlevels(value.contiguous().float(), ctx.levels[0], ctx.levels[1], loc.contiguous(),
-                                              attw.contiguous(), grad_output.contiguous())
+                                              attw.contiguous(), grad_output.contiguous().float())
         return gv.to(value.dtype), None, None, gl, gw, None
 
 
@@ -419,6 +434,12 @@ def mask_logits(embed, packed, want_logits=True, want_bits=False, out=None):
                                      stream_ptr(embed.device))
     check(rc, 'cgg_mask_logits')
     return out, bits
+
+
+def mask_logits_ok(embed, packed):
+    """operands `mask_logits` runs (its kernels are built for 256 channels; callers keep the torch contraction otherwise)"""
+    return (embed.is_cuda and embed.dtype == torch.float32 and embed.dim() == 3 and embed.shape[-1] == 256 and packed.C == 256
+            and embed.shape[0] == packed.B)
 
 
 def mask_logits_launches(Q, split):
@@ -995,10 +1016,10 @@ def add_layernorm_stream(a, b, gamma, beta, eps=1e-5, pos=None, want_f32=True, w
     y32 = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_f32 else None
     y16 = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if want_bf16 else None
     yp16 = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if want_pos else None
-    adt = CGG_BF16 if a.dtype == torch.bfloat16 else CGG_F32
-    bdt = CGG_BF16 if (b is not None and b.dtype == torch.bfloat16) else CGG_F32
+    adt = _f32_bf16_tag(a, 'add_layernorm_stream: a')
+    bdt = _f32_bf16_tag(b, 'add_layernorm_stream: b')
     rc = _lib_().cgg_add_layernorm_ex(
-        dev_ptr(a, 'a'), adt, dev_ptr(b, 'b'), bdt, dev_ptr(gamma, 'gamma', torch.float32),
+        dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32),
         dev_ptr(beta, 'beta', torch.float32), dev_ptr(pos, 'pos', torch.float32),
         pos.shape[0] if pos is not None else 0, dev_ptr(y32), dev_ptr(y16), dev_ptr(yp16), rows, N, float(eps),
         stream_ptr(a.device))
@@ -1172,16 +1193,16 @@ def add_layernorm_backward(dy, a, b, gamma, eps, want_bf16=False, dy16a=None, dy
     the pre-scale of the x3 contractions that consume dx as grad_output (no `absmax` pass)."""
     N = a.shape[-1]
     rows = a.numel() // N
+    bdt = _f32_bf16_tag(b, 'add_layernorm_backward: b')
     dx = torch.empty(a.shape, dtype=torch.float32, device=a.device)
     dx16 = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if want_bf16 else None
     nb = _lib_().cgg_add_layernorm_backward_partials(rows)
     partial = torch.empty((nb, 2 * N), dtype=torch.float32, device=a.device)
-    bdt = CGG_BF16 if (b is not None and b.dtype == torch.bfloat16) else CGG_F32
     if want_amax:
         amax = torch.empty(1, dtype=torch.float32, device=a.device)
         rc = _lib_().cgg_add_layernorm_backward_amax(dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
                                                      dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32),
-                                                     dev_ptr(b, 'b'), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
+                                                     dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
                                                      dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), dev_ptr(amax), rows, N,
                                                      stream_ptr(a.device))
         check(rc, 'cgg_add_layernorm_backward_amax')
@@ -1189,7 +1210,7 @@ def add_layernorm_backward(dy, a, b, gamma, eps, want_bf16=False, dy16a=None, dy
         return dx, dx16, sums[:N], sums[N:], amax
     rc = _lib_().cgg_add_layernorm_backward(dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
                                             dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32),
-                                            dev_ptr(b, 'b'), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
+                                            dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
                                             dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), rows, N, stream_ptr(a.device))
     check(rc, 'cgg_add_layernorm_backward')
     sums = partial.sum(0)
@@ -1253,10 +1274,10 @@ def add_layernorm_kv(a, b, gamma, beta, eps, shift, pos, level_start, want_f32=T
     y32 = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_f32 else None
     m16 = torch.empty((B * S, N), dtype=torch.bfloat16, device=a.device)
     mp16 = torch.empty((B * S, N), dtype=torch.bfloat16, device=a.device)
-    adt = CGG_BF16 if a.dtype == torch.bfloat16 else CGG_F32
-    bdt = CGG_BF16 if (b is not None and b.dtype == torch.bfloat16) else CGG_F32
+    adt = _f32_bf16_tag(a, 'add_layernorm_kv: a')
+    bdt = _f32_bf16_tag(b, 'add_layernorm_kv: b')
     rc = _lib_().cgg_add_layernorm_kv(
-        dev_ptr(a, 'a'), adt, dev_ptr(b, 'b'), bdt, dev_ptr(gamma, 'gamma', torch.float32),
+        dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32),
         dev_ptr(beta, 'beta', torch.float32), dev_ptr(shift, 'shift', torch.float32), dev_ptr(pos, 'pos', torch.float32),
         S, _int_array(level_start), len(level_start), dev_ptr(y32), dev_ptr(m16), dev_ptr(mp16), B * S, N, float(eps),
         stream_ptr(a.device))
@@ -2426,9 +2447,10 @@ def point_sample_nhwc(feat, points):
 
 
 def point_sample_nhwc_x3_ok(feat, points, groups):
-    """shapes `point_sample_nhwc_x3` covers"""
-    return (feat.dim() == 4 and feat.dtype == torch.float32 and feat.is_cuda and feat.is_contiguous() and feat.shape[-1] % 8 == 0
-            and feat.shape[-1] <= 1024 and points.dim() == 3 and points.dtype == torch.float32 and groups > 0
+    """shapes `point_sample_nhwc_x3` covers. The sampler itself packs any C % 8 == 0, but its images have one consumer, `mask_logits`,
+    which is built for C == 256: a feature of another width takes `point_sample_nhwc` + bmm."""
+    return (feat.dim() == 4 and feat.dtype == torch.float32 and feat.is_cuda and feat.is_contiguous() and feat.shape[-1] == 256
+            and points.dim() == 3 and points.dtype == torch.float32 and groups > 0
             and points.shape[1] % groups == 0 and (points.shape[1] // groups) % 32 == 0)
 
 
@@ -2440,7 +2462,7 @@ def point_sample_nhwc_x3(feat, points, groups):
     B, H, W, C = feat.shape
     Pt = points.shape[1]
     if not point_sample_nhwc_x3_ok(feat, points, groups) or tuple(points.shape) != (B, Pt, 2):
-        raise CggError('point_sample_nhwc_x3: feat (B, H, W, C) contiguous float32 (C % 8 == 0), points (B, groups * P, 2) float32 '
+        raise CggError('point_sample_nhwc_x3: feat (B, H, W, C) contiguous float32 (C == 256), points (B, groups * P, 2) float32 '
                        'with P % 32 == 0 expected')
     P = Pt // groups
     pts = points.contiguous()

@@ -775,11 +775,13 @@ class _X3FpnLevelFn(torch.autograd.Function):
 
 def nhwc_to_nchw_train(xn):
     """channel-last (B, H, W, C) f32 under autograd -> contiguous (B, C, H, W) (tiled transpose kernel both ways); the channel-last
-    original rides along as `_cgg_rows` (B, H W, C) for consumers that read rows under autograd."""
+    original rides along as `_cgg_rows` (B, H W, C) for consumers that read rows under autograd, with both version counters: valid only
+    while neither tensor is written in place (`input_level_x3_train` checks them, as `handed_nhwc` does for `hand_nhwc`)."""
     B, H, W, C = xn.shape
     rows = xn.reshape(B, H * W, C)
     out = _RowsToNchwFn.apply(rows, (H, W))
     out._cgg_rows = rows
+    out._cgg_rows_versions = (out._version, rows._version)
     return out
 
 
@@ -805,7 +807,9 @@ def input_level_x3_train(cm, feat):
         return None
     B, Cin, H, W = feat.shape
     rows = getattr(feat, '_cgg_rows', None)
-    if rows is not None and (tuple(rows.shape) != (B, H * W, Cin) or rows.dtype != torch.float32):
+    # (an in-place edit of either tensor since `nhwc_to_nchw_train` -- a hook that rescales the map, say -- leaves the rows stale)
+    if rows is not None and (tuple(rows.shape) != (B, H * W, Cin) or rows.dtype != torch.float32
+                             or getattr(feat, '_cgg_rows_versions', None) != (feat._version, rows._version)):
         rows = None
     if rows is None:
         nh = handed_nhwc(feat)

@@ -307,7 +307,9 @@ int cgg_masked_xattn_backward(const float* q, const void* kv, const uint32_t* bi
  * contractions of the backward (scores, dP, dV, dK, dQ) as three v_mfma_f32_32x32x8_f16 per four f32 k-steps instead of four
  * v_mfma_f32_32x32x2_f32 -- as accurate as the f32 MFMA form (tests/test_kernels_gpu.py), 2.7 x less matrix-pipe time.
  * grad_out_amax = device scalar max |grad_out| (cgg_absmax_f32): the per-tensor pre-scale of the gradient operands; q, K, V
- * must be unit scale (|value| < 4094) like every x3 activation operand. Same tensors, workspace and limits otherwise. */
+ * must be unit scale (|value| < 4094) like every x3 activation operand; inside that range and for a finite grad_out the
+ * gradients are finite (dS is pre-scaled by a bound the kernel computes from max |grad_out|, the L1 norms of the V rows and
+ * delta -- csrc/xattn_bwd.hip). Same tensors, workspace and limits otherwise. */
 int cgg_masked_xattn_backward_x3(const float* q, const void* kv, const uint32_t* bits, const float* out, const float* lse,
                                  const float* grad_out, const float* grad_out_amax, float* grad_q, void* grad_kv, void* ws, int B,
                                  int Q, int H, int D, int S, float scale, cgg_stream_t stream);

@@ -170,7 +170,10 @@ def main(argv=None):
             it += 1
             if (it % args.log_interval == 0 or it == max_iters) and args.precision == 'fp32' and runtime.x3_enabled():
                 # parity mode's f16 x 3 kernels hold activations up to |a| < 4094 (csrc/x3.h): beyond it the forward turns into
-                # inf / NaN; name the cause once per logging interval instead of letting a NaN loss speak for itself
+                # inf / NaN; name the cause once per logging interval instead of letting a NaN loss speak for itself.
+                # (Inside that range nothing overflows silently: the cross-attention backward, whose dS = P (dP - delta) grows with the
+                # L1 norm of a V row, scales it by a bound the kernel computes itself -- csrc/xattn_bwd.hip -- and returns finite
+                # f32-class gradients for every scale q, K, V with |a| < 4094 and finite grad_out.)
                 from cgg_amd import ops
                 over = torch.tensor([int(bool(ops.x3_overflow_check(device, reset=True)))], device=device)
                 if distributed:
