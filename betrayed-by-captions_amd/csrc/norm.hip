@@ -437,6 +437,25 @@ extern "C" int cgg_group_norm_nhwc_f32_x3a(const float* x, const float* gamma, c
                     (float*)y_x3a, y_bstride, nullptr, pos, nullptr, 0, stream, (float*)yp_x3a, up_src_x3a ? 3 : 1);
 }
 
+// The two statistics passes of cgg_group_norm_nhwc_f32 alone: ws[b][g] = (mean, variance) of the f32 map, by the same kernels and
+// launch geometry (the same bits) -- for a consumer that applies the normalisation itself (csrc/mask_feature_head.hip).
+extern "C" int cgg_group_norm_nhwc_f32_stats(const float* x, void* ws, int B, int HW, int C, int groups, cgg_stream_t stream) {
+  CGG_REQUIRE(x && ws, CGG_EINVAL, "cgg_group_norm_nhwc_f32_stats: null pointer");
+  CGG_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0, CGG_EINVAL, "cgg_group_norm_nhwc_f32_stats: bad sizes");
+  CGG_REQUIRE(C == groups * 8 && groups <= 256 && 256 % groups == 0, CGG_EUNSUPPORTED,
+              "cgg_group_norm_nhwc_f32_stats: needs C / groups == 8 and groups | 256 (C=%d, groups=%d)", C, groups);
+  CGG_REQUIRE(cgg_aligned16(x) && (((uintptr_t)ws) & 7u) == 0, CGG_EALIGN, "cgg_group_norm_nhwc_f32_stats: alignment");
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = (HW + GNH_PIX - 1) / GNH_PIX;
+  const int head = B * groups * 2;
+  hipLaunchKernelGGL(cgg_gn_nhwc_stats_kernel<true>, dim3(nblk, B), dim3(256), 0, s, (const uint4*)x, (float*)ws, HW, groups, GNH_PIX,
+                     head);
+  const float inv_n = 1.f / ((float)HW * 8.f);
+  hipLaunchKernelGGL(cgg_gn_nhwc_reduce_kernel, dim3(B * groups), dim3(64), 0, s, (float*)ws, head, nblk, groups, B, x, HW, inv_n);
+  CGG_CHECK_LAUNCH("cgg_group_norm_nhwc_f32_stats");
+  return CGG_OK;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Backward of the channel-last f32 GroupNorm above (training, parity mode: the FPN level of the pixel decoder kept channel-last --
 // [3P] MSDeformAttnPixelDecoder lateral / output ConvModules behind open_set/models/mask2former_head.py:787; torch's GroupNorm

@@ -590,18 +590,28 @@ class Mask2FormerHeadOpen(nn.Module):
             packed = {p: ops.pack_mask_feature_nhwc(mf, p) for p in uniq}
         return packed[1], [packed[p] if p is not None else None for p in pools]
 
+    @staticmethod
+    def _x3_pools(H4, W4, sizes):
+        """(pool of every decoder level's size against the (H4, W4) mask feature | None, the distinct pools to pack)"""
+        pools = []
+        for h, w in sizes:
+            s = H4 // h
+            pools.append(s if (h * s == H4 and w * s == W4 and s in (2, 4, 8)) else None)
+        return pools, [1] + sorted({p for p in pools if p is not None})
+
     def _finish_encode(self, enc):
         """The tail of `_encode` for a deferred stream encoding: packed (full + pooled) mask feature and K / V."""
         if enc.get('x3a'):
             sizes, memorys = enc['sizes'], enc['memorys']
-            mf = enc['mf'] if 'mf' in enc else self.pixel_decoder.stream_fpn_x3a(*enc['fpn'])
-            H4, W4 = int(mf.shape[1]), int(mf.shape[2])
-            pools = []
-            for h, w in sizes:
-                s = H4 // h
-                pools.append(s if (h * s == H4 and w * s == W4 and s in (2, 4, 8)) else None)
-            uniq = [1] + sorted({p for p in pools if p is not None})
-            packed = dict(zip(uniq, ops.pack_mask_feature_nhwc_x3(mf, uniq)))
+            if 'mf' in enc:
+                mf = enc['mf']
+                pools, uniq = self._x3_pools(int(mf.shape[1]), int(mf.shape[2]), sizes)
+            else:
+                # the pools are known before the FPN runs: its last three kernels become one that writes the images (where it applies)
+                fpn = enc['fpn']
+                pools, uniq = self._x3_pools(int(fpn[1]), int(fpn[2]), sizes)
+                mf = self.pixel_decoder.stream_fpn_x3a(*fpn[:8], pack_pools=uniq)
+            packed = mf if isinstance(mf, dict) else dict(zip(uniq, ops.pack_mask_feature_nhwc_x3(mf, uniq)))
             return dict(stream=True, kvs=self._project_kv_x3a(memorys, sizes), sizes=sizes, packed_full=packed[1],
                         pooled=[packed[p] if p is not None else None for p in pools], mask_features=None)
         kv16, sizes = enc['kv16'], enc['sizes']
@@ -714,21 +724,22 @@ class Mask2FormerHeadOpen(nn.Module):
                 mf, memorys, level_hw = pd.forward_stream_x3(feats, defer_fpn=defer_tail == 2)
                 return dict(stream=True, deferred=True, x3a=True, memorys=memorys, sizes=[level_hw[i] for i in range(L)],
                             **({'fpn': mf} if defer_tail == 2 else {'mf': mf}))
-            mf, memorys, level_hw = pd.forward_stream_x3(feats)
+            # the pools are known before the pixel decoder runs (level i = the i-th coarsest backbone map, `_stream_levels`): its
+            # FPN then ends in one kernel that writes the packed images (`stream_fpn_x3a`, where the fused head applies)
+            fl = list(feats)
+            H4, W4 = int(fl[0].shape[2]), int(fl[0].shape[3])
+            pools, uniq = self._x3_pools(H4, W4, [(int(f.shape[2]), int(f.shape[3]))
+                                                  for f in (fl[pd.num_input_levels - i - 1] for i in range(L))])
+            mf, memorys, level_hw = pd.forward_stream_x3(feats, pack_pools=uniq)
             mask_features = None
-            H4, W4 = int(mf.shape[1]), int(mf.shape[2])
-            pools = []
             x3a_mem = all(ops.is_x3a(m) for m in memorys[:L])
             for i in range(L):
                 h, w = level_hw[i]
                 sizes.append((h, w))
                 if not x3a_mem:
                     mems.append(memorys[i] + self.level_embed.weight[i].view(1, 1, -1))
-                    poss.append(self.decoder_positional_encoding.flat_unpadded(h, w, mf.device))
-                s = H4 // h
-                pools.append(s if (h * s == H4 and w * s == W4 and s in (2, 4, 8)) else None)
-            uniq = [1] + sorted({p for p in pools if p is not None})
-            packed = dict(zip(uniq, ops.pack_mask_feature_nhwc_x3(mf, uniq)))
+                    poss.append(self.decoder_positional_encoding.flat_unpadded(h, w, fl[0].device))
+            packed = mf if isinstance(mf, dict) else dict(zip(uniq, ops.pack_mask_feature_nhwc_x3(mf, uniq)))
             packed_full, pooled = packed[1], [packed[p] if p is not None else None for p in pools]
             if x3a_mem:
                 # round 4: the memories are x3a rows -- ONE LDS-DMA GEMM per level projects the K / V of every decoder layer that

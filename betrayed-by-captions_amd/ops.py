@@ -1362,6 +1362,19 @@ def group_norm_nhwc_x3a(x, gamma, beta, groups, eps, ws, out, relu=False, up=Non
     check(rc, 'cgg_group_norm_nhwc_f32_x3a')
 
 
+def group_norm_nhwc_stats(x, groups, ws):
+    """The statistics passes of `group_norm_nhwc` alone on a channel-last F32 map x (B, HW, C): ws[:B * groups * 2] = (mean,
+    variance) per (b, group), the bits the full call computes. For `mask_feature_head_x3`, which applies the normalisation itself."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise CggError('group_norm_nhwc_stats: x must be a contiguous (B, HW, C) float32 tensor')
+    B, HW, C = x.shape
+    need = _lib_().cgg_group_norm_nhwc_workspace_bytes(B, HW, int(groups))
+    if ws is None or ws.dtype != torch.float32 or ws.numel() * ws.element_size() < need:
+        raise CggError(f'group_norm_nhwc_stats: workspace too small ({need} bytes needed; see group_norm_nhwc_workspace)')
+    check(_lib_().cgg_group_norm_nhwc_f32_stats(dev_ptr(x, 'x', torch.float32), dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups),
+                                                stream_ptr(x.device)), 'cgg_group_norm_nhwc_f32_stats')
+
+
 def zero_border_map(B, H, W, C, device):
     """(B, H + 2, W + 2, C) f32 channel-last map whose one-pixel border is zero and whose interior is uninitialised (four thin fills)."""
     y = torch.empty((B, H + 2, W + 2, C), dtype=torch.float32, device=device)
@@ -1472,6 +1485,84 @@ def pack_mask_feature_nhwc_x3(feat, pools):
                                                    B, C, H, W, stream_ptr(feat.device))
     check(rc, 'cgg_pack_mask_feature_nhwc_f32_x3')
     return outs
+
+
+_MFH_C = 256                                        # the one width csrc/mask_feature_head.hip is built for
+_MFH_W_BYTES = 2 * (_MFH_C // 32) * (_MFH_C // 16) * 64 * 16 + (_MFH_C // 32) * 32 * 4     # cgg_x3_packed_bytes(256, 256)
+
+
+def _mfh_problem(z, ws, gn, weight_x3, bias, pools):
+    """Why `mask_feature_head_x3` does not apply to these operands (None when it does). No native call."""
+    def f32_dev(t, n=None):
+        return (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0
+                and (n is None or t.numel() == n))
+    if not (torch.is_tensor(z) and z.dim() == 4 and f32_dev(z)):
+        return 'z must be a contiguous, 16-byte aligned (B, H, W, C) float32 ROCm tensor'
+    B, H, W, C = (int(s) for s in z.shape)
+    if C != _MFH_C or B < 1 or B > 65535:
+        return f'C={C} (only {_MFH_C} is built) / B={B}'
+    if H < 8 or W < 8 or H % 8 or W % 8:
+        return f'{H}x{W} is not a multiple of the 8 x 8 tile'
+    if not (isinstance(gn, (tuple, list)) and len(gn) == 4):
+        return 'gn must be (gamma, beta, eps, groups)'
+    gamma, beta, _, groups = gn
+    if int(groups) != 32 or not f32_dev(gamma, C) or not f32_dev(beta, C):
+        return 'GroupNorm must have 32 groups and contiguous float32 ROCm gamma / beta of 256'
+    if not (f32_dev(ws) and ws.numel() >= B * 32 * 2):
+        return 'ws must be the float32 GroupNorm workspace (>= B * 32 * 2 floats)'
+    if not (is_x3(weight_x3) and weight_x3.is_cuda and weight_x3.is_contiguous() and weight_x3.data_ptr() % 16 == 0
+            and weight_x3.numel() * weight_x3.element_size() == _MFH_W_BYTES):
+        return 'weight_x3 must be the x3 image of a (256, 256) weight'
+    if bias is not None and not f32_dev(bias, _MFH_C):
+        return 'bias must be a contiguous float32 ROCm tensor of 256'
+    pools = list(pools) if pools is not None else []
+    if not 1 <= len(pools) <= 4 or any(p not in (1, 2, 4, 8) or H % p or W % p for p in pools) or len(set(pools)) != len(pools):
+        return f'pools={pools}: 1 to 4 distinct values out of 1, 2, 4, 8 that divide {H}x{W}'
+    devs = {t.device for t in (z, ws, gamma, beta, weight_x3) + ((bias,) if bias is not None else ())}
+    if len(devs) != 1:
+        return 'operands on different devices'
+    return None
+
+
+def mask_feature_head_x3_ok(z, ws, gn, weight_x3, bias, pools, want_f32=False):
+    """True when `mask_feature_head_x3` takes these operands: C_in = C_out = 256, 32 groups, H and W multiples of 8, pools out of
+    {1, 2, 4, 8}, contiguous 16-byte aligned float32 ROCm tensors. Never raises; anything else goes GroupNorm -> GEMM -> pack."""
+    try:
+        return _mfh_problem(z, ws, gn, weight_x3, bias, pools) is None
+    except Exception:
+        return False
+
+
+def mask_feature_head_x3(z, ws, gn, weight_x3, bias, pools, want_f32=False, cfg=-1):
+    """The pixel decoder's mask-feature head in ONE launch (csrc/mask_feature_head.hip): z (B, H, W, 256) f32 channel-last = the raw
+    3 x 3 output, ws = the GroupNorm workspace whose head holds (mean, variance) per (b, group) (the statistics passes ran),
+    gn = (gamma, beta, eps, groups) -> relu(GN(z)) -> 1 x 1 convolution with `weight_x3` (x3 image of the (256, 256) weight) + bias ->
+    {pool: PackedFeature (hi / lo x3 images)} for each pool in `pools`, bit-identical to `group_norm_nhwc_x3a(relu=True)` ->
+    `runtime.linear_x3s` -> `pack_mask_feature_nhwc_x3`. want_f32: also the f32 mask feature (B, H, W, 256) -> (images, mf)."""
+    why = _mfh_problem(z, ws, gn, weight_x3, bias, pools)
+    if why is not None:
+        raise CggError(f'mask_feature_head_x3: {why}')
+    B, H, W, C = (int(s) for s in z.shape)
+    gamma, beta, eps, groups = gn
+    pools = [int(p) for p in pools]
+    outs, hp, lp = {}, [], []
+    for pool in pools:
+        h, w = H // pool, W // pool
+        hi = torch.empty((B, (h * w + 31) // 32, C // 8, 32, 8), dtype=torch.bfloat16, device=z.device)
+        lo = torch.empty_like(hi)
+        outs[pool] = PackedFeature(hi, lo, B, C, h, w)
+        hp.append(hi.data_ptr())
+        lp.append(lo.data_ptr())
+    mf = torch.empty((B, H, W, C), dtype=torch.float32, device=z.device) if want_f32 else None
+    n = len(pools)
+    with _timed('mask_feature_head_x3', flops=2.0 * B * H * W * C * C, bytes=4.0 * B * H * W * C * (2.4 + (1 if want_f32 else 0)),
+                shape=(B * H * W, C, C)):
+        rc = _lib_().cgg_mask_feature_head_x3_cfg(
+            dev_ptr(z), dev_ptr(ws), dev_ptr(gamma), dev_ptr(beta), float(eps), int(groups), dev_ptr(weight_x3),
+            dev_ptr(bias) if bias is not None else None, (ctypes.c_void_p * n)(*hp), (ctypes.c_void_p * n)(*lp), _int_array(pools), n,
+            dev_ptr(mf) if mf is not None else None, B, H, W, C, C, int(cfg), stream_ptr(z.device))
+    check(rc, 'cgg_mask_feature_head_x3')
+    return (outs, mf) if want_f32 else outs
 
 
 def pack_mask_feature_nhwc_multi(feat, pools):

@@ -951,7 +951,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 and n_cat == 3 * H * attn.num_levels * attn.num_points and (C + n_cat) % 32 == 0
                 and all(m.bias is not None for m in (vp, so, aw)))
 
-    def _forward_stream_x3a(self, feats, defer_fpn=False):
+    def _forward_stream_x3a(self, feats, defer_fpn=False, pack_pools=None):
         """`forward_stream_x3` on x3a rows: the backbone maps arrive as x3a (`ops.X3ATensor`; plain f32 maps are encoded), every
         GEMM-consumed tensor of the stream stays x3a -- GroupNorm / the encoder tail write it, the LDS-DMA GEMMs read it -- and
         only the tensors a non-GEMM kernel gathers from (MSDeformAttn's value / offsets, the mask feature) are f32. The memories
@@ -978,14 +978,16 @@ class MSDeformAttnPixelDecoder(nn.Module):
                                     outp=(srcp, level_start[i] * C) if need_srcp else None)
         src = self._encoder_stream_x3a(src, srcp, pos, ref, level_hw, level_start)
         mems = [ops.as_x3a(src[:, s0:s0 + h * w, :]) for s0, (h, w) in zip(level_start, level_hw)]
-        fpn = (rows(feats[0]), int(feats[0].shape[2]), int(feats[0].shape[3]), src, level_start[-1], N, level_hw[-1], ws)
+        fpn = (rows(feats[0]), int(feats[0].shape[2]), int(feats[0].shape[3]), src, level_start[-1], N, level_hw[-1], ws, pack_pools)
         if defer_fpn:        # pipeline balancing: the FPN (0.75 ms of throughput kernels at configs[1]) runs in the next stage
             return fpn, mems, level_hw
         return self.stream_fpn_x3a(*fpn), mems, level_hw
 
-    def stream_fpn_x3a(self, frows, H4, W4, src, fine_start, N, fine_hw, ws):
+    def stream_fpn_x3a(self, frows, H4, W4, src, fine_start, N, fine_hw, ws, pack_pools=None):
         """FPN of the x3a stream: lateral 1x1 + GN on the stride-4 map, + bilinear up-sample of the finest encoder level, 3x3 + GN +
-        ReLU, mask_feature -> (B, H4, W4, C) f32."""
+        ReLU, mask_feature -> (B, H4, W4, C) f32. With `pack_pools` (the pools of `ops.pack_mask_feature_nhwc_x3` the caller would
+        ask for), where `ops.mask_feature_head_x3_ok` passes: the last GroupNorm's apply pass, the mask_feature GEMM and the pack are
+        ONE launch and the result is {pool: PackedFeature} instead -- the f32 mask feature is never written."""
         C = 256
         B = src.shape[0]
         lat, outc = self.lateral_convs[0], self.output_convs[0]
@@ -998,17 +1000,25 @@ class MSDeformAttnPixelDecoder(nn.Module):
         w3 = runtime.derived_cached('x3_conv_image', (outc.conv.weight,), lambda: ops.pack_conv_weight_x3(outc.conv.weight))
         z = ops.conv_x3s_nhwc(y.view(B, H4, W4, C), w3, C, 3, 1, 1, outc.conv.bias, out_split=False).view(B, H4 * W4, C)
         gn = getattr(outc, outc.norm_name)
+        if pack_pools is not None:
+            wm = self.mask_feature.weight.flatten(1)
+            bm = self.mask_feature.bias.detach() if self.mask_feature.bias is not None else None
+            wk = runtime.derived_cached('x3_image', (wm,), lambda: ops.pack_linear_weight_x3(wm))      # `runtime.linear_x3s`'s image
+            head = (z.view(B, H4, W4, C), ws, (gn.weight, gn.bias, gn.eps, gn.num_groups), wk, bm, list(pack_pools))
+            if ops.mask_feature_head_x3_ok(*head):
+                ops.group_norm_nhwc_stats(z, 32, ws)
+                return ops.mask_feature_head_x3(*head)
         ops.group_norm_nhwc_x3a(z, gn.weight, gn.bias, 32, gn.eps, ws, out=(z, 0, H4 * W4 * C), relu=True)
         mf = runtime.linear_x3s(z.view(B * H4 * W4, C), self.mask_feature.weight.flatten(1), self.mask_feature.bias)
         return mf.view(B, H4, W4, -1)
 
-    def forward_stream_x3(self, feats, defer_fpn=False):
+    def forward_stream_x3(self, feats, defer_fpn=False, pack_pools=None):
         """-> (mask_feature (B, H4, W4, C) f32 channel-last, [memories (B, hw_l, C) f32 low->high res], level sizes). 1x1
         convolutions are x3 GEMMs on the (B*H*W, C) views, the 3x3 output convolution the x3 implicit GEMM, every GroupNorm the
         channel-last kernel on f32 input (the three encoder inputs normalised straight into the (B, N, C) stream, the FPN's
         `cur + up-sample(out)` in the GroupNorm's epilogue)."""
         if runtime.x3a_enabled():
-            return self._forward_stream_x3a(feats, defer_fpn=defer_fpn)
+            return self._forward_stream_x3a(feats, defer_fpn=defer_fpn, pack_pools=pack_pools)
         feats = [ops.x3a_to_f32(f) if ops.is_x3a(f) else f for f in feats]
         B = feats[0].shape[0]
         dev = feats[0].device

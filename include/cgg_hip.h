@@ -652,6 +652,25 @@ int cgg_encoder_layer_tail_x3a(const float* a32, const void* x_x3a, const void* 
                                const float* beta0, float eps0, const void* w1_x3, const float* b1, const void* w2_x3,
                                const float* b2, const float* gamma1, const float* beta1, float eps1, const float* pos,
                                int pos_rows, void* y_x3a, void* yp_x3a, int M, int C, int F, cgg_stream_t stream);
+/* The statistics passes of cgg_group_norm_nhwc_f32 alone: ws (>= cgg_group_norm_nhwc_workspace_bytes) receives (mean, variance) per
+ * (b, group) at its head, exactly as the full call leaves them; nothing is normalised (the consumer applies it: below). */
+int cgg_group_norm_nhwc_f32_stats(const float* x, void* ws, int B, int HW, int C, int groups, cgg_stream_t stream);
+/* The mask-feature head of parity mode's pixel decoder as ONE launch (csrc/mask_feature_head.hip): GroupNorm apply + ReLU over the
+ * raw 3 x 3 output z [B, H W, C] f32 channel-last (gn_ws = the (mean, variance) per (b, group) that cgg_group_norm_nhwc_f32*'s
+ * statistics passes leave at the head of their workspace), the 1 x 1 mask_feature convolution on the f32-class contraction (w_x3 =
+ * cgg_x3_pack of the (N x C) weight, bias nullable) and the x3 images of cgg_pack_mask_feature_nhwc_f32_x3 for n <= 4 pools out of
+ * {1, 2, 4, 8} (hi_host / lo_host / pools_host as there). Bit-identical to cgg_group_norm_nhwc_f32_x3a(relu) -> cgg_gemm_x3s ->
+ * cgg_pack_mask_feature_nhwc_f32_x3, whose x3a and f32 intermediates never reach memory here; mf (nullable) additionally receives
+ * the f32 map [B, H, W, N]. C = N = 256, groups = 32, H % 8 == 0, W % 8 == 0. Raises the x3 overflow flag where the GroupNorm's
+ * x3a store does. */
+int cgg_mask_feature_head_x3(const float* z, const void* gn_ws, const float* gamma, const float* beta, float eps, int groups,
+                             const void* w_x3, const float* bias, void* const* hi_host, void* const* lo_host, const int* pools_host,
+                             int n, float* mf, int B, int H, int W, int C, int N, cgg_stream_t stream);
+/* ... with the wavefront configuration as an argument (0: four wavefronts per workgroup, 1: eight, -1: the default). */
+int cgg_mask_feature_head_x3_cfg(const float* z, const void* gn_ws, const float* gamma, const float* beta, float eps, int groups,
+                                 const void* w_x3, const float* bias, void* const* hi_host, void* const* lo_host,
+                                 const int* pools_host, int n, float* mf, int B, int H, int W, int C, int N, int cfg,
+                                 cgg_stream_t stream);
 
 /* Batched transpose of f32 matrices, in (B, R, C) -> out (B, C, R): the NCHW <-> NHWC layout changes around the x3 kernels under
  * autograd (torch `x.permute(0, 2, 3, 1).contiguous()` and back), 64 x 64 tiles through LDS. */
