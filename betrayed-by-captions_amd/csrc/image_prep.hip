@@ -1,0 +1,231 @@
+// The reference's test pipeline on the device, one launch per batch: raw HWC uint8 images -> the (B, 3, Hb, Wb) float32 NCHW batch the
+// stem reads. Replaces, per image, [3P] mmdet Resize (mmcv imrescale, 8-bit bilinear) -> Pad -> Normalize(to_rgb) -> ImageToTensor and
+// the batch collation ([3P] mmcv collate of DataContainer(stack=True, padding_value=0)), which the reference runs on the CPU and ships
+// as 12.6 MB of float32 per image. The arithmetic is the rule written down in image_prep.py (`prepare_host`), bit for bit:
+//   taps      scale = 1 / (d / s) in double; fx = float((k + 0.5) * scale - 0.5), two separately rounded double operations;
+//             i = floor(fx), fx -= i, clamped at both ends; a0 = rint((1 - fx) * 2048), a1 = rint(fx * 2048)
+//   pixel     R = p[i] a0 + p[i + 1] a1 per source row; out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2
+//   value     float(float(out - mean) * (1 / std)); the pad region holds one constant per plane, the collate region 0
+// The rounding of (k + 0.5) * scale - 0.5 decides which source pixel a tap lands on, so nothing here may be contracted into a fused
+// multiply-add: the file is built with contraction off (the flag below, and the pragma for a build that ignores the flag line).
+//
+// Geometry: a workgroup of 4 wavefronts owns an IP_TH x IP_TW = 16 x 256 tile of one image's output planes; a lane owns 4 consecutive
+// columns, a wavefront one 256-column row segment at a time (1 KiB per plane per store instruction), 4 rows each. The source bytes the
+// tile needs -- rows i(y0) .. i(y1) + 1, bytes 3 i(x0) .. 3 (i(x1) + 2) of each -- are staged into LDS with aligned dword loads (a 3-byte
+// pixel, a pitch that is no multiple of 4 and an arbitrary image offset make every row start at its own byte phase; the phase is kept
+// in LDS and added back when a tap is read), so each source byte crosses the memory pipeline once per tile instead of once per tap.
+// A dword that is not wholly inside the image's bytes is assembled from guarded byte loads: nothing outside offset .. offset + h * pitch
+// is read. A tile whose span does not fit IP_LDS_BYTES (downsampling by more than ~1.5 x) reads its taps from global memory instead.
+// Every element of `out` is written exactly once, with non-temporal float4 stores when Wb % 4 == 0 (scalar stores otherwise).
+//
+// build-flags: -ffp-contract=off
+#include "cgg_common.h"
+
+#pragma clang fp contract(off)
+
+#define IP_TW 256
+#define IP_TH 16
+#define IP_LDS_BYTES 32768
+#define IP_COLS 8 /* descriptor row: byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w */
+
+struct IpConst {
+  float mean[3], rstd[3], pad[3];
+  int to_rgb;
+};
+
+// rule 2 for one target index k of an axis with source length s: taps i0 / i1 and their 11-bit weights
+__device__ __forceinline__ void ip_coef(int k, int s, double scale, int& i0, int& i1, int& a0, int& a1) {
+  const double t = ((double)k + 0.5) * scale;
+  float fx = (float)(t - 0.5);
+  const float fl = floorf(fx);
+  int i = (int)fl;
+  fx -= fl;
+  if (i < 0) {
+    i = 0;
+    fx = 0.f;
+  }
+  if (i >= s - 1) {
+    i = s - 1;
+    fx = 0.f;
+  }
+  a0 = (int)rintf((1.f - fx) * 2048.f);
+  a1 = (int)rintf(fx * 2048.f);
+  i0 = i;
+  i1 = min(i + 1, s - 1);
+}
+
+__device__ __forceinline__ int ip_pixel(int p00, int p01, int p10, int p11, int a0, int a1, int b0, int b1) {
+  const int r0 = (p00 * a0 + p01 * a1) >> 4, r1 = (p10 * a0 + p11 * a1) >> 4;
+  return (((b0 * r0) >> 16) + ((b1 * r1) >> 16) + 2) >> 2;
+}
+
+__global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                                                 IpConst cst, float* __restrict__ out, int Hb, int Wb) {
+  __shared__ uint32_t lds[IP_LDS_BYTES / 4];
+  const int b = blockIdx.z;
+  const int32_t* d = table + IP_COLS * b;
+  const int off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], ph = d[6], pw = d[7];
+  const int x0 = blockIdx.x * IP_TW, y0 = blockIdx.y * IP_TH;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double sx = 1.0 / ((double)nw / (double)w), sy = 1.0 / ((double)nh / (double)h);
+
+  // ---- the tile's source span (workgroup-uniform) and its LDS image -----------------------------------------------------------
+  const bool resized = x0 < nw && y0 < nh;
+  int r0 = 0, cb0 = 0, ls = 0;
+  bool use_lds = false;
+  if (resized) {
+    int i0, i1, a0, a1, r1, cb1;
+    ip_coef(y0, h, sy, r0, i1, a0, a1);
+    ip_coef(min(y0 + IP_TH, nh) - 1, h, sy, i0, r1, a0, a1);
+    ip_coef(x0, w, sx, i0, i1, a0, a1);
+    cb0 = 3 * i0;
+    ip_coef(min(x0 + IP_TW, nw) - 1, w, sx, i0, i1, a0, a1);
+    cb1 = 3 * (i1 + 1);
+    const int nrows = r1 - r0 + 1, nbytes = cb1 - cb0;
+    ls = (nbytes + 6) & ~3;                       // row stride in LDS: the bytes, up to 3 of phase, rounded up to dwords
+    use_lds = (long long)nrows * ls <= IP_LDS_BYTES;
+    if (use_lds) {
+      const int lo = off, hi = off + h * pitch;  // the image's bytes
+      for (int rr = wv; rr < nrows; rr += 4) {
+        const int a = off + (r0 + rr) * pitch + cb0, phase = a & 3, a4 = a - phase;
+        const int ndw = (phase + nbytes + 3) >> 2;   // <= ls / 4
+        for (int j = lane; j < ndw; j += 64) {
+          const int g = a4 + 4 * j;
+          uint32_t v;
+          if (g >= lo && g <= hi - 4) {
+            v = *reinterpret_cast<const uint32_t*>(src + g);
+          } else {
+            v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (g + q >= lo && g + q < hi) v |= (uint32_t)src[g + q] << (8 * q);
+          }
+          lds[(rr * ls >> 2) + j] = v;
+        }
+      }
+    }
+  }
+  if (use_lds) __syncthreads();                    // uniform: every wavefront of the workgroup takes the same side
+  const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
+
+  // ---- this lane's 4 columns ----------------------------------------------------------------------------------------------------
+  const int xl = x0 + 4 * lane;
+  int xi0[4], xi1[4], xa0[4], xa1[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    xi0[c] = xi1[c] = xa0[c] = xa1[c] = 0;
+    if (resized && xl + c < nw) {
+      ip_coef(xl + c, w, sx, xi0[c], xi1[c], xa0[c], xa1[c]);
+      xi0[c] *= 3;
+      xi1[c] *= 3;
+    }
+  }
+  const bool vec = (Wb & 3) == 0;
+  const size_t plane = (size_t)Hb * Wb;
+
+#pragma unroll 1
+  for (int r = 0; r < IP_TH / 4; ++r) {
+    const int y = y0 + 4 * wv + r;
+    if (y >= Hb || xl >= Wb) break;
+    float v[3][4];
+    const bool yin = y < nh;
+    int j0 = 0, j1 = 0, b0 = 0, b1 = 0;
+    if (resized && yin) ip_coef(y, h, sy, j0, j1, b0, b1);
+    // byte address of column-byte 0 of the two source rows, in LDS (phase included, relative to cb0) or in global memory
+    int base0, base1;
+    if (use_lds) {
+      base0 = (j0 - r0) * ls + ((off + j0 * pitch + cb0) & 3) - cb0;
+      base1 = (j1 - r0) * ls + ((off + j1 * pitch + cb0) & 3) - cb0;
+    } else {
+      base0 = off + j0 * pitch;
+      base1 = off + j1 * pitch;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int x = xl + c;
+      if (resized && yin && x < nw) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int ch = cst.to_rgb ? 2 - q : q;
+          int p00, p01, p10, p11;
+          if (use_lds) {
+            p00 = lb[base0 + xi0[c] + ch], p01 = lb[base0 + xi1[c] + ch];
+            p10 = lb[base1 + xi0[c] + ch], p11 = lb[base1 + xi1[c] + ch];
+          } else {
+            p00 = src[base0 + xi0[c] + ch], p01 = src[base0 + xi1[c] + ch];
+            p10 = src[base1 + xi0[c] + ch], p11 = src[base1 + xi1[c] + ch];
+          }
+          const int o = ip_pixel(p00, p01, p10, p11, xa0[c], xa1[c], b0, b1);
+          v[q][c] = ((float)o - cst.mean[q]) * cst.rstd[q];
+        }
+      } else {
+        const bool padded = y < ph && x < pw;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) v[q][c] = padded ? cst.pad[q] : 0.f;
+      }
+    }
+    float* o = out + (size_t)b * 3 * plane + (size_t)y * Wb + xl;
+    if (vec) {                                       // Wb % 4 == 0 and xl % 4 == 0: xl < Wb implies xl + 3 < Wb
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        f32x4 t = {v[q][0], v[q][1], v[q][2], v[q][3]};
+        __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(o + q * plane));
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (xl + c < Wb) o[q * plane + c] = v[q][c];
+    }
+  }
+}
+
+extern "C" int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table_offset, const int32_t* table_host, int B,
+                                 const float* mean, const float* std_, const float* pad_val, int to_rgb, int pad_before_norm,
+                                 float* out, int Hb, int Wb, cgg_stream_t stream) {
+  const char* me = "cgg_image_prep_u8";
+  CGG_REQUIRE(staged && table_host && mean && std_ && pad_val && out, CGG_EINVAL, "%s: null pointer", me);
+  CGG_REQUIRE(B >= 1 && Hb >= 1 && Wb >= 1, CGG_EINVAL, "%s: B, Hb, Wb must be >= 1 (got %d, %d, %d)", me, B, Hb, Wb);
+  CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && Hb <= CGG_IMAGE_PREP_MAX_DIM && Wb <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+              "%s: B, Hb, Wb must be <= %d (got %d, %d, %d)", me, CGG_IMAGE_PREP_MAX_DIM, B, Hb, Wb);
+  // the kernel forms byte addresses up to 7 past an image's end in int arithmetic before it guards them
+  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
+              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
+  CGG_REQUIRE(table_offset >= 0 && (table_offset & 3) == 0 && table_offset + (int64_t)B * IP_COLS * 4 <= staged_bytes, CGG_EINVAL,
+              "%s: the descriptor table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
+              (long long)table_offset, (long long)staged_bytes);
+  CGG_REQUIRE((((uintptr_t)staged) & 3u) == 0, CGG_EALIGN, "%s: staged must be 4-byte aligned", me);
+  CGG_REQUIRE((Wb & 3) != 0 || cgg_aligned16(out), CGG_EALIGN, "%s: out must be 16-byte aligned when Wb %% 4 == 0", me);
+  for (int c = 0; c < 3; ++c)
+    CGG_REQUIRE(std_[c] != 0.f && std_[c] == std_[c] && mean[c] == mean[c] && pad_val[c] == pad_val[c], CGG_EINVAL,
+                "%s: mean / std / pad_val must be numbers and std non-zero (channel %d)", me, c);
+  for (int b = 0; b < B; ++b) {
+    const int32_t* d = table_host + IP_COLS * b;
+    const int64_t off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], ph = d[6], pw = d[7];
+    CGG_REQUIRE(h >= 1 && w >= 1 && nh >= 1 && nw >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld -> %lld x %lld)", me, b,
+                (long long)h, (long long)w, (long long)nh, (long long)nw);
+    CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+                "%s: image %d is %lld x %lld, larger than %d on a side", me, b, (long long)h, (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+    CGG_REQUIRE(nh <= ph && ph <= Hb && nw <= pw && pw <= Wb, CGG_EINVAL,
+                "%s: image %d: need new <= pad <= batch, got rows %lld / %lld / %d, columns %lld / %lld / %d", me, b, (long long)nh,
+                (long long)ph, Hb, (long long)nw, (long long)pw, Wb);
+    CGG_REQUIRE(pitch >= 3 * w, CGG_EINVAL, "%s: image %d: row pitch %lld < 3 * w = %lld", me, b, (long long)pitch, (long long)(3 * w));
+    CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
+                "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
+                (long long)(off + h * pitch), (long long)staged_bytes);
+  }
+  IpConst cst;
+  for (int q = 0; q < 3; ++q) {
+    cst.mean[q] = mean[q];
+    cst.rstd[q] = (float)(1.0 / (double)std_[q]);
+    const float p = pad_val[(pad_before_norm && to_rgb) ? 2 - q : q];   // a per-channel value is in source order ahead of Normalize
+    cst.pad[q] = pad_before_norm ? (p - cst.mean[q]) * cst.rstd[q] : p;
+  }
+  cst.to_rgb = to_rgb ? 1 : 0;
+  const dim3 grid((unsigned)((Wb + IP_TW - 1) / IP_TW), (unsigned)((Hb + IP_TH - 1) / IP_TH), (unsigned)B);
+  hipLaunchKernelGGL(cgg_image_prep_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, staged,
+                     reinterpret_cast<const int32_t*>(staged + table_offset), cst, out, Hb, Wb);
+  CGG_CHECK_LAUNCH(me);
+  return CGG_OK;
+}

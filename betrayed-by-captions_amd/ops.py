@@ -2576,6 +2576,55 @@ def subsample_nhwc(x, stride):
 
 
 # ------------------------------------------------------------------------------------------------
+# input side: the reference's test pipeline on raw uint8 images (image_prep.py states the rule)
+# ------------------------------------------------------------------------------------------------
+IMAGE_PREP_TABLE_COLS = 8     # byte offset, h, w, row pitch, new_h, new_w, pad_h, pad_w
+
+
+def three_floats(v, name):
+    """one number, or three of them (per channel; grayscale sources are out of scope) -> a tuple of 3 floats"""
+    vals = tuple(float(x) for x in (v if hasattr(v, '__len__') else [v] * 3))
+    if len(vals) != 3:
+        raise CggError(f'{name} must be one number or three (got {len(vals)})')
+    return vals
+
+
+def image_prep_u8(staged, table, out, mean, std, pad_val=0.0, to_rgb=True, pad_before_norm=True, table_offset=0, staged_bytes=None):
+    """Resize (8-bit bilinear) + Pad + Normalize(to_rgb) + collate of a whole batch in one launch (`cgg_image_prep_u8`, no
+    synchronisation). staged: DEVICE uint8 (n,) -- the raw HWC images back to back and the descriptor table at byte `table_offset`;
+    table: HOST int32 (B, 8) copy of those rows (byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w), read for validation during
+    the call; out: DEVICE float32 (B, 3, Hb, Wb) contiguous, every element of which is written. Returns `out`."""
+    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
+        raise CggError(f'image_prep_u8: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))}, '
+                       f'{getattr(staged, "dim", lambda: "?")()} dims)')
+    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != IMAGE_PREP_TABLE_COLS:
+        raise CggError(f'image_prep_u8: table must be a (B, {IMAGE_PREP_TABLE_COLS}) torch.int32 tensor '
+                       f'(got {getattr(table, "dtype", type(table))}, shape {tuple(getattr(table, "shape", ()))})')
+    if table.is_cuda or not table.is_contiguous():
+        raise CggError('image_prep_u8: table must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
+    if not torch.is_tensor(out) or out.dtype != torch.float32:
+        raise CggError(f'image_prep_u8: out must be torch.float32 (got {getattr(out, "dtype", type(out))})')
+    B = int(table.shape[0])
+    if out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3:
+        raise CggError(f'image_prep_u8: out must be ({B}, 3, Hb, Wb) (got {tuple(out.shape)})')
+    if B < 1:
+        raise CggError('image_prep_u8: an empty batch')
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if nbytes > staged.numel():
+        raise CggError(f'image_prep_u8: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
+    sp, op = dev_ptr(staged, 'image_prep_u8: staged'), dev_ptr(out, 'image_prep_u8: out')
+    if staged.device != out.device:
+        raise CggError(f'image_prep_u8: staged ({staged.device}) and out ({out.device}) live on different devices')
+    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'image_prep_u8: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    Hb, Wb = int(out.shape[2]), int(out.shape[3])
+    with _timed('image_prep_u8', bytes=float(nbytes + out.numel() * 4), shape=(B, Hb, Wb)):
+        rc = _lib_().cgg_image_prep_u8(sp, nbytes, int(table_offset), ctypes.c_void_p(table.data_ptr()), B, m, s, p, int(bool(to_rgb)),
+                                       int(bool(pad_before_norm)), op, Hb, Wb, stream_ptr(out.device))
+    check(rc, 'cgg_image_prep_u8')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # host side of the inference tail: COCO RLE of bit-packed masks (host function of the library, no device work)
 # ------------------------------------------------------------------------------------------------
 def rle_encode_bitmasks(bits, width, threads=8):

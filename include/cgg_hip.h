@@ -672,6 +672,29 @@ int cgg_mask_feature_head_x3_cfg(const float* z, const void* gn_ws, const float*
                                  const int* pools_host, int n, float* mf, int B, int H, int W, int C, int N, int cfg,
                                  cgg_stream_t stream);
 
+/* The reference's test pipeline for a batch of raw images as ONE launch (csrc/image_prep.hip): [3P] mmdet Resize (mmcv imrescale,
+ * 8-bit bilinear) -> Pad -> Normalize(to_rgb) -> ImageToTensor per image and the [3P] mmcv collate of the batch, from HWC uint8 bytes
+ * to out (B, 3, Hb, Wb) f32 contiguous NCHW -- what cgg_stem_conv7x7_nchw / cgg_stem_conv7x7_x3_nchw read. The arithmetic is the rule
+ * of image_prep.py (`prepare_host`), bit for bit; it restates OpenCV's INTER_LINEAR for 8-bit images and claims equality with no
+ * particular cv2 build.
+ *   staged          DEVICE bytes (4-byte aligned base): the B images, 3-byte pixels, back to back at arbitrary byte offsets, and the
+ *                   descriptor table at byte `table_offset` (a multiple of 4); staged_bytes = how many of them are valid
+ *   table_host      HOST copy of the same B rows of 8 int32: byte offset, h, w, row pitch in bytes (>= 3 w), new_h, new_w, pad_h, pad_w.
+ *                   It is read during the call, for validation only: the kernel reads the device rows
+ *   mean, std, pad_val   HOST, 3 floats each; mean / std index the OUTPUT plane (after to_rgb). pad_before_norm != 0: Pad ran ahead of
+ *                   Normalize -- pad_val indexes the SOURCE channel and the pad region holds (pad_val - mean) / std; 0: the pad
+ *                   region holds pad_val[plane] itself. value = float(float(x - mean) * float(1 / std))
+ *   out             every element is written exactly once: resized region (new_h x new_w), pad region (up to pad_h x pad_w), and 0.0
+ *                   up to Hb x Wb (the collate padding); the caller does not clear it. 16-byte aligned when Wb % 4 == 0
+ * Does not synchronise. Checked on the host before the launch: CGG_EINVAL for B < 1, a zero-sized image, new > pad or pad > batch on
+ * either axis, pitch < 3 w, an image or the table extending past staged_bytes, std == 0; CGG_EUNSUPPORTED beyond the index arithmetic
+ * of the kernel: B, h, w, Hb, Wb <= CGG_IMAGE_PREP_MAX_DIM and staged_bytes <= 2^31 - 9. The kernel reads no byte outside the table rows
+ * and offset .. offset + h * pitch of each image. */
+#define CGG_IMAGE_PREP_MAX_DIM 65535
+int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table_offset, const int32_t* table_host, int B,
+                      const float* mean, const float* std, const float* pad_val, int to_rgb, int pad_before_norm, float* out, int Hb,
+                      int Wb, cgg_stream_t stream);
+
 /* Batched transpose of f32 matrices, in (B, R, C) -> out (B, C, R): the NCHW <-> NHWC layout changes around the x3 kernels under
  * autograd (torch `x.permute(0, 2, 3, 1).contiguous()` and back), 64 x 64 tiles through LDS. */
 int cgg_transpose_f32(const float* in, float* out, int B, int R, int C, cgg_stream_t stream);

@@ -47,7 +47,13 @@ def parse_args(argv=None):
     p.add_argument('--num-images', type=int, default=16)
     p.add_argument('--samples-per-gpu', type=int, default=2)
     p.add_argument('--synthetic', type=int, default=1024, help='synthetic image size (H = W) when --data is not given')
-    p.add_argument('--data', default=None, help='pkg.module:function -> iterable of (img (3,H,W) float tensor, img_meta)')
+    p.add_argument('--data', default=None,
+                   help='pkg.module:function(cfg, rank, world) -> iterable of (img (3,H,W) float tensor, img_meta) -- already resized, '
+                        'normalised and padded --, or of raw (h,w,3) uint8 BGR arrays / tensors (alone, or with a dict of extra meta '
+                        'keys such as filename): those are prepared on the device by the config\'s data.test.pipeline')
+    p.add_argument('--synthetic-u8', default=None, metavar='HxW',
+                   help='synthetic raw uint8 frames of this size (e.g. 480x640) instead of --synthetic\'s prepared float tensors: '
+                        'exercises the device-side test pipeline without a dataset')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                    help='fp32 = parity mode: every contraction in f32-class f16 x 3 arithmetic (as accurate as f32 GEMMs; activations '
                         'must satisfy |a| < 4094 -- the run fails loudly otherwise, CGG_X3=0 lifts the limit); bf16 = throughput mode')
@@ -75,6 +81,22 @@ def synthetic_images(n, size, seed, pool=4):
         imgs = [t.pin_memory() for t in imgs]
     for i in range(n):
         yield imgs[i % len(imgs)], dict(meta, filename=f'synthetic_{i}.jpg')
+
+
+def synthetic_u8_images(n, hw, seed, pool=4):
+    """n raw (h, w, 3) uint8 frames from a pool of `pool` distinct pinned tensors, as `synthetic_images` does for float batches."""
+    g = torch.Generator().manual_seed(seed)
+    imgs = [torch.randint(0, 256, (hw[0], hw[1], 3), dtype=torch.uint8, generator=g) for _ in range(min(pool, n))]
+    if torch.cuda.is_available():
+        imgs = [t.pin_memory() for t in imgs]
+    for i in range(n):
+        yield imgs[i % len(imgs)], dict(filename=f'synthetic_{i}.jpg')
+
+
+def is_raw_u8(img):
+    """a raw (h, w, 3) uint8 image, as opposed to the prepared (3, H, W) float tensor"""
+    u8 = img.dtype == torch.uint8 if torch.is_tensor(img) else isinstance(img, np.ndarray) and img.dtype == np.uint8
+    return bool(u8) and img.ndim == 3 and img.shape[2] == 3
 
 
 def to_numpy(result):
@@ -139,6 +161,13 @@ def main(argv=None):
     if args.data:
         mod, fn = args.data.split(':')
         stream = getattr(importlib.import_module(mod), fn)(cfg, rank, world)
+    elif args.synthetic_u8:
+        try:
+            hw = tuple(int(v) for v in args.synthetic_u8.lower().split('x'))
+            assert len(hw) == 2 and min(hw) >= 1
+        except (ValueError, AssertionError):
+            raise SystemExit(f'--synthetic-u8 {args.synthetic_u8!r}: expected HxW, e.g. 480x640')
+        stream = (s for i, s in enumerate(synthetic_u8_images(args.num_images, hw, seed=11)) if i % world == rank)
     else:
         stream = (s for i, s in enumerate(synthetic_images(args.num_images, args.synthetic, seed=11)) if i % world == rank)
 
@@ -163,6 +192,19 @@ def main(argv=None):
         while len(in_copy) > keep:
             RleCollector.wait_copied(in_copy.pop(0))
 
+    prep = None                        # device-side test pipeline, built when the stream yields its first raw uint8 image
+
+    def image_prep():
+        nonlocal prep
+        if prep is None:
+            from cgg_amd.image_prep import ImagePrep, parse_test_pipeline
+            try:
+                pipeline = cfg.data.test.pipeline
+            except (AttributeError, KeyError):
+                raise SystemExit('tools/test.py: raw uint8 images need the config\'s data.test.pipeline (Resize / Pad / Normalize)')
+            prep = ImagePrep(parse_test_pipeline(pipeline), device)
+        return prep
+
     results, pending = [], []          # pending: (pipeline, slot) pairs -- a slot is only meaningful for ITS pipeline
     slot_copied = {}                   # (pipeline, slot) -> event: that slot's last results have been copied to the host
     n_img, t0 = 0, None
@@ -178,20 +220,31 @@ def main(argv=None):
 
         def run(group):
             nonlocal pipe, t0, n_img
-            # straight into a device batch (pinned sources copy asynchronously; torch.stack would build a pageable staging tensor)
-            imgs = torch.empty((len(group),) + tuple(group[0][0].shape), dtype=group[0][0].dtype, device=device)
-            for k, g in enumerate(group):
-                imgs[k].copy_(g[0], non_blocking=True)
-            metas = [dict(g[1], batch_input_shape=tuple(imgs.shape[-2:])) for g in group]
+            raw = [g[0] for g in group] if is_raw_u8(group[0][0]) else None
+            if raw is not None:
+                # raw uint8 images: resized, padded, normalised and collated by ONE kernel (cgg_amd.image_prep), which is launched
+                # below -- into the pipeline's own input buffer when a captured pipeline serves this batch
+                shape, metas = image_prep().describe(raw)
+                metas = [dict(m, **(g[1] or {}), batch_input_shape=tuple(shape[-2:])) for m, g in zip(metas, group)]
+                imgs = None
+            else:
+                # straight into a device batch (pinned sources copy asynchronously; torch.stack would build a pageable staging tensor)
+                imgs = torch.empty((len(group),) + tuple(group[0][0].shape), dtype=group[0][0].dtype, device=device)
+                for k, g in enumerate(group):
+                    imgs[k].copy_(g[0], non_blocking=True)
+                metas = [dict(g[1], batch_input_shape=tuple(imgs.shape[-2:])) for g in group]
+                shape = tuple(imgs.shape)
             use_pipe = (not args.no_pipeline and len(group) == B
                         and all(m['img_shape'] == metas[0]['img_shape'] and m['ori_shape'] == metas[0]['ori_shape'] for m in metas))
             if use_pipe:
-                key = (tuple(imgs.shape), metas[0]['img_shape'], metas[0]['ori_shape'])
+                key = (tuple(shape), metas[0]['img_shape'], metas[0]['ori_shape'])
                 if pipe is None or pipe.meta_key != key:
                     drain()            # the old pipeline's results leave before its buffers are dropped
                     pipe = pipes.get(key)
                     if pipe is None:
                         from cgg_amd.pipeline import detector_pipeline
+                        if imgs is None:
+                            imgs = image_prep()(raw)[0]        # the example batch the graphs are captured on
                         pipe = detector_pipeline(model, imgs, metas, stages=_test_stages(), defer_tail=False, rescale=True, device_results=True, mask_bits=args.mask_bits)
                         pipe.meta_key = key
                         pipes[key] = pipe
@@ -206,11 +259,18 @@ def main(argv=None):
                     ev = slot_copied.pop((id(pipe), pipe._n % pipe.slots), None)
                     if ev is not None:
                         pipe.streams[-1].wait_event(ev)
+                if imgs is None:
+                    # the kernel writes the static input of the slot this submit takes, once stage 0 of the slot's previous batch
+                    # has read it (a wait on the GPU; an event that was never recorded does not wait)
+                    s_in = pipe._n % pipe.slots
+                    torch.cuda.current_stream(device).wait_event(pipe.done[0][s_in])
+                    imgs = image_prep()(raw, out=pipe.inputs[s_in])[0]
                 slot = pipe.submit(imgs)
                 # `imgs` was filled on this stream but is READ by stage 0 on the pipeline's first stream, after `run` has dropped
                 # its reference: without this the caching allocator may hand the block to the next batch's host->device copy
                 # while stage 0 has not copied the previous batch yet (batch k served with batch k + 1's pixels)
-                imgs.record_stream(pipe.streams[0])
+                if imgs is not pipe.inputs[slot]:      # (a raw batch was written into the pipeline's own persistent input)
+                    imgs.record_stream(pipe.streams[0])
                 pending.append((pipe, slot))
                 # results of the batch `depth` submits back are copied out while the newer ones run
                 while len(pending) > depth:
@@ -222,16 +282,28 @@ def main(argv=None):
                 drain()                # keep dataset order: earlier batches first
                 if t0 is None:
                     t0 = time.perf_counter()
+                if imgs is None:
+                    imgs = image_prep()(raw)[0]
                 emit(model.simple_test(imgs, metas, rescale=True, device_results=True, mask_bits=args.mask_bits))
                 if collector is not None:
                     copies_done()
             n_img += len(group)
 
         pipes = {}                     # one captured pipeline per (batch shape, img_shape, ori_shape)
+
+        def shape_key(sample):
+            """what the images of one batch share: the prepared tensor's shape, or a raw image's padded shape"""
+            if is_raw_u8(sample[0]):
+                from cgg_amd.image_prep import image_geometry
+                return ('u8',) + image_geometry(sample[0].shape[:2], image_prep().spec)[2:]
+            return tuple(sample[0].shape)
+
         for sample in stream:
+            if is_raw_u8(sample):
+                sample = (sample, None)        # a raw image without extra meta keys
             # a batch holds images of ONE padded shape (the reference pads a batch to its largest image through the
             # dataset's collate; this driver takes pre-sized tensors and starts a new batch when the shape changes)
-            if group and tuple(sample[0].shape) != tuple(group[0][0].shape):
+            if group and shape_key(sample) != shape_key(group[0]):
                 run(group)
                 group = []
             group.append(sample)
