@@ -349,6 +349,62 @@ class CaptionTransformer(nn.Module):
             state['length'] += 1
         return outs
 
+    # ---- the same for a batch of images with a fixed number of slots each (caption_search.beam_search_batched) ----
+    def begin_decode_batched(self, memory, slots, max_len):
+        """State of an incremental decode over `memory` (B, Q, in) with `slots` rows per image (row b * slots + s): the
+        cross-attention keys / values of every block once per IMAGE, (B, Q, H, d) -- the state holds no copy per slot, a step
+        expands them over the image's slots where it uses them -- and per-block self-attention key / value prefixes preallocated as
+        (B * slots, max_len, H, d). Every shape is fixed for the whole search."""
+        B, Q = memory.shape[:2]
+        with runtime.autocast():
+            mem = self.adapter(memory)
+            cross = []
+            for blk in self.transformer_decoder.decoders:
+                c = blk.crx_layer
+                cross.append((c.to_key(mem).view(B, Q, c.nbr_heads, c.heads_dim),
+                              c.to_val(mem).view(B, Q, c.nbr_heads, c.heads_dim)))
+        n = len(self.transformer_decoder.decoders)
+        m = self.transformer_decoder.decoders[0].mha_layer
+        shape = (B * int(slots), int(max_len), m.nbr_heads, m.heads_dim)
+        return dict(cross=cross, k=[cross[0][0].new_zeros(shape) for _ in range(n)], v=[cross[0][0].new_zeros(shape) for _ in range(n)],
+                    length=0, B=B, slots=int(slots), max_len=int(max_len))
+
+    def decode_step_batched(self, tok, state, parents):
+        """`decode_step` for every slot of every image at once: `tok` (B * slots, 1, in), `parents` (B * slots,) long = the GLOBAL
+        row each slot continues. The same arithmetic per row in the same order of operations; the prefixes are re-gathered by
+        parent, the new position is written in place and attention runs over positions [: t + 1]. Rows of dead slots compute
+        values nobody reads (their token and parent are valid, so nothing is indexed out of range). Returns the per-block outputs
+        at the new position, each (B * slots, hidden)."""
+        B, S, t = state['B'], state['slots'], state['length']
+        nb = B * S
+        if t >= state['max_len']:
+            raise ValueError(f'decode_step_batched: position {t} is past the {state["max_len"]} the state was sized for')
+        with runtime.autocast():
+            x = tok + self.position_encoder.psne_layer[t][None, None]
+            outs = []
+            for i, blk in enumerate(self.transformer_decoder.decoders):
+                n, m, c = blk.layer_normalz, blk.mha_layer, blk.crx_layer
+                H, d = m.nbr_heads, m.heads_dim
+                h = n['mha'][0](x)
+                qkv = m.qkv_layer(h).view(nb, 1, H, 3, d)
+                pk, pv = state['k'][i], state['v'][i]
+                if t > 0:
+                    pk, pv = pk.index_select(0, parents), pv.index_select(0, parents)
+                pk[:, t] = qkv[:, 0, :, 1, :].to(pk.dtype)
+                pv[:, t] = qkv[:, 0, :, 2, :].to(pv.dtype)
+                state['k'][i], state['v'][i] = pk, pv
+                h = n['mha'][1](h + m.out_layer(_attend(qkv[..., 0, :], pk[:, :t + 1], pv[:, :t + 1], H)))
+                y = n['crx'][0](h)
+                ck, cv = state['cross'][i]
+                # per row exactly `decode_step`'s product: the image's keys / values, expanded over its slots where they are used
+                ck, cv = (a[:, None].expand(B, S, -1, -1, -1).reshape(nb, -1, H, d) for a in (ck, cv))
+                att = _attend(c.to_qry(y).view(nb, 1, H, d), ck, cv, H)
+                y = n['crx'][1](y + c.to_out(att))
+                x = n['ffn'][1](n['ffn'][0](y) + blk.ffn_layer(y))
+                outs.append(x[:, 0])
+            state['length'] += 1
+        return outs
+
     def generator_ce_rows(self, hidden, target, ignore_index=None):
         """`F.cross_entropy(generator(hidden), target, reduction='none', ignore_index=...)` for hidden (M, hidden) and
         target (M,) without materialising the (M, nb_tokens) logits (HIP row kernels + chunked library GEMMs)."""

@@ -163,7 +163,10 @@ class MaskFormerOpen(nn.Module):
         for i in range(len(results)):
             for res_type in self.test_cfg.get('eval_types', []):
                 if res_type == 'cap_results':
-                    results[i][res_type] = caption_results
+                    # the batched search returns one caption per image, the single-image search the caption itself
+                    # (the head's own condition: the single-image result may itself be a list, of token ids)
+                    per_image = isinstance(caption_results, list) and (len(results) > 1 or kwargs.get('caption_batched', False))
+                    results[i][res_type] = caption_results[i] if per_image else caption_results
                     continue
                 pred_classes = {'all_results': getattr(fh, 'all_classes', None),
                                 'novel_results': getattr(fh, 'novel_classes', None),

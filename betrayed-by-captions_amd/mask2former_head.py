@@ -1522,10 +1522,15 @@ class Mask2FormerHeadOpen(nn.Module):
         with_caption = kwargs.get('with_caption', False) or ('cap_results' in eval_types)
         caption_generation_results = None
         if with_caption:
-            from .caption_search import beam_search
-            caption_generation_results = beam_search(self, mask_cls_emb_results, BOS_TOKEN, EOS_TOKEN,
-                                                     max_len=35, beam_width=7,
-                                                     logging=kwargs.get('logging', False))
+            from .caption_search import beam_search, beam_search_batched
+            if mask_cls_emb_results.shape[0] > 1 or kwargs.get('caption_batched', False):
+                # a batch of images (or `caption_batched=True`): one search for all of them, a LIST of captions, one per image
+                caption_generation_results = beam_search_batched(self, mask_cls_emb_results, BOS_TOKEN, EOS_TOKEN,
+                                                                 max_len=35, beam_width=7)
+            else:
+                caption_generation_results = beam_search(self, mask_cls_emb_results, BOS_TOKEN, EOS_TOKEN,
+                                                         max_len=35, beam_width=7,
+                                                         logging=kwargs.get('logging', False))
         att = None
         if kwargs.get('with_att', False):
             nouns_embs = self.bert_embeddings(kwargs['nouns_ids']).squeeze(0)

@@ -2625,6 +2625,93 @@ def image_prep_u8(staged, table, out, mean, std, pad_val=0.0, to_rgb=True, pad_b
 
 
 # ------------------------------------------------------------------------------------------------
+# caption search: one beam-search step for a whole batch, decided on the device (caption_search.py states the rule)
+# ------------------------------------------------------------------------------------------------
+BEAM_STEP_MAX_BEAM = 8        # CGG_BEAM_STEP_MAX_BEAM
+BEAM_STEP_MAX_LEN = 256       # CGG_BEAM_STEP_MAX_LEN
+
+
+class BeamState:
+    """The fixed-slot state of a batched caption search (`caption_search.beam_step_host` / `beam_step`): `beam` slots per image,
+    rows of `max_len` tokens, zero-initialised except for the one live sequence [BOS] of every image. Lives wherever `device` says
+    (the host rule runs on a CPU state; `float_dtype=torch.float64` is its comparison form)."""
+
+    INT_FIELDS = ('seqs', 'nlive', 'fin_seqs', 'fin_len', 'nfin', 'best_idx', 'done', 'ndone')
+    FLOAT_FIELDS = ('weights', 'fin_score')
+    FIELDS = INT_FIELDS + FLOAT_FIELDS
+
+    def __init__(self, B, beam, max_len, BOS, EOS, device='cpu', float_dtype=torch.float32):
+        B, beam, max_len = int(B), int(beam), int(max_len)
+        if B < 1 or not 1 <= beam <= BEAM_STEP_MAX_BEAM:
+            raise CggError(f'BeamState: B >= 1 and 1 <= beam <= {BEAM_STEP_MAX_BEAM} expected (got {B}, {beam})')
+        self.B, self.beam, self.BOS, self.EOS = B, beam, int(BOS), int(EOS)
+        # a step at length 2 always runs and may finish a sequence of 3 tokens, whatever max_len says
+        self.max_len = max(max_len, 4)
+        if self.max_len > BEAM_STEP_MAX_LEN:
+            raise CggError(f'BeamState: max_len must be <= {BEAM_STEP_MAX_LEN} (got {max_len})')
+        i32 = dict(dtype=torch.int32, device=device)
+        f = dict(dtype=float_dtype, device=device)
+        self.seqs = torch.zeros((B, beam, self.max_len), **i32)
+        self.seqs[:, 0, 0] = self.BOS
+        self.weights = torch.zeros((B, beam), **f)
+        self.nlive = torch.ones((B,), **i32)
+        self.fin_seqs = torch.zeros((B, beam, self.max_len), **i32)
+        self.fin_len = torch.zeros((B, beam), **i32)
+        self.fin_score = torch.zeros((B, beam), **f)
+        self.nfin = torch.zeros((B,), **i32)
+        self.best_idx = torch.zeros((B,), **i32)
+        self.done = torch.zeros((B,), **i32)
+        self.ndone = torch.zeros((1,), **i32)
+        # what the next decoder step reads: every slot starts from BOS and continues itself
+        self.tokens = torch.full((B * beam,), self.BOS, dtype=torch.int64, device=device)
+        self.parents = torch.arange(B * beam, dtype=torch.int64, device=device)
+        self.ws = None
+
+    def clone(self, device=None, float_dtype=None):
+        """A deep copy, optionally on another device / with the float fields in another dtype."""
+        o = object.__new__(BeamState)
+        o.B, o.beam, o.BOS, o.EOS, o.max_len, o.ws = self.B, self.beam, self.BOS, self.EOS, self.max_len, None
+        for k in self.FIELDS + ('tokens', 'parents'):
+            t = getattr(self, k)
+            t = t.to(device) if device is not None else t
+            if float_dtype is not None and k in self.FLOAT_FIELDS:
+                t = t.to(float_dtype)
+            setattr(o, k, t.clone())
+        return o
+
+
+def beam_step(logits, state, length, alpha, max_len, first=False, passes=3):
+    """One step of the batched caption search on the device (`cgg_beam_step`: two launches, no allocation after the first call on a
+    state, no synchronisation). logits (L, B * beam, V) f32 contiguous; `state` a device `BeamState`, updated in place together with
+    `state.tokens` / `state.parents`; `length` = the current length of the live sequences. The rule is
+    `caption_search.beam_step_host`."""
+    if not isinstance(state, BeamState):
+        raise CggError(f'beam_step: state must be a BeamState (got {type(state).__name__})')
+    if not torch.is_tensor(logits) or logits.dim() != 3:
+        raise CggError('beam_step: logits must be a (L, B * beam, V) tensor')
+    lp = dev_ptr(logits, 'beam_step: logits', torch.float32)
+    L, rows, V = (int(v) for v in logits.shape)
+    B, beam = state.B, state.beam
+    if rows != B * beam:
+        raise CggError(f'beam_step: logits has {rows} rows, the state {B} x {beam} slots')
+    ptrs = []
+    for k in ('seqs', 'weights', 'nlive', 'fin_seqs', 'fin_len', 'fin_score', 'nfin', 'best_idx', 'done', 'ndone', 'tokens', 'parents'):
+        t = getattr(state, k)
+        want = torch.float32 if k in BeamState.FLOAT_FIELDS else torch.int64 if k in ('tokens', 'parents') else torch.int32
+        ptrs.append(dev_ptr(t, f'beam_step: state.{k}', want))
+        if t.device != logits.device:
+            raise CggError(f'beam_step: state.{k} ({t.device}) and logits ({logits.device}) live on different devices')
+    need = int(_lib_().cgg_beam_step_workspace_bytes(B, beam, V))
+    if state.ws is None or state.ws.numel() < need or state.ws.device != logits.device:
+        state.ws = torch.empty(max(need, 4), dtype=torch.uint8, device=logits.device)
+    with _timed('beam_step', bytes=float(logits.numel() * 4), shape=(L, B, beam, V)):
+        rc = _lib_().cgg_beam_step_passes(lp, L, B, beam, V, *ptrs, dev_ptr(state.ws), int(length), float(alpha), state.EOS,
+                                          int(max_len), state.max_len, int(bool(first)), int(passes), stream_ptr(logits.device))
+    check(rc, 'cgg_beam_step')
+    return state
+
+
+# ------------------------------------------------------------------------------------------------
 # host side of the inference tail: COCO RLE of bit-packed masks (host function of the library, no device work)
 # ------------------------------------------------------------------------------------------------
 def rle_encode_bitmasks(bits, width, threads=8):

@@ -695,6 +695,38 @@ int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table
                       const float* mean, const float* std, const float* pad_val, int to_rgb, int pad_before_norm, float* out, int Hb,
                       int Wb, cgg_stream_t stream);
 
+/* One step of the caption beam search for a whole batch of images, decision and bookkeeping on the device (csrc/beam_step.hip):
+ * the loop body of the reference's beam_search, open_set/utils/eval/inference.py:113-149 -- mean over the decoder blocks' generator
+ * outputs, log-softmax, (log p + parent weight) / length^alpha, the top `beam` of an image's live rows, the walk over them that
+ * finishes sequences at EOS and continues the others -- which the reference (and caption_search.beam_search) runs on the host for
+ * one image. The rule, quirks included, is written down in caption_search.py (`beam_step_host`); equal candidates are ordered by
+ * the smaller row * V + col. Two launches (per-chunk partials, then one workgroup per image); nothing is allocated, nothing
+ * synchronises, the host reads no candidate.
+ *   logits          (L, B * beam, V) f32 contiguous, 4-byte aligned: row b * beam + s = slot s of image b at the newest position
+ *   state, all DEVICE, beam slots per image, rows of `state_max_len` tokens (<= CGG_BEAM_STEP_MAX_LEN):
+ *     seqs (B, beam, state_max_len) i32 -- live sequences in slots 0 .. nlive - 1 in the order they were accepted; weights (B, beam)
+ *     f32; nlive (B) i32; fin_seqs (B, beam, state_max_len) i32, fin_len / fin_score (B, beam) i32 / f32, nfin (B) i32 -- finished
+ *     sequences in order; best_idx (B) i32; done (B) i32; ndone (1) i32 = how many images are done
+ *   tokens, parents (B * beam) i64, written by every call: newest token and global parent row of each slot for the next decoder
+ *                   step; dead slots (and every slot of a done image) get eos and their own row
+ *   ws              cgg_beam_step_workspace_bytes(B, beam, V) bytes of scratch
+ *   length          current length of every live sequence (1 at the BOS step); first != 0: the BOS step (every candidate becomes a
+ *                   live sequence with its OWN weight, no EOS / max_len handling: inference.py:96-104)
+ * An image whose `done` is set is left untouched. CGG_EINVAL: a null pointer, L < 1, B < 1, beam outside 1 .. CGG_BEAM_STEP_MAX_BEAM,
+ * V < beam, max_len > state_max_len, length outside 1 .. state_max_len - 1; CGG_EUNSUPPORTED: state_max_len > CGG_BEAM_STEP_MAX_LEN. */
+#define CGG_BEAM_STEP_MAX_BEAM 8
+#define CGG_BEAM_STEP_MAX_LEN 256
+int64_t cgg_beam_step_workspace_bytes(int B, int beam, int V);
+int cgg_beam_step(const float* logits, int L, int B, int beam, int V, int32_t* seqs, float* weights, int32_t* nlive,
+                  int32_t* fin_seqs, int32_t* fin_len, float* fin_score, int32_t* nfin, int32_t* best_idx, int32_t* done,
+                  int32_t* ndone, int64_t* tokens, int64_t* parents, void* ws, int length, float alpha, int eos, int max_len,
+                  int state_max_len, int first, cgg_stream_t stream);
+/* ... one launch at a time, for measurements: passes = 1 the partials, 2 the decision over the partials that `ws` holds, 3 both. */
+int cgg_beam_step_passes(const float* logits, int L, int B, int beam, int V, int32_t* seqs, float* weights, int32_t* nlive,
+                         int32_t* fin_seqs, int32_t* fin_len, float* fin_score, int32_t* nfin, int32_t* best_idx, int32_t* done,
+                         int32_t* ndone, int64_t* tokens, int64_t* parents, void* ws, int length, float alpha, int eos,
+                         int max_len, int state_max_len, int first, int passes, cgg_stream_t stream);
+
 /* Batched transpose of f32 matrices, in (B, R, C) -> out (B, C, R): the NCHW <-> NHWC layout changes around the x3 kernels under
  * autograd (torch `x.permute(0, 2, 3, 1).contiguous()` and back), 64 x 64 tiles through LDS. */
 int cgg_transpose_f32(const float* in, float* out, int B, int R, int C, cgg_stream_t stream);
