@@ -110,6 +110,8 @@ PROTOTYPES = {
     'cgg_mask_feature_head_x3': (_c_int, [_c_vp] * 4 + [_c_f, _c_int] + [_c_vp] * 5 + [_c_int, _c_vp] + [_c_int] * 5 + [_c_vp]),
     'cgg_mask_feature_head_x3_cfg': (_c_int, [_c_vp] * 4 + [_c_f, _c_int] + [_c_vp] * 5 + [_c_int, _c_vp] + [_c_int] * 6 + [_c_vp]),
     'cgg_image_prep_u8': (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp]),
+    'cgg_train_prep_u8': (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp] + [_c_int] * 4 +
+                          [_c_vp] * 4 + [_c_int, _c_int, _c_vp]),
     'cgg_beam_step_workspace_bytes': (_c_i64, [_c_int] * 3),
     'cgg_beam_step': (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 13 + [_c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     'cgg_beam_step_passes': (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 13 + [_c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),

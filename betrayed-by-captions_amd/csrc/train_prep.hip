@@ -1,0 +1,430 @@
+// The reference's training pipeline (large-scale jitter) on the device, two launches per batch: raw HWC uint8 images, instance masks
+// and semantic maps -> the (B, 3, H, W) float32 batch, the (N, H, W) uint8 masks, the (B, 1, H, W) semantic maps and the per-instance
+// area / box the annotation filter needs. Replaces, per sample, [3P] mmdet RandomFlip -> Resize(ratio_range, keep_ratio) ->
+// RandomCrop(absolute) -> FilterAnnotations(by_mask) -> Pad(size) -> Normalize(to_rgb), which the reference runs on the CPU: at ratio 2
+// it resizes a float image and every mask to 2048^2 and throws three quarters away. Flip, resize and crop compose into index
+// arithmetic, so every output pixel of the window is ONE gather from the raw sample: 4 source pixels (image) or 1 (masks, semantic map).
+// The random decisions (flip, resized size, window corner) arrive in the descriptor rows. The arithmetic is the rule written down in
+// train_prep.py (`prepare_train_host`), bit for bit:
+//   window    output (y, x) is resized pixel (Y, X) = (y + oy, x + ox); inside the image iff y < min(nh - oy, ch), x < min(nw - ox, cw)
+//   taps      scale = 1 / (d / s) in double; fx = float((k + 0.5) * scale - 0.5), two separately rounded double operations;
+//             i = floor(fx), fx -= i, clamped at both ends; a0 = 1 - fx, a1 = fx (float32: the image is float from the loader on)
+//   pixel     R = float(float(p[i0] a0) + float(p[i1] a1)) per source row; v = float(float(R0 b0) + float(R1 b1));
+//             value = float(float(v - mean) * (1 / std)); under flip source column c is read at w - 1 - c
+//   nearest   row min(floor(Y * scale), h - 1) in double, columns likewise and mirrored under flip; a mask pixel is set where the
+//             source byte is non-zero, the semantic map copies the byte
+//   outside   the image planes hold one constant per plane, masks 0, the semantic map seg_pad
+// The rounding of (k + 0.5) * scale - 0.5 decides which source pixel a tap lands on and every product and sum above is rounded on its
+// own, so nothing here may be contracted into a fused multiply-add: the file is built with contraction off (the flag below, and the
+// pragma for a build that ignores the flag line).
+//
+// Image kernel: the tile geometry of image_prep.hip -- a workgroup of 4 wavefronts owns a 16 x 256 tile of one image's output planes,
+// a lane 4 consecutive columns, non-temporal float4 stores when W % 4 == 0. Only the window is computed. The source bytes a tile needs
+// are staged into LDS with aligned dword loads when they fit TP_LDS_BYTES (always when upsampling, where up to 4 output pixels share a
+// source pixel at ratio 2); a tile that downsamples by more than ~1.5 x reads its taps from global memory. A dword that is not wholly
+// inside the image's bytes is assembled from guarded byte loads: nothing outside offset .. offset + h * pitch is read. The workgroup of
+// an image's first tile also initialises the statistics rows of the image's instances, so the caller clears nothing.
+//
+// Plane kernel: one 16 x 256 tile of one instance mask or one semantic map per workgroup, one byte gathered per pixel, 4 pixels packed
+// into one dword store when W % 4 == 0. A mask tile reduces its area, and the smallest / largest set column and row, inside the
+// wavefront from the ballots of the 4 pixel columns (population count; first and last set lane = the cross-lane minimum and maximum),
+// combines the 4 wavefronts through LDS and leaves with one atomicAdd / atomicMin / atomicMax each on the instance's int32
+// statistics row -- issued by one lane, and only by tiles that hold a set pixel.
+//
+// build-flags: -ffp-contract=off
+#include "cgg_common.h"
+
+#pragma clang fp contract(off)
+
+#define TP_TW 256
+#define TP_TH 16
+#define TP_LDS_BYTES 32768
+#define TP_IMG_COLS 12 /* byte offset, h, w, pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset or -1 */
+#define TP_INST_COLS 3 /* image index, byte offset, pitch */
+
+struct TpConst {
+  float mean[3], rstd[3], pad[3];
+  int to_rgb;
+};
+
+// rule 2 for one resized index k of an axis with source length s: taps i0 / i1 and their float32 weights
+__device__ __forceinline__ void tp_coef(int k, int s, double scale, int& i0, int& i1, float& a0, float& a1) {
+  const double t = ((double)k + 0.5) * scale;
+  float fx = (float)(t - 0.5);
+  const float fl = floorf(fx);
+  int i = (int)fl;
+  fx -= fl;
+  if (i < 0) {
+    i = 0;
+    fx = 0.f;
+  }
+  if (i >= s - 1) {
+    i = s - 1;
+    fx = 0.f;
+  }
+  a0 = 1.f - fx;
+  a1 = fx;
+  i0 = i;
+  i1 = min(i + 1, s - 1);
+}
+
+// rule 3: the source index of resized index k
+__device__ __forceinline__ int tp_nearest(int k, int s, double scale) { return min((int)floor((double)k * scale), s - 1); }
+
+__device__ __forceinline__ float tp_pixel(int p00, int p01, int p10, int p11, float a0, float a1, float b0, float b1) {
+  const float r0 = (float)p00 * a0 + (float)p01 * a1, r1 = (float)p10 * a0 + (float)p11 * a1;
+  return r0 * b0 + r1 * b1;
+}
+
+__global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                                                    TpConst cst, float* __restrict__ out, int32_t* __restrict__ stats,
+                                                                    int H, int W, int ch, int cw) {
+  __shared__ uint32_t lds[TP_LDS_BYTES / 4];
+  const int b = blockIdx.z;
+  const int32_t* d = table + TP_IMG_COLS * b;
+  const int off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8];
+  const int eh = min(nh - oy, ch), ew = min(nw - ox, cw);     // the image's extent inside the plane (>= 1: oy <= max(nh - ch, 0))
+  const int x0 = blockIdx.x * TP_TW, y0 = blockIdx.y * TP_TH;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double sx = 1.0 / ((double)nw / (double)w), sy = 1.0 / ((double)nh / (double)h);
+
+  if (blockIdx.x == 0 && blockIdx.y == 0) {                    // the statistics rows of this image's instances: 0, +max, +max, -1, -1
+    const int first = d[9], n = d[10];
+    for (int t = threadIdx.x; t < 5 * n; t += 256) {
+      const int j = t % 5;
+      stats[(size_t)5 * first + t] = j == 0 ? 0 : (j <= 2 ? INT32_MAX : -1);
+    }
+  }
+
+  // ---- the tile's source span (workgroup-uniform) and its LDS image -----------------------------------------------------------
+  const bool inside = x0 < ew && y0 < eh;
+  int r0 = 0, cb0 = 0, ls = 0;
+  bool use_lds = false;
+  if (inside) {
+    int i0, i1, r1, cb1, lo_c, hi_c;
+    float a0, a1;
+    tp_coef(y0 + oy, h, sy, r0, i1, a0, a1);
+    tp_coef(min(y0 + TP_TH, eh) - 1 + oy, h, sy, i0, r1, a0, a1);
+    tp_coef(x0 + ox, w, sx, lo_c, i1, a0, a1);
+    tp_coef(min(x0 + TP_TW, ew) - 1 + ox, w, sx, i0, hi_c, a0, a1);
+    if (flip) {                                               // columns lo_c .. hi_c of the mirrored image
+      const int t = w - 1 - hi_c;
+      hi_c = w - 1 - lo_c;
+      lo_c = t;
+    }
+    cb0 = 3 * lo_c;
+    cb1 = 3 * (hi_c + 1);
+    const int nrows = r1 - r0 + 1, nbytes = cb1 - cb0;
+    ls = (nbytes + 6) & ~3;                       // row stride in LDS: the bytes, up to 3 of phase, rounded up to dwords
+    use_lds = (long long)nrows * ls <= TP_LDS_BYTES;
+    if (use_lds) {
+      const int lo = off, hi = off + h * pitch;  // the image's bytes
+      for (int rr = wv; rr < nrows; rr += 4) {
+        const int a = off + (r0 + rr) * pitch + cb0, phase = a & 3, a4 = a - phase;
+        const int ndw = (phase + nbytes + 3) >> 2;   // <= ls / 4
+        for (int j = lane; j < ndw; j += 64) {
+          const int g = a4 + 4 * j;
+          uint32_t v;
+          if (g >= lo && g <= hi - 4) {
+            v = *reinterpret_cast<const uint32_t*>(src + g);
+          } else {
+            v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (g + q >= lo && g + q < hi) v |= (uint32_t)src[g + q] << (8 * q);
+          }
+          lds[(rr * ls >> 2) + j] = v;
+        }
+      }
+    }
+  }
+  if (use_lds) __syncthreads();                    // uniform: every wavefront of the workgroup takes the same side
+  const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
+
+  // ---- this lane's 4 columns ----------------------------------------------------------------------------------------------------
+  const int xl = x0 + 4 * lane;
+  int xi0[4], xi1[4];
+  float xa0[4], xa1[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    xi0[c] = xi1[c] = 0;
+    xa0[c] = xa1[c] = 0.f;
+    if (inside && xl + c < ew) {
+      tp_coef(xl + c + ox, w, sx, xi0[c], xi1[c], xa0[c], xa1[c]);
+      xi0[c] = 3 * (flip ? w - 1 - xi0[c] : xi0[c]);
+      xi1[c] = 3 * (flip ? w - 1 - xi1[c] : xi1[c]);
+    }
+  }
+  const bool vec = (W & 3) == 0;
+  const size_t plane = (size_t)H * W;
+
+#pragma unroll 1
+  for (int r = 0; r < TP_TH / 4; ++r) {
+    const int y = y0 + 4 * wv + r;
+    if (y >= H || xl >= W) break;
+    float v[3][4];
+    const bool yin = y < eh;
+    int j0 = 0, j1 = 0;
+    float b0 = 0.f, b1 = 0.f;
+    if (inside && yin) tp_coef(y + oy, h, sy, j0, j1, b0, b1);
+    // byte address of column-byte 0 of the two source rows, in LDS (phase included, relative to cb0) or in global memory
+    int base0, base1;
+    if (use_lds) {
+      base0 = (j0 - r0) * ls + ((off + j0 * pitch + cb0) & 3) - cb0;
+      base1 = (j1 - r0) * ls + ((off + j1 * pitch + cb0) & 3) - cb0;
+    } else {
+      base0 = off + j0 * pitch;
+      base1 = off + j1 * pitch;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int x = xl + c;
+      if (inside && yin && x < ew) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const int chn = cst.to_rgb ? 2 - q : q;
+          int p00, p01, p10, p11;
+          if (use_lds) {
+            p00 = lb[base0 + xi0[c] + chn], p01 = lb[base0 + xi1[c] + chn];
+            p10 = lb[base1 + xi0[c] + chn], p11 = lb[base1 + xi1[c] + chn];
+          } else {
+            p00 = src[base0 + xi0[c] + chn], p01 = src[base0 + xi1[c] + chn];
+            p10 = src[base1 + xi0[c] + chn], p11 = src[base1 + xi1[c] + chn];
+          }
+          const float o = tp_pixel(p00, p01, p10, p11, xa0[c], xa1[c], b0, b1);
+          v[q][c] = (o - cst.mean[q]) * cst.rstd[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) v[q][c] = cst.pad[q];
+      }
+    }
+    float* o = out + (size_t)b * 3 * plane + (size_t)y * W + xl;
+    if (vec) {                                       // W % 4 == 0 and xl % 4 == 0: xl < W implies xl + 3 < W
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        f32x4 t = {v[q][0], v[q][1], v[q][2], v[q][3]};
+        __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(o + q * plane));
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (xl + c < W) o[q * plane + c] = v[q][c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                                                    const int32_t* __restrict__ itable, uint8_t* __restrict__ masks,
+                                                                    uint8_t* __restrict__ seg, int32_t* __restrict__ stats, int N,
+                                                                    int H, int W, int ch, int cw, int seg_pad) {
+  __shared__ int red[4][5];
+  const int z = blockIdx.z;
+  const bool is_seg = z >= N;                                  // workgroup-uniform: planes N .. N + B - 1 are the semantic maps
+  int b, moff = -1, mpitch = 0;
+  if (is_seg) {
+    b = z - N;
+  } else {
+    b = itable[TP_INST_COLS * z];
+    moff = itable[TP_INST_COLS * z + 1];
+    mpitch = itable[TP_INST_COLS * z + 2];
+  }
+  const int32_t* d = table + TP_IMG_COLS * b;
+  const int h = d[1], w = d[2], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8];
+  if (is_seg) {
+    moff = d[11];
+    mpitch = w;
+  }
+  uint8_t* dst = is_seg ? seg + (size_t)b * H * W : masks + (size_t)z * H * W;
+  const int fill = is_seg ? seg_pad : 0;
+  const bool have = moff >= 0;                                 // a sample without a semantic map: the whole plane is seg_pad
+  const int eh = have ? min(nh - oy, ch) : 0, ew = have ? min(nw - ox, cw) : 0;
+  const int x0 = blockIdx.x * TP_TW, y0 = blockIdx.y * TP_TH;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double sx = 1.0 / ((double)nw / (double)w), sy = 1.0 / ((double)nh / (double)h);
+
+  const int xl = x0 + 4 * lane;
+  int rx[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    rx[c] = 0;
+    if (xl + c < ew) {
+      const int i = tp_nearest(xl + c + ox, w, sx);
+      rx[c] = flip ? w - 1 - i : i;
+    }
+  }
+  const bool vec = (W & 3) == 0;
+  int area = 0, ymin = INT32_MAX, ymax = -1;                   // wavefront-uniform: they are built from ballots
+  unsigned long long cols[4] = {0, 0, 0, 0};
+
+#pragma unroll 1
+  for (int r = 0; r < TP_TH / 4; ++r) {
+    const int y = y0 + 4 * wv + r;                             // wavefront-uniform
+    if (y >= H) break;
+    const bool yin = y < eh;
+    const int rowbase = yin ? moff + tp_nearest(y + oy, h, sy) * mpitch : 0;
+    int v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      v[c] = fill;
+      if (yin && xl + c < ew) {
+        const int p = src[rowbase + rx[c]];
+        v[c] = is_seg ? p : (p != 0);
+      }
+    }
+    if (!is_seg) {
+      unsigned long long row = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const unsigned long long m = __ballot(v[c] != 0);      // pixels outside the extent or the plane are 0 here
+        area += __popcll(m);
+        cols[c] |= m;
+        row |= m;
+      }
+      if (row) {
+        ymin = min(ymin, y);
+        ymax = max(ymax, y);
+      }
+    }
+    if (xl < W) {
+      uint8_t* o = dst + (size_t)y * W + xl;
+      if (vec) {                                               // W % 4 == 0 and xl % 4 == 0: a whole, aligned dword
+        *reinterpret_cast<uint32_t*>(o) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (xl + c < W) o[c] = (uint8_t)v[c];
+      }
+    }
+  }
+
+  if (!is_seg) {                                               // workgroup-uniform
+    int xmin = INT32_MAX, xmax = -1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (cols[c]) {                                           // first / last lane with a set pixel in column c of its four
+        xmin = min(xmin, x0 + 4 * (int)__builtin_ctzll(cols[c]) + c);
+        xmax = max(xmax, x0 + 4 * (63 - (int)__builtin_clzll(cols[c])) + c);
+      }
+    if (lane == 0) {
+      red[wv][0] = area;
+      red[wv][1] = xmin;
+      red[wv][2] = ymin;
+      red[wv][3] = xmax;
+      red[wv][4] = ymax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int a = 0, x_lo = INT32_MAX, y_lo = INT32_MAX, x_hi = -1, y_hi = -1;
+      for (int k = 0; k < 4; ++k) {
+        a += red[k][0];
+        x_lo = min(x_lo, red[k][1]);
+        y_lo = min(y_lo, red[k][2]);
+        x_hi = max(x_hi, red[k][3]);
+        y_hi = max(y_hi, red[k][4]);
+      }
+      if (a > 0) {
+        int32_t* s = stats + (size_t)5 * z;
+        atomicAdd(s, a);
+        atomicMin(s + 1, x_lo);
+        atomicMin(s + 2, y_lo);
+        atomicMax(s + 3, x_hi);
+        atomicMax(s + 4, y_hi);
+      }
+    }
+  }
+}
+
+extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                                 const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N, const float* mean,
+                                 const float* std_, const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img,
+                                 uint8_t* masks, uint8_t* seg, int32_t* stats, int H, int W, cgg_stream_t stream) {
+  const char* me = "cgg_train_prep_u8";
+  CGG_REQUIRE(staged && img_table_host && mean && std_ && pad_val && img, CGG_EINVAL, "%s: null pointer", me);
+  CGG_REQUIRE(N >= 0 && (N == 0 || (inst_table_host && masks && stats)), CGG_EINVAL,
+              "%s: N = %d instances need inst_table_host, masks and stats", me, N);
+  CGG_REQUIRE(B >= 1 && H >= 1 && W >= 1, CGG_EINVAL, "%s: B, H, W must be >= 1 (got %d, %d, %d)", me, B, H, W);
+  CGG_REQUIRE(crop_h >= 1 && crop_w >= 1 && crop_h <= H && crop_w <= W, CGG_EINVAL,
+              "%s: the crop window %d x %d must be >= 1 and fit the %d x %d plane", me, crop_h, crop_w, H, W);
+  CGG_REQUIRE(seg_pad >= 0 && seg_pad <= 255, CGG_EINVAL, "%s: seg_pad must be a byte (got %d)", me, seg_pad);
+  CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && H <= CGG_IMAGE_PREP_MAX_DIM && W <= CGG_IMAGE_PREP_MAX_DIM &&
+                  (int64_t)N + B <= CGG_IMAGE_PREP_MAX_DIM,
+              CGG_EUNSUPPORTED, "%s: B + N, H, W must be <= %d (got %d + %d, %d, %d)", me, CGG_IMAGE_PREP_MAX_DIM, B, N, H, W);
+  // the kernels form byte addresses up to 7 past an image's end in int arithmetic before they guard them
+  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
+              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
+  CGG_REQUIRE(img_table_offset >= 0 && (img_table_offset & 3) == 0 && img_table_offset + (int64_t)B * TP_IMG_COLS * 4 <= staged_bytes,
+              CGG_EINVAL, "%s: the image table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
+              (long long)img_table_offset, (long long)staged_bytes);
+  CGG_REQUIRE(inst_table_offset >= 0 && (inst_table_offset & 3) == 0 && inst_table_offset + (int64_t)N * TP_INST_COLS * 4 <= staged_bytes,
+              CGG_EINVAL, "%s: the instance table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, N,
+              (long long)inst_table_offset, (long long)staged_bytes);
+  CGG_REQUIRE((((uintptr_t)staged) & 3u) == 0 && (((uintptr_t)stats) & 3u) == 0, CGG_EALIGN, "%s: staged and stats must be 4-byte aligned",
+              me);
+  CGG_REQUIRE((W & 3) != 0 || (cgg_aligned16(img) && (((uintptr_t)masks) & 3u) == 0 && (((uintptr_t)seg) & 3u) == 0), CGG_EALIGN,
+              "%s: when W %% 4 == 0, img must be 16-byte and masks / seg 4-byte aligned", me);
+  for (int c = 0; c < 3; ++c)
+    CGG_REQUIRE(std_[c] != 0.f && std_[c] == std_[c] && mean[c] == mean[c] && pad_val[c] == pad_val[c], CGG_EINVAL,
+                "%s: mean / std / pad_val must be numbers and std non-zero (channel %d)", me, c);
+  int64_t next = 0;
+  for (int b = 0; b < B; ++b) {
+    const int32_t* d = img_table_host + TP_IMG_COLS * b;
+    const int64_t off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8], first = d[9],
+                  n = d[10], soff = d[11];
+    CGG_REQUIRE(h >= 1 && w >= 1 && nh >= 1 && nw >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld -> %lld x %lld)", me, b,
+                (long long)h, (long long)w, (long long)nh, (long long)nw);
+    CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+                "%s: image %d is %lld x %lld, larger than %d on a side", me, b, (long long)h, (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+    CGG_REQUIRE(oy >= 0 && ox >= 0 && oy <= (nh > crop_h ? nh - crop_h : 0) && ox <= (nw > crop_w ? nw - crop_w : 0), CGG_EINVAL,
+                "%s: image %d: the window at (%lld, %lld) lies outside the %lld x %lld resized image (crop %d x %d)", me, b,
+                (long long)oy, (long long)ox, (long long)nh, (long long)nw, crop_h, crop_w);
+    CGG_REQUIRE(flip == 0 || flip == 1, CGG_EINVAL, "%s: image %d: flip must be 0 or 1 (got %lld)", me, b, (long long)flip);
+    CGG_REQUIRE(pitch >= 3 * w, CGG_EINVAL, "%s: image %d: row pitch %lld < 3 * w = %lld", me, b, (long long)pitch, (long long)(3 * w));
+    CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
+                "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
+                (long long)(off + h * pitch), (long long)staged_bytes);
+    CGG_REQUIRE(n >= 0 && first == next && first + n <= N, CGG_EINVAL,
+                "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
+                (long long)first, (long long)(first + n), (long long)next, N);
+    CGG_REQUIRE(!seg || soff == -1 || (soff >= 0 && soff + h * w <= staged_bytes), CGG_EINVAL,
+                "%s: image %d: the semantic map at byte %lld extends past the %lld staged bytes", me, b, (long long)soff,
+                (long long)staged_bytes);
+    for (int64_t i = first; i < first + n; ++i) {
+      const int32_t* t = inst_table_host + TP_INST_COLS * i;
+      const int64_t ib = t[0], ioff = t[1], ipitch = t[2];
+      CGG_REQUIRE(ib >= 0 && ib < B, CGG_EINVAL, "%s: instance %lld: image index %lld out of range (B = %d)", me, (long long)i,
+                  (long long)ib, B);
+      CGG_REQUIRE(ib == b, CGG_EINVAL, "%s: instance %lld belongs to image %lld but lies in image %d's range", me, (long long)i,
+                  (long long)ib, b);
+      CGG_REQUIRE(ipitch >= w, CGG_EINVAL, "%s: instance %lld: row pitch %lld < w = %lld", me, (long long)i, (long long)ipitch,
+                  (long long)w);
+      CGG_REQUIRE(ioff >= 0 && ioff + h * ipitch <= staged_bytes, CGG_EINVAL,
+                  "%s: instance %lld (bytes %lld .. %lld) extends past the %lld staged bytes", me, (long long)i, (long long)ioff,
+                  (long long)(ioff + h * ipitch), (long long)staged_bytes);
+    }
+    next = first + n;
+  }
+  CGG_REQUIRE(next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)next, N);
+  TpConst cst;
+  for (int q = 0; q < 3; ++q) {
+    cst.mean[q] = mean[q];
+    cst.rstd[q] = (float)(1.0 / (double)std_[q]);
+    const float p = pad_val[to_rgb ? 2 - q : q];                 // Pad runs ahead of Normalize: pad_val is in source channel order
+    cst.pad[q] = (p - cst.mean[q]) * cst.rstd[q];
+  }
+  cst.to_rgb = to_rgb ? 1 : 0;
+  const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
+  const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
+  hipLaunchKernelGGL(cgg_train_prep_image_kernel, dim3(gx, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, staged, table, cst, img,
+                     stats, H, W, crop_h, crop_w);
+  CGG_CHECK_LAUNCH(me);
+  const int planes = N + (seg ? B : 0);
+  if (planes > 0) {
+    hipLaunchKernelGGL(cgg_train_prep_plane_kernel, dim3(gx, gy, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, staged, table,
+                       reinterpret_cast<const int32_t*>(staged + inst_table_offset), masks, seg, stats, N, H, W, crop_h, crop_w, seg_pad);
+    CGG_CHECK_LAUNCH(me);
+  }
+  return CGG_OK;
+}

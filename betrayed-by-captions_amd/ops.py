@@ -2624,6 +2624,64 @@ def image_prep_u8(staged, table, out, mean, std, pad_val=0.0, to_rgb=True, pad_b
     return out
 
 
+TRAIN_PREP_IMG_COLS = 12      # byte offset, h, w, row pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset / -1
+TRAIN_PREP_INST_COLS = 3      # image index, byte offset, row pitch
+
+
+def train_prep_u8(staged, img_table, inst_table, img, masks, seg, stats, mean, std, pad_val=0.0, to_rgb=True, crop_size=None, seg_pad=255,
+                  img_table_offset=0, inst_table_offset=None, staged_bytes=None):
+    """Flip + jittered Resize + RandomCrop + Pad + Normalize(to_rgb) of a whole batch of raw samples -- images, instance bitmaps,
+    semantic maps -- in two launches (`cgg_train_prep_u8`, no synchronisation; train_prep.py states the rule). staged: DEVICE uint8
+    (n,) -- the two tables at bytes `img_table_offset` / `inst_table_offset` and the planes; img_table (B, 12) / inst_table (N, 3):
+    HOST int32 copies of those rows, read for validation during the call; img (B, 3, H, W) f32, masks (N, H, W) u8, seg (B, 1, H, W)
+    u8 or None, stats (N, 5) i32: DEVICE, contiguous, every element written (the caller clears nothing). crop_size (h, w) defaults
+    to the plane. Returns (img, masks, seg, stats)."""
+    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
+        raise CggError(f'train_prep_u8: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
+    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_INST_COLS)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
+            raise CggError(f'train_prep_u8: {name} must be a (rows, {cols}) torch.int32 tensor '
+                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
+        if t.is_cuda or not t.is_contiguous():
+            raise CggError(f'train_prep_u8: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
+    B, N = int(img_table.shape[0]), int(inst_table.shape[0])
+    if B < 1:
+        raise CggError('train_prep_u8: an empty batch')
+    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
+        raise CggError(f'train_prep_u8: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
+                       f'shape {tuple(getattr(img, "shape", ()))})')
+    H, W = int(img.shape[2]), int(img.shape[3])
+    for name, t, shape, dt in (('masks', masks, (N, H, W), torch.uint8), ('seg', seg, (B, 1, H, W), torch.uint8),
+                               ('stats', stats, (N, 5), torch.int32)):
+        if t is None and name == 'seg':
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise CggError(f'train_prep_u8: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
+                           f'shape {tuple(getattr(t, "shape", ()))})')
+        if t.device != img.device:
+            raise CggError(f'train_prep_u8: {name} ({t.device}) and img ({img.device}) live on different devices')
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if nbytes > staged.numel():
+        raise CggError(f'train_prep_u8: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
+    sp, ip = dev_ptr(staged, 'train_prep_u8: staged'), dev_ptr(img, 'train_prep_u8: img')
+    if staged.device != img.device:
+        raise CggError(f'train_prep_u8: staged ({staged.device}) and img ({img.device}) live on different devices')
+    mp = dev_ptr(masks, 'train_prep_u8: masks') if N else None
+    tp = dev_ptr(stats, 'train_prep_u8: stats') if N else None
+    gp = dev_ptr(seg, 'train_prep_u8: seg')
+    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'train_prep_u8: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    if inst_table_offset is None:
+        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
+    with _timed('train_prep_u8', bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)),
+                shape=(B, N, H, W)):
+        rc = _lib_().cgg_train_prep_u8(sp, nbytes, int(img_table_offset), int(inst_table_offset), ctypes.c_void_p(img_table.data_ptr()),
+                                       ctypes.c_void_p(inst_table.data_ptr()) if N else None, B, N, m, s, p, int(bool(to_rgb)),
+                                       int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
+    check(rc, 'cgg_train_prep_u8')
+    return img, masks, seg, stats
+
+
 # ------------------------------------------------------------------------------------------------
 # caption search: one beam-search step for a whole batch, decided on the device (caption_search.py states the rule)
 # ------------------------------------------------------------------------------------------------

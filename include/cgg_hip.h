@@ -695,6 +695,41 @@ int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table
                       const float* mean, const float* std, const float* pad_val, int to_rgb, int pad_before_norm, float* out, int Hb,
                       int Wb, cgg_stream_t stream);
 
+/* The reference's training pipeline (large-scale jitter) for a batch of raw samples in TWO launches (csrc/train_prep.hip): [3P] mmdet
+ * RandomFlip -> Resize(ratio_range, keep_ratio) -> RandomCrop(absolute, recompute_bbox) -> FilterAnnotations(by_mask) -> Pad(size) ->
+ * Normalize(to_rgb) per sample, from HWC uint8 images, uint8 instance bitmaps and uint8 semantic maps to img (B, 3, H, W) f32 NCHW,
+ * masks (N, H, W) u8 (0 / 1), seg (B, 1, H, W) u8 and stats (N, 5) i32 = area, xmin, ymin, xmax, ymax of each output mask (an empty
+ * one: 0, INT32_MAX, INT32_MAX, -1, -1). Flip, resize and crop are index arithmetic: each output pixel is one gather from the raw
+ * sample, the resized sample never exists. The random decisions arrive in the table rows. The arithmetic is the rule of train_prep.py
+ * (`prepare_train_host`), bit for bit: float32 bilinear taps for the image (no 8-bit rounding: the image is float from the loader on),
+ * nearest for masks and semantic maps; it restates the [3P] steps from their published behaviour and claims equality with no
+ * particular mmdet / mmcv / cv2 build.
+ *   staged          DEVICE bytes (4-byte aligned base): the image table at byte `img_table_offset`, the instance table at byte
+ *                   `inst_table_offset` (multiples of 4), and the images (3-byte pixels), instance bitmaps and semantic maps (1-byte
+ *                   pixels, non-zero = set for a bitmap) back to back at arbitrary byte offsets; staged_bytes = how many are valid
+ *   img_table_host  HOST copy of the B image rows of 12 int32: byte offset, h, w, row pitch in bytes (>= 3 w), new_h, new_w, oy, ox
+ *                   (the window's corner in the resized image), flip (0 / 1: horizontal), first instance, instances (the images own
+ *                   consecutive ranges of the N instances, in order), byte offset of the semantic map (rows of w bytes) or -1
+ *   inst_table_host HOST copy of the N instance rows of 3 int32: image index, byte offset, row pitch in bytes (>= w); nullable when
+ *                   N == 0. Both copies are read during the call, for validation only: the kernels read the device rows
+ *   mean, std, pad_val   HOST, 3 floats each; mean / std index the OUTPUT plane (after to_rgb), pad_val the SOURCE channel: outside
+ *                   the image's extent (min(new_h - oy, crop_h) x min(new_w - ox, crop_w)) img holds (pad_val - mean) / std, masks 0,
+ *                   seg seg_pad. value = float(float(x - mean) * float(1 / std))
+ *   img, masks, seg every element is written exactly once; the caller clears nothing, stats included (its rows are initialised by the
+ *                   first launch and reduced into by the second with int32 atomicAdd / atomicMin / atomicMax, at most one each per
+ *                   workgroup tile). masks / stats nullable when N == 0; seg nullable (no semantic maps: the table column is
+ *                   ignored). img 16-byte, masks / seg 4-byte aligned when W % 4 == 0; stats 4-byte aligned
+ * Does not synchronise. Checked on the host before the first launch: CGG_EINVAL for null pointers, B < 1, a zero-sized image, a
+ * window outside the resized image (oy > max(new_h - crop_h, 0), likewise ox), a crop larger than the plane, a pitch too small, any
+ * plane or table extending past staged_bytes, an instance whose image index is out of range or not the image that owns it, instance
+ * ranges that do not tile 0 .. N, std == 0; CGG_EUNSUPPORTED beyond the index arithmetic of the kernels: B + N, h, w, H, W <=
+ * CGG_IMAGE_PREP_MAX_DIM and staged_bytes <= 2^31 - 9; CGG_EALIGN as above. The kernels read no byte outside the table rows and
+ * offset .. offset + h * pitch of each image, bitmap and map. */
+int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                      const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N, const float* mean, const float* std,
+                      const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img, uint8_t* masks, uint8_t* seg,
+                      int32_t* stats, int H, int W, cgg_stream_t stream);
+
 /* One step of the caption beam search for a whole batch of images, decision and bookkeeping on the device (csrc/beam_step.hip):
  * the loop body of the reference's beam_search, open_set/utils/eval/inference.py:113-149 -- mean over the decoder blocks' generator
  * outputs, log-softmax, (log p + parent weight) / length^alpha, the top `beam` of an image's live rows, the walk over them that

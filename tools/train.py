@@ -5,13 +5,16 @@ process per GPU under `--launcher pytorch` (torchrun; RCCL), detector from `cfg.
 `cfg.optimizer`, `--resume-from` / periodic mmcv-layout checkpoints in `--work-dir` -- and nothing of mmcv's runner /
 hook machinery. Datasets are out of this build's scope (no COCO on the box): samples come from a user function
 (`--data pkg.module:function`, a generator of raw sample dicts that go through OpenFormatBundle + collate) or, by
-default, from the synthetic COCO-shaped stream used by bench.py.
+default, from the synthetic COCO-shaped stream used by bench.py. Samples whose `img` is uint8 are RAW -- image, instance bitmaps,
+labels, captions as the dataset loads them -- and go through `cfg.data.train.pipeline` on the device (cgg_amd.train_prep:
+flip, large-scale jitter, crop, annotation filter, pad, normalize); `--synthetic-u8 HxW` generates such samples.
 
     python tools/train.py configs/instance/coco_b48n17.py --work-dir work --max-iters 100 --synthetic 512
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py CONFIG --launcher pytorch
 """
 import argparse
 import importlib
+import itertools
 import json
 import os
 import sys
@@ -49,7 +52,13 @@ def parse_args(argv=None):
     p.add_argument('--max-iters', type=int, default=None, help='stop after this many iterations')
     p.add_argument('--samples-per-gpu', type=int, default=None, help='default: cfg.data.samples_per_gpu or 2')
     p.add_argument('--synthetic', type=int, default=512, help='synthetic sample size (H = W) when --data is not given')
-    p.add_argument('--data', default=None, help='pkg.module:function -> iterable of raw sample dicts')
+    p.add_argument('--data', default=None,
+                   help='pkg.module:function(cfg, rank, world) -> iterable of sample dicts: float `img` = already augmented, padded '
+                        'and formatted; uint8 `img` (h, w, 3) BGR with gt_masks (n, h, w) bitmaps and gt_labels = raw, prepared on '
+                        'the device by the config\'s data.train.pipeline')
+    p.add_argument('--synthetic-u8', default=None, metavar='HxW',
+                   help='synthetic RAW uint8 samples of this size (e.g. 480x640) with blob masks of mixed sizes instead of '
+                        '--synthetic\'s prepared float samples: exercises the device-side training pipeline without a dataset')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--log-interval', type=int, default=10)
     p.add_argument('--save-interval', type=int, default=0, help='iterations between checkpoints (0: only at the end)')
@@ -72,6 +81,71 @@ def synthetic_samples(size, num_classes, seed, vocab=30522):
                    gt_caption_nouns_ids=b['gt_caption_nouns_ids'][0].numpy(),
                    gt_caption_nouns_mask=b['gt_caption_nouns_mask'][0].numpy())
         i += 1
+
+
+def synthetic_u8_samples(hw, num_classes, seed, vocab=30522):
+    """Endless stream of RAW samples: a uint8 BGR image, rectangle / ellipse bitmaps from a few pixels to a third of the image on a
+    side, labels and captions -- what the dataset's loaders hand to the training pipeline."""
+    i = 0
+    while True:
+        b = synthetic.train_batch(1, hw[0], hw[1], num_classes=num_classes, max_inst=7, vocab=vocab, seed=seed + i)
+        rng = np.random.default_rng(seed + i)
+        yield dict(img=rng.integers(0, 256, size=(hw[0], hw[1], 3), dtype=np.uint8), filename=f'synthetic_{i}.jpg',
+                   ori_filename=f'synthetic_{i}.jpg', gt_labels=b['gt_labels'][0].numpy(), gt_masks=b['gt_masks'][0].numpy(),
+                   gt_caption_ids=b['gt_caption_ids'][0].numpy(), gt_caption_mask=b['gt_caption_mask'][0].numpy(),
+                   gt_caption_nouns_ids=b['gt_caption_nouns_ids'][0].numpy(),
+                   gt_caption_nouns_mask=b['gt_caption_nouns_mask'][0].numpy())
+        i += 1
+
+
+def is_raw(sample):
+    img = sample.get('img') if hasattr(sample, 'get') else None
+    return getattr(img, 'dtype', None) in (np.uint8, torch.uint8)
+
+
+def raw_batches(samples, samples_per_gpu, prep, rng, name='the sample stream'):
+    """Batches of RAW samples through the device-side training pipeline (`prep`: a cgg_amd.train_prep.TrainPrep; `rng`: the
+    numpy Generator the random decisions are drawn from). [3P] mmdet draws another sample when no annotation survives the crop; so
+    does this: a sample that comes back without an instance is replaced by the next raw sample of the stream, prepared by a second,
+    one-sample call and copied into its slot of the batch. After 8 x samples_per_gpu replacements within one batch the stream is
+    taken to hold nothing but empty samples, and a CggError names it."""
+    from cgg_amd._lib import CggError
+    from cgg_amd.train_prep import draw_train_params
+    it = iter(samples)
+    spec = prep.spec
+
+    def draw(group):
+        return [draw_train_params(rng, tuple(s['img'].shape[:2]), spec) for s in group]
+
+    while True:
+        group = []
+        for raw in it:
+            group.append(raw)
+            if len(group) == samples_per_gpu:
+                break
+        if len(group) < samples_per_gpu:
+            return
+        kw, kept = prep.prep(group, draw(group))
+        replaced = 0
+        for b in range(samples_per_gpu):
+            while kept[b] == 0:
+                if replaced >= 8 * samples_per_gpu:
+                    raise CggError(f'tools/train.py: {replaced} samples of {name} in a row came out of the training pipeline without '
+                                   'a single instance inside the crop window; a stream of empty samples cannot be trained on')
+                raw = next(it, None)
+                if raw is None:
+                    return
+                replaced += 1
+                one, k1 = prep.prep([raw], draw([raw]))
+                kept[b] = k1[0]
+                if k1[0] == 0:
+                    continue
+                for key, val in one.items():
+                    if key in ('img', 'gt_semantic_seg'):
+                        kw[key][b].copy_(val[0])
+                    else:
+                        kw[key][b] = val[0]
+        yield kw
 
 
 KEYS = ['img', 'gt_bboxes', 'gt_labels', 'gt_masks', 'gt_caption_ids', 'gt_caption_mask', 'gt_caption_nouns_ids',
@@ -147,22 +221,44 @@ def main(argv=None):
     spg = args.samples_per_gpu or (cfg.get('data') or {}).get('samples_per_gpu', 2)
     head = cfg.model['panoptic_head']
     num_classes = head['num_things_classes'] + head['num_stuff_classes']
+    stream_name = f'--data {args.data}' if args.data else f'--synthetic-u8 {args.synthetic_u8}' if args.synthetic_u8 else '--synthetic'
+    vocab = ((head.get('caption_generator') or {}).get('nb_tokens')) or 30522          # token ids must index the table
     if args.data:
         mod, fn = args.data.split(':')
         samples = getattr(importlib.import_module(mod), fn)(cfg, rank, world)
+    elif args.synthetic_u8:
+        try:
+            hw = tuple(int(v) for v in args.synthetic_u8.lower().split('x'))
+            assert len(hw) == 2 and min(hw) >= 1
+        except (ValueError, AssertionError):
+            raise SystemExit(f'--synthetic-u8 {args.synthetic_u8!r}: expected HxW, e.g. 480x640')
+        samples = synthetic_u8_samples(hw, num_classes, seed=1000 * rank + seed, vocab=vocab)
     else:
-        vocab = ((head.get('caption_generator') or {}).get('nb_tokens')) or 30522      # token ids must index the table
         samples = synthetic_samples(args.synthetic, num_classes, seed=1000 * rank + seed, vocab=vocab)
     max_iters = args.max_iters or (cfg.get('runner') or {}).get('max_iters')
     if not max_iters:
         # EpochBasedRunner configs (max_epochs) need the dataset length, which this driver does not have
         raise SystemExit('tools/train.py: the config has no runner.max_iters (epoch-based runner); pass --max-iters N')
 
+    # raw (uint8) samples are augmented on the device; float samples are already augmented and keep the formatting path
+    samples = iter(samples)
+    first = next(samples, None)
+    samples = itertools.chain([] if first is None else [first], samples)
+    if first is not None and is_raw(first):
+        from cgg_amd._lib import CggError
+        from cgg_amd.train_prep import TrainPrep
+        pipeline = ((cfg.get('data') or {}).get('train') or {}).get('pipeline')
+        if not pipeline:
+            raise CggError('tools/train.py: raw uint8 samples need cfg.data.train.pipeline (the training pipeline they go through)')
+        feed = raw_batches(samples, spg, TrainPrep(pipeline, device), np.random.default_rng(1000 * rank + seed), stream_name)
+    else:
+        feed = batches(samples, spg, device)
+
     log = open(os.path.join(work_dir, 'train.log.json'), 'a') if rank == 0 else None
     t0 = time.perf_counter()
     it = start_iter
     with runtime.precision_scope(args.precision):
-        for data in batches(samples, spg, device):
+        for data in feed:
             if it >= max_iters:
                 break
             schedule.apply(it)
