@@ -112,6 +112,8 @@ PROTOTYPES = {
     'cgg_image_prep_u8': (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_vp]),
     'cgg_train_prep_u8': (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp] + [_c_int] * 4 +
                           [_c_vp] * 4 + [_c_int, _c_int, _c_vp]),
+    'cgg_train_prep_panoptic_u8': (_c_int, [_c_vp] + [_c_i64] * 4 + [_c_vp] * 3 + [_c_int] * 3 + [_c_vp] * 3 + [_c_int] * 4 + [_c_vp] * 4 +
+                                   [_c_int, _c_int, _c_vp]),
     'cgg_beam_step_workspace_bytes': (_c_i64, [_c_int] * 3),
     'cgg_beam_step': (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 13 + [_c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     'cgg_beam_step_passes': (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 13 + [_c_int, _c_f, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),

@@ -31,6 +31,9 @@
 // combines the 4 wavefronts through LDS and leaves with one atomicAdd / atomicMin / atomicMax each on the instance's int32
 // statistics row -- issued by one lane, and only by tiles that hold a set pixel.
 //
+// Panoptic samples (cgg_train_prep_panoptic_u8): the image kernel, then ONE kernel that gathers one id of the panoptic id map per output
+// pixel and derives every thing mask, the semantic plane and the statistics from it (stated at the kernel).
+//
 // build-flags: -ffp-contract=off
 #include "cgg_common.h"
 
@@ -337,14 +340,218 @@ __global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t
   }
 }
 
-extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
-                                 const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N, const float* mean,
-                                 const float* std_, const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img,
-                                 uint8_t* masks, uint8_t* seg, int32_t* stats, int H, int W, cgg_stream_t stream) {
-  const char* me = "cgg_train_prep_u8";
+// ---- panoptic samples: every plane from ONE gather of the id map -------------------------------------------------------------------
+#define TP_PAN_COLS 5 /* byte offset of the id map, row pitch in bytes, format (0: int32, 1: R, G, B bytes), first segment row, rows */
+#define TP_SEG_COLS 2 /* id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t */
+#define TP_MAX_SEG CGG_TRAIN_PREP_MAX_SEGMENTS
+
+// the packed (slot, category) of `id` among the n rows sorted by id (lower bound, then equality); an id no row lists: no slot, 255
+__device__ __forceinline__ int tp_find(const int32_t* ids, const int32_t* pks, int n, int id) {
+  int lo = 0, len = n;
+  while (len > 0) {
+    const int half = len >> 1;
+    if (ids[lo + half] < id) {
+      lo += half + 1;
+      len -= half + 1;
+    } else {
+      len = half;
+    }
+  }
+  int r = 255;
+  if (lo < n && ids[lo] == id) r = pks[lo];
+  return r;
+}
+
+// Panoptic kernel: one 16 x 256 tile of ALL of one image's mask planes and of its semantic plane per workgroup (the tile geometry of
+// the plane kernel: a lane owns 4 consecutive columns, a wavefront 4 rows). The image's segment rows sit in LDS (<= 256 rows, 2 KB);
+// each pixel inside the extent gathers one id (rule 3), finds it by binary search and keeps (slot << 8) | category in a register --
+// 16 per lane. The semantic byte is the low byte; plane `first + t` is slot == t + 1. Nearest gathers commute with "compare the id",
+// so this is the plane kernel's output for the bitmaps pan == id. A bit set in LDS records which slots the tile holds: an absent
+// slot's tile is zeros without any reduction; a present one reduces exactly as the plane kernel does (ballots, LDS across the four
+// wavefronts -- two buffers in turn, so one barrier per slot -- then one atomic of each kind from one lane).
+__global__ __launch_bounds__(256) void cgg_train_prep_panoptic_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                                                       const int32_t* __restrict__ ptable,
+                                                                       const int32_t* __restrict__ stable, uint8_t* __restrict__ masks,
+                                                                       uint8_t* __restrict__ seg, int32_t* __restrict__ stats, int H,
+                                                                       int W, int ch, int cw, int seg_pad) {
+  __shared__ int32_t s_id[TP_MAX_SEG], s_pk[TP_MAX_SEG];
+  __shared__ uint32_t s_present[TP_MAX_SEG / 32 + 1];          // bit s: slot field s (1 .. 256) occurs in this tile
+  __shared__ int red[2][4][5];
+  const int b = blockIdx.z;
+  const int32_t* d = table + TP_IMG_COLS * b;
+  const int h = d[1], w = d[2], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8], first = d[9], things = d[10];
+  const int32_t* pd = ptable + TP_PAN_COLS * b;
+  const int moff = pd[0], mpitch = pd[1], rgb = pd[2], sfirst = pd[3], ns = pd[4];
+  if ((int)threadIdx.x < ns) {                                 // ns <= 256: one row per thread
+    s_id[threadIdx.x] = stable[TP_SEG_COLS * (sfirst + (int)threadIdx.x)];
+    s_pk[threadIdx.x] = stable[TP_SEG_COLS * (sfirst + (int)threadIdx.x) + 1];
+  }
+  if (threadIdx.x < TP_MAX_SEG / 32 + 1) s_present[threadIdx.x] = 0;
+  __syncthreads();
+
+  const int eh = min(nh - oy, ch), ew = min(nw - ox, cw);
+  const int x0 = blockIdx.x * TP_TW, y0 = blockIdx.y * TP_TH;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double sx = 1.0 / ((double)nw / (double)w), sy = 1.0 / ((double)nh / (double)h);
+  const int xl = x0 + 4 * lane;
+  const int bpp = rgb ? 3 : 4;
+  int rx[4];                                                   // byte offset of the source pixel inside its row
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    rx[c] = 0;
+    if (xl + c < ew) {
+      const int i = tp_nearest(xl + c + ox, w, sx);
+      rx[c] = bpp * (flip ? w - 1 - i : i);
+    }
+  }
+
+  // ---- one id per pixel -> (slot << 8) | category; outside the extent: no slot, seg_pad
+  int pk[4][4];
+  bool have_last = false;
+  int last_id = 0, last_pk = 0, last_slot = 0;
+#pragma unroll
+  for (int r = 0; r < TP_TH / 4; ++r) {
+    const int y = y0 + 4 * wv + r;
+    const bool yin = y < eh;                                   // eh <= ch <= H
+    const int rowbase = yin ? moff + tp_nearest(y + oy, h, sy) * mpitch : 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      int v = seg_pad;
+      if (yin && xl + c < ew) {
+        const int a = rowbase + rx[c];
+        int id;
+        if (rgb)
+          id = (int)src[a] | ((int)src[a + 1] << 8) | ((int)src[a + 2] << 16);
+        else
+          id = *reinterpret_cast<const int32_t*>(src + a);    // moff, mpitch and the base are multiples of 4
+        if (!have_last || id != last_id) {                     // neighbours mostly share their segment
+          last_pk = tp_find(s_id, s_pk, ns, id);
+          last_id = id;
+          have_last = true;
+        }
+        v = last_pk;
+        const int slot = v >> 8;
+        if (slot != last_slot) {
+          if (slot) atomicOr(&s_present[slot >> 5], 1u << (slot & 31));
+          last_slot = slot;
+        }
+      }
+      pk[r][c] = v;
+    }
+  }
+  __syncthreads();
+
+  const bool vec = (W & 3) == 0;
+  const size_t plane = (size_t)H * W;
+  if (seg != nullptr && xl < W) {
+    uint8_t* dst = seg + (size_t)b * plane;
+#pragma unroll
+    for (int r = 0; r < TP_TH / 4; ++r) {
+      const int y = y0 + 4 * wv + r;
+      if (y < H) {
+        uint8_t* o = dst + (size_t)y * W + xl;
+        if (vec) {                                             // W % 4 == 0 and xl % 4 == 0: a whole, aligned dword
+          *reinterpret_cast<uint32_t*>(o) = (uint32_t)(pk[r][0] & 255) | ((uint32_t)(pk[r][1] & 255) << 8) |
+                                            ((uint32_t)(pk[r][2] & 255) << 16) | ((uint32_t)(pk[r][3] & 255) << 24);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (xl + c < W) o[c] = (uint8_t)(pk[r][c] & 255);
+        }
+      }
+    }
+  }
+
+  int par = 0;
+#pragma unroll 1
+  for (int t = 1; t <= things; ++t) {                          // slot field t = plane first + t - 1
+    uint8_t* dst = masks + (size_t)(first + t - 1) * plane;
+    const bool present = (s_present[t >> 5] >> (t & 31)) & 1u; // workgroup-uniform
+    int area = 0, ymin = INT32_MAX, ymax = -1;
+    unsigned long long cols[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < TP_TH / 4; ++r) {
+      const int y = y0 + 4 * wv + r;                           // wavefront-uniform
+      if (y < H) {
+        int v[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = (pk[r][c] >> 8) == t;   // all 0 where the slot is absent, and outside the extent
+        if (present) {
+          unsigned long long row = 0;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const unsigned long long m = __ballot(v[c] != 0);
+            area += __popcll(m);
+            cols[c] |= m;
+            row |= m;
+          }
+          if (row) {
+            ymin = min(ymin, y);
+            ymax = max(ymax, y);
+          }
+        }
+        if (xl < W) {
+          uint8_t* o = dst + (size_t)y * W + xl;
+          if (vec) {
+            *reinterpret_cast<uint32_t*>(o) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+          } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+              if (xl + c < W) o[c] = (uint8_t)v[c];
+          }
+        }
+      }
+    }
+    if (present) {                                             // workgroup-uniform: the barrier is reached by all or none
+      int xmin = INT32_MAX, xmax = -1;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (cols[c]) {
+          xmin = min(xmin, x0 + 4 * (int)__builtin_ctzll(cols[c]) + c);
+          xmax = max(xmax, x0 + 4 * (63 - (int)__builtin_clzll(cols[c])) + c);
+        }
+      if (lane == 0) {
+        red[par][wv][0] = area;
+        red[par][wv][1] = xmin;
+        red[par][wv][2] = ymin;
+        red[par][wv][3] = xmax;
+        red[par][wv][4] = ymax;
+      }
+      __syncthreads();
+      // the other buffer is written next: a wavefront reaches that write only after the NEXT barrier, which thread 0 reaches
+      // after it has read this one
+      if (threadIdx.x == 0) {
+        int a = 0, x_lo = INT32_MAX, y_lo = INT32_MAX, x_hi = -1, y_hi = -1;
+        for (int k = 0; k < 4; ++k) {
+          a += red[par][k][0];
+          x_lo = min(x_lo, red[par][k][1]);
+          y_lo = min(y_lo, red[par][k][2]);
+          x_hi = max(x_hi, red[par][k][3]);
+          y_hi = max(y_hi, red[par][k][4]);
+        }
+        if (a > 0) {
+          int32_t* s = stats + (size_t)5 * (first + t - 1);
+          atomicAdd(s, a);
+          atomicMin(s + 1, x_lo);
+          atomicMin(s + 2, y_lo);
+          atomicMax(s + 3, x_hi);
+          atomicMax(s + 4, y_hi);
+        }
+      }
+      par ^= 1;
+    }
+  }
+}
+
+// Everything both entry points check about the scalar arguments, the outputs and the image rows, before any launch. `panoptic`: there
+// is no instance table (the things are found in the id map) and no staged semantic map (column 11 must be -1).
+static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset,
+                       int64_t inst_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N,
+                       const float* mean, const float* std_, const float* pad_val, int seg_pad, int crop_h, int crop_w, float* img,
+                       uint8_t* masks, uint8_t* seg, int32_t* stats, int H, int W) {
   CGG_REQUIRE(staged && img_table_host && mean && std_ && pad_val && img, CGG_EINVAL, "%s: null pointer", me);
-  CGG_REQUIRE(N >= 0 && (N == 0 || (inst_table_host && masks && stats)), CGG_EINVAL,
-              "%s: N = %d instances need inst_table_host, masks and stats", me, N);
+  CGG_REQUIRE(N >= 0 && (N == 0 || ((panoptic || inst_table_host) && masks && stats)), CGG_EINVAL,
+              "%s: N = %d instances need %smasks and stats", me, N, panoptic ? "" : "inst_table_host, ");
   CGG_REQUIRE(B >= 1 && H >= 1 && W >= 1, CGG_EINVAL, "%s: B, H, W must be >= 1 (got %d, %d, %d)", me, B, H, W);
   CGG_REQUIRE(crop_h >= 1 && crop_w >= 1 && crop_h <= H && crop_w <= W, CGG_EINVAL,
               "%s: the crop window %d x %d must be >= 1 and fit the %d x %d plane", me, crop_h, crop_w, H, W);
@@ -358,7 +565,8 @@ extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
   CGG_REQUIRE(img_table_offset >= 0 && (img_table_offset & 3) == 0 && img_table_offset + (int64_t)B * TP_IMG_COLS * 4 <= staged_bytes,
               CGG_EINVAL, "%s: the image table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
               (long long)img_table_offset, (long long)staged_bytes);
-  CGG_REQUIRE(inst_table_offset >= 0 && (inst_table_offset & 3) == 0 && inst_table_offset + (int64_t)N * TP_INST_COLS * 4 <= staged_bytes,
+  CGG_REQUIRE(panoptic ||
+                  (inst_table_offset >= 0 && (inst_table_offset & 3) == 0 && inst_table_offset + (int64_t)N * TP_INST_COLS * 4 <= staged_bytes),
               CGG_EINVAL, "%s: the instance table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, N,
               (long long)inst_table_offset, (long long)staged_bytes);
   CGG_REQUIRE((((uintptr_t)staged) & 3u) == 0 && (((uintptr_t)stats) & 3u) == 0, CGG_EALIGN, "%s: staged and stats must be 4-byte aligned",
@@ -388,10 +596,13 @@ extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
     CGG_REQUIRE(n >= 0 && first == next && first + n <= N, CGG_EINVAL,
                 "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
                 (long long)first, (long long)(first + n), (long long)next, N);
+    CGG_REQUIRE(!panoptic || soff == -1, CGG_EINVAL,
+                "%s: image %d: the semantic-map offset must be -1 (got %lld): the semantic plane comes from the id map", me, b,
+                (long long)soff);
     CGG_REQUIRE(!seg || soff == -1 || (soff >= 0 && soff + h * w <= staged_bytes), CGG_EINVAL,
                 "%s: image %d: the semantic map at byte %lld extends past the %lld staged bytes", me, b, (long long)soff,
                 (long long)staged_bytes);
-    for (int64_t i = first; i < first + n; ++i) {
+    for (int64_t i = first; i < (panoptic ? first : first + n); ++i) {
       const int32_t* t = inst_table_host + TP_INST_COLS * i;
       const int64_t ib = t[0], ioff = t[1], ipitch = t[2];
       CGG_REQUIRE(ib >= 0 && ib < B, CGG_EINVAL, "%s: instance %lld: image index %lld out of range (B = %d)", me, (long long)i,
@@ -407,6 +618,13 @@ extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
     next = first + n;
   }
   CGG_REQUIRE(next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)next, N);
+  return CGG_OK;
+}
+
+// the first launch of both entry points: the image planes, and the statistics rows initialised
+static int tp_launch_image(const char* me, const uint8_t* staged, const int32_t* table, int B, const float* mean, const float* std_,
+                           const float* pad_val, int to_rgb, int crop_h, int crop_w, float* img, int32_t* stats, int H, int W,
+                           cgg_stream_t stream) {
   TpConst cst;
   for (int q = 0; q < 3; ++q) {
     cst.mean[q] = mean[q];
@@ -416,14 +634,100 @@ extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
   }
   cst.to_rgb = to_rgb ? 1 : 0;
   const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
-  const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
   hipLaunchKernelGGL(cgg_train_prep_image_kernel, dim3(gx, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, staged, table, cst, img,
                      stats, H, W, crop_h, crop_w);
   CGG_CHECK_LAUNCH(me);
+  return CGG_OK;
+}
+
+extern "C" int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                                 const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N, const float* mean,
+                                 const float* std_, const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img,
+                                 uint8_t* masks, uint8_t* seg, int32_t* stats, int H, int W, cgg_stream_t stream) {
+  const char* me = "cgg_train_prep_u8";
+  int rc = tp_validate(me, false, staged, staged_bytes, img_table_offset, inst_table_offset, img_table_host, inst_table_host, B, N, mean,
+                       std_, pad_val, seg_pad, crop_h, crop_w, img, masks, seg, stats, H, W);
+  if (rc != CGG_OK) return rc;
+  const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
+  rc = tp_launch_image(me, staged, table, B, mean, std_, pad_val, to_rgb, crop_h, crop_w, img, stats, H, W, stream);
+  if (rc != CGG_OK) return rc;
+  const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
   const int planes = N + (seg ? B : 0);
   if (planes > 0) {
     hipLaunchKernelGGL(cgg_train_prep_plane_kernel, dim3(gx, gy, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, staged, table,
                        reinterpret_cast<const int32_t*>(staged + inst_table_offset), masks, seg, stats, N, H, W, crop_h, crop_w, seg_pad);
+    CGG_CHECK_LAUNCH(me);
+  }
+  return CGG_OK;
+}
+
+extern "C" int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset,
+                                          int64_t pan_table_offset, int64_t seg_table_offset, const int32_t* img_table_host,
+                                          const int32_t* pan_table_host, const int32_t* seg_table_host, int B, int N, int S,
+                                          const float* mean, const float* std_, const float* pad_val, int to_rgb, int seg_pad,
+                                          int crop_h, int crop_w, float* img, uint8_t* masks, uint8_t* seg, int32_t* stats, int H, int W,
+                                          cgg_stream_t stream) {
+  const char* me = "cgg_train_prep_panoptic_u8";
+  CGG_REQUIRE(pan_table_host && S >= 0 && (S == 0 || seg_table_host), CGG_EINVAL,
+              "%s: null pointer (pan_table_host, or seg_table_host with S = %d segment rows)", me, S);
+  int rc = tp_validate(me, true, staged, staged_bytes, img_table_offset, 0, img_table_host, nullptr, B, N, mean, std_, pad_val, seg_pad,
+                       crop_h, crop_w, img, masks, seg, stats, H, W);
+  if (rc != CGG_OK) return rc;
+  CGG_REQUIRE(pan_table_offset >= 0 && (pan_table_offset & 3) == 0 && pan_table_offset + (int64_t)B * TP_PAN_COLS * 4 <= staged_bytes,
+              CGG_EINVAL, "%s: the panoptic table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
+              (long long)pan_table_offset, (long long)staged_bytes);
+  CGG_REQUIRE(seg_table_offset >= 0 && (seg_table_offset & 3) == 0 && seg_table_offset + (int64_t)S * TP_SEG_COLS * 4 <= staged_bytes,
+              CGG_EINVAL, "%s: the segment table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, S,
+              (long long)seg_table_offset, (long long)staged_bytes);
+  int64_t next = 0;
+  for (int b = 0; b < B; ++b) {
+    const int32_t* d = img_table_host + TP_IMG_COLS * b;
+    const int32_t* p = pan_table_host + TP_PAN_COLS * b;
+    const int64_t h = d[1], w = d[2], things = d[10], off = p[0], pitch = p[1], fmt = p[2], first = p[3], n = p[4];
+    CGG_REQUIRE(fmt == 0 || fmt == 1, CGG_EINVAL, "%s: image %d: id-map format must be 0 (int32) or 1 (RGB bytes) (got %lld)", me, b,
+                (long long)fmt);
+    CGG_REQUIRE(pitch >= (fmt ? 3 : 4) * w, CGG_EINVAL, "%s: image %d: id-map row pitch %lld < %d * w = %lld", me, b, (long long)pitch,
+                fmt ? 3 : 4, (long long)((fmt ? 3 : 4) * w));
+    CGG_REQUIRE(fmt == 1 || ((off & 3) == 0 && (pitch & 3) == 0), CGG_EINVAL,
+                "%s: image %d: an int32 id map needs a byte offset (%lld) and a row pitch (%lld) that are multiples of 4", me, b,
+                (long long)off, (long long)pitch);
+    CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
+                "%s: image %d: the id map (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
+                (long long)(off + h * pitch), (long long)staged_bytes);
+    CGG_REQUIRE(n >= 0 && first == next && first + n <= S, CGG_EINVAL,
+                "%s: image %d: segment rows %lld .. %lld must follow the previous image's (%lld) and stay below S = %d", me, b,
+                (long long)first, (long long)(first + n), (long long)next, S);
+    CGG_REQUIRE(n <= TP_MAX_SEG, CGG_EUNSUPPORTED, "%s: image %d has %lld segment rows, more than %d", me, b, (long long)n, TP_MAX_SEG);
+    bool seen[TP_MAX_SEG + 1] = {false};
+    int64_t slots = 0;
+    for (int64_t i = first; i < first + n; ++i) {
+      const int32_t* t = seg_table_host + TP_SEG_COLS * i;
+      const int64_t id = t[0], slot = (int64_t)t[1] >> 8, cat = t[1] & 255;
+      CGG_REQUIRE(i == first || id > t[-TP_SEG_COLS], CGG_EINVAL,
+                  "%s: image %d: segment row %lld: ids must ascend strictly (%lld after %lld)", me, b, (long long)i, (long long)id,
+                  (long long)(i == first ? 0 : t[-TP_SEG_COLS]));
+      CGG_REQUIRE(cat <= 254, CGG_EINVAL, "%s: image %d: segment row %lld: category %lld > 254", me, b, (long long)i, (long long)cat);
+      CGG_REQUIRE(slot >= 0 && slot <= things && slot <= TP_MAX_SEG && (slot == 0 || !seen[slot]), CGG_EINVAL,
+                  "%s: image %d: segment row %lld: slot %lld -- the non-zero slots must be a permutation of 1 .. %lld", me, b,
+                  (long long)i, (long long)slot, (long long)things);
+      if (slot) {
+        seen[slot] = true;
+        ++slots;
+      }
+    }
+    CGG_REQUIRE(slots == things, CGG_EINVAL, "%s: image %d: %lld thing slots in the segment rows, %lld instances in the image row", me,
+                b, (long long)slots, (long long)things);
+    next = first + n;
+  }
+  CGG_REQUIRE(next == S, CGG_EINVAL, "%s: the images own %lld segment rows, S = %d", me, (long long)next, S);
+  const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
+  rc = tp_launch_image(me, staged, table, B, mean, std_, pad_val, to_rgb, crop_h, crop_w, img, stats, H, W, stream);
+  if (rc != CGG_OK) return rc;
+  if (N > 0 || seg) {
+    const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
+    hipLaunchKernelGGL(cgg_train_prep_panoptic_kernel, dim3(gx, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, staged, table,
+                       reinterpret_cast<const int32_t*>(staged + pan_table_offset),
+                       reinterpret_cast<const int32_t*>(staged + seg_table_offset), masks, seg, stats, H, W, crop_h, crop_w, seg_pad);
     CGG_CHECK_LAUNCH(me);
   }
   return CGG_OK;

@@ -2682,6 +2682,77 @@ def train_prep_u8(staged, img_table, inst_table, img, masks, seg, stats, mean, s
     return img, masks, seg, stats
 
 
+TRAIN_PREP_PAN_COLS = 5       # byte offset of the id map, row pitch, format (0: int32 ids, 1: R, G, B bytes), first segment row, segment rows
+TRAIN_PREP_SEG_COLS = 2       # id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t
+TRAIN_PREP_MAX_SEGMENTS = 256  # CGG_TRAIN_PREP_MAX_SEGMENTS
+
+
+def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, seg, stats, mean, std, pad_val=0.0, to_rgb=True,
+                           crop_size=None, seg_pad=255, img_table_offset=0, pan_table_offset=None, seg_table_offset=None,
+                           staged_bytes=None):
+    """`train_prep_u8` for panoptic samples: the thing masks, the semantic plane and the statistics come from ONE gather of the staged
+    id map per output pixel (`cgg_train_prep_panoptic_u8`, two launches, no synchronisation; train_prep.py states the rule). staged:
+    DEVICE uint8 (n,) -- the three tables at bytes `img_table_offset` / `pan_table_offset` / `seg_table_offset` (by default back to
+    back), the images and the id maps; img_table (B, 12) with the thing counts and -1 for the semantic-map offset, pan_table (B, 5),
+    seg_table (S, 2) rows sorted by id within an image: HOST int32 copies, read for validation during the call; img (B, 3, H, W)
+    f32, masks (N, H, W) u8, seg (B, 1, H, W) u8 or None, stats (N, 5) i32: DEVICE, contiguous, every element written (the caller
+    clears nothing). Returns (img, masks, seg, stats)."""
+    me = 'train_prep_panoptic_u8'
+    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
+        raise CggError(f'{me}: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
+    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('pan_table', pan_table, TRAIN_PREP_PAN_COLS),
+                          ('seg_table', seg_table, TRAIN_PREP_SEG_COLS)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
+            raise CggError(f'{me}: {name} must be a (rows, {cols}) torch.int32 tensor '
+                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
+        if t.is_cuda or not t.is_contiguous():
+            raise CggError(f'{me}: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
+    B, S = int(img_table.shape[0]), int(seg_table.shape[0])
+    if B < 1:
+        raise CggError(f'{me}: an empty batch')
+    if pan_table.shape[0] != B:
+        raise CggError(f'{me}: pan_table must have one row per image ({B}), got {int(pan_table.shape[0])}')
+    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
+        raise CggError(f'{me}: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
+                       f'shape {tuple(getattr(img, "shape", ()))})')
+    H, W = int(img.shape[2]), int(img.shape[3])
+    if not torch.is_tensor(masks) or masks.dtype != torch.uint8 or masks.dim() != 3 or tuple(masks.shape[1:]) != (H, W):
+        raise CggError(f'{me}: masks must be a (N, {H}, {W}) torch.uint8 tensor (got {getattr(masks, "dtype", type(masks))}, '
+                       f'shape {tuple(getattr(masks, "shape", ()))})')
+    N = int(masks.shape[0])
+    for name, t, shape, dt in (('seg', seg, (B, 1, H, W), torch.uint8), ('stats', stats, (N, 5), torch.int32)):
+        if t is None and name == 'seg':
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise CggError(f'{me}: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
+                           f'shape {tuple(getattr(t, "shape", ()))})')
+    for name, t in (('masks', masks), ('seg', seg), ('stats', stats)):
+        if t is not None and t.device != img.device:
+            raise CggError(f'{me}: {name} ({t.device}) and img ({img.device}) live on different devices')
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if nbytes > staged.numel():
+        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
+    sp, ip = dev_ptr(staged, f'{me}: staged'), dev_ptr(img, f'{me}: img')
+    if staged.device != img.device:
+        raise CggError(f'{me}: staged ({staged.device}) and img ({img.device}) live on different devices')
+    mp = dev_ptr(masks, f'{me}: masks') if N else None
+    tp = dev_ptr(stats, f'{me}: stats') if N else None
+    gp = dev_ptr(seg, f'{me}: seg')
+    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'{me}: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    if pan_table_offset is None:
+        pan_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
+    if seg_table_offset is None:
+        seg_table_offset = int(pan_table_offset) + 4 * TRAIN_PREP_PAN_COLS * B
+    with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)), shape=(B, N, H, W)):
+        rc = _lib_().cgg_train_prep_panoptic_u8(sp, nbytes, int(img_table_offset), int(pan_table_offset), int(seg_table_offset),
+                                                ctypes.c_void_p(img_table.data_ptr()), ctypes.c_void_p(pan_table.data_ptr()),
+                                                ctypes.c_void_p(seg_table.data_ptr()) if S else None, B, N, S, m, s, p,
+                                                int(bool(to_rgb)), int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
+    check(rc, 'cgg_train_prep_panoptic_u8')
+    return img, masks, seg, stats
+
+
 # ------------------------------------------------------------------------------------------------
 # caption search: one beam-search step for a whole batch, decided on the device (caption_search.py states the rule)
 # ------------------------------------------------------------------------------------------------

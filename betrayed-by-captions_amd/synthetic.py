@@ -1,13 +1,14 @@
 """Synthetic stand-ins for everything the benchmark cannot fetch offline:
 class-embedding JSON / known / unknown files with the reference's schema, a model config with the
 reference's keys (the `model = dict(type='Mask2FormerOpen', ...)` block of
-configs/instance/coco_b48n17.py:16-188 and configs/openset_panoptic/coco_panoptic_p20.py), and
-COCO-shaped seeded input batches.
+configs/instance/coco_b48n17.py:16-188 and configs/openset_panoptic/coco_panoptic_p20.py),
+COCO-shaped seeded input batches, and raw panoptic samples (an id map and its segment records).
 """
 import json
 import os
 import tempfile
 
+import numpy as np
 import torch
 
 _TMP = {}
@@ -203,3 +204,59 @@ def train_batch(B, H, W, num_classes, max_inst=20, T=35, vocab=30522, seed=0, de
         out['gt_caption_nouns_ids'].append(nouns.to(device))
         out['gt_caption_nouns_mask'].append((nouns != 0).long().to(device))
     return out
+
+
+def panoptic_sample(hw, num_things, num_stuff, seed=0, vocab=30522, rgb=None, blocks=(4, 5)):
+    """One RAW panoptic sample as the dataset holds it before LoadOpenPanopticAnnotations (train_prep.py, rule 5): a uint8 BGR
+    image, `pan_seg` = a block-structured id map (blocks[0] x blocks[1] rectangles at random cuts, one 24-bit id each, some >= 2^23;
+    (h, w, 3) uint8 RGB when `rgb` -- by default for odd seeds -- else (h, w) int32), `segments` = the records in shuffled order:
+    things, stuff (when num_stuff > 0), one crowd thing (a thing category with is_thing false) and two blocks whose ids NO record
+    lists (they come out as 255), `gt_labels` = the categories of the is_thing records in record order, and the caption fields."""
+    h, w = int(hw[0]), int(hw[1])
+    r = np.random.default_rng(seed)
+    gy, gx = min(blocks[0], h), min(blocks[1], w)
+    ycut = np.concatenate([[0], np.sort(r.choice(np.arange(1, h), size=gy - 1, replace=False)), [h]]).astype(int)
+    xcut = np.concatenate([[0], np.sort(r.choice(np.arange(1, w), size=gx - 1, replace=False)), [w]]).astype(int)
+    nb = gy * gx
+    ids = r.choice(2**24, size=nb, replace=False).astype(np.int64)
+    ids[0] |= 2**23                                          # at least one id with the top bit of the blue byte
+    ids = np.unique(ids)
+    while ids.size < nb:
+        ids = np.unique(np.concatenate([ids, r.integers(0, 2**24, size=nb - ids.size)]))
+    ids = r.permutation(ids)
+    pan = np.empty((h, w), dtype=np.int32)
+    for k in range(nb):
+        i, j = divmod(k, gx)
+        pan[ycut[i]:ycut[i + 1], xcut[j]:xcut[j + 1]] = ids[k]
+    order = r.permutation(nb)
+    unlisted = set(order[:2].tolist()) if nb > 3 else set()
+    crowd = int(order[2]) if nb > 3 else -1
+    segments = []
+    for k in r.permutation(nb).tolist():
+        if k in unlisted:
+            continue
+        if k == crowd:
+            segments.append(dict(id=int(ids[k]), category=int(r.integers(0, num_things)), is_thing=False))
+        elif num_stuff > 0 and k % 3 == 0:
+            segments.append(dict(id=int(ids[k]), category=int(num_things + r.integers(0, num_stuff)), is_thing=False))
+        else:
+            segments.append(dict(id=int(ids[k]), category=int(r.integers(0, num_things)), is_thing=True))
+    labels = np.array([s['category'] for s in segments if s['is_thing']], dtype=np.int64)
+    if rgb is None:
+        rgb = bool(seed % 2)
+    if rgb:
+        pan = np.stack([pan & 255, (pan >> 8) & 255, (pan >> 16) & 255], axis=2).astype(np.uint8)
+    cap = train_batch(1, 8, 8, num_classes=max(num_things, 1), max_inst=1, vocab=vocab, seed=seed)
+    out = dict(img=r.integers(0, 256, size=(h, w, 3), dtype=np.uint8), pan_seg=pan, segments=segments, gt_labels=labels,
+               filename=f'synthetic_panoptic_{seed}.jpg', ori_filename=f'synthetic_panoptic_{seed}.jpg')
+    for k in ('gt_caption_ids', 'gt_caption_mask', 'gt_caption_nouns_ids', 'gt_caption_nouns_mask'):
+        out[k] = cap[k][0].numpy()
+    return out
+
+
+def panoptic_samples(hw, num_things, num_stuff, seed=0, vocab=30522, blocks=(4, 5)):
+    """Endless seeded stream of `panoptic_sample`s, the two id-map forms in turn."""
+    i = 0
+    while True:
+        yield panoptic_sample(hw, num_things, num_stuff, seed=seed + i, vocab=vocab, blocks=blocks)
+        i += 1

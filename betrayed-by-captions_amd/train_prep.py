@@ -39,6 +39,21 @@ so equality with a particular build is NOT claimed; what is pinned is this rule 
 with mmdet's use of the global `np.random` stream: the random decisions are drawn by `draw_train_params` in a documented order and
 are an argument of the rule, so a caller may supply its own. PhotoMetricDistortion, multi-scale value lists and polygon masks are
 not restated and are refused by name.
+
+PANOPTIC SAMPLES. The panoptic configs start from `LoadOpenPanopticAnnotations(with_mask=True, with_seg=True)`, which turns the
+panoptic PNG into one bitmap per thing and a semantic map on the host (open_set/datasets/pipelines/loading.py:317-341). A raw
+panoptic sample carries the id map itself instead: `pan_seg`, (h, w) int32 ids >= 0 or (h, w, 3) uint8 in RGB order as the loader
+reads the PNG (id = R + 256 G + 65536 B, `rgb2id`), `segments` = the `ann_info['masks']` records (dicts with id, category,
+is_thing) and `gt_labels`, one per record with is_thing true. `load_panoptic_host` is the loader's rule:
+
+5. the semantic map starts at 255 -- the loader's constant, not Pad's pad_val['seg'] -- and every record, crowd things (is_thing
+   false) and stuff included, writes its category where pan == id; a pixel whose id no record lists stays 255. Every is_thing
+   record yields the bitmap pan == id, in record order.
+
+`prepare_train_host` of panoptic samples is DEFINED as `prepare_train_host` of the bitmap samples rule 5 makes. Rule 3 is a nearest
+gather, which commutes with "compare the id": (pan[ry, rx] == id) is the resized bitmap and category_of(pan[ry, rx]) the resized
+semantic map, so `TrainPrep` stages the id map (3 or 4 bytes per pixel, against 1 + n_things bytes for the planes) and a table of
+the records, and one gather per output pixel yields every plane, bit for bit. With with_seg=False only the thing planes are made.
 """
 from dataclasses import dataclass
 from typing import NamedTuple, Tuple
@@ -48,7 +63,8 @@ import torch
 
 from ._lib import CggError
 from .image_prep import ImagePrep, PrepSpec, _as_hwc_u8, norm_constants, rescale_size
-from .ops import TRAIN_PREP_IMG_COLS, TRAIN_PREP_INST_COLS, three_floats
+from .ops import (TRAIN_PREP_IMG_COLS, TRAIN_PREP_INST_COLS, TRAIN_PREP_MAX_SEGMENTS, TRAIN_PREP_PAN_COLS, TRAIN_PREP_SEG_COLS,
+                  three_floats)
 
 CAPTION_FIELDS = ('gt_caption_ids', 'gt_caption_mask', 'gt_caption_nouns_ids', 'gt_caption_nouns_mask')
 
@@ -115,7 +131,10 @@ def parse_train_pipeline(pipeline):
             if step.get('poly2mask', True) is False:
                 raise _unsupported(t, 'poly2mask=False (polygon masks are out of scope)')
             if not step.get('with_mask', t != 'LoadAnnotations'):
-                raise _unsupported(t, 'with_mask=False')
+                raise _unsupported(t, 'with_mask=False' + (' (the thing masks are what the panoptic rule yields)' if 'Panoptic' in t else ''))
+            # the panoptic loaders' with_mask_based_bbox (either value) and with_seg=False are accepted: neither makes the result differ
+            # from the rule -- the boxes are those of the cropped masks whatever boxes the loader made (recompute_bbox is required),
+            # and without with_seg only the thing planes are produced
             kw['with_seg'] = bool(step.get('with_seg', 'Panoptic' in t))
         elif t == 'RandomFlip':
             if step.get('direction', 'horizontal') != 'horizontal':
@@ -299,6 +318,109 @@ def _check_sample(s, spec):
     return img, masks, labels, seg
 
 
+def _check_pan_seg(pan, hw=None):
+    """(array, format) of an id map: (h, w) int32 -> 0, (h, w, 3) uint8 RGB -> 1; anything else raises naming pan_seg"""
+    pan = pan.cpu().numpy() if torch.is_tensor(pan) else np.asarray(pan)
+    fmt = 0 if (pan.dtype == np.int32 and pan.ndim == 2) else 1 if (pan.dtype == np.uint8 and pan.ndim == 3 and pan.shape[2] == 3) else -1
+    if fmt < 0 or (hw is not None and tuple(pan.shape[:2]) != (int(hw[0]), int(hw[1]))):
+        want = '(h, w)' if hw is None else f'({int(hw[0])}, {int(hw[1])})'
+        raise CggError(f'train_prep: pan_seg must be {want} int32 ids or {want[:-1]}, 3) uint8 RGB (got {pan.dtype}, shape {pan.shape})')
+    if fmt == 0 and pan.size and int(pan.min()) < 0:
+        raise CggError(f'train_prep: pan_seg holds a negative id ({int(pan.min())}); ids are 0 .. 2^31 - 1')
+    return pan, fmt
+
+
+def _check_segments(segments, fmt):
+    """[(id, category, is_thing)] of the `ann_info['masks']` records, in record order; anything outside rule 5 raises naming segments"""
+    if segments is None or isinstance(segments, (str, bytes)) or not hasattr(segments, '__iter__'):
+        raise CggError("train_prep: segments must be a sequence of dicts with id, category, is_thing (ann_info['masks'])")
+    recs, seen = [], set()
+    top = 2**24 - 1 if fmt == 1 else 2**31 - 1
+    for i, r in enumerate(segments):
+        if not hasattr(r, 'get') or r.get('id') is None or r.get('category') is None:
+            raise CggError(f'train_prep: segments[{i}] must be a dict with id, category, is_thing (got {r!r})')
+        sid, cat = int(r['id']), int(r['category'])
+        if sid != r['id'] or not 0 <= sid <= top:
+            raise CggError(f'train_prep: segments[{i}]: id {r["id"]!r} outside 0 .. {top}' + (' (an RGB id map holds 24 bits)' if fmt == 1 else ''))
+        if cat != r['category'] or not 0 <= cat <= 254:
+            raise CggError(f'train_prep: segments[{i}]: category {r["category"]!r} outside 0 .. 254 (255 is the ignore label)')
+        if sid in seen:
+            raise CggError(f'train_prep: segments[{i}]: id {sid} appears twice')
+        seen.add(sid)
+        recs.append((sid, cat, bool(r.get('is_thing'))))
+    if len(recs) > TRAIN_PREP_MAX_SEGMENTS:
+        raise CggError(f'train_prep: segments: {len(recs)} records for one image, more than {TRAIN_PREP_MAX_SEGMENTS}')
+    return recs
+
+
+def _pan_ids(pan, fmt):
+    """the (h, w) int32 ids of an id map: rgb2id for the RGB form"""
+    if fmt == 0:
+        return pan
+    p = pan.astype(np.int32)
+    return p[:, :, 0] + 256 * p[:, :, 1] + 65536 * p[:, :, 2]
+
+
+def _load_panoptic(pan, fmt, recs):
+    ids = _pan_ids(pan, fmt)
+    seg = np.full(ids.shape, 255, dtype=np.uint8)            # 255 as ignore: the loader's constant
+    masks = []
+    for sid, cat, is_thing in recs:
+        m = ids == sid
+        seg = np.where(m, np.uint8(cat), seg)
+        if is_thing:                                         # the legal thing masks
+            masks.append(m.astype(np.uint8))
+    masks = np.stack(masks) if masks else np.zeros((0,) + ids.shape, dtype=np.uint8)
+    return masks, seg
+
+
+def load_panoptic_host(pan_seg, segments):
+    """Rule 5, the reference's LoadOpenPanopticAnnotations._load_masks_and_semantic_segs (loading.py:317-341) in numpy: the id map
+    ((h, w) int32, or (h, w, 3) uint8 RGB) and the `ann_info['masks']` records -> (gt_masks (n_things, h, w) uint8, one bitmap per
+    is_thing record in record order; gt_semantic_seg (h, w) uint8, each record's category where pan == id, 255 elsewhere)."""
+    pan, fmt = _check_pan_seg(pan_seg)
+    return _load_panoptic(pan, fmt, _check_segments(segments, fmt))
+
+
+def _check_pan_sample(s):
+    """(img, id map, format, records, labels) of one raw panoptic sample"""
+    if not hasattr(s, 'get') or s.get('img') is None:
+        raise CggError('train_prep: a panoptic sample is a dict with img, pan_seg, segments, gt_labels')
+    if s.get('gt_masks') is not None:
+        raise CggError('train_prep: a sample with both gt_masks and pan_seg (bitmaps or the id map, not both)')
+    img = _as_hwc_u8(s['img'])
+    h, w = img.shape[:2]
+    if h < 1 or w < 1:
+        raise CggError(f'train_prep: a zero-sized image ({h} x {w})')
+    pan, fmt = _check_pan_seg(s['pan_seg'], (h, w))
+    recs = _check_segments(s.get('segments'), fmt)
+    things = sum(1 for r in recs if r[2])
+    labels = s.get('gt_labels')
+    labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if labels.shape != (things,):
+        raise CggError(f'train_prep: gt_labels must be ({things},), one per is_thing record of segments (got shape {labels.shape})')
+    return img, pan, fmt, recs, labels
+
+
+def _is_panoptic(s):
+    return hasattr(s, 'get') and s.get('pan_seg') is not None
+
+
+def _batch_is_panoptic(samples):
+    pan = [_is_panoptic(s) for s in samples]
+    if any(pan) and not all(pan):
+        raise CggError('train_prep: a batch that mixes bitmap samples (gt_masks) and panoptic samples (pan_seg)')
+    return pan[0]
+
+
+def panoptic_to_bitmap_sample(s):
+    """the bitmap sample rule 5 makes of a raw panoptic one: pan_seg / segments replaced by gt_masks and gt_semantic_seg"""
+    _, pan, fmt, recs, _ = _check_pan_sample(s)
+    out = {k: v for k, v in s.items() if k not in ('pan_seg', 'segments')}
+    out['gt_masks'], out['gt_semantic_seg'] = _load_panoptic(pan, fmt, recs)
+    return out
+
+
 def _check_batch(samples, params):
     if not isinstance(samples, (list, tuple)) or not samples:
         raise CggError('train_prep: expected a non-empty list of samples')
@@ -322,11 +444,14 @@ def mask_stats(m, eh, ew):
 
 def prepare_train_host(samples, params, spec):
     """The rule in numpy. samples: dicts with img (h, w, 3) uint8 BGR, gt_masks (n, h, w) uint8 / bool, gt_labels (n,), optionally
-    gt_semantic_seg (h, w) uint8, the caption fields and filename / ori_filename (passed through); params: one TrainParams each.
+    gt_semantic_seg (h, w) uint8, the caption fields and filename / ori_filename (passed through) -- or raw panoptic samples with
+    pan_seg and segments in place of gt_masks / gt_semantic_seg (rule 5; all of a batch or none); params: one TrainParams each.
     -> (kwargs, kept): kwargs holds img (B, 3, H, W) float32, img_metas, gt_masks (list of (k_b, H, W) uint8), gt_bboxes (list of
     (k_b, 4) float32), gt_labels, gt_semantic_seg (B, 1, H, W) uint8 when the pipeline loads one, and the caption fields as lists --
     numpy arrays, named as `forward_train` names them (`to_device` uploads them); kept = [k_b], the surviving instances per sample."""
     _check_batch(samples, params)
+    if _batch_is_panoptic(samples):                          # by definition: the rule on the bitmap samples rule 5 makes
+        return prepare_train_host([panoptic_to_bitmap_sample(s) for s in samples], params, spec)
     H, W = spec.size
     mean, rstd, pad = norm_constants(_norm_spec(spec))
     B = len(samples)
@@ -394,6 +519,9 @@ class TrainPrep:
     One call = one host copy into a pinned staging slot (the two descriptor tables, then the raw images, instance masks and semantic
     maps back to back), ONE asynchronous H2D copy and at most TWO launches of `cgg_train_prep_u8` on the current stream (image
     planes; mask and semantic planes with the per-instance area / box reduction), then ONE small D2H copy of the (N, 5) int32
+    statistics. A batch of raw panoptic samples (pan_seg + segments) stages three tables, the images and the id maps -- no bitmap, no
+    semantic map -- and runs `cgg_train_prep_panoptic_u8` instead (image planes; every thing mask, the semantic plane and the
+    statistics from one gather of the id map per pixel); the rest is the same. So, either way: ONE small D2H copy of the
     statistics. Waiting for that copy is the SINGLE synchronisation per batch: which instances survive decides the shapes of
     gt_masks / gt_bboxes / gt_labels, and the host has to know them. gt_masks[b] is a zero-copy slice of the masks tensor when every
     instance of image b survived, an index_select otherwise; gt_bboxes come from the statistics. A sample without a surviving
@@ -412,19 +540,13 @@ class TrainPrep:
         self.spec, self.device = spec, device
         self._slots = [None] * slots
         self._n = 0
+        self.last_staged_bytes = 0
 
     _slot = ImagePrep._slot                                  # the same rotation of pinned staging slots
 
-    def prep(self, samples, params):
-        from . import ops
-        spec = self.spec
-        _check_batch(samples, params)
-        H, W = spec.size
-        B = len(samples)
-        parsed = [_check_sample(s, spec) for s in samples]
-        geoms = [sample_geometry(q[0].shape[:2], p, spec) for q, p in zip(parsed, params)]
-        counts = [int(q[1].shape[0]) for q in parsed]
-        N = sum(counts)
+    def _layout_bitmaps(self, parsed, params, geoms, counts):
+        """the staged bytes of a bitmap batch: (n, [(byte offset, int32 rows)] image table first, [(byte offset, array)], op)"""
+        B, N = len(parsed), sum(counts)
         img_rows, inst_rows, copies = [], [], []
         inst_off = 4 * TRAIN_PREP_IMG_COLS * B
         n = inst_off + 4 * TRAIN_PREP_INST_COLS * N
@@ -445,6 +567,63 @@ class TrainPrep:
                 n += h * w
             img_rows.append((off, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], seg_off))
             first += counts[b]
+        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
+                  (inst_off, np.asarray(inst_rows, dtype=np.int32).reshape(N, TRAIN_PREP_INST_COLS))]
+        return n, tables, copies, 'train_prep_u8'
+
+    def _layout_panoptic(self, parsed, params, geoms, counts):
+        """the staged bytes of a panoptic batch: the image, panoptic and segment tables, then per sample the image and the id map (an
+        int32 map on a 4-byte boundary). No bitmap and no semantic map is staged."""
+        B = len(parsed)
+        S = sum(len(q[3]) for q in parsed)
+        pan_off = 4 * TRAIN_PREP_IMG_COLS * B
+        seg_off = pan_off + 4 * TRAIN_PREP_PAN_COLS * B
+        n = seg_off + 4 * TRAIN_PREP_SEG_COLS * S
+        img_rows, pan_rows, seg_rows, copies = [], [], [], []
+        first = sfirst = 0
+        for b, ((img, pan, fmt, recs, _), p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
+            h, w = int(img.shape[0]), int(img.shape[1])
+            img_rows.append((n, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], -1))
+            copies.append((n, img))
+            n += h * w * 3
+            if fmt == 0:
+                n = (n + 3) & ~3
+            bpp = 3 if fmt else 4
+            pan_rows.append((n, bpp * w, fmt, sfirst, len(recs)))
+            copies.append((n, pan))
+            n += h * w * bpp
+            slot, rows = 0, []
+            for sid, cat, is_thing in recs:                  # slot t + 1 = the image's thing t, in record order; 0 = no thing
+                slot += int(is_thing)
+                rows.append((sid, ((slot if is_thing else 0) << 8) | cat))
+            seg_rows += sorted(rows)                         # the kernel searches them by id
+            first += counts[b]
+            sfirst += len(recs)
+        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
+                  (pan_off, np.asarray(pan_rows, dtype=np.int32).reshape(B, TRAIN_PREP_PAN_COLS)),
+                  (seg_off, np.asarray(seg_rows, dtype=np.int32).reshape(S, TRAIN_PREP_SEG_COLS))]
+        return n, tables, copies, 'train_prep_panoptic_u8'
+
+    def prep(self, samples, params):
+        from . import ops
+        spec = self.spec
+        _check_batch(samples, params)
+        H, W = spec.size
+        B = len(samples)
+        if _batch_is_panoptic(samples):
+            parsed = [_check_pan_sample(s) for s in samples]
+            labels_all = [q[4] for q in parsed]
+            counts = [int(q[4].shape[0]) for q in parsed]
+            layout = self._layout_panoptic
+        else:
+            parsed = [_check_sample(s, spec) for s in samples]
+            labels_all = [q[2] for q in parsed]
+            counts = [int(q[1].shape[0]) for q in parsed]
+            layout = self._layout_bitmaps
+        geoms = [sample_geometry(q[0].shape[:2], p, spec) for q, p in zip(parsed, params)]
+        N = sum(counts)
+        n, tables, copies, op = layout(parsed, params, geoms, counts)
+        self.last_staged_bytes = n                            # tables + raw planes of this call (what the one H2D copy moves)
         img_out = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
         masks_out = torch.empty((N, H, W), dtype=torch.uint8, device=self.device)
         seg_out = torch.empty((B, 1, H, W), dtype=torch.uint8, device=self.device) if spec.with_seg else None
@@ -453,21 +632,27 @@ class TrainPrep:
         with torch.cuda.device(self.device):
             slot = self._slot(n)
             stream = torch.cuda.current_stream(self.device)
-            img_table = slot.pinned[:inst_off].view(torch.int32).view(B, TRAIN_PREP_IMG_COLS)
-            inst_table = slot.pinned[inst_off:inst_off + 4 * TRAIN_PREP_INST_COLS * N].view(torch.int32).view(N, TRAIN_PREP_INST_COLS)
-            img_table.numpy()[:] = np.asarray(img_rows, dtype=np.int32)
-            if N:
-                inst_table.numpy()[:] = np.asarray(inst_rows, dtype=np.int32)
+            host_tables = []
+            for off, rows in tables:                         # written into the slot; the views are the host copies the op validates
+                t = slot.pinned[off:off + 4 * rows.size].view(torch.int32).view(rows.shape)
+                if rows.size:
+                    t.numpy()[:] = rows
+                host_tables.append(t)
             for off, a in copies:
-                np.copyto(slot.host[off:off + a.size].reshape(a.shape), a)
+                np.copyto(slot.host[off:off + a.nbytes].view(a.dtype).reshape(a.shape), a)
             if slot.consumed is not None:
                 stream.wait_event(slot.consumed)             # device: the kernels that read this slot last are done (another stream)
             slot.dev[:n].copy_(slot.pinned[:n], non_blocking=True)
             slot.copied = torch.cuda.Event()
             slot.copied.record(stream)
-            ops.train_prep_u8(slot.dev, img_table, inst_table, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
-                              to_rgb=spec.to_rgb, crop_size=spec.crop_size, seg_pad=spec.pad_val[2], img_table_offset=0,
-                              inst_table_offset=inst_off, staged_bytes=n)
+            offsets = [off for off, _ in tables]
+            common = dict(to_rgb=spec.to_rgb, crop_size=spec.crop_size, seg_pad=spec.pad_val[2], img_table_offset=offsets[0], staged_bytes=n)
+            if op == 'train_prep_panoptic_u8':
+                ops.train_prep_panoptic_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
+                                           pan_table_offset=offsets[1], seg_table_offset=offsets[2], **common)
+            else:
+                ops.train_prep_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
+                                  inst_table_offset=offsets[1], **common)
             slot.consumed = torch.cuda.Event()
             slot.consumed.record(stream)
             stats_host.copy_(stats, non_blocking=True)
@@ -478,7 +663,7 @@ class TrainPrep:
             keep = st[:, 0] >= 1
             keep_idx = torch.from_numpy(np.nonzero(keep)[0]).to(self.device) if not keep.all() else None
             boxes = (stats[:, 1:5] + torch.tensor([0, 0, 1, 1], dtype=torch.int32, device=self.device)).float()
-            labels_np = [q[2][keep[f:f + c]] for q, f, c in zip(parsed, np.cumsum([0] + counts[:-1]).tolist(), counts)]
+            labels_np = [lab[keep[f:f + c]] for lab, f, c in zip(labels_all, np.cumsum([0] + counts[:-1]).tolist(), counts)]
             out = dict(img=img_out, img_metas=[], gt_bboxes=[], gt_labels=[], gt_masks=[])
             kept, first, kfirst = [], 0, 0
             for b, (s, p, q, g) in enumerate(zip(samples, params, parsed, geoms)):

@@ -730,6 +730,38 @@ int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_t
                       const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img, uint8_t* masks, uint8_t* seg,
                       int32_t* stats, int H, int W, cgg_stream_t stream);
 
+/* The same pipeline for PANOPTIC samples, from the id map instead of host-made bitmaps, in TWO launches (csrc/train_prep.hip): the
+ * image kernel of cgg_train_prep_u8, then one kernel that gathers ONE id per output pixel (rule 3 of train_prep.py: nearest, flip,
+ * window), looks it up in the image's segment rows and writes every plane the reference's LoadOpenPanopticAnnotations
+ * (open_set/datasets/pipelines/loading.py:317-341) followed by the augmentation chain yields: the thing masks (1 where the pixel's
+ * segment is thing slot t), the semantic byte (the segment's category; 255 for an id that no row lists) and the per-thing
+ * statistics. Nearest gathers commute with "compare the id", so the result equals cgg_train_prep_u8 on the bitmaps and the semantic
+ * map that `train_prep.load_panoptic_host` makes, bit for bit.
+ *   staged          DEVICE bytes (4-byte aligned base): the three tables at bytes img / pan / seg_table_offset (multiples of 4), the
+ *                   images and the id maps; staged_bytes = how many are valid
+ *   img_table_host  HOST copy of the B image rows of cgg_train_prep_u8: first instance / instances count the image's THINGS (planes
+ *                   of `masks`, rows of `stats`), the semantic-map offset is -1
+ *   pan_table_host  HOST copy of the B rows of 5 int32: byte offset of the id map, row pitch in bytes, format (0: int32 ids, offset
+ *                   and pitch multiples of 4, pitch >= 4 w; 1: 3 bytes R, G, B per pixel with id = R + 256 G + 65536 B, pitch >= 3 w),
+ *                   first segment row, segment rows (<= CGG_TRAIN_PREP_MAX_SEGMENTS; the images own consecutive ranges of the S rows)
+ *   seg_table_host  HOST copy of the S segment rows of 2 int32: id, and (slot << 8) | category with category <= 254 and slot = 0
+ *                   for a segment that is no thing, t + 1 for the image's thing t. Within an image ids ascend strictly and the
+ *                   non-zero slots are a permutation of 1 .. instances. Nullable when S == 0
+ *   img, masks, seg, stats, mean, std, pad_val, seg_pad, crop   as for cgg_train_prep_u8; the caller clears nothing. seg nullable:
+ *                   no semantic plane is written
+ * Does not synchronise. Checked on the host before the first launch: everything cgg_train_prep_u8 checks for the image rows, and
+ * CGG_EINVAL for a null table, a table or a map extending past staged_bytes, a pitch too small, a format other than 0 / 1, an
+ * unaligned int32 map, a semantic-map offset other than -1, segment ranges that do not tile 0 .. S, ids that do not ascend, a
+ * category > 254, slots that are no permutation; CGG_EUNSUPPORTED for more than CGG_TRAIN_PREP_MAX_SEGMENTS rows of one image;
+ * CGG_EALIGN as for cgg_train_prep_u8. The kernels read no byte outside the table rows and offset .. offset + h * pitch of each
+ * image and map. */
+#define CGG_TRAIN_PREP_MAX_SEGMENTS 256
+int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t pan_table_offset,
+                               int64_t seg_table_offset, const int32_t* img_table_host, const int32_t* pan_table_host,
+                               const int32_t* seg_table_host, int B, int N, int S, const float* mean, const float* std,
+                               const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img, uint8_t* masks,
+                               uint8_t* seg, int32_t* stats, int H, int W, cgg_stream_t stream);
+
 /* One step of the caption beam search for a whole batch of images, decision and bookkeeping on the device (csrc/beam_step.hip):
  * the loop body of the reference's beam_search, open_set/utils/eval/inference.py:113-149 -- mean over the decoder blocks' generator
  * outputs, log-softmax, (log p + parent weight) / length^alpha, the top `beam` of an image's live rows, the walk over them that

@@ -7,7 +7,9 @@ hook machinery. Datasets are out of this build's scope (no COCO on the box): sam
 (`--data pkg.module:function`, a generator of raw sample dicts that go through OpenFormatBundle + collate) or, by
 default, from the synthetic COCO-shaped stream used by bench.py. Samples whose `img` is uint8 are RAW -- image, instance bitmaps,
 labels, captions as the dataset loads them -- and go through `cfg.data.train.pipeline` on the device (cgg_amd.train_prep:
-flip, large-scale jitter, crop, annotation filter, pad, normalize); `--synthetic-u8 HxW` generates such samples.
+flip, large-scale jitter, crop, annotation filter, pad, normalize); `--synthetic-u8 HxW` generates such samples. Raw PANOPTIC samples
+carry the panoptic id map (`pan_seg`) and its segment records (`segments`) instead of bitmaps: the thing masks and the semantic map
+are made on the device too (train_prep.py, rule 5); `--synthetic-panoptic HxW` generates such samples.
 
     python tools/train.py configs/instance/coco_b48n17.py --work-dir work --max-iters 100 --synthetic 512
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py CONFIG --launcher pytorch
@@ -55,10 +57,15 @@ def parse_args(argv=None):
     p.add_argument('--data', default=None,
                    help='pkg.module:function(cfg, rank, world) -> iterable of sample dicts: float `img` = already augmented, padded '
                         'and formatted; uint8 `img` (h, w, 3) BGR with gt_masks (n, h, w) bitmaps and gt_labels = raw, prepared on '
-                        'the device by the config\'s data.train.pipeline')
+                        'the device by the config\'s data.train.pipeline; with pan_seg (the panoptic id map) and segments (its '
+                        'records) in place of gt_masks = raw panoptic, loaded and prepared on the device')
     p.add_argument('--synthetic-u8', default=None, metavar='HxW',
                    help='synthetic RAW uint8 samples of this size (e.g. 480x640) with blob masks of mixed sizes instead of '
                         '--synthetic\'s prepared float samples: exercises the device-side training pipeline without a dataset')
+    p.add_argument('--synthetic-panoptic', default=None, metavar='HxW',
+                   help='synthetic RAW panoptic samples of this size: a uint8 image, a block-structured panoptic id map (int32 and RGB '
+                        'forms in turn) and its segment records -- things, stuff, a crowd thing, ids that no record lists; exercises '
+                        'the device-side panoptic loader + training pipeline (the config needs a Load*PanopticAnnotations pipeline)')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--log-interval', type=int, default=10)
     p.add_argument('--save-interval', type=int, default=0, help='iterations between checkpoints (0: only at the end)')
@@ -221,18 +228,24 @@ def main(argv=None):
     spg = args.samples_per_gpu or (cfg.get('data') or {}).get('samples_per_gpu', 2)
     head = cfg.model['panoptic_head']
     num_classes = head['num_things_classes'] + head['num_stuff_classes']
-    stream_name = f'--data {args.data}' if args.data else f'--synthetic-u8 {args.synthetic_u8}' if args.synthetic_u8 else '--synthetic'
+    stream_name = (f'--data {args.data}' if args.data else f'--synthetic-u8 {args.synthetic_u8}' if args.synthetic_u8 else
+                   f'--synthetic-panoptic {args.synthetic_panoptic}' if args.synthetic_panoptic else '--synthetic')
     vocab = ((head.get('caption_generator') or {}).get('nb_tokens')) or 30522          # token ids must index the table
     if args.data:
         mod, fn = args.data.split(':')
         samples = getattr(importlib.import_module(mod), fn)(cfg, rank, world)
-    elif args.synthetic_u8:
+    elif args.synthetic_u8 or args.synthetic_panoptic:
+        flag, val = ('--synthetic-u8', args.synthetic_u8) if args.synthetic_u8 else ('--synthetic-panoptic', args.synthetic_panoptic)
         try:
-            hw = tuple(int(v) for v in args.synthetic_u8.lower().split('x'))
+            hw = tuple(int(v) for v in val.lower().split('x'))
             assert len(hw) == 2 and min(hw) >= 1
         except (ValueError, AssertionError):
-            raise SystemExit(f'--synthetic-u8 {args.synthetic_u8!r}: expected HxW, e.g. 480x640')
-        samples = synthetic_u8_samples(hw, num_classes, seed=1000 * rank + seed, vocab=vocab)
+            raise SystemExit(f'{flag} {val!r}: expected HxW, e.g. 480x640')
+        if args.synthetic_u8:
+            samples = synthetic_u8_samples(hw, num_classes, seed=1000 * rank + seed, vocab=vocab)
+        else:
+            samples = synthetic.panoptic_samples(hw, head['num_things_classes'], head['num_stuff_classes'], seed=1000 * rank + seed,
+                                                 vocab=vocab)
     else:
         samples = synthetic_samples(args.synthetic, num_classes, seed=1000 * rank + seed, vocab=vocab)
     max_iters = args.max_iters or (cfg.get('runner') or {}).get('max_iters')
