@@ -2,10 +2,39 @@
 // configs/instance/coco_b48n17.py:40; [3P] MSDeformAttnPixelDecoder input/lateral/output convs).
 // HBM-bound: at 256x256 a (batch, group) row holds 524288 elements but there are only B*32 = 64 rows, so a
 // row-per-block reduction leaves 3/4 of the chip idle. Here every row is split into chunks (pass 1: partial
-// sum / sum of squares per chunk, full-chip), and pass 2 folds the partials and normalises.
+// statistics per chunk, full-chip), and pass 2 folds the partials and normalises.
+// The statistics are two-pass per chunk -- the chunk sits in registers: its mean c, then r = sum (x - c) and
+// q = sum (x - c)^2 -- and the chunks are merged in double about the first chunk's c (Chan et al.). The one-pass
+// E[x^2] - mean^2 this replaces lost log2(mean^2 / var) bits of the variance when |mean| >> std.
 #include "x3.h"
 
 #define GN_CHUNK 16384  // elements per partial
+#define GN_PART 3       // floats per partial: (c, r, q)
+#define GN_SPAN 4       // vectors per thread of the apply pass: the merge of the partials in front of it is paid once per 256 * GN_SPAN of them
+
+// sum of v over the 256 threads of the block, returned to every thread (sm: 4 floats)
+__device__ __forceinline__ float gn_block_sum(float v, float* sm) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// sums of a and of b over the 256 threads of the block, returned to every thread (sm: 8 floats, reusable after the call)
+__device__ __forceinline__ void gn_block_sum2(float& a, float& b, float* sm) {
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o);
+    b += __shfl_xor(b, o);
+  }
+  __syncthreads();  // the previous call's readers are done with sm
+  if ((threadIdx.x & 63) == 0) {
+    sm[threadIdx.x >> 6] = a;
+    sm[4 + (threadIdx.x >> 6)] = b;
+  }
+  __syncthreads();
+  a = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  b = (sm[4] + sm[5]) + (sm[6] + sm[7]);
+}
 
 template <int VEC>
 __global__ __launch_bounds__(256) void cgg_gn_partial_kernel(const float* __restrict__ x,
@@ -15,34 +44,54 @@ __global__ __launch_bounds__(256) void cgg_gn_partial_kernel(const float* __rest
   const long long beg = (long long)chunk * GN_CHUNK;
   const long long end = min(row_len, beg + GN_CHUNK);
   const float* xr = x + (size_t)row * row_len;
-  float s = 0.f, ss = 0.f;
+  constexpr int PER = GN_CHUNK / 256;  // elements of the chunk per thread, held in registers; slots past `end` hold 0
+  float v[PER];
+  float s = 0.f;
   if (VEC == 4) {  // H*W % 4 == 0 and 16-B aligned rows -> float4 loads
-    for (long long i = beg + threadIdx.x * 4; i < end; i += 256 * 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
-      s += (v[0] + v[1]) + (v[2] + v[3]);
-      ss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+#pragma unroll
+    for (int k = 0; k < PER / 4; ++k) {
+      const long long i = beg + ((long long)k * 256 + threadIdx.x) * 4;
+      const f32x4 t = i < end ? *reinterpret_cast<const f32x4*>(xr + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[4 * k + e] = t[e];
+      s += (t[0] + t[1]) + (t[2] + t[3]);
     }
   } else {
-    for (long long i = beg + threadIdx.x; i < end; i += 256) {
-      const float v = xr[i];
-      s += v;
-      ss += v * v;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const long long i = beg + (long long)k * 256 + threadIdx.x;
+      v[k] = i < end ? xr[i] : 0.f;
+      s += v[k];
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o);
-    ss += __shfl_xor(ss, o);
-  }
   __shared__ float sm[8];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sm[wave] = s;
-    sm[4 + wave] = ss;
+  const float c = gn_block_sum(s, sm) / (float)(end - beg);
+  float r = 0.f, q = 0.f;
+  if (VEC == 4) {
+#pragma unroll
+    for (int k = 0; k < PER / 4; ++k) {
+      if (beg + ((long long)k * 256 + threadIdx.x) * 4 < end) {
+        const float d0 = v[4 * k] - c, d1 = v[4 * k + 1] - c, d2 = v[4 * k + 2] - c, d3 = v[4 * k + 3] - c;
+        r += (d0 + d1) + (d2 + d3);
+        q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      if (beg + (long long)k * 256 + threadIdx.x < end) {
+        const float d = v[k] - c;
+        r += d;
+        q += d * d;
+      }
+    }
   }
-  __syncthreads();
+  gn_block_sum2(r, q, sm);
   if (threadIdx.x == 0) {
-    part[((size_t)row * chunks + chunk) * 2] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    part[((size_t)row * chunks + chunk) * 2 + 1] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
+    float* o = part + ((size_t)row * chunks + chunk) * GN_PART;
+    o[0] = c;
+    o[1] = r;
+    o[2] = q;
   }
 }
 
@@ -53,35 +102,47 @@ __global__ __launch_bounds__(256) void cgg_gn_apply_kernel(const float* __restri
                                                            const float* __restrict__ beta,
                                                            float* __restrict__ y, int C, int groups,
                                                            long long hw, int chunks, float eps, int relu) {
-  // blockIdx.y = (b, channel), blockIdx.x = 1024-element span of that plane
+  // blockIdx.y = (b, channel), blockIdx.x = span of 256 * GN_SPAN vectors of that plane
   const int bc = blockIdx.y;
   const int c = bc % C, b = bc / C;
   const int cpg = C / groups;
   const int row = b * groups + c / cpg;
-  double s = 0.0, ss = 0.0;
+  const long long row_len = (long long)cpg * hw;
+  const float* pr = part + (size_t)row * chunks * GN_PART;
+  // chunk i holds n_i elements with sum n_i c_i + r_i and, about c0 = the first chunk's c, sum (x - c0)^2 = q_i + 2 d_i r_i + n_i d_i^2
+  // with d_i = c_i - c0: moments as large as the spread between the chunks, summed in double
+  const double c0 = (double)pr[0];
+  double s = 0.0, t = 0.0;
   for (int i = 0; i < chunks; ++i) {
-    s += (double)part[((size_t)row * chunks + i) * 2];
-    ss += (double)part[((size_t)row * chunks + i) * 2 + 1];
+    const double ni = (double)(min(row_len, (long long)(i + 1) * GN_CHUNK) - (long long)i * GN_CHUNK);
+    const double d = (double)pr[i * GN_PART] - c0, r = (double)pr[i * GN_PART + 1];
+    s += ni * d + r;
+    t += (double)pr[i * GN_PART + 2] + d * (2.0 * r + ni * d);
   }
-  const double n = (double)cpg * (double)hw;
-  const double mean = s / n;
-  const double var = fmax(ss / n - mean * mean, 0.0);
+  const double n = (double)row_len;
+  const double dm = s / n;
+  const double mean = c0 + dm;
+  const double var = fmax(t / n - dm * dm, 0.0);
   const float rstd = (float)(1.0 / sqrt(var + (double)eps));
   const float a = gamma[c] * rstd;
-  const float sh = beta[c] - (float)mean * a;
-  const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
-  if (i < hw) {
+  const float bt = beta[c];
+  // y = (x - mean) a + beta with the mean as two floats: x - mh is exact for x near the mean, where x a - mean a cancelled
+  const float mh = (float)mean, ml = (float)(mean - (double)mh);
+#pragma unroll
+  for (int k = 0; k < GN_SPAN; ++k) {
+    const long long i = (((long long)blockIdx.x * GN_SPAN + k) * 256 + threadIdx.x) * VEC;
+    if (i >= hw) break;
     const size_t off = (size_t)bc * hw + i;
     if (VEC == 4) {
       f32x4 v = *reinterpret_cast<const f32x4*>(x + off);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float r = v[e] * a + sh;
+        float r = ((v[e] - mh) - ml) * a + bt;
         v[e] = relu ? fmaxf(r, 0.f) : r;
       }
       *reinterpret_cast<f32x4*>(y + off) = v;
     } else {
-      const float r = x[off] * a + sh;
+      const float r = ((x[off] - mh) - ml) * a + bt;
       y[off] = relu ? fmaxf(r, 0.f) : r;
     }
   }
@@ -91,7 +152,7 @@ extern "C" int64_t cgg_group_norm_workspace_bytes(int B, int C, int H, int W, in
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || groups <= 0 || C % groups) return 0;
   const long long row_len = (long long)(C / groups) * H * W;
   const int chunks = (int)((row_len + GN_CHUNK - 1) / GN_CHUNK);
-  return (int64_t)B * groups * chunks * 2 * (int64_t)sizeof(float);
+  return (int64_t)B * groups * chunks * GN_PART * (int64_t)sizeof(float);
 }
 
 extern "C" int cgg_group_norm(const float* x, const float* gamma, const float* beta, float* y, void* ws, int B,
@@ -107,12 +168,12 @@ extern "C" int cgg_group_norm(const float* x, const float* gamma, const float* b
   if (vec) {
     hipLaunchKernelGGL(cgg_gn_partial_kernel<4>, dim3(chunks, B * groups), dim3(256), 0, s, x, (float*)ws,
                        row_len, chunks);
-    hipLaunchKernelGGL(cgg_gn_apply_kernel<4>, dim3((unsigned)((hw / 4 + 255) / 256), B * C), dim3(256), 0, s,
+    hipLaunchKernelGGL(cgg_gn_apply_kernel<4>, dim3((unsigned)((hw / 4 + 256 * GN_SPAN - 1) / (256 * GN_SPAN)), B * C), dim3(256), 0, s,
                        x, (const float*)ws, gamma, beta, y, C, groups, hw, chunks, eps, relu);
   } else {
     hipLaunchKernelGGL(cgg_gn_partial_kernel<1>, dim3(chunks, B * groups), dim3(256), 0, s, x, (float*)ws,
                        row_len, chunks);
-    hipLaunchKernelGGL(cgg_gn_apply_kernel<1>, dim3((unsigned)((hw + 255) / 256), B * C), dim3(256), 0, s, x,
+    hipLaunchKernelGGL(cgg_gn_apply_kernel<1>, dim3((unsigned)((hw + 256 * GN_SPAN - 1) / (256 * GN_SPAN)), B * C), dim3(256), 0, s, x,
                        (const float*)ws, gamma, beta, y, C, groups, hw, chunks, eps, relu);
   }
   CGG_CHECK_LAUNCH("cgg_group_norm");
@@ -122,7 +183,7 @@ extern "C" int cgg_group_norm(const float* x, const float* gamma, const float* b
 // -------------------------------------------------------------------------------------------------
 // Channel-last (NHWC) bf16 GroupNorm for the throughput-mode pixel decoder: x [B, HW, C] is the bf16 output of
 // a 1x1-conv GEMM / MIOpen NHWC conv; C / groups == 8, so ONE 16-byte vector is exactly one group of one pixel.
-//   stats : per (b, g) sum and sum of squares (f32 partials per thread, LDS tree, one atomic pair per block)
+//   stats : per (b, g) mean and variance: two-pass (mean, then deviations) inside each 64-pixel block, blocks merged in double
 //   apply : y = (x - mean) * rstd * gamma + beta [+ bilinear x2 up-sample of a low-res f32 NHWC map] [ReLU], with
 //           up to three outputs from the one pass:
 //             y32 f32, rows at b * y32_bstride (lets the three encoder levels land directly in the (B, N, 256)
@@ -152,69 +213,111 @@ __device__ __forceinline__ void gnh_load(const uint4* __restrict__ x, size_t i, 
   }
 }
 
+#define GNH_PART 4   // floats per (block, group) partial: (c, r, q, n) -- see the stats kernel
+#define GNH_REG 8    // pixels per thread the stats kernel keeps in registers (all of them for groups <= 32)
+
 template <bool XF32>
 __global__ __launch_bounds__(256) void cgg_gn_nhwc_stats_kernel(const uint4* __restrict__ x, float* __restrict__ ws,
                                                                int HW, int G, int ppb, int B_G2_floats) {
   // thread t: group g = t % G (G <= 256 and 256 % G == 0), pixel lane = t / G
+  // Two passes over the block's pixels, which sit in registers (the ones past GNH_REG per thread -- groups > 32 -- are read again):
+  // c = the block's mean of the group, then r = sum (x - c) and q = sum (x - c)^2. The reduce kernel merges the blocks around the
+  // image's mean. A one-pass E[x^2] - mean^2 cancels catastrophically when |mean| >> std, which torch's GroupNorm (Welford /
+  // two-pass) does not; sums about one pivot element of x do too as soon as that element is an outlier.
   __shared__ float red[2][256];
   const int b = blockIdx.y;
   const int tid = threadIdx.x;
   const int g = tid % G, pl = tid / G, PL = 256 / G;
   const int p0 = blockIdx.x * ppb;
   const int p1 = min(p0 + ppb, HW);
-  float s = 0.f, q = 0.f;
-  // f32 maps (parity mode): sums of (x - pivot), pivot = the group's first value of the image, the same for every block -- the
-  // one-pass E[x^2] - mean^2 of the bf16 path cancels catastrophically when |mean| >> std, which torch's f32 GroupNorm
-  // (Welford / two-pass) does not
-  const float pv = XF32 ? reinterpret_cast<const float*>(x)[((size_t)b * HW * G + g) * 8] : 0.f;
-  for (int p = p0 + pl; p < p1; p += PL) {
-    float f[8];
-    gnh_load<XF32>(x, ((size_t)b * HW + p) * G + g, f);
+  const size_t base = (size_t)b * HW * G + g;
+  float f[GNH_REG][8];
+  float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float lo = f[2 * k] - pv, hi = f[2 * k + 1] - pv;
-      s += lo + hi;
+  for (int k = 0; k < GNH_REG; ++k) {
+    const int p = p0 + pl + k * PL;
+    if (p < p1) {
+      gnh_load<XF32>(x, base + (size_t)p * G, f[k]);
+      s += ((f[k][0] + f[k][1]) + (f[k][2] + f[k][3])) + ((f[k][4] + f[k][5]) + (f[k][6] + f[k][7]));
+    }
+  }
+  for (int p = p0 + pl + GNH_REG * PL; p < p1; p += PL) {
+    float t[8];
+    gnh_load<XF32>(x, base + (size_t)p * G, t);
+    s += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+  }
+  red[0][tid] = s;
+  __syncthreads();
+  s = 0.f;
+  for (int k = 0; k < PL; ++k) s += red[0][g + k * G];
+  const float n = (float)((p1 - p0) * 8);
+  const float c = s / n;
+  __syncthreads();                      // red[0] is written again below
+  float r = 0.f, q = 0.f;
+#pragma unroll
+  for (int k = 0; k < GNH_REG; ++k) {
+    if (p0 + pl + k * PL < p1) {
+#pragma unroll
+      for (int e = 0; e < 8; e += 2) {
+        const float lo = f[k][e] - c, hi = f[k][e + 1] - c;
+        r += lo + hi;
+        q += lo * lo + hi * hi;
+      }
+    }
+  }
+  for (int p = p0 + pl + GNH_REG * PL; p < p1; p += PL) {
+    float t[8];
+    gnh_load<XF32>(x, base + (size_t)p * G, t);
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+      const float lo = t[e] - c, hi = t[e + 1] - c;
+      r += lo + hi;
       q += lo * lo + hi * hi;
     }
   }
-  red[0][tid] = s;
+  red[0][tid] = r;
   red[1][tid] = q;
   __syncthreads();
   if (tid < G) {
     for (int k = 1; k < PL; ++k) {
-      s += red[0][tid + k * G];
+      r += red[0][tid + k * G];
       q += red[1][tid + k * G];
     }
     // per-block partials (no atomics: 512 blocks hammering 64 addresses made this pass 3x slower than the read)
-    float* part = ws + (size_t)B_G2_floats + (((size_t)b * gridDim.x + blockIdx.x) * G + g) * 2;
-    part[0] = s;
-    part[1] = q;
+    float* part = ws + (size_t)B_G2_floats + (((size_t)b * gridDim.x + blockIdx.x) * G + g) * GNH_PART;
+    reinterpret_cast<float2*>(part)[0] = make_float2(c, r);
+    reinterpret_cast<float2*>(part)[1] = make_float2(q, n);
   }
 }
 
-// second level: one 64-lane wave per (b, g) sums the per-block partials -> ws[b][g][2]
-__global__ __launch_bounds__(64) void cgg_gn_nhwc_reduce_kernel(float* __restrict__ ws, int B_G2_floats, int nblk, int G,
-                                                               int B, const float* __restrict__ x32, int HW, float inv_n) {
+// second level: one 64-lane wave per (b, g) merges the per-block partials -> ws[b][g] = (mean, variance). Block k holds n_k values
+// with sum n_k c_k + r_k and, about any c0, sum (x - c0)^2 = q_k + 2 d_k r_k + n_k d_k^2 with d_k = c_k - c0 (Chan et al.). c0 is the
+// first block's c: the moments about it are as large as the spread between the blocks, not as the mean, and they are summed in
+// double (nblk / 64 partials per lane), so that the final t - s^2 / n has nothing to cancel that f32 would have kept.
+__global__ __launch_bounds__(64) void cgg_gn_nhwc_reduce_kernel(float* __restrict__ ws, int B_G2_floats, int nblk, int G) {
   const int i = blockIdx.x;                  // (b, g)
   const int b = i / G, g = i - b * G;
-  const float* part = ws + B_G2_floats + ((size_t)b * nblk * G + g) * 2;
-  float s = 0.f, q = 0.f;
+  const float* part = ws + B_G2_floats + ((size_t)b * nblk * G + g) * GNH_PART;
+  const double c0 = (double)part[0];
+  double s = 0.0, t = 0.0, n = 0.0;
+#pragma unroll 4
   for (int k = threadIdx.x; k < nblk; k += 64) {
-    const float2 v = *reinterpret_cast<const float2*>(part + (size_t)k * G * 2);
-    s += v.x;
-    q += v.y;
+    const float2* v = reinterpret_cast<const float2*>(part + (size_t)k * G * GNH_PART);
+    const float2 cr = v[0], qn = v[1];
+    const double d = (double)cr.x - c0, r = (double)cr.y, nk = (double)qn.y;
+    s += nk * d + r;
+    t += (double)qn.x + d * (2.0 * r + nk * d);
+    n += nk;
   }
   for (int o = 32; o > 0; o >>= 1) {
     s += __shfl_xor(s, o);
-    q += __shfl_xor(q, o);
+    t += __shfl_xor(t, o);
+    n += __shfl_xor(n, o);
   }
   if (threadIdx.x == 0) {
-    // -> (mean, variance). x32 != NULL: the sums are of (x - pivot) (see the stats kernel); the pivot is read HERE, before the
-    // apply pass -- which may run in place -- overwrites it
-    const float pv = x32 ? x32[((size_t)b * HW * G + g) * 8] : 0.f;
-    const float dm = s * inv_n;
-    ws[(size_t)i * 2] = pv + dm;
-    ws[(size_t)i * 2 + 1] = fmaxf(q * inv_n - dm * dm, 0.f);
+    const double dm = s / n;
+    ws[(size_t)i * 2] = (float)(c0 + dm);
+    ws[(size_t)i * 2 + 1] = (float)fmax(t / n - dm * dm, 0.0);
   }
 }
 
@@ -348,7 +451,7 @@ __global__ __launch_bounds__(256) void cgg_gn_nhwc_apply_kernel(
 extern "C" int64_t cgg_group_norm_nhwc_workspace_bytes(int B, int HW, int groups) {
   if (B <= 0 || HW <= 0 || groups <= 0) return 0;
   const int64_t nblk = (HW + GNH_PIX - 1) / GNH_PIX;
-  return ((int64_t)B * groups * 2 + (int64_t)B * nblk * groups * 2) * (int64_t)sizeof(float);
+  return ((int64_t)B * groups * 2 + (int64_t)B * nblk * groups * GNH_PART) * (int64_t)sizeof(float);
 }
 
 int* cgg_x3_overflow_flag_ptr();       // x3s_gemm.hip
@@ -359,6 +462,7 @@ static int gnh_launch(bool xf32, const void* x, const float* gamma, const float*
                       const float* pos, void* yp16, int64_t y16_bstride, cgg_stream_t stream, float* yp32 = nullptr,
                       int x3a = 0, int out_padw = 0) {
   CGG_REQUIRE(x && gamma && beta && ws, CGG_EINVAL, "cgg_group_norm_nhwc: null pointer");
+  CGG_REQUIRE((((uintptr_t)ws) & 7u) == 0, CGG_EALIGN, "cgg_group_norm_nhwc: ws must be 8-byte aligned");
   CGG_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0, CGG_EINVAL, "cgg_group_norm_nhwc: bad sizes");
   CGG_REQUIRE(C == groups * 8 && groups <= 256 && 256 % groups == 0, CGG_EUNSUPPORTED,
               "cgg_group_norm_nhwc: needs C / groups == 8 and groups | 256 (C=%d, groups=%d)", C, groups);
@@ -373,7 +477,7 @@ static int gnh_launch(bool xf32, const void* x, const float* gamma, const float*
               CGG_EALIGN, "cgg_group_norm_nhwc: pointers / strides must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int nblk = (HW + GNH_PIX - 1) / GNH_PIX;
-  const int head = B * groups * 2;        // ws = [B][G][2] totals, then [B][nblk][G][2] per-block partials
+  const int head = B * groups * 2;        // ws = [B][G][2] (mean, variance), then [B][nblk][G][GNH_PART] per-block partials
   if (xf32)
     hipLaunchKernelGGL(cgg_gn_nhwc_stats_kernel<true>, dim3(nblk, B), dim3(256), 0, s, (const uint4*)x, (float*)ws, HW, groups,
                        GNH_PIX, head);
@@ -381,8 +485,7 @@ static int gnh_launch(bool xf32, const void* x, const float* gamma, const float*
     hipLaunchKernelGGL(cgg_gn_nhwc_stats_kernel<false>, dim3(nblk, B), dim3(256), 0, s, (const uint4*)x, (float*)ws, HW, groups,
                        GNH_PIX, head);
   const float inv_n = 1.f / ((float)HW * 8.f);
-  hipLaunchKernelGGL(cgg_gn_nhwc_reduce_kernel, dim3(B * groups), dim3(64), 0, s, (float*)ws, head, nblk, groups, B,
-                     xf32 ? (const float*)x : nullptr, HW, inv_n);
+  hipLaunchKernelGGL(cgg_gn_nhwc_reduce_kernel, dim3(B * groups), dim3(64), 0, s, (float*)ws, head, nblk, groups);
   const long long nvec = (long long)HW * groups;
   const dim3 grid((unsigned)((nvec + 255) / 256), B);
 #define GNH_APPLY(UP, XF)                                                                                                   \
@@ -450,8 +553,7 @@ extern "C" int cgg_group_norm_nhwc_f32_stats(const float* x, void* ws, int B, in
   const int head = B * groups * 2;
   hipLaunchKernelGGL(cgg_gn_nhwc_stats_kernel<true>, dim3(nblk, B), dim3(256), 0, s, (const uint4*)x, (float*)ws, HW, groups, GNH_PIX,
                      head);
-  const float inv_n = 1.f / ((float)HW * 8.f);
-  hipLaunchKernelGGL(cgg_gn_nhwc_reduce_kernel, dim3(B * groups), dim3(64), 0, s, (float*)ws, head, nblk, groups, B, x, HW, inv_n);
+  hipLaunchKernelGGL(cgg_gn_nhwc_reduce_kernel, dim3(B * groups), dim3(64), 0, s, (float*)ws, head, nblk, groups);
   CGG_CHECK_LAUNCH("cgg_group_norm_nhwc_f32_stats");
   return CGG_OK;
 }

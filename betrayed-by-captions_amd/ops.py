@@ -1305,7 +1305,7 @@ def _ptr_at(t, elem_offset=0):
 
 
 def group_norm_nhwc_workspace(B, HW, groups, device):
-    """f32 scratch for `group_norm_nhwc` (totals + per-block partial sums)."""
+    """f32 scratch for `group_norm_nhwc` ((mean, variance) per (b, group) + per-block partial statistics)."""
     n = _lib_().cgg_group_norm_nhwc_workspace_bytes(int(B), int(HW), int(groups))
     return torch.empty((max(n // 4, 1),), dtype=torch.float32, device=device)
 

@@ -937,7 +937,7 @@ int cgg_add_layernorm_kv(const void* a, int a_dtype, const void* b, int b_dtype,
  *   F.interpolate(outs[-1])` step) (+ ReLU); outputs (each nullable, at least one): y32 f32 with batch stride
  *   y32_bstride elements (writes straight into the (B, N, C) encoder stream), y16 = bf16(y) and yp16 =
  *   bf16(y + pos), pos [HW, C] f32, both with batch stride y16_bstride elements. ws:
- *   cgg_group_norm_nhwc_workspace_bytes(B, HW, groups) bytes of scratch (per-block partial sums, no atomics).
+ *   cgg_group_norm_nhwc_workspace_bytes(B, HW, groups) bytes of scratch (per-block partial statistics, no atomics).
  * cgg_pack_mask_feature_nhwc: cgg_pack_mask_feature for a [B, H, W, C] bf16 map (hi image only).              */
 int64_t cgg_group_norm_nhwc_workspace_bytes(int B, int HW, int groups);
 int cgg_group_norm_nhwc(const void* x, const float* gamma, const float* beta, void* ws, int B, int HW, int C,
