@@ -189,6 +189,9 @@ PROTOTYPES = {
     'cgg_instance_masks_picks': (_c_int, [_c_vp] * 3 + [_c_int] + [_c_vp] * 3 + [_c_int] * 10 + [_c_vp]),
     'cgg_panoptic_argmax': (_c_int, [_c_vp] * 6 + [_c_int] * 10 + [_c_vp]),
     'cgg_panoptic_paint': (_c_int, [_c_vp] * 5 + [_c_i64, _c_int, _c_vp]),
+    'cgg_panoptic_fuse_batched_workspace_bytes': (_c_i64, [_c_int, _c_int, _c_i64]),
+    'cgg_panoptic_fuse_batched': (_c_int, [_c_vp] * 9 + [_c_i64] + [_c_int] * 8 + [_c_i64, _c_int, _c_int, _c_f, ctypes.c_double] +
+                                  [_c_int] * 3 + [_c_vp]),
     'cgg_rowwise_softmax_argmax': (_c_int, [_c_vp] * 4 + [_c_int, _c_int, _c_vp]),
 }
 

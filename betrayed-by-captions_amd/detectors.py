@@ -12,6 +12,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .config import to_config_dict
+from .maskformer_fusion_head import segments_info
 from .registry import DETECTORS, build_backbone, build_head, build_neck
 
 
@@ -186,6 +187,11 @@ class MaskFormerOpen(nn.Module):
                     for j, label in enumerate(labels_per_image.detach().cpu().tolist()):
                         mask_results[label].append(masks_np[j])
                     results[i][res_type] = bbox_results, mask_results
+            if isinstance(results[i].get('panoptic_segments'), dict):
+                # `with_segments=True` (this build's extension): the device segment table -> COCO-panoptic `segments_info` dicts
+                seg = results[i]['panoptic_segments']
+                results[i]['panoptic_segments'] = segments_info(seg['table'].cpu().numpy(), int(seg['n_kept']),
+                                                                fh.num_things_classes, seg['scores'].cpu().numpy())
             if kwargs.get('with_mask', False):
                 results[i]['mask'] = mask_pred_results.upsampled().cpu().numpy()
             if kwargs.get('with_att', False):

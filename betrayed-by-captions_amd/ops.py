@@ -907,6 +907,51 @@ def panoptic_paint(ids, win_half, lut_val, lut_half, void_label):
     return seg
 
 
+PANOPTIC_FUSE_MAX_Q = 1024
+
+
+def panoptic_fuse_geometry(out_sizes, crop_sizes, device):
+    """Geometry of a batch for `panoptic_fuse_batched`: (device table (B, 5) int64 [crop_h, crop_w, out_h, out_w, first pixel
+    in the flat map], (max out_h, max out_w), total pixels, [(first pixel, out_h, out_w)])."""
+    rows, views, off = [], [], 0
+    for (oh, ow), (ch, cw) in zip(out_sizes, crop_sizes):
+        rows.append([int(ch), int(cw), int(oh), int(ow), off])
+        views.append((off, int(oh), int(ow)))
+        off += int(oh) * int(ow)
+    table = torch.tensor(rows, dtype=torch.int64).to(device)
+    return table, (max(r[2] for r in rows), max(r[3] for r in rows)), off, views
+
+
+def panoptic_fuse_batched(logits, score, label, geometry, up_size, num_classes, num_things, object_mask_thr, iou_thr,
+                          filter_low_score, stuff_area_limit, defer_stuff, debug=False):
+    """logits (B,Q,H,W) f32, score (B,Q) f32 / label (B,Q) int64 of `rowwise_softmax_argmax`, `geometry` of
+    `panoptic_fuse_geometry` -> (flat int32 map, n_kept (B,), segments (B,Q,4) int32 [value, category, area, query], kept scores
+    (B,Q)); no host read, four launches (`cgg_panoptic_fuse_batched`). `debug` adds the (B, 2) int32 count of argmax blocks that
+    staged their footprint in LDS / read global memory."""
+    B, Q, H, W = logits.shape
+    table, (moh, mow), total, _ = geometry
+    if table.shape != (B, 5) or tuple(score.shape) != (B, Q) or tuple(label.shape) != (B, Q):
+        raise CggError(f'panoptic_fuse_batched: logits {tuple(logits.shape)}, score {tuple(score.shape)}, label {tuple(label.shape)}, '
+                       f'geometry {tuple(table.shape)} disagree')
+    dev = logits.device
+    seg = torch.empty((total,), dtype=torch.int32, device=dev)
+    n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
+    segments = torch.empty((B, Q, 4), dtype=torch.int32, device=dev)
+    kscore = torch.empty((B, Q), dtype=torch.float32, device=dev)
+    nbytes = int(_lib_().cgg_panoptic_fuse_batched_workspace_bytes(B, Q, total))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
+    rc = _lib_().cgg_panoptic_fuse_batched(dev_ptr(logits, 'logits', torch.float32), dev_ptr(score, 'score', torch.float32),
+                                           dev_ptr(label, 'label', torch.int64), dev_ptr(table, 'geometry', torch.int64),
+                                           dev_ptr(seg), dev_ptr(n_kept), dev_ptr(segments), dev_ptr(kscore), dev_ptr(ws), nbytes,
+                                           B, Q, H, W, int(up_size[0]), int(up_size[1]), moh, mow, total, int(num_classes),
+                                           int(num_things), float(object_mask_thr), float(iou_thr), int(bool(filter_low_score)),
+                                           int(math.ceil(stuff_area_limit)), int(bool(defer_stuff)), stream_ptr(dev))
+    check(rc, 'cgg_panoptic_fuse_batched')
+    if debug:
+        return seg, n_kept, segments, kscore, ws[:2 * B].view(B, 2)
+    return seg, n_kept, segments, kscore
+
+
 def rowwise_softmax_argmax(x, want_prob=True):
     """x (rows,n) f32 -> (prob (rows,n) | None, max prob (rows,), argmax (rows,) int64)."""
     rows, n = x.shape

@@ -43,7 +43,7 @@ class StagePipeline:
 
     def __init__(self, stages, example, slots=None, warmup=2, streams=None, tail=None):
         """tail -- optional callable applied EAGERLY (not captured) to the last graph stage's output: post-processing with
-                   data-dependent host reads (the panoptic fusion head reads segment counts: no hipGraph can hold that). It runs
+                   data-dependent host reads (the PER-IMAGE panoptic path reads segment counts: no hipGraph can hold that). It runs
                    on its own stream ONE BATCH BEHIND the graph stages -- `submit(k + 1)` first enqueues batch k + 1's graphs, then
                    runs batch k's tail -- so the host waits of the tail overlap the next batch's device work."""
         self.stages = list(stages)
@@ -175,14 +175,22 @@ class StagePipeline:
             cur.wait_stream(st)
 
 
-def detector_pipeline(model, example, metas, stages=3, defer_tail=True, **decode_kwargs):
+def detector_pipeline(model, example, metas, stages=3, defer_tail=True, panoptic_tail=None, **decode_kwargs):
     """Pipeline of a `MaskFormerOpen` detector: 2 stages = (backbone + head encode | decode + post-processing),
     3 stages = (backbone | head encode | decode + post-processing). `defer_tail` moves the K / V projections and the
-    mask-feature packing from the encode stage (the longer one) to the head of the decode stage."""
+    mask-feature packing from the encode stage (the longer one) to the head of the decode stage. `panoptic_tail` runs the
+    fusion head eagerly behind the graphs (None: only where the per-image panoptic path is in use)."""
     head = model.panoptic_head
-    if getattr(model.panoptic_fusion_head, 'panoptic_mode', False):
-        # panoptic post-processing reads data-dependent sizes on the host (kept queries, segment areas): the graph stages end with
-        # the query decoder, the fusion head runs eagerly one batch behind (`StagePipeline(tail=...)`)
+    fh = model.panoptic_fusion_head
+    from . import maskformer_fusion_head as _mfh
+    if panoptic_tail is None:
+        # the batched panoptic path (`panoptic_postprocess_batched`) reads nothing on the host, so panoptic models get the same
+        # stage lists as instance models and their post-processing is captured; the per-image path (PER_IMAGE_PANOPTIC, or more
+        # queries than the batched kernel takes) reads data-dependent sizes on the host and needs the eager tail
+        panoptic_tail = getattr(fh, 'panoptic_mode', False) and (
+            _mfh.PER_IMAGE_PANOPTIC or getattr(head, 'num_queries', 0) > _mfh.ops.PANOPTIC_FUSE_MAX_Q)
+    if panoptic_tail:
+        # the graph stages end with the query decoder, the fusion head runs eagerly one batch behind (`StagePipeline(tail=...)`)
         post = lambda out: model.stage_post(out, metas, **decode_kwargs)      # noqa: E731
         if stages in (2, 4):
             fns = [lambda x: model.stage_encode(x, defer_tail=defer_tail), lambda enc: model.stage_head(enc, metas, **decode_kwargs)]

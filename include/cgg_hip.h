@@ -1097,6 +1097,35 @@ int cgg_panoptic_paint(const int32_t* ids, const uint8_t* win_half, const int32_
                        const int32_t* lut_half, int32_t* seg, int64_t npix, int void_label,
                        cgg_stream_t stream);
 
+/* Batched panoptic fusion (maskformer_fusion_head.py:77-225) with no host read: select (keep = label != num_classes &&
+ * score > object_mask_thr, compacted in query order), tiled argmax of score * sigmoid(resized logit) with the three areas
+ * per kept query, the segment decisions (`maskformer_fusion_head.panoptic_decide_host` states the rule) and the painted
+ * map, for B images in four launches (the select kernel zeroes the counters: no memset node). Every data-dependent size is
+ * read from device memory by the kernels: no allocation, no synchronisation, legal under stream capture and replayable on
+ * new data.
+ *   logits [B, Q, H, W] f32;  score [B, Q] f32 and label [B, Q] int64 as cgg_rowwise_softmax_argmax writes them
+ *   geom   DEVICE [B, 5] int64: crop_h, crop_w, out_h, out_w, first pixel of the image in `seg`. up_h, up_w, H, W are
+ *          shared. A row with crop outside (up_h, up_w), out outside (max_out_h, max_out_w) or pixels outside
+ *          [0, total_out_pixels) is skipped by every kernel (its pixels stay unwritten).
+ *   seg    [total_out_pixels] int32, image b at geom[b][4] as [out_h, out_w]: category + instance_id * 1000 for things,
+ *          the category for stuff, num_classes for void
+ *   n_kept [B] int32;  kept_score [B, Q] f32 in slot order (0 past n_kept)
+ *   segments [B, Q, 4] int32, row k = the image's k-th kept query: value in the map (-1: nothing painted), category,
+ *          painted area, query index; rows past n_kept are -1, -1, 0, -1
+ *   ws     cgg_panoptic_fuse_batched_workspace_bytes(B, Q, total_out_pixels) bytes (4-byte aligned); its first 2 * B
+ *          int32 count, per image, the argmax blocks that staged their footprint in LDS and those that read global memory
+ *          (a tile whose footprint leaves room for fewer than 8 queries in the 32 KB window)
+ * defer_stuff = 1 is the `_emb` variant (stuff after the things, unfiltered area >= stuff_area_limit, painted without
+ * the 0.5 filter); 0 paints stuff in query order. CGG_EINVAL: null pointer, bad sizes, workspace too small;
+ * CGG_EUNSUPPORTED: Q > 1024 (the LDS histogram is sized by Q). */
+int64_t cgg_panoptic_fuse_batched_workspace_bytes(int B, int Q, int64_t total_out_pixels);
+int cgg_panoptic_fuse_batched(const float* logits, const float* score, const int64_t* label, const int64_t* geom,
+                              int32_t* seg, int32_t* n_kept, int32_t* segments, float* kept_score, void* ws,
+                              int64_t ws_bytes, int B, int Q, int H, int W, int up_h, int up_w, int max_out_h,
+                              int max_out_w, int64_t total_out_pixels, int num_classes, int num_things,
+                              float object_mask_thr, double iou_thr, int filter_low_score, int stuff_area_limit,
+                              int defer_stuff, cgg_stream_t stream);
+
 /* Row-wise softmax + max/argmax: scores = softmax(x) over the last dim, one wavefront per row
  * (MaskFormerFusionHeadOpen.get_cls_emb_scores, maskformer_fusion_head.py:297-315, and the
  * `.max(-1)` at :99).  x [rows, n] f32 -> prob [rows, n] f32 (nullable), maxv [rows] f32,
