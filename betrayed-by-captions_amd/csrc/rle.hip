@@ -62,6 +62,32 @@ struct RunWriter {
   }
 };
 
+// Peel the runs off the words of `ncols` columns (col[c * HB + by] = rows by*64 .. of column c, LSB = topmost row) with
+// count-trailing-zeros; (p, cnt) = value and length so far of the run that is open when the first column starts / the last ends.
+inline void peel_columns(const uint64_t* col, int ncols, int HB, int H, int& p, long long& cnt, RunWriter& rw) {
+  for (int c = 0; c < ncols; ++c) {
+    for (int by = 0; by < HB; ++by) {
+      uint64_t w = col[(size_t)c * HB + by];
+      int left = H - by * 64 < 64 ? H - by * 64 : 64;
+      while (left > 0) {
+        uint64_t diff = p ? ~w : w;                // bits that differ from the current run's value
+        if (left < 64) diff &= (~0ull >> (64 - left));
+        if (diff == 0) {
+          cnt += left;
+          break;
+        }
+        const int tz = __builtin_ctzll(diff);
+        cnt += tz;
+        rw.emit(cnt);
+        cnt = 0;
+        p ^= 1;
+        w = tz ? (w >> tz) : w;
+        left -= tz;
+      }
+    }
+  }
+}
+
 void encode_one(const uint8_t* bits, int H, int W, int row_bytes, std::string& out) {
   RunWriter rw;
   rw.out.reserve(4096);
@@ -105,28 +131,20 @@ void encode_one(const uint8_t* bits, int H, int W, int row_bytes, std::string& o
         for (int c = 0; c < ncols; ++c) col[(size_t)c * HB + by] = blk[c];
       }
     }
-    for (int c = 0; c < ncols; ++c) {
-      for (int by = 0; by < HB; ++by) {
-        uint64_t w = col[(size_t)c * HB + by];
-        int left = H - by * 64 < 64 ? H - by * 64 : 64;
-        while (left > 0) {
-          uint64_t diff = p ? ~w : w;                // bits that differ from the current run's value
-          if (left < 64) diff &= (~0ull >> (64 - left));
-          if (diff == 0) {
-            cnt += left;
-            break;
-          }
-          const int tz = __builtin_ctzll(diff);
-          cnt += tz;
-          rw.emit(cnt);
-          cnt = 0;
-          p ^= 1;
-          w = tz ? (w >> tz) : w;
-          left -= tz;
-        }
-      }
-    }
+    peel_columns(col.data(), ncols, HB, H, p, cnt, rw);
   }
+  rw.emit(cnt);
+  out.swap(rw.out);
+}
+
+// the second half of encode_one alone, on the column-major planes the device wrote (cgg_rle_transitions' `cols` layout:
+// cols[x * HB + by], bits beyond H zero): the columns of a mask are already contiguous, so one call peels them all
+void encode_one_colmajor(const uint64_t* cols, int H, int W, std::string& out) {
+  RunWriter rw;
+  rw.out.reserve(4096);
+  int p = 0;
+  long long cnt = 0;
+  peel_columns(cols, W, (H + 63) / 64, H, p, cnt, rw);
   rw.emit(cnt);
   out.swap(rw.out);
 }
@@ -213,14 +231,9 @@ RlePool& rle_pool() {
   return *p;
 }
 
-}  // namespace
-
-extern "C" int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, int W, int64_t mask_stride_bytes,
-                                           int row_bytes, int threads, uint8_t* out, int64_t out_cap, int64_t* offsets) {
-  if (!bits || !offsets || n < 0 || H <= 0 || W <= 0 || row_bytes * 8 < W || mask_stride_bytes < (int64_t)H * row_bytes) {
-    cgg_set_error("cgg_rle_encode_bitmasks: bad arguments (n=%d H=%d W=%d row_bytes=%d)", n, H, W, row_bytes);
-    return -(int64_t)CGG_EINVAL;
-  }
+// n strings, built by `one(i, string&)` on `threads` threads (the caller + helpers of the persistent pool), packed into out / offsets
+int64_t encode_many(const char* name, int n, int threads, const std::function<void(int, std::string&)>& one, uint8_t* out,
+                    int64_t out_cap, int64_t* offsets) {
   try {                                   // no C++ exception may cross the C ABI (std::thread / allocation failures)
   std::vector<std::string> enc((size_t)n);
   if (threads < 1) threads = 1;
@@ -232,7 +245,7 @@ extern "C" int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, in
       for (;;) {
         const int i = next.fetch_add(1);
         if (i >= n) break;
-        encode_one(bits + (size_t)i * mask_stride_bytes, H, W, row_bytes, enc[(size_t)i]);
+        one(i, enc[(size_t)i]);
       }
     } catch (...) {
       failed.store(true);                 // an exception must not leave a worker thread either
@@ -247,8 +260,8 @@ extern "C" int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, in
     rle_pool().run(threads - 1, work);
   }
   if (failed.load()) {                    // (dropped with the move to the pool in round 4: a failed mask came back as an empty RLE)
-    cgg_set_error("cgg_rle_encode_bitmasks: encoding failed (allocation failure inside a worker)");
-    return -(int64_t)CGG_EINVAL;
+    cgg_set_error("%s: encoding failed (allocation failure inside a worker)", name);
+    return (int64_t)CGG_EINVAL;
   }
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
@@ -261,10 +274,82 @@ extern "C" int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, in
   }
   return total;     // > out_cap: nothing was copied, call again with a larger buffer
   } catch (const std::exception& e) {
-    cgg_set_error("cgg_rle_encode_bitmasks: %s", e.what());
-    return -(int64_t)CGG_EINVAL;
+    cgg_set_error("%s: %s", name, e.what());
+    return (int64_t)CGG_EINVAL;
   } catch (...) {
-    cgg_set_error("cgg_rle_encode_bitmasks: unknown C++ exception");
-    return -(int64_t)CGG_EINVAL;
+    cgg_set_error("%s: unknown C++ exception", name);
+    return (int64_t)CGG_EINVAL;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, int W, int64_t mask_stride_bytes,
+                                           int row_bytes, int threads, uint8_t* out, int64_t out_cap, int64_t* offsets) {
+  if (!bits || !offsets || n < 0 || H <= 0 || W <= 0 || row_bytes * 8 < W || mask_stride_bytes < (int64_t)H * row_bytes) {
+    cgg_set_error("cgg_rle_encode_bitmasks: bad arguments (n=%d H=%d W=%d row_bytes=%d)", n, H, W, row_bytes);
+    return (int64_t)CGG_EINVAL;
+  }
+  return encode_many("cgg_rle_encode_bitmasks", n, threads, [&](int i, std::string& s) {
+    encode_one(bits + (size_t)i * mask_stride_bytes, H, W, row_bytes, s);
+  }, out, out_cap, offsets);
+}
+
+extern "C" int64_t cgg_rle_encode_colmajor(const uint64_t* cols, int n, int H, int W, int threads, uint8_t* out, int64_t out_cap,
+                                           int64_t* out_offsets) {
+  if (!out_offsets || n < 0 || (n > 0 && !cols) || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) ||
+      (((uintptr_t)cols) & 7u) != 0) {
+    cgg_set_error("cgg_rle_encode_colmajor: bad arguments (n=%d H=%d W=%d)", n, H, W);
+    return (int64_t)CGG_EINVAL;
+  }
+  const size_t plane = (size_t)((W + 63) / 64) * 64 * (size_t)((H + 63) / 64);      // words per mask
+  return encode_many("cgg_rle_encode_colmajor", n, threads, [&](int i, std::string& s) {
+    encode_one_colmajor(cols + (size_t)i * plane, H, W, s);
+  }, out, out_cap, out_offsets);
+}
+
+extern "C" int64_t cgg_rle_strings_from_transitions(const uint32_t* positions, const int64_t* offsets, int n, int H, int W,
+                                                    uint8_t* out, int64_t out_cap, int64_t* out_offsets) {
+  if (!offsets || !out_offsets || n < 0 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31)) {
+    cgg_set_error("cgg_rle_strings_from_transitions: bad arguments (n=%d H=%d W=%d)", n, H, W);
+    return (int64_t)CGG_EINVAL;
+  }
+  const long long hw = (long long)H * W;
+  for (int i = 0; i < n; ++i) {
+    if (offsets[i] < 0 || offsets[i + 1] < offsets[i] || (offsets[i + 1] > offsets[i] && !positions)) {
+      cgg_set_error("cgg_rle_strings_from_transitions: offsets[%d..%d] = %lld, %lld", i, i + 1, (long long)offsets[i],
+                    (long long)offsets[i + 1]);
+      return (int64_t)CGG_EINVAL;
+    }
+  }
+  try {
+    std::string all;
+    all.reserve(n > 0 ? (size_t)(offsets[n] - offsets[0]) * 2 + (size_t)n * 4 : 0);
+    for (int i = 0; i < n; ++i) {
+      out_offsets[i] = (int64_t)all.size();
+      RunWriter rw;
+      rw.out.swap(all);                    // append in place
+      long long last = 0;
+      for (int64_t k = offsets[i]; k < offsets[i + 1]; ++k) {
+        const long long t = positions[k];
+        if (t >= hw || (k > offsets[i] && t <= last)) {
+          cgg_set_error("cgg_rle_strings_from_transitions: mask %d: position %lld after %lld (H * W = %lld)", i, t, last, hw);
+          return (int64_t)CGG_EINVAL;
+        }
+        rw.emit(t - last);
+        last = t;
+      }
+      rw.emit(hw - last);
+      all.swap(rw.out);
+    }
+    out_offsets[n] = (int64_t)all.size();
+    if (out != nullptr && (int64_t)all.size() <= out_cap) std::memcpy(out, all.data(), all.size());
+    return (int64_t)all.size();
+  } catch (const std::exception& e) {
+    cgg_set_error("cgg_rle_strings_from_transitions: %s", e.what());
+    return (int64_t)CGG_EINVAL;
+  } catch (...) {
+    cgg_set_error("cgg_rle_strings_from_transitions: unknown C++ exception");
+    return (int64_t)CGG_EINVAL;
   }
 }

@@ -2914,3 +2914,114 @@ def rle_encode_bitmasks(bits, width, threads=8):
     raw = out[:total].tobytes()
     o = offs.tolist()
     return [dict(size=[H, W], counts=raw[o[i]:o[i + 1]]) for i in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------
+# device side of the same encoding: run boundaries on the GPU (csrc/rle_device.hip), strings on the host
+# ------------------------------------------------------------------------------------------------
+def rle_cols_shape(H, width):
+    """(padded columns, block-rows) of one mask's column-major plane in the workspace of `rle_transitions`."""
+    return 64 * ((int(width) + 63) // 64), (int(H) + 63) // 64
+
+
+def rle_transitions(bits, width, capacity=None, positions=None, offsets=None, ws=None):
+    """bits: DEVICE uint8 (n, H, row_bytes), rows contiguous (stride(0) may exceed H * row_bytes), pixel x in bit (x & 7) of byte
+    (x >> 3) -> (positions uint32 [capacity], offsets int64 [n + 1], ws uint8) on the device, on the current stream:
+    the transitions of the column-major bit stream of every mask (`host_results.rle_transitions_host` states the rule).
+    offsets is always complete; the positions of mask i are written iff offsets[i + 1] <= capacity. ws begins with the
+    column-major planes: ws[:n * Wp * Hb * 8].view(int64).view(n, Wp, Hb) with (Wp, Hb) = rle_cols_shape(H, width).
+    positions / offsets / ws may be handed in (reused buffers); no host read, no allocation then."""
+    if not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 3:
+        raise CggError('rle_transitions: (n, H, row_bytes) uint8 device tensor expected')
+    if not bits.is_cuda:
+        raise CggError(f'rle_transitions: bits must live on a ROCm device (got {bits.device})')
+    n, H, rb = bits.shape
+    W = int(width)
+    if n > 0 and (bits.stride(2) != 1 or bits.stride(1) != rb or bits.stride(0) < H * rb):
+        raise CggError(f'rle_transitions: rows must be contiguous and planes at least H * row_bytes apart (strides {bits.stride()})')
+    lib = _lib_()
+    dev = bits.device
+    if positions is None:
+        if capacity is None:
+            raise CggError('rle_transitions: give `capacity` or a `positions` buffer')
+        positions = torch.empty(max(int(capacity), 1), dtype=torch.int32, device=dev)
+    cap = positions.numel() if capacity is None else int(capacity)
+    if cap > positions.numel():
+        raise CggError(f'rle_transitions: capacity {cap} exceeds the positions buffer ({positions.numel()})')
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    if offsets.numel() < n + 1:
+        raise CggError(f'rle_transitions: offsets has {offsets.numel()} elements, n + 1 = {n + 1} needed')
+    need = int(lib.cgg_rle_transitions_workspace_bytes(n, H, W))
+    if ws is None:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    if ws.numel() < need:
+        raise CggError(f'rle_transitions: workspace of {ws.numel()} bytes, {need} needed')
+    for t, name in ((positions, 'positions'), (offsets, 'offsets'), (ws, 'ws')):
+        if t.device != dev:
+            raise CggError(f'rle_transitions: {name} ({t.device}) and bits ({dev}) live on different devices')
+    stride = bits.stride(0) if n > 0 else H * rb
+    with _timed('rle_transitions', bytes=float(n * H * rb), shape=(n, H, W)):
+        rc = lib.cgg_rle_transitions(ctypes.c_void_p(bits.data_ptr()), n, H, W, int(stride), rb, dev_ptr(ws, 'ws', torch.uint8),
+                                     dev_ptr(positions, 'positions', torch.int32), cap,
+                                     dev_ptr(offsets, 'offsets', torch.int64), stream_ptr(dev))
+    check(rc, 'cgg_rle_transitions')
+    return positions, offsets, ws
+
+
+def _rle_strings(call, what, n, H, W, cap):
+    import numpy as np
+    offs = np.empty(n + 1, dtype=np.int64)
+    while True:
+        out = np.empty(cap, dtype=np.uint8)
+        total = call(ctypes.c_void_p(out.ctypes.data), cap, ctypes.c_void_p(offs.ctypes.data))
+        if total < 0:
+            check(int(total), what)
+        if total <= cap:
+            break
+        cap = int(total)
+    raw = out[:total].tobytes()
+    o = offs.tolist()
+    return [dict(size=[H, W], counts=raw[o[i]:o[i + 1]]) for i in range(n)]
+
+
+def rle_strings_from_transitions(positions, offsets, H, width):
+    """HOST: positions (uint32 / int32 array, as `rle_transitions` wrote them) + offsets (int64 [n + 1]) -> list of n COCO RLE
+    dicts, byte-identical to `rle_encode_bitmasks` on the same masks."""
+    import numpy as np
+    pos = positions.numpy() if torch.is_tensor(positions) else np.asarray(positions)
+    off = offsets.numpy() if torch.is_tensor(offsets) else np.asarray(offsets)
+    if pos.dtype not in (np.uint32, np.int32) or pos.ndim != 1 or not pos.flags['C_CONTIGUOUS']:
+        raise CggError('rle_strings_from_transitions: contiguous 1-d uint32 host array of positions expected')
+    if off.dtype != np.int64 or off.ndim != 1 or off.size < 1 or not off.flags['C_CONTIGUOUS']:
+        raise CggError('rle_strings_from_transitions: contiguous int64 host array of n + 1 offsets expected')
+    n = off.size - 1
+    if n == 0:
+        return []
+    if int(off.max()) > pos.size:
+        raise CggError(f'rle_strings_from_transitions: offsets reach {int(off.max())}, {pos.size} positions given')
+    lib = _lib_()
+    H, W = int(H), int(width)
+    return _rle_strings(lambda out, cap, oo: lib.cgg_rle_strings_from_transitions(
+        ctypes.c_void_p(pos.ctypes.data), ctypes.c_void_p(off.ctypes.data), n, H, W, out, cap, oo),
+        'cgg_rle_strings_from_transitions', n, H, W, max(1 << 12, 2 * int(off[-1] - off[0]) + 8 * n))
+
+
+def rle_encode_colmajor(cols, H, width, threads=8):
+    """HOST: cols (n, Wp, Hb) 64-bit words, the column-major planes at the head of `rle_transitions`' workspace ((Wp, Hb) =
+    rle_cols_shape(H, width); bit r of cols[i, x, by] = pixel (by * 64 + r, x), bits beyond H or width zero) -> list of n COCO
+    RLE dicts, byte-identical to `rle_encode_bitmasks` on the same masks."""
+    import numpy as np
+    arr = cols.numpy() if torch.is_tensor(cols) else np.asarray(cols)
+    H, W = int(H), int(width)
+    if arr.dtype not in (np.uint64, np.int64) or arr.ndim != 3 or not arr.flags['C_CONTIGUOUS'] or \
+            tuple(arr.shape[1:]) != rle_cols_shape(H, W):
+        raise CggError(f'rle_encode_colmajor: contiguous (n, {rle_cols_shape(H, W)[0]}, {rle_cols_shape(H, W)[1]}) 64-bit host '
+                       'array expected')
+    n = arr.shape[0]
+    if n == 0:
+        return []
+    lib = _lib_()
+    return _rle_strings(lambda out, cap, oo: lib.cgg_rle_encode_colmajor(
+        ctypes.c_void_p(arr.ctypes.data), n, H, W, int(threads), out, cap, oo),
+        'cgg_rle_encode_colmajor', n, H, W, max(1 << 16, n * 4096))

@@ -418,10 +418,49 @@ int cgg_match_cost_rows(const float* x, float* sig, float* sp_sum, float* sig_su
  *           pycocotools' rleToString: column-major runs, first run = zeros); offsets[i] .. offsets[i+1] = string i
  *   offsets host int64[n + 1] (always written)
  * Returns the total number of bytes of all strings; if that exceeds out_cap nothing is copied (call again with a larger
- * buffer); negative = -CGG_E*.
+ * buffer); negative = CGG_E*.
  * ---------------------------------------------------------------------------------------------- */
 int64_t cgg_rle_encode_bitmasks(const uint8_t* bits, int n, int H, int W, int64_t mask_stride_bytes, int row_bytes,
                                 int threads, uint8_t* out, int64_t out_cap, int64_t* offsets);
+
+/* ----------------------------------------------------------------------------------------------
+ * Device side of the same encoding: where the column-major bit stream of each mask changes value.
+ *
+ * A run-length code is determined by those positions; the format (delta coding, 5-bit groups) is per run and stays on
+ * the host (cgg_rle_strings_from_transitions). `host_results.rle_transitions_host` states the rule in numpy and the
+ * kernels equal it exactly: with p = x * H + y and v(p) the pixel (v(-1) = 0), p is a transition iff v(p) != v(p - 1) --
+ * the bottom pixel of column x precedes the top pixel of column x + 1, and a mask whose pixel (0, 0) is set has a
+ * transition at 0. The COCO counts of mask i are then t0, t1 - t0, ..., H * W - t_last ([H * W] for an empty mask).
+ *
+ *   bits      DEVICE pointer, as cgg_rle_encode_bitmasks reads it on the host: n planes of H rows x row_bytes bytes, plane i
+ *             at bits + i * mask_stride_bytes, pixel x of a row = bit (x & 7) of byte (x >> 3); only the first W pixels of
+ *             a row count, pad bits may hold anything
+ *   ws        DEVICE, cgg_rle_transitions_workspace_bytes(n, H, W) bytes, 8-byte aligned. It BEGINS with the column-major
+ *             planes `cols[i][x][by]` (uint64; x in [0, 64 * ceil(W / 64)), by in [0, ceil(H / 64))): bit r = pixel
+ *             (by * 64 + r, x), bits beyond H or W zero. This layout is part of the contract (cgg_rle_encode_colmajor reads
+ *             it); the per-(mask, 64-column strip) transition counts (uint32) and their exclusive scan (int64) follow.
+ *   positions DEVICE uint32[capacity]: ascending per mask, packed mask after mask. The positions of mask i are written iff
+ *             offsets[i + 1] <= capacity (so: a prefix of the masks); nothing is written at or past `capacity`.
+ *   offsets   DEVICE int64[n + 1], always complete (also when the positions do not fit): mask i = offsets[i] .. offsets[i+1]
+ * Three launches (transpose + count, scan, emit) on `stream`; no host read, no allocation, no atomics: legal under stream
+ * capture. CGG_EINVAL before any device call: null pointer, n < 0, H, W < 1, row_bytes * 8 < W, mask_stride_bytes <
+ * H * row_bytes, capacity < 0, H * W >= 2^31, misaligned ws / offsets / positions. No limit on H beyond H * W < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t cgg_rle_transitions_workspace_bytes(int n, int H, int W);
+int cgg_rle_transitions(const uint8_t* bits, int n, int H, int W, int64_t mask_stride_bytes, int row_bytes, void* ws,
+                        uint32_t* positions, int64_t capacity, int64_t* offsets, cgg_stream_t stream);
+
+/* HOST functions for the two ways a mask leaves cgg_rle_transitions; out / out_cap / out_offsets and the return value as
+ * in cgg_rle_encode_bitmasks (total bytes; > out_cap: nothing copied; negative = CGG_E*), strings byte-identical to it.
+ *   cgg_rle_strings_from_transitions  positions (uint32, strictly ascending per mask, < H * W) + offsets (int64[n + 1])
+ *                                     -> the n counts strings
+ *   cgg_rle_encode_colmajor           n contiguous `cols` planes of the workspace layout above -> the n counts strings
+ *                                     (the run peeling of cgg_rle_encode_bitmasks without its transposes), on `threads`
+ *                                     host threads                                                                   */
+int64_t cgg_rle_strings_from_transitions(const uint32_t* positions, const int64_t* offsets, int n, int H, int W,
+                                         uint8_t* out, int64_t out_cap, int64_t* out_offsets);
+int64_t cgg_rle_encode_colmajor(const uint64_t* cols, int n, int H, int W, int threads, uint8_t* out, int64_t out_cap,
+                                int64_t* out_offsets);
 
 /* Throughput-mode self-attention of the query decoder ([3P] DetrTransformerDecoderLayer self_attn, no mask; S = Q <= 128):
  * q [B*Q, ldq] and kv = [k | v] [B*Q, ldkv] f32 rows (as written by the fused q|k|v projection) -> out [B*Q, H*D] f32 =

@@ -62,6 +62,9 @@ def parse_args(argv=None):
                    help='results in the evaluation format: masks as COCO RLE dicts (what results2json builds with pycocotools from '
                         'the reference\'s arrays), from bit-packed device masks through pinned staging buffers, one asynchronous '
                         'copy per tensor and the C++ host encoder of the extension, overlapped with the next batch')
+    p.add_argument('--rle-device', action='store_true',
+                   help='--rle with the run boundaries found on the device (RleCollector(device_rle=True)): per mask a few hundred '
+                        '4-byte positions cross PCIe instead of its bit plane, and the host only writes the counts strings. Same results')
     p.add_argument('--mask-bits', action='store_true',
                    help='keep the masks bit-packed ((n, H, W / 8) uint8, pixel x = bit x & 7 of byte x >> 3) in the results: '
                         '8x less PCIe traffic and 8x smaller result files; unpacking 315 MB of bool masks per 1024^2 image on '
@@ -173,10 +176,12 @@ def main(argv=None):
 
     B = args.samples_per_gpu
     collector, in_copy = None, []
+    if args.rle_device:
+        args.rle = True
     if args.rle:
         from cgg_amd.host_results import RleCollector, fusion_class_counts
         args.mask_bits = True
-        collector = RleCollector(device, fusion_class_counts(model.panoptic_fusion_head))
+        collector = RleCollector(device, fusion_class_counts(model.panoptic_fusion_head), device_rle=args.rle_device)
 
     def emit(device_results):
         """device results of one batch -> `results` (numpy now, or a future of the RLE collector)"""
