@@ -1,5 +1,9 @@
-// Library-level entry points of libcgg_hip.so: version + thread-local error string.
+// Library-level entry points of libcgg_hip.so: version, thread-local error string, and the one place that
+// raises a kernel's dynamic-LDS limit.
 #include "cgg_common.h"
+
+#include <map>
+#include <mutex>
 
 static thread_local char g_cgg_err[512] = "";
 
@@ -8,6 +12,27 @@ void cgg_set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_cgg_err, sizeof(g_cgg_err), fmt, ap);
   va_end(ap);
+}
+
+// Largest dynamic-LDS limit granted so far, per (device, kernel host address). Host memory only: nothing
+// to set up at cgg_init, and a lookup is legal under stream capture.
+static std::mutex g_lds_mu;
+static std::map<const void*, size_t> g_lds_granted[CGG_MAX_DEVICES];
+
+int cgg_raise_dynamic_lds(const void* kernel, size_t bytes, const char* who) {
+  if (bytes <= 64 * 1024) return CGG_OK;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+  const bool tabled = dev >= 0 && dev < CGG_MAX_DEVICES;   // an untabled device sets the attribute every time
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  if (tabled) {
+    auto it = g_lds_granted[dev].find(kernel);
+    if (it != g_lds_granted[dev].end() && it->second >= bytes) return CGG_OK;
+  }
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu: %s", who, bytes, hipGetErrorString(e));
+  if (tabled) g_lds_granted[dev][kernel] = bytes;
+  return CGG_OK;
 }
 
 extern "C" int cgg_version(void) { return CGG_VERSION; }

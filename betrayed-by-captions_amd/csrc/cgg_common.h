@@ -33,6 +33,21 @@ void cgg_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+// ---- dynamic LDS above 64 KiB ---------------------------------------------------------------------
+// per-device state (overflow flag words, LDS limits already granted) is tabled for devices below this
+#define CGG_MAX_DEVICES 16
+
+// Call immediately before launching `kernel` with `bytes` of dynamic LDS. At most 64 KiB: nothing to do.
+// Above: raises the function's limit on the current device unless a limit >= bytes was already granted
+// there (the attribute belongs to the function on ONE device). Thread-safe; CGG_OK or the hipError_t.
+int cgg_raise_dynamic_lds(const void* kernel, size_t bytes, const char* who);
+
+#define CGG_RAISE_LDS(kernel, bytes, who)                                        \
+  do {                                                                           \
+    int rc__ = cgg_raise_dynamic_lds((const void*)(kernel), (bytes), (who));     \
+    if (rc__ != CGG_OK) return rc__;                                             \
+  } while (0)
+
 static inline bool cgg_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // ---- bf16 helpers (round-to-nearest-even, NaN preserved) ----------------------------------------

@@ -120,16 +120,6 @@ __device__ __forceinline__ void dt_store4(const DtImg<X3>& frag, int o, const f3
 template <bool X3>
 __device__ __forceinline__ float dt_us(float a, float cs) { return X3 ? a * cs : a; }
 
-// dynamic LDS above 64 KiB needs the attribute once per kernel
-template <typename KernelT>
-static int dt_raise_lds(KernelT kern, size_t lds, const char* who) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu: %s", who, lds, hipGetErrorString(e));
-  }
-  return CGG_OK;
-}
-
 template <bool X3>
 __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
     const float* __restrict__ planes, int nsum, long long plane_stride, int ld, const float* __restrict__ ga,
@@ -278,8 +268,7 @@ static int dt_tail_launch(bool x3, const char* who, const float* planes, int nsu
   const size_t lds = (size_t)3 * DT_IMG_SLOTS(x3) * 16;
 #define DT_TAIL(X3)                                                                                                          \
   do {                                                                                                                       \
-    int rc = dt_raise_lds(cgg_decoder_tail_kernel<X3>, lds, who);                                                            \
-    if (rc != CGG_OK) return rc;                                                                                             \
+    CGG_RAISE_LDS(cgg_decoder_tail_kernel<X3>, lds, who);                                                                    \
     hipLaunchKernelGGL(cgg_decoder_tail_kernel<X3>, dim3((M + 31) / 32), dim3(512), lds, (hipStream_t)stream, planes, nsum,   \
                        (long long)plane_stride, ld, gamma_a, beta_a, eps_a, pos, pos_rows, gamma_b, beta_b, eps_b,           \
                        dt_view(X3, w1, DT_C, DT_C), b1, dt_view(X3, w2, DT_C, DT_C), b2, dt_view(X3, w3, DT_C, DT_C), b3,    \
@@ -435,8 +424,7 @@ static int dt_mid_launch(bool x3, const char* who, const float* core, int ldc, c
 #define DT_MID(X3)                                                                                                           \
   do {                                                                                                                       \
     const size_t lds = DM_LDS_BYTES(X3);                                                                                     \
-    int rc = dt_raise_lds(cgg_decoder_mid_kernel<X3>, lds, who);                                                             \
-    if (rc != CGG_OK) return rc;                                                                                             \
+    CGG_RAISE_LDS(cgg_decoder_mid_kernel<X3>, lds, who);                                                                     \
     hipLaunchKernelGGL(cgg_decoder_mid_kernel<X3>, dim3((M + 31) / 32), dim3(512), lds, (hipStream_t)stream, core, ldc,      \
                        dt_view(X3, wo, DT_C, DT_C), bo, res, ldr, gamma, beta, eps, pos, pos_rows,                           \
                        dt_view(X3, wqkv, 3 * DT_C, DT_C), bqkv, x1, q, kv, M);                                               \
@@ -531,8 +519,7 @@ static int dt_ffn_launch(bool x3, const char* who, const float* x, int ldx, cons
 #define DT_FFN(X3)                                                                                                           \
   do {                                                                                                                       \
     const size_t lds = (size_t)2 * DT_IMG_SLOTS(X3) * 16;                                                                    \
-    int rc = dt_raise_lds(cgg_decoder_ffn_kernel<X3>, lds, who);                                                             \
-    if (rc != CGG_OK) return rc;                                                                                             \
+    CGG_RAISE_LDS(cgg_decoder_ffn_kernel<X3>, lds, who);                                                                     \
     hipLaunchKernelGGL(cgg_decoder_ffn_kernel<X3>, dim3(F / 256, (M + 31) / 32), dim3(512), lds, (hipStream_t)stream, x, ldx, \
                        dt_view(X3, w1, F, DT_C), b1, dt_view(X3, w2, DT_C, F), b2, planes, M, F);                            \
   } while (0)

@@ -457,21 +457,14 @@ static int ef_launch(bool kv, const EfPro* prop, const void* x16, const void* w1
                 CGG_EALIGN, "%s: 16-B alignment (attention tail)", who);
   }
   const size_t lds = (size_t)EF_RB * EF_TS * sizeof(float);          // >= the two fragment images (64 KiB)
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[4] = {(const void*)cgg_encoder_ffn_ln_kernel<false, false>, (const void*)cgg_encoder_ffn_ln_kernel<true, false>,
-                          (const void*)cgg_encoder_ffn_ln_kernel<false, true>, (const void*)cgg_encoder_ffn_ln_kernel<true, true>};
-    for (const void* fn : fns) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu", who, lds);
-    }
-    attr_set = true;
-  }
   const dim3 grid((M + EF_RB - 1) / EF_RB), block(EF_NT);
 #define EF_LAUNCH(KV, PRO)                                                                                                    \
-  hipLaunchKernelGGL((cgg_encoder_ffn_ln_kernel<KV, PRO>), grid, block, lds, (hipStream_t)stream, (const uint16_t*)x16,       \
-                     (const ef_u32x4*)w1_packed, b1, (const ef_u32x4*)w2_packed, b2, gamma, beta, eps, pos, pos_rows,          \
-                     (uint16_t*)y16, (uint16_t*)yp16, y32, M, F, shift, lv, pro)
+  do {                                                                                                                        \
+    CGG_RAISE_LDS((cgg_encoder_ffn_ln_kernel<KV, PRO>), lds, who);                                                            \
+    hipLaunchKernelGGL((cgg_encoder_ffn_ln_kernel<KV, PRO>), grid, block, lds, (hipStream_t)stream, (const uint16_t*)x16,     \
+                       (const ef_u32x4*)w1_packed, b1, (const ef_u32x4*)w2_packed, b2, gamma, beta, eps, pos, pos_rows,        \
+                       (uint16_t*)y16, (uint16_t*)yp16, y32, M, F, shift, lv, pro);                                           \
+  } while (0)
   if (kv && prop) EF_LAUNCH(true, true);
   else if (kv) EF_LAUNCH(true, false);
   else if (prop) EF_LAUNCH(false, true);

@@ -450,16 +450,8 @@ static int e3_launch(const float* a32, const float* x32, const void* wo_x3, cons
                   (!pos || cgg_aligned16(pos)) && cgg_aligned16(y32) && (!yp32 || cgg_aligned16(yp32)),
               CGG_EALIGN, "%s: 16-B alignment", who);
   const size_t lds = (size_t)2 * E3_IMG * 16 + (size_t)E3_RB * E3_TS * sizeof(float);      // row images + tile (>= hidden images)
-  // the attribute is per device (a process-wide flag broke launches on a second device)
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    hipError_t e =
-        hipFuncSetAttribute((const void*)cgg_encoder_tail_x3_kernel<E3_NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu", who, lds);
-    if (dev >= 0 && dev < 16) attr_set[dev] = true;
-  }
+  // cgg_raise_dynamic_lds remembers the limit per device (a process-wide flag broke launches on a second device)
+  CGG_RAISE_LDS(cgg_encoder_tail_x3_kernel<E3_NWV>, lds, who);
   hipLaunchKernelGGL(cgg_encoder_tail_x3_kernel<E3_NWV>, dim3((M + E3_RB - 1) / E3_RB), dim3(64 * E3_NWV), lds, (hipStream_t)stream, a32,
                      x32, cgg_x3_view(wo_x3, E3_C, E3_C), bo, gamma0, beta0, eps0, cgg_x3_view(w1_x3, F, E3_C), b1,
                      cgg_x3_view(w2_x3, E3_C, F), b2, gamma1, beta1, eps1, pos, pos_rows, y32, yp32, M, F, x3a,

@@ -159,8 +159,7 @@ static int grounding_launch(const float* pred, const float* cap, const int32_t* 
                        Bp, Bc, Q, T, d, inv_t);
   } else {
     auto kern = cgg_grounding_kernel<BWD, 8>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_grounding: cannot raise dynamic LDS to %zu", lds);
+    CGG_RAISE_LDS(kern, lds, "cgg_grounding");
     hipLaunchKernelGGL(kern, dim3(Bc, Bp), dim3(512), lds, s, pred, cap, cap_mask, cost, gcost, dsim, Bp, Bc, Q, T, d, inv_t);
   }
   return CGG_OK;

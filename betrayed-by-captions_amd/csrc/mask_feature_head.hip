@@ -271,14 +271,7 @@ static int mh_go(const char* who, const float* z, const void* gn_ws, const float
                  const float* bias, const MhJobs& jobs, float* mf, int B, int H, int W, hipStream_t stream) {
   constexpr size_t lds = (size_t)MH_RB * MH_TS * sizeof(float);              // the tile (>= the two row images)
   static_assert(lds >= (size_t)2 * MH_IMG * 16, "the tile must cover the row images");
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)cgg_mask_feature_head_x3_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %zu", who, lds);
-    if (dev >= 0 && dev < 16) attr_set[dev] = true;
-  }
+  CGG_RAISE_LDS(cgg_mask_feature_head_x3_kernel<NWV>, lds, who);
   hipLaunchKernelGGL(cgg_mask_feature_head_x3_kernel<NWV>, dim3((unsigned)((H / 8) * (W / 8)), (unsigned)B), dim3(64 * NWV), lds, stream, z,
                      (const float*)gn_ws, gamma, beta, eps, cgg_x3_view(w_x3, MH_C, MH_C), bias, -__builtin_inff(), jobs, mf, H, W,
                      cgg_x3_overflow_flag_ptr());

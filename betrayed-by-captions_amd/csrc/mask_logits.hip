@@ -594,15 +594,7 @@ static int launch_mask_logits(const float* embed, const void* hi, const void* lo
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
   auto kern = cgg_mask_logits_kernel<SPLIT>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) {
-      cgg_set_error("cgg_mask_logits: cannot raise dynamic LDS to %zu: %s", lds,
-                    hipGetErrorString(e));
-      return (int)e;
-    }
-  }
+  CGG_RAISE_LDS(kern, lds, "cgg_mask_logits");
   hipLaunchKernelGGL(kern, dim3(gx * G, B), dim3(512), lds, s, embed, (const u32x4*)hi,
                      (const u32x4*)lo, out, bits, Q, npix, T, MT, q_total, G);
   CGG_CHECK_LAUNCH("cgg_mask_logits");

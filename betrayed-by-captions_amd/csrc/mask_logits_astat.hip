@@ -391,15 +391,13 @@ extern "C" int cgg_mask_logits_bits_astat(const float* embed, const void* hi, ui
     gr = (T + 2 * per - 1) / (2 * per);
     const size_t ldsr = (size_t)MLR_STAGE + 2 * MLR_D * (MLA_KS * 1024);
     auto kr = cgg_mask_logits_astat_ring_kernel;
-    hipError_t er = hipFuncSetAttribute((const void*)kr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr);
-    CGG_REQUIRE(er == hipSuccess, (int)er, "cgg_mask_logits_bits_astat: cannot raise dynamic LDS to %zu", ldsr);
+    CGG_RAISE_LDS(kr, ldsr, "cgg_mask_logits_bits_astat(ring)");
     hipLaunchKernelGGL(kr, dim3(gr, B), dim3(512), ldsr, (hipStream_t)stream, embed, (const u32x4*)hi, bits, Q, npix, T, MT, per);
     CGG_CHECK_LAUNCH("cgg_mask_logits_bits_astat(ring)");
     return CGG_OK;
   }
   auto kern = cgg_mask_logits_astat_kernel<4>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_mask_logits_bits_astat: cannot raise dynamic LDS to %zu", lds);
+  CGG_RAISE_LDS(kern, lds, "cgg_mask_logits_bits_astat");
   hipLaunchKernelGGL(kern, dim3(gx, B), dim3(256), lds, (hipStream_t)stream, embed, (const u32x4*)hi, bits, Q, npix, T, MT);
   CGG_CHECK_LAUNCH("cgg_mask_logits_bits_astat");
   return CGG_OK;

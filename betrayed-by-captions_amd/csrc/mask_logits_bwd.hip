@@ -283,10 +283,7 @@ extern "C" int cgg_mask_logits_backward(const float* embed, const float* feat, c
       const int qc = Q - q0 < lim ? Q - q0 : lim;
       const int KS = (qc + 15) / 16;
       const size_t lds = (size_t)8 * KS * 64 * 16 * (split ? 2 : 1);
-      if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_mask_logits_backward: cannot raise dynamic LDS to %zu", lds);
-      }
+      CGG_RAISE_LDS(kern, lds, "cgg_mask_logits_backward(grad_feat)");
       hipLaunchKernelGGL(kern, dim3(gx, B), dim3(512), lds, s, embed, grad_out, grad_feat, qc, npix, T, KS, q0, Q, q0 > 0 ? 1 : 0);
       CGG_CHECK_LAUNCH("cgg_mask_logits_backward(grad_feat)");
     }

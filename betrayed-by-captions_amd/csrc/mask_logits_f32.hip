@@ -85,11 +85,7 @@ extern "C" int cgg_mask_logits_f32(const float* embed, const float* feat, float*
   const size_t lds = (size_t)MT * 32 * MLF_LD * sizeof(float);
   int gx = (T + 3) / 4, cap = (512 + B - 1) / B;
   if (gx > cap) gx = cap;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)cgg_mask_logits_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_mask_logits_f32: cannot raise dynamic LDS to %zu", lds);
-  }
+  CGG_RAISE_LDS(cgg_mask_logits_f32_kernel, lds, "cgg_mask_logits_f32");
   hipLaunchKernelGGL(cgg_mask_logits_f32_kernel, dim3(gx, B), dim3(256), lds, (hipStream_t)stream, embed, feat, out, bits, Q,
                      npix, T, MT);
   CGG_CHECK_LAUNCH("cgg_mask_logits_f32");

@@ -422,11 +422,7 @@ static int msda_sorted_go(const MsdaLevels& lv, const MsdaSortPlan& pl, size_t l
   auto kern = nt == 512 ? cgg_msda_bwd_sorted_kernel<512, 3, 0, MODE>
               : (items > 256 ? (P == 4 ? cgg_msda_bwd_sorted_kernel<256, 2, 4, MODE> : cgg_msda_bwd_sorted_kernel<256, 2, 0, MODE>)
                              : cgg_msda_bwd_sorted_kernel<256, 1, 0, MODE>);
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    cgg_set_error("cgg_msda_backward: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-    return (int)e;
-  }
+  CGG_RAISE_LDS(kern, lds, "cgg_msda_backward(sorted scatter)");
   hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(nt), lds, s, lv, pl, loc, attw, gout, gvalue, Nv, H, L, Nq, P, ovf, aflags, gvld);
   CGG_CHECK_LAUNCH("cgg_msda_backward(sorted scatter)");
   return CGG_OK;
@@ -477,11 +473,7 @@ static int msda_list_go(const MsdaLevels& lv, const MsdaSortPlan& pl, size_t lds
                         const uint32_t* list, const uint32_t* count, uint32_t* cursor, hipStream_t s, int gvld) {
   auto kern = cgg_msda_bwd_list_kernel<512, 3, 0, MODE>;                     // (pass-B tiles: c = 4, 1 344 taps at P = 4)
   if (pl.maxslots * P > 3 * 512) return CGG_EUNSUPPORTED;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    cgg_set_error("cgg_msda_backward: cannot reserve %zu B of LDS: %s", lds, hipGetErrorString(e));
-    return (int)e;
-  }
+  CGG_RAISE_LDS(kern, lds, "cgg_msda_backward(sorted scatter, second pass)");
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, lv, pl, loc, attw, gout, gvalue, Nv, H, L, Nq, P, ovf, aflags, list, count,
                      cursor, gvld);
   CGG_CHECK_LAUNCH("cgg_msda_backward(sorted scatter, second pass)");

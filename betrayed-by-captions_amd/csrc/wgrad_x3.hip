@@ -287,14 +287,7 @@ static int wgrad_launch(const float* dy, int ldy, const float* x, int ldx, float
                        ldy, x, ldx, ws, ws_bias, M, N, K, tiles_k, rps, dy_amax);
   } else {
     const int lds = 2 * 4 * 32 * (2 * 256 + 64);       // two stages of 72 KiB: above the default dynamic-LDS limit
-    static bool attr_set[16] = {false};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-      hipError_t e = hipFuncSetAttribute((const void*)cgg_wgrad_x3_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_wgrad_x3: cannot raise dynamic LDS to %d", lds);
-      if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    CGG_RAISE_LDS(cgg_wgrad_x3_kernel<256>, lds, "cgg_wgrad_x3");
     hipLaunchKernelGGL(cgg_wgrad_x3_kernel<256>, dim3(tiles_n * tiles_k, sp), dim3(512), lds, (hipStream_t)stream, dy, ldy, x, ldx, ws,
                        ws_bias, M, N, K, tiles_k, rps, dy_amax);
   }

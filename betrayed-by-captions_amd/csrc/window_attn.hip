@@ -470,12 +470,7 @@ extern "C" int cgg_window_attn_backward(const float* qkv, const float* table, co
                        scale, wpc, nwtot);
   } else {
     const size_t lds = (size_t)(4 * 144 * WA_LD + WA_TAB + 4 * 144) * sizeof(float);      // 87 KB: above the 64 KB default limit
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cgg_window_attn_bwd_kernel<9>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    CGG_RAISE_LDS(cgg_window_attn_bwd_kernel<9>, lds, "cgg_window_attn_backward(main)");
     hipLaunchKernelGGL(cgg_window_attn_bwd_kernel<9>, grid, dim3(576), lds, s, qkv, table, lse, grad_out, grad_qkv, (float*)ws_buf, g,
                        scale, wpc, nwtot);
   }

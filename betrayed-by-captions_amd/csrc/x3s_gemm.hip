@@ -509,15 +509,17 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 // (round 5: the tile configuration of a call is an ARGUMENT of the *_cfg entry points -- no process-global override, no
-// measurement-only branches in the production loop; the library keeps no mutable state besides the per-device overflow flag word)
+// measurement-only branches in the production loop; the library keeps no mutable state besides the per-device overflow flag word
+// below and cgg_raise_dynamic_lds's host-side table of LDS limits already granted, which holds no device memory, needs nothing
+// at cgg_init and is safe under graph capture)
 
 // the device-side overflow flag of the x3a producers (one word per process and device, zeroed at creation; read by
 // cgg_x3_overflow_check)
-static int* g_xs_flag[16] = {nullptr};
-static std::once_flag g_xs_once[16];
+static int* g_xs_flag[CGG_MAX_DEVICES] = {nullptr};
+static std::once_flag g_xs_once[CGG_MAX_DEVICES];
 int* cgg_x3_overflow_flag_ptr() {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CGG_MAX_DEVICES) return nullptr;
   // created once per device, race-free (two autograd / DDP threads may make the first call together); cgg_init(device) makes the
   // creation explicit -- it must have happened before a graph capture, hipMalloc is not capturable
   std::call_once(g_xs_once[dev], [dev] {
@@ -533,7 +535,7 @@ extern "C" int cgg_init(int device) {
   int prev = 0;
   hipError_t e = hipGetDevice(&prev);
   CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_init: %s", hipGetErrorString(e));
-  CGG_REQUIRE(device >= 0 && device < 16, CGG_EINVAL, "cgg_init: device %d (0..15)", device);
+  CGG_REQUIRE(device >= 0 && device < CGG_MAX_DEVICES, CGG_EINVAL, "cgg_init: device %d (0..%d)", device, CGG_MAX_DEVICES - 1);
   e = hipSetDevice(device);
   CGG_REQUIRE(e == hipSuccess, (int)e, "cgg_init: hipSetDevice(%d): %s", device, hipGetErrorString(e));
   int* f = cgg_x3_overflow_flag_ptr();
@@ -557,15 +559,7 @@ template <bool CONV, int TM, int TN, int WM, int WN, int KG, int SA, int SB>
 static int xs_go(const XsArgs& a, hipStream_t stream, const char* who) {
   constexpr int BN = 32 * TN * WN, BM = 32 * TM * WM;
   constexpr int LDS = KG * (SA * BM + SB * BN) * 128;
-  static bool attr[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (LDS > 65536 && dev >= 0 && dev < 16 && !attr[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)cgg_gemm_x3s_kernel<CONV, TM, TN, WM, WN, KG, SA, SB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    CGG_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise dynamic LDS to %d", who, LDS);
-    attr[dev] = true;
-  }
+  CGG_RAISE_LDS((cgg_gemm_x3s_kernel<CONV, TM, TN, WM, WN, KG, SA, SB>), LDS, who);
   XsArgs b = a;
   b.tiles_n = (a.N + BN - 1) / BN;
   const dim3 grid((unsigned)(((a.M + BM - 1) / BM) * b.tiles_n)), block(64 * WM * WN * KG);

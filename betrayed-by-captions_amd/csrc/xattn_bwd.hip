@@ -400,25 +400,11 @@ static int xattn_bwd_launch(const float* q, const void* kv, const uint32_t* bits
   const int words = (S + 31) / 32;
   const size_t lds = (size_t)(2 * 128 * XB_LD + 256 + 8 * 32 * XB_LD) * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cgg_xattn_bwd_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cgg_xattn_bwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(cgg_xattn_bwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    attr_set = true;
-  }
-  if (kv_dtype == CGG_F32_X3)
-    hipLaunchKernelGGL(cgg_xattn_bwd_kernel<2>, dim3(nch, H, B), dim3(256), lds, s, q, (const float*)kv, bits, out, lse, grad_out,
-                       (float*)grad_kv, (float*)ws, Q, H, S, words, KC, nch, scale, gout_amax);
-  else if (kv_dtype == CGG_F32_BF16MFMA)
-    hipLaunchKernelGGL(cgg_xattn_bwd_kernel<1>, dim3(nch, H, B), dim3(256), lds, s, q, (const float*)kv, bits, out, lse, grad_out,
-                       (float*)grad_kv, (float*)ws, Q, H, S, words, KC, nch, scale, gout_amax);
-  else
-    hipLaunchKernelGGL(cgg_xattn_bwd_kernel<0>, dim3(nch, H, B), dim3(256), lds, s, q, (const float*)kv, bits, out, lse, grad_out,
-                       (float*)grad_kv, (float*)ws, Q, H, S, words, KC, nch, scale, gout_amax);
+  auto kern = kv_dtype == CGG_F32_X3 ? cgg_xattn_bwd_kernel<2>
+              : kv_dtype == CGG_F32_BF16MFMA ? cgg_xattn_bwd_kernel<1> : cgg_xattn_bwd_kernel<0>;
+  CGG_RAISE_LDS(kern, lds, "cgg_masked_xattn_backward(main)");
+  hipLaunchKernelGGL(kern, dim3(nch, H, B), dim3(256), lds, s, q, (const float*)kv, bits, out, lse, grad_out, (float*)grad_kv,
+                     (float*)ws, Q, H, S, words, KC, nch, scale, gout_amax);
   CGG_CHECK_LAUNCH("cgg_masked_xattn_backward(main)");
   const long long total = (long long)B * Q * H * D;
   hipLaunchKernelGGL(cgg_xattn_bwd_reduce_dq, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)ws,

@@ -332,6 +332,10 @@ def test_msda_mmcv_function_reads_the_level_table_once_per_tensor(dev):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('B,Q,H,W', [(2, 100, 32, 32), (1, 100, 20, 28), (2, 37, 16, 24), (1, 128, 64, 64)])
 def test_mask_logits_split_within_1e3(dev, B, Q, H, W):
+    check_mask_logits_split(dev, B, Q, H, W)
+
+
+def check_mask_logits_split(dev, B, Q, H, W):
     g = torch.Generator().manual_seed(10)
     embed = torch.randn(B, Q, 256, generator=g)
     feat = torch.randn(B, 256, H, W, generator=g)
@@ -511,8 +515,20 @@ def test_masked_xattn_backward_vs_float64_autograd(dev, B, Q, S, H, masked, form
     tile, the unmasked self-attention case, several key chunks per head, rows with a single visible key. Both forms of the backward:
     `x3` = the f16 x 3 contraction parity mode takes (cgg_masked_xattn_backward_x3; also with a 1e-6-scale grad_out: its pre-scale comes
     from max |grad_out|), `f32` = the exact f32 MFMA (CGG_XATTN_X3_BWD=0) -- the same bound for both."""
-    from cgg_amd.query_decoder import pack_bool_mask
     monkeypatch.setattr(ops, 'XATTN_X3_BWD', form == 'x3')
+    q, kv, bits, out, lse, go, gq, gkv = check_masked_xattn_backward(dev, B, Q, S, H, masked)
+    # run to run bit-identical (no floating-point atomics)
+    gq2, gkv2 = ops.masked_xattn_backward(q, kv, bits, out, lse, go, H)
+    assert torch.equal(gq, gq2) and torch.equal(gkv, gkv2)
+    # a gradient-scale grad_out (what the training step hands over): the backward is linear in it, to the last bit for a power of two
+    gq3, gkv3 = ops.masked_xattn_backward(q, kv, bits, out, lse, go * 2.0**-20, H)
+    assert torch.equal(gq3 * 2.0**20, gq) and torch.equal(gkv3 * 2.0**20, gkv)
+
+
+def check_masked_xattn_backward(dev, B, Q, S, H, masked):
+    """forward with lse + backward on `dev` within the bounds of test_masked_xattn_backward_vs_float64_autograd; returns the device
+    tensors (q, kv, bits, out, lse, grad_out, grad_q, grad_kv)"""
+    from cgg_amd.query_decoder import pack_bool_mask
     g = torch.Generator().manual_seed(23 + S)
     D = 32
     E = H * D
@@ -545,12 +561,7 @@ def test_masked_xattn_backward_vs_float64_autograd(dev, B, Q, S, H, masked, form
         scale = ref_.abs().max().item()
         err = (got.cpu().double() - ref_).abs().max().item()
         assert err <= 2e-5 * scale + 1e-6, (name, err, scale)
-    # run to run bit-identical (no floating-point atomics)
-    gq2, gkv2 = ops.masked_xattn_backward(q.to(dev), kv.to(dev), bits, out, lse, go.to(dev), H)
-    assert torch.equal(gq, gq2) and torch.equal(gkv, gkv2)
-    # a gradient-scale grad_out (what the training step hands over): the backward is linear in it, to the last bit for a power of two
-    gq3, gkv3 = ops.masked_xattn_backward(q.to(dev), kv.to(dev), bits, out, lse, (go * 2.0**-20).to(dev), H)
-    assert torch.equal(gq3 * 2.0**20, gq) and torch.equal(gkv3 * 2.0**20, gkv)
+    return q.to(dev), kv.to(dev), bits, out, lse, go.to(dev), gq, gkv
 
 
 def test_xattn_autograd_function_uses_hip_backward(dev):
@@ -1333,6 +1344,23 @@ def test_mask_logits_backward_vs_float64(dev, B, Q, h, w, split):
     (40 x 56 = 70 tiles of 32), row counts that are not multiples of 16 / 32, row groups beyond one launch (160 split,
     300 plain), full resolution; and the autograd function end to end."""
     from cgg_amd.mask2former_head import _MaskLogitsFn
+    E, F_, go, ge, gf = check_mask_logits_backward(dev, B, Q, h, w, split)
+    tol = 2e-5 if split else 1e-2
+    ge2, gf2 = ops.mask_logits_backward(E.to(dev), F_.to(dev), go.to(dev), split)
+    assert torch.equal(ge, ge2) and torch.equal(gf, gf2)                    # deterministic
+    # autograd function (forward on the packed image + this backward)
+    Ed, Fd = E.to(dev).requires_grad_(True), F_.to(dev).requires_grad_(True)
+    packed = ops.pack_mask_feature(Fd.detach(), 1, split)
+    out = _MaskLogitsFn.apply(Ed, Fd, packed)
+    want_o = torch.einsum('bqc,bchw->bqhw', E.double(), F_.double())
+    assert (out.detach().cpu().double() - want_o).abs().max().item() <= tol * want_o.abs().max().item()
+    a, b = torch.autograd.grad(out, (Ed, Fd), go.to(dev))
+    assert torch.equal(a, ge) and torch.equal(b, gf)
+
+
+def check_mask_logits_backward(dev, B, Q, h, w, split):
+    """one cgg_mask_logits_backward on `dev` within the bound of test_mask_logits_backward_vs_float64; returns the host inputs and
+    the device gradients (E, F_, grad_out, grad_embed, grad_feat)"""
     g = torch.Generator().manual_seed(70 + Q)
     C = 256
     E = torch.randn(B, Q, C, generator=g)
@@ -1346,16 +1374,7 @@ def test_mask_logits_backward_vs_float64(dev, B, Q, h, w, split):
         scale = want.abs().max().item()
         err = (got.cpu().double() - want).abs().max().item()
         assert err <= tol * scale, (name, err, scale)
-    ge2, gf2 = ops.mask_logits_backward(E.to(dev), F_.to(dev), go.to(dev), split)
-    assert torch.equal(ge, ge2) and torch.equal(gf, gf2)                    # deterministic
-    # autograd function (forward on the packed image + this backward)
-    Ed, Fd = E.to(dev).requires_grad_(True), F_.to(dev).requires_grad_(True)
-    packed = ops.pack_mask_feature(Fd.detach(), 1, split)
-    out = _MaskLogitsFn.apply(Ed, Fd, packed)
-    want_o = torch.einsum('bqc,bchw->bqhw', E.double(), F_.double())
-    assert (out.detach().cpu().double() - want_o).abs().max().item() <= tol * want_o.abs().max().item()
-    a, b = torch.autograd.grad(out, (Ed, Fd), go.to(dev))
-    assert torch.equal(a, ge) and torch.equal(b, gf)
+    return E, F_, go, ge, gf
 
 
 def test_point_sample_planes_vs_grid_sample(dev):
@@ -1406,6 +1425,11 @@ def test_encoder_ffn_ln_fused_vs_float64(dev, M, N, FF):
     bf16-rounded operands (x, W1, W2; hidden rounded to bf16 as the kernel does): outputs are bf16, so the bound is one
     bf16 ulp of |y| <= ~4 (2^-6 = 0.0157) for both y and y + pos; ragged M (not a multiple of the 64-row block) and
     pos rows wrapping per image (row % N); three runs bit-identical."""
+    check_encoder_ffn_ln(dev, M, N, FF, n_runs=3)
+
+
+def check_encoder_ffn_ln(dev, M, N, FF, n_runs=1):
+    """`n_runs` bit-identical launches on `dev`, the first within the bounds of test_encoder_ffn_ln_fused_vs_float64"""
     import torch.nn.functional as F
     g = torch.Generator().manual_seed(M + FF)
     C = 256
@@ -1419,7 +1443,7 @@ def test_encoder_ffn_ln_fused_vs_float64(dev, M, N, FF):
     pos = torch.randn(N, C, generator=g).to(dev)
     w1p, w2p = ops.pack_linear_weight(w1), ops.pack_linear_weight(w2)
     runs = []
-    for _ in range(3):
+    for _ in range(n_runs):
         y32, y16, yp16 = ops.encoder_ffn_ln(x16, w1p, b1, w2p, b2, gamma, beta, 1e-5, pos=pos, want_f32=True,
                                             want_bf16=True, want_pos=True)
         torch.cuda.synchronize()

@@ -57,6 +57,10 @@ def test_window_attention_forward_backward_vs_float64_dense(dev, ws, hw, shift, 
     """Op forward (out, lse within 1e-4 absolute) and backward (grad_qkv, grad_table within 2e-5 max|ref| + 1e-6) against float64
     autograd of the dense formulation; several windows in both directions, Hp != Wp, B = 2. The backward is bit-reproducible and,
     being exact f32 products, linear in grad_out to the last bit for a power-of-two factor."""
+    check_window_attention(dev, ws, hw, shift, heads)
+
+
+def check_window_attention(dev, ws, hw, shift, heads):
     g = torch.Generator().manual_seed(1000 * ws + 10 * shift + heads)
     B, L, C = 2, hw[0] * hw[1], heads * 32
     qkv = torch.randn(B, L, 3 * C, generator=g)

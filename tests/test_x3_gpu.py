@@ -220,6 +220,10 @@ def test_conv_x3_nhwc_vs_float64(dev, B, H, W, C, N, k, stride):
 def test_encoder_layer_tail_x3_vs_float64(dev, M, N, FF):
     """cgg_encoder_layer_tail_x3 (output_proj + LN + FFN + LN in one launch, f32-class arithmetic) vs float64 on the same f32
     inputs: 2e-5 of the unit-scale outputs (the bf16 twin: one bf16 ulp = 4e-3); ragged row counts; y + pos; reproducible."""
+    check_encoder_layer_tail_x3(dev, M, N, FF)
+
+
+def check_encoder_layer_tail_x3(dev, M, N, FF):
     g = torch.Generator().manual_seed(500 + FF)
     C = 256
     r = lambda *s, k=1.0: (torch.randn(*s, generator=g) * k)
