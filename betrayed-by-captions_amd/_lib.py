@@ -176,6 +176,10 @@ PROTOTYPES = {
     'cgg_stem_conv7x7_packed_bytes': (_c_i64, []),
     'cgg_stem_conv7x7_nchw': (_c_int, [_c_vp] * 3 + [_c_int] * 3 + [_c_vp]),
     'cgg_linear_sum_assignment_f32': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    'cgg_lsap_device_lds_bytes': (_c_i64, [_c_int, _c_int]),
+    'cgg_lsap_device_f32': (_c_int, [_c_vp, _c_i64, _c_vp, _c_int, _c_i64, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64,
+                                     _c_vp, _c_vp]),
+    'cgg_dynamic_lds_limit': (_c_i64, []),
     'cgg_point_sample_planes': (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [_c_vp]),
     'cgg_point_sample_planes_backward': (_c_int, [_c_vp] * 4 + [_c_int] * 5 + [_c_vp]),
     'cgg_point_sample_planes_backward_rows': (_c_int, [_c_vp] * 3 + [_c_int] * 4 + [_c_vp]),

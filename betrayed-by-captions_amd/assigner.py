@@ -2,10 +2,12 @@
 with the [3P] mmdet match costs / sampler / point-sampling helpers its config names
 (configs/instance/coco_b48n17.py:165-177; semantics in SURVEY.md A6-A8).
 
-The cost matrix stays f32 (assignment indices must be bit-exact with the reference CPU path); the
-solve runs on the host like the reference's scipy `linear_sum_assignment` (:126-131), in the C++ solver of the
-extension (`cgg_linear_sum_assignment_f32`: same algorithm, scan order and tie rule -> same indices).
-`assign_batch` batches the device->host copies of a whole (layers x images) step into one transfer.
+The cost matrix stays f32 (assignment indices must be bit-exact with the reference CPU path). There are two solvers with
+scipy's `linear_sum_assignment` indices (:126-131; same algorithm, f64 arithmetic, scan order and tie rule):
+`cgg_linear_sum_assignment_f32` on the host (this module's `assign` / `assign_batch`, which batches the device->host copies of a
+whole (layers x images) step into one transfer, and the fallback of the training step), and `cgg_lsap_device_f32` on the
+device, one wavefront per problem, which the batched training targets use so that a step waits for no host
+(`mask2former_head._targets_batched`). `lsap_wave_rule_host` states the device solver's parallel column-selection rule.
 """
 import torch
 import torch.nn.functional as F
@@ -19,6 +21,81 @@ def linear_sum_assignment(cost):
     """scipy.optimize.linear_sum_assignment's contract (and indices) from the C++ solver in libcgg_hip.so."""
     rows, cols = ops.linear_sum_assignment_batch([torch.as_tensor(cost)])[0]
     return rows.numpy(), cols.numpy()
+
+
+def lsap_wave_rule_host(cost):
+    """The decision rule of the device solver (csrc/lsap_device.hip), written down in numpy: `lsap_solve` of csrc/lsap.hip with
+    the sequential column scan replaced by what the wavefront does. All remaining positions `it` update dist / path at once; the
+    winner is the minimum dist and, among the positions that hold it, the LARGEST position whose column is unassigned if there
+    is one, else the SMALLEST position -- what the sequential `dist < lowest or (dist == lowest and row4col[j] == -1)` ends on.
+    The swap-remove keeps the host code's order. cost: 2-D array-like, read as f32. -> (rows, cols, status): scipy's indices
+    (rows ascending) and 0, or the identity pairing k -> (k, k) and 1 (NaN / -inf entries) or 2 (infeasible)."""
+    import numpy as np
+    c32 = np.asarray(cost, dtype=np.float32)
+    nr, nc = c32.shape
+    n = min(nr, nc)
+    ident = np.arange(n, dtype=np.int64)
+    if n == 0:
+        return ident, ident.copy(), 0
+    if np.isnan(c32).any() or (c32 == -np.inf).any():
+        return ident, ident.copy(), 1
+    transpose = nc < nr
+    c = (c32.T if transpose else c32).astype(np.float64)          # exact widening
+    R, C = c.shape
+    u, v = np.zeros(R), np.zeros(C)
+    path = np.full(C, -1, dtype=np.int64)
+    row4col = np.full(C, -1, dtype=np.int64)
+    col4row = np.full(R, -1, dtype=np.int64)
+    with np.errstate(invalid='ignore'):
+        for cur in range(R):
+            remaining = np.arange(C - 1, -1, -1, dtype=np.int64)
+            n_rem = C
+            dist = np.full(C, np.inf)
+            SR, SC = np.zeros(R, dtype=bool), np.zeros(C, dtype=bool)
+            min_val, sink, i = 0.0, -1, cur
+            for _ in range(C):
+                SR[i] = True
+                js = remaining[:n_rem]
+                r = min_val + c[i, js] - u[i] - v[js]                # ((min_val + c) - u[i]) - v[j]
+                better = r < dist[js]
+                path[js[better]] = i
+                dist[js[better]] = r[better]
+                d = dist[js]
+                lowest = d.min()
+                if not lowest < np.inf:
+                    return ident, ident.copy(), 2
+                at = np.flatnonzero(d == lowest)
+                free = at[row4col[js[at]] == -1]
+                index = int(free[-1]) if free.size else int(at[0])
+                min_val = lowest
+                j = int(remaining[index])
+                if row4col[j] == -1:
+                    sink = j
+                else:
+                    i = int(row4col[j])
+                SC[j] = True
+                n_rem -= 1
+                remaining[index] = remaining[n_rem]
+                if sink != -1:
+                    break
+            if sink == -1:
+                return ident, ident.copy(), 2
+            u[cur] += min_val
+            for r_ in np.flatnonzero(SR):
+                if r_ != cur:
+                    u[r_] += min_val - dist[col4row[r_]]
+            v[SC] -= min_val - dist[SC]
+            j = sink
+            while True:
+                r_ = int(path[j])
+                row4col[j] = r_
+                col4row[r_], j = j, int(col4row[r_])
+                if r_ == cur:
+                    break
+    if transpose:
+        order = np.argsort(col4row, kind='stable')                   # col4row[g] = query of ground truth g: ranked by query
+        return col4row[order].astype(np.int64), order.astype(np.int64), 0
+    return ident, col4row.astype(np.int64), 0
 
 
 # ---- [3P] mmcv.ops.point_sample / mmdet point utilities -------------------------------------------

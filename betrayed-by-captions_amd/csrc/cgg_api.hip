@@ -35,6 +35,16 @@ int cgg_raise_dynamic_lds(const void* kernel, size_t bytes, const char* who) {
   return CGG_OK;
 }
 
+// The most dynamic LDS one workgroup may ask for on the current device; without a device, gfx950's 160 KiB (the only
+// target this library is built for), so that a gate can be evaluated where nothing can be launched.
+extern "C" int64_t cgg_dynamic_lds_limit(void) {
+  int dev = -1, v = 0;
+  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
+      v > 0)
+    return v;
+  return 160 * 1024;
+}
+
 extern "C" int cgg_version(void) { return CGG_VERSION; }
 
 extern "C" const char* cgg_last_error_string(void) { return g_cgg_err; }

@@ -32,6 +32,9 @@ from .registry import (HEADS, build_assigner, build_head, build_loss, build_plug
 
 # parity-mode training: the matching costs' point logits on the x3 einsum over sampler-written x3 images (CGG_POINT_LOGITS_X3=0: f32 rows + library bmm)
 POINT_LOGITS_X3 = os.environ.get('CGG_POINT_LOGITS_X3', '1') != '0'
+# the Hungarian problems of a training step on the device (cgg_lsap_device_f32), no cost copy to the host and no host solve
+# (CGG_DEVICE_ASSIGN=0: one D2H of the cost matrices, the C++ host solver, one H2D of the targets)
+DEVICE_ASSIGN = os.environ.get('CGG_DEVICE_ASSIGN', '1') != '0'
 BOS_TOKEN = 101
 EOS_TOKEN = 102
 
@@ -274,6 +277,8 @@ class Mask2FormerHeadOpen(nn.Module):
         # callable(layer_idx, image_idx, rows, cols, cost) -> (rows, cols); tests check the Hungarian solution against the oracle's
         # cost matrix and inject the oracle's own (a near-tie may legitimately resolve either way in float32)
         self.assign_hook = None
+        # device solver's two status words [code, problem + 1]: the first failure since they were last zeroed (ops.lsap_status_check)
+        self.assign_status = None
         self.init_kwargs(**kwargs)
 
     # ------------------------------------------------------------------------------------------
@@ -989,7 +994,10 @@ class Mask2FormerHeadOpen(nn.Module):
         overlap: optional callable run AFTER the cost matrices' device->host copy is enqueued (on a side stream, pinned target) and
         BEFORE the host waits for it: device work that does not depend on the targets (the caption branch) then executes while the
         host waits, solves the assignments and enqueues the loss kernels -- otherwise the device idles from the copy to the first
-        loss kernel. Its return value is stored in `self._overlap_result`."""
+        loss kernel. Its return value is stored in `self._overlap_result`.
+        With `DEVICE_ASSIGN` (default), costs on a GPU, no `assign_hook` and every problem inside `ops.lsap_device_ok`, the
+        transfers and the host solve above do not happen: `_targets_device` solves all problems in one launch where the costs are
+        and `overlap` is simply enqueued behind it. Both paths return the same values; `cost_trace` works on both."""
         n, B, Q = len(all_cls_scores), all_cls_scores[0].shape[0], all_cls_scores[0].shape[1]
         dev = all_cls_scores[0].device
         P = self.num_points
@@ -1068,6 +1076,16 @@ class Mask2FormerHeadOpen(nn.Module):
                 if getattr(self, 'cost_trace', None) is not None:      # test hook: the (n, Q, G) cost matrices of image b
                     self.cost_trace.append((b, cost.detach().float().clone()))
                 costs.append(cost.float().reshape(-1))                                        # (n*Q*G,)
+            if DEVICE_ASSIGN and dev.type == 'cuda' and self.assign_hook is None \
+                    and all(ops.lsap_device_ok(Q, G) for G in shapes if G):
+                # every problem solved where its costs are: the host contributes what the SHAPES say and waits for nothing
+                out = self._targets_device(costs, shapes, gt_labels_list, n, B, Q, dev)
+                costs = None
+        if costs is None:
+            if overlap is not None:
+                self._overlap_result = overlap()
+            return out
+        with torch.no_grad():
             flat = None
             if costs and overlap is not None and costs[0].is_cuda:
                 flat_dev = torch.cat(costs)
@@ -1143,6 +1161,49 @@ class Mask2FormerHeadOpen(nn.Module):
             devi = dict(b=idx_dev[0, o:o + k], q=idx_dev[1, o:o + k], g=idx_dev[2, o:o + k], r=idx_dev[3, o:o + k], pm=pm)
             out.append((labels[li], weights[li], pos_b[li], pos_g[li], k, devi))
             o += k
+        return out
+
+    def _targets_device(self, costs, shapes, gt_labels_list, n, B, Q, dev):
+        """The targets of `_targets_batched` with the assignment on the device (csrc/lsap_device.hip), same 6-tuple per layer.
+        Image b contributes min(Q, G_b) positives to every layer whatever the solution is, so the counts, `pm`, the image and slot
+        rows of the index table and every offset of the descriptor table follow from `shapes`; only which query meets which
+        ground truth is computed, and that stays on the device: the kernel writes the (query, gt) pairs of problem (layer, image)
+        at that layer's offset in ascending query order -- the host loop's `np.argsort(rows)` -- and scatters `labels` /
+        `weights` itself. No call here waits for the device. Failures (NaN / -inf costs, an infeasible matrix) do not raise here:
+        they pair k with k and leave their code in `self.assign_status` for `ops.lsap_status_check`."""
+        m = [min(Q, G) for G in shapes]
+        K = sum(m)                                                    # positives per layer
+        table, coff, loff, slot, lds = [], 0, 0, 0, 0
+        for b, G in enumerate(shapes):
+            if G:
+                # (cost offset, nr, nc, output offset, label-row offset, gt-label offset); problems image-major like `costs`
+                table.extend((coff + li * Q * G, Q, G, li * K + slot, (li * B + b) * Q, loff) for li in range(n))
+                coff += n * Q * G
+                lds = max(lds, ops.lsap_device_lds_bytes(Q, G))
+            slot += m[b]
+            loff += G
+        pos_b = [b for b in range(B) for _ in range(m[b])]
+        pos_r = [r for b in range(B) for r in range(m[b])]           # rank of the positive inside its image (padded-batch slot)
+        labels = torch.full((n, B, Q), self.num_classes, dtype=torch.int64, device=dev)
+        weights = torch.zeros((n, B, Q), dtype=torch.float32, device=dev)
+        q_all = torch.zeros((n * K,), dtype=torch.int64, device=dev)
+        g_all = torch.zeros((n * K,), dtype=torch.int64, device=dev)
+        if self.assign_status is None or self.assign_status.device != dev:
+            self.assign_status = torch.zeros((2,), dtype=torch.int32, device=dev)
+        b_dev = r_dev = q_all[:0]
+        if table:
+            nP = len(table)
+            host = torch.tensor([v for row in table for v in row] + pos_b + pos_r, dtype=torch.int64)
+            up = host.pin_memory().to(dev, non_blocking=True)        # descriptors + image / slot rows: ONE H2D
+            b_dev, r_dev = up[6 * nP:6 * nP + K], up[6 * nP + K:]
+            lab_dev = torch.cat([g.reshape(-1) for g in gt_labels_list]).to(torch.int64)
+            ops.lsap_device_launch(torch.cat(costs), up[:6 * nP].view(nP, 6), lds, q_all, g_all, self.assign_status,
+                                   gt_labels=lab_dev, labels=labels, weights=weights)
+        pm = max(m, default=0)
+        out = []
+        for li in range(n):
+            q, g = q_all[li * K:(li + 1) * K], g_all[li * K:(li + 1) * K]
+            out.append((labels[li], weights[li], pos_b, g, K, dict(b=b_dev, q=q, g=g, r=r_dev, pm=pm)))
         return out
 
     def gather_captions_and_preds(self, gt_caption_embs_list, gt_caption_mask_list, cls_emb_preds):

@@ -2508,6 +2508,85 @@ def linear_sum_assignment_batch(costs):
     return out
 
 
+LSAP_MAX_SIDE = 1024                # cgg_lsap_device_f32: sides of a problem
+LSAP_OK, LSAP_INVALID, LSAP_INFEASIBLE, LSAP_BAD_DESCRIPTOR = 0, 1, 2, 3
+
+
+def lsap_device_lds_bytes(nr, nc):
+    """LDS one problem of `cgg_lsap_device_f32` needs: the staged f32 cost matrix plus the solver's state."""
+    return int(_lib_().cgg_lsap_device_lds_bytes(int(nr), int(nc)))
+
+
+def lsap_device_ok(nr, nc):
+    """Gate of the device solver: both sides in 1 .. 1024 and the staged cost + state within the dynamic-LDS limit of the current
+    device (gfx950's 160 KiB where there is none). Host arithmetic only."""
+    nr, nc = int(nr), int(nc)
+    if min(nr, nc) < 1 or max(nr, nc) > LSAP_MAX_SIDE:
+        return False
+    return lsap_device_lds_bytes(nr, nc) <= int(_lib_().cgg_dynamic_lds_limit())
+
+
+def lsap_device_launch(cost_flat, desc, lds_bytes, q_out, g_out, status, gt_labels=None, labels=None, weights=None):
+    """One launch of `cgg_lsap_device_f32`: cost_flat (f32), desc (P, 6) int64 (cost offset, nr, nc, output offset, label-row
+    offset, gt-label offset) and every output on the device; lds_bytes = the largest `lsap_device_lds_bytes` of the table.
+    Enqueues on the current stream and waits for nothing."""
+    P = int(desc.shape[0])
+    if P == 0:
+        return
+    if desc.dim() != 2 or desc.shape[1] != 6 or q_out.numel() != g_out.numel() or status.numel() != 2:
+        raise CggError('lsap_device_launch: desc must be (P, 6), q_out / g_out of one size, status two words')
+    if (gt_labels is None) != (labels is None) or (labels is None) != (weights is None):
+        raise CggError('lsap_device_launch: the epilogue needs gt_labels, labels and weights together')
+    if labels is not None and labels.numel() != weights.numel():
+        raise CggError('lsap_device_launch: labels and weights must have one size')
+    rc = _lib_().cgg_lsap_device_f32(
+        dev_ptr(cost_flat, 'cost_flat', torch.float32), cost_flat.numel(), dev_ptr(desc, 'desc', torch.int64), P, int(lds_bytes),
+        dev_ptr(q_out, 'q_out', torch.int64), dev_ptr(g_out, 'g_out', torch.int64), q_out.numel(),
+        dev_ptr(gt_labels, 'gt_labels', torch.int64), 0 if gt_labels is None else gt_labels.numel(),
+        dev_ptr(labels, 'labels', torch.int64), dev_ptr(weights, 'weights', torch.float32), 0 if labels is None else labels.numel(),
+        dev_ptr(status, 'status', torch.int32), stream_ptr(cost_flat.device))
+    check(rc, 'cgg_lsap_device_f32')
+
+
+def linear_sum_assignment_device(cost_flat, nr, nc):
+    """cost_flat: the f32 row-major cost matrices of all problems, concatenated, on the device; problem p is nr[p] x nc[p]
+    (host ints, every one inside `lsap_device_ok`). -> (rows, cols, status): int64 device tensors with min(nr[p], nc[p]) pairs
+    per problem, concatenated in problem order, rows ascending (scipy's indices, ties included), and the two int32 status words
+    [code, first failing problem + 1] for `lsap_status_check`. One launch (csrc/lsap_device.hip); nothing waits for the device."""
+    nr, nc = [int(v) for v in nr], [int(v) for v in nc]
+    if len(nr) != len(nc):
+        raise CggError('linear_sum_assignment_device: nr and nc differ in length')
+    dev = cost_flat.device
+    table, coff, ooff, lds = [], 0, 0, 0
+    for a, b in zip(nr, nc):
+        if not lsap_device_ok(a, b):
+            raise CggError(f'linear_sum_assignment_device: a {a} x {b} problem is outside lsap_device_ok')
+        table.append((coff, a, b, ooff, 0, 0))
+        coff += a * b
+        ooff += min(a, b)
+        lds = max(lds, lsap_device_lds_bytes(a, b))
+    if cost_flat.dim() != 1 or cost_flat.numel() != coff:
+        raise CggError(f'linear_sum_assignment_device: cost_flat has {cost_flat.numel()} elements, the problems {coff}')
+    rows = torch.zeros((ooff,), dtype=torch.int64, device=dev)
+    cols = torch.zeros((ooff,), dtype=torch.int64, device=dev)
+    status = torch.zeros((2,), dtype=torch.int32, device=dev)
+    if table:
+        desc = torch.tensor(table, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        lsap_device_launch(cost_flat, desc, lds, rows, cols, status)
+    return rows, cols, status
+
+
+def lsap_status_check(status):
+    """Reads the two status words of the device solver (this WAITS for the device) and raises, naming the problem, with the host
+    solver's messages. `status`: the device tensor, or its two values."""
+    code, where = (int(v) for v in (status.tolist() if torch.is_tensor(status) else status))
+    if code == LSAP_OK:
+        return
+    what = {LSAP_INVALID: 'matrix contains invalid numeric entries', LSAP_INFEASIBLE: 'cost matrix is infeasible',
+            LSAP_BAD_DESCRIPTOR: 'descriptor outside the buffers or the LDS of the launch'}.get(code, f'status {code}')
+    raise CggError(f'cgg_lsap_device_f32: problem {where - 1}: {what}')
+
+
 def point_sample_planes(planes, index, points):
     """planes (N, H, W) f32, index (rows,) int32, points (rows, P, 2) f32 in [0, 1] (x, y) -> (rows, P): row j = bilinear
     sample (grid_sample arithmetic, zeros outside) of planes[index[j]] at points[j]."""

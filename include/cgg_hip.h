@@ -1024,6 +1024,25 @@ int cgg_im2col3x3_nhwc(const void* x, void* y, int B, int H, int W, int C, int s
 int cgg_linear_sum_assignment_f32(const float* cost, int n_problems, const int* nr, const int* nc, int64_t* rows,
                                   int64_t* cols);
 
+/* The same assignment on the DEVICE (csrc/lsap_device.hip): one launch, one wavefront per problem, the cost matrix and the
+ * solver's state in LDS; same algorithm, f64 arithmetic, scan order and tie rule as the host function above, so the INDICES
+ * are its (and scipy's). cost: flat f32 device buffer of cost_numel elements. desc: n_problems x 6 int64 on the device, per
+ * problem: cost offset, nr, nc (1 .. 1024 each), output offset, label-row offset, gt-label offset (all in elements).
+ * lds_bytes: the largest cgg_lsap_device_lds_bytes(nr, nc) of the table (<= cgg_dynamic_lds_limit()). Problem p writes
+ * min(nr, nc) pairs at q_out / g_out[output offset ...], rows ascending as scipy returns them (out_numel elements each).
+ * Optional epilogue (gt_labels, labels, weights all non-null): labels[label-row offset + q] = gt_labels[gt-label offset + g]
+ * and weights[label-row offset + q] = 1 for every pair (gt_numel / rows_numel elements). status: two int32 words, 8-byte
+ * aligned, that the caller zeroes; they keep [code, problem + 1] of the failing problem with the lowest index (a word that is
+ * already non-zero is only replaced by a lower index): 1 = NaN / -inf entries, 2 = infeasible (both write the identity
+ * pairing k -> (k, k), in range for every consumer), 3 = a descriptor that does not fit the buffers or lds_bytes (nothing
+ * written). The other problems of the launch are unaffected; nothing here waits for the device.                          */
+int64_t cgg_lsap_device_lds_bytes(int nr, int nc);
+int cgg_lsap_device_f32(const float* cost, int64_t cost_numel, const int64_t* desc, int n_problems, int64_t lds_bytes,
+                        int64_t* q_out, int64_t* g_out, int64_t out_numel, const int64_t* gt_labels, int64_t gt_numel,
+                        int64_t* labels, float* weights, int64_t rows_numel, int32_t* status, cgg_stream_t stream);
+/* The most dynamic LDS a workgroup may request on the current device (160 KiB, gfx950's, when there is no device).      */
+int64_t cgg_dynamic_lds_limit(void);
+
 /* [3P] mmcv.ops.point_sample (= F.grid_sample(2 p - 1, bilinear, zeros, align_corners=False)) on a CHANNEL-LAST f32 map:
  * out[b, p, :] = bilinear sample of feat[b] (H, W, C) at pts[b, p] = (x, y) in [0, 1]; taps outside the map contribute 0.
  * Used for sample(E F) = E sample(F) at the matching points of all decoder layers (mask2former_head.py:357-366). C % 4 == 0. */

@@ -298,6 +298,24 @@ def main(argv=None):
                                        '(|a| >= 4094, csrc/x3.h: the x3s GEMM / convolution / norm epilogues raise the flag) on at '
                                        'least one rank -- the losses since the last check are invalid; re-run with CGG_X3A=0 '
                                        '(f32 rows, in-kernel split) or --precision bf16')
+            if it % args.log_interval == 0 or it == max_iters:
+                # the device Hungarian solver (csrc/lsap_device.hip) does not stop a step for NaN / -inf costs or an infeasible
+                # matrix: it pairs k with k and keeps the first failure in the head's two status words. Read them here, once per
+                # logging interval, with the pattern of the overflow flag above: all-reduce first, so every rank raises.
+                from cgg_amd import ops
+                words = [m.assign_status for m in model.modules() if getattr(m, 'assign_status', None) is not None]
+                status = words[0].clone() if words else torch.zeros((2,), dtype=torch.int32, device=device)
+                for w in words:
+                    w.zero_()
+                failed = (status[:1] != 0).to(torch.int32)
+                if distributed:
+                    torch.distributed.all_reduce(failed, op=torch.distributed.ReduceOp.MAX)
+                code, where = status.tolist()
+                if int(failed.item()):
+                    if code == 0:
+                        raise RuntimeError(f'iteration {it}: the device Hungarian solver failed on another rank -- the losses since '
+                                           'the last check are invalid')
+                    ops.lsap_status_check((code, where))
             if rank == 0 and (it % args.log_interval == 0 or it == max_iters):
                 dt = (time.perf_counter() - t0) / max(it - start_iter, 1)
                 rec = dict(iter=it, time=round(dt, 4), lr=optimizer.param_groups[0]['lr'],
