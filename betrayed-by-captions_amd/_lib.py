@@ -65,6 +65,13 @@ PROTOTYPES = {
     'cgg_rle_transitions': (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp]),
     'cgg_rle_strings_from_transitions': (_c_i64, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_i64, _c_vp]),
     'cgg_rle_encode_colmajor': (_c_i64, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_i64, _c_vp]),
+    'cgg_paint_instances_u8': (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_i64, _c_int] + [_c_vp] * 4 +
+                               [ctypes.c_double, ctypes.c_double, _c_int, _c_int, _c_vp]),
+    'cgg_pack_bool_rows_u8': (_c_int, [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp]),
+    'cgg_label_components_workspace_bytes': (_c_i64, [_c_int, _c_int]),
+    'cgg_label_components_i32': (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp]),
+    'cgg_paint_panoptic_u8': (_c_int, [_c_vp] * 3 + [_c_int, _c_int, _c_vp, _c_vp, _c_int, ctypes.c_double, ctypes.c_double, _c_int,
+                                        _c_vp]),
     'cgg_masked_xattn_forward_bf16': (_c_int, [_c_vp] * 6 + [_c_int] * 5 + [_c_f, _c_int, _c_i64, _c_int, _c_vp]),
     'cgg_linear_rows': (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp] + [_c_int] * 6 + [_c_vp]),
     'cgg_add_layernorm': (_c_int, [_c_vp] * 5 + [_c_int, _c_int, _c_f, _c_vp]),

@@ -3,6 +3,7 @@
 
     model = init_detector('configs/instance/coco_b48n17.py', 'cgg.pth', device='cuda:0')
     result = inference_detector(model, bgr_uint8_image, with_caption=True)
+    show_result_pyplot(model, bgr_uint8_image, result, score_thr=0.95)
 """
 import numpy as np
 import torch
@@ -81,3 +82,12 @@ def inference_detector(model, imgs, **kwargs):
     with torch.no_grad():
         results = model(img=[batch], img_metas=[metas], return_loss=False, rescale=True, **kwargs)
     return results if is_batch else results[0]
+
+
+def show_result_pyplot(model, img, result, score_thr=0.3, title='result', wait_time=0, palette=None, out_file=None):
+    """[3P] mmdet.apis.show_result_pyplot, the last line of the reference's demo: `model.show_result` with one `palette` for boxes,
+    text and masks, shown in a matplotlib window titled `title` -- or written to `out_file` (then no window is opened)."""
+    if hasattr(model, 'module'):
+        model = model.module
+    return model.show_result(img, result, score_thr=score_thr, show=True, wait_time=wait_time, win_name=title, bbox_color=palette,
+                             text_color=(200, 200, 200), mask_color=palette, out_file=out_file)

@@ -48,6 +48,8 @@ class MaskFormerOpen(nn.Module):
         self.num_classes = self.panoptic_fusion_head.num_classes
         self.train_cfg = to_config_dict(train_cfg) if train_cfg is not None else None
         self.test_cfg = to_config_dict(test_cfg) if test_cfg is not None else to_config_dict({})
+        if self.num_stuff_classes > 0:          # maskformer.py:49-51
+            self.show_result = self._show_pan_result
 
     @property
     def with_neck(self):
@@ -224,6 +226,32 @@ class MaskFormerOpen(nn.Module):
 
     def aug_test(self, imgs, img_metas, **kwargs):
         raise NotImplementedError
+
+    def show_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241), mask_color=None,
+                    thickness=2, font_size=13, win_name='', show=False, wait_time=0, out_file=None, show_labels=True, seed=0):
+        """maskformer.py:228-309: draw `result['all_results']` over `img` (a file name, an (h, w, 3) uint8 array or a tensor, in the
+        channel order `inference_detector` takes). The result is the host form (bbox_results, mask_results) or the device form of
+        `device_results=True` (labels, boxes (n, 5), masks bool or bit-packed); device masks are painted where they are
+        (csrc/paint.hip) and never copied to the host -- labels, scores and boxes come over in one small copy. Order: by class,
+        within a class in result order; filter: `scores > score_thr` when score_thr > 0. Fills follow the reference's arithmetic
+        exactly; mask edges and box frames follow this build's pixel rules (paint.py), not matplotlib's anti-aliased artists; text
+        (`name|score`, `class {label}` without CLASSES) is drawn with PIL. `seed` seeds the colour jitter the reference draws from
+        numpy's global state. Returns the (h, w, 3) uint8 array unless `show` or `out_file`."""
+        from .paint import show_instances
+        return show_instances(self, img, result, score_thr=score_thr, bbox_color=bbox_color, text_color=text_color,
+                              mask_color=mask_color, thickness=thickness, font_size=font_size, win_name=win_name, show=show,
+                              wait_time=wait_time, out_file=out_file, show_labels=show_labels, seed=seed)
+
+    def _show_pan_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241), mask_color=None,
+                         thickness=2, font_size=20, win_name='', show=False, wait_time=0, out_file=None, show_labels=True, seed=0):
+        """maskformer.py:311-382: draw the panoptic map `result['panoptic_all_results']` (host array or device tensor) over `img`.
+        Ids in descending order without void, label = id % 1000. The device labels the connected components and paints; one small
+        copy of the component records gives the host the ids, their colours and, per id, the centroid and area of its largest
+        component, where the label text goes."""
+        from .paint import show_panoptic
+        return show_panoptic(self, img, result, score_thr=score_thr, bbox_color=bbox_color, text_color=text_color,
+                             mask_color=mask_color, thickness=thickness, font_size=font_size, win_name=win_name, show=show,
+                             wait_time=wait_time, out_file=out_file, show_labels=show_labels, seed=seed)
 
     def onnx_export(self, img, img_metas):
         raise NotImplementedError(f'{self.__class__.__name__} does not support ONNX EXPORT')

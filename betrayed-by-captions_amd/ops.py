@@ -3104,3 +3104,131 @@ def rle_encode_colmajor(cols, H, width, threads=8):
     return _rle_strings(lambda out, cap, oo: lib.cgg_rle_encode_colmajor(
         ctypes.c_void_p(arr.ctypes.data), n, H, W, int(threads), out, cap, oo),
         'cgg_rle_encode_colmajor', n, H, W, max(1 << 16, n * 4096))
+
+
+# ------------------------------------------------------------------------------------------------
+# drawing a result over its image on the device (csrc/paint.hip; paint.py states the rules in numpy)
+# ------------------------------------------------------------------------------------------------
+PAINT_MAX_MASKS = 1024
+PAINT_MAX_IDS = 1024
+PAINT_MAX_IMAGE_BYTES = 1 << 31
+
+
+def _u8_image_ok(img):
+    return (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
+            and img.is_contiguous() and 0 < img.numel() <= PAINT_MAX_IMAGE_BYTES)
+
+
+def pack_bool_masks(masks):
+    """DEVICE bool (n, H, W) -> bit-packed uint8 (n, H, ceil(W / 8)): pixel x in bit (x & 7) of byte (x >> 3), pad bits zero."""
+    if not torch.is_tensor(masks) or masks.dtype != torch.bool or masks.dim() != 3:
+        raise CggError('pack_bool_masks: (n, H, W) bool device tensor expected')
+    n, H, W = masks.shape
+    masks = masks.contiguous()
+    rb = (W + 7) // 8
+    bits = torch.empty((n, H, rb), dtype=torch.uint8, device=masks.device)
+    if n * H > 0:
+        rc = _lib_().cgg_pack_bool_rows_u8(dev_ptr(masks.view(torch.uint8), 'masks', torch.uint8), n * H, W, rb, dev_ptr(bits),
+                                           stream_ptr(masks.device))
+        check(rc, 'cgg_pack_bool_rows_u8')
+    return bits
+
+
+def paint_instances_ok(img, bits):
+    """The gate of `paint_instances`: a contiguous (H, W, 3) uint8 device image of at most 2^31 bytes, and bit-packed masks
+    (n <= 1024, H, row_bytes) on the same device with contiguous rows -- the layout `rle_transitions` reads."""
+    if not _u8_image_ok(img) or not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 3:
+        return False
+    n, H, rb = bits.shape
+    if bits.device != img.device or H != img.shape[0] or rb * 8 < img.shape[1] or n > PAINT_MAX_MASKS:
+        return False
+    return n == 0 or (bits.stride(2) == 1 and bits.stride(1) == rb and bits.stride(0) >= H * rb)
+
+
+def paint_instances(img, bits, keep, colors, boxes=None, box_colors=None, alpha=0.8, thickness=2, edges=True, out=None):
+    """img (H, W, 3) uint8, bits (n, H, row_bytes) uint8 bit-packed masks, keep (n) uint8, colors (n, 3) uint8, boxes (n, 4) int32
+    with box_colors (n, 3) uint8 or None -- all on one device -> the painted image (a new tensor, or `out`, which may be `img`),
+    equal to `paint.paint_instances_host` bit for bit. One launch on the current stream, no host read."""
+    if not paint_instances_ok(img, bits):
+        raise CggError('paint_instances: outside the kernel gate (contiguous (H, W, 3) uint8 device image of at most 2^31 bytes; '
+                       f'(n <= {PAINT_MAX_MASKS}, H, row_bytes) uint8 masks with contiguous rows on the same device)')
+    H, W, _ = img.shape
+    n, _, rb = bits.shape
+    dev = img.device
+    if out is None:
+        out = torch.empty_like(img)
+    elif out.shape != img.shape or out.device != dev:
+        raise CggError('paint_instances: out must have the image\'s shape and device')
+    if (boxes is None) != (box_colors is None):
+        raise CggError('paint_instances: boxes and box_colors go together')
+    for t, name, shape in ((keep, 'keep', (n,)), (colors, 'colors', (n, 3)), (boxes, 'boxes', (n, 4)), (box_colors, 'box_colors', (n, 3))):
+        if t is not None and (tuple(t.shape) != shape or t.device != dev):
+            raise CggError(f'paint_instances: {name} must be {shape} on {dev} (got {tuple(t.shape)} on {t.device})')
+    alpha = float(alpha)
+    stride = bits.stride(0) if n > 0 else H * rb
+    with _timed('paint_instances', bytes=float(n * H * rb + 2 * img.numel()), shape=(n, H, W)):
+        rc = _lib_().cgg_paint_instances_u8(dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8), H, W,
+                                            ctypes.c_void_p(bits.data_ptr()) if n > 0 else None, n, int(stride), rb,
+                                            dev_ptr(keep, 'keep', torch.uint8), dev_ptr(colors, 'colors', torch.uint8),
+                                            dev_ptr(boxes, 'boxes', torch.int32), dev_ptr(box_colors, 'box_colors', torch.uint8),
+                                            alpha, 1 - alpha, int(thickness), int(bool(edges)), stream_ptr(dev))
+    check(rc, 'cgg_paint_instances_u8')
+    return out
+
+
+def label_components_ok(pan):
+    """The gate of `label_components`: a contiguous (H, W) int32 device map with H * W < 2^31 (ids >= 0: the kernel reports a
+    negative id in its status word, it cannot be seen here without a host read)."""
+    return (torch.is_tensor(pan) and pan.is_cuda and pan.dtype == torch.int32 and pan.dim() == 2 and pan.is_contiguous()
+            and 0 < pan.numel() < (1 << 31))
+
+
+def label_components(pan, void, capacity=4096):
+    """pan (H, W) int32 on the device -> (records int64 (capacity, 5), status int32 (2)) on the device, on the current stream, no host
+    read: the 8-connected components of equal non-void id as `paint.components_host` lists them, [root, id, area, sum_x, sum_y],
+    in no particular order. status[0] = number of components (records[:min(status[0], capacity)] are valid; more than `capacity`:
+    overflow, the caller falls back to `components_host`), status[1] != 0: the records are not to be used (see cgg_hip.h)."""
+    if not label_components_ok(pan):
+        raise CggError('label_components: contiguous (H, W) int32 device tensor with H * W < 2^31 expected')
+    H, W = pan.shape
+    dev = pan.device
+    lib = _lib_()
+    cap = int(capacity)
+    ws = torch.empty(max(int(lib.cgg_label_components_workspace_bytes(H, W)), 8), dtype=torch.uint8, device=dev)
+    records = torch.empty((max(cap, 1), 5), dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    with _timed('label_components', bytes=float(pan.numel() * 4), shape=(H, W)):
+        rc = lib.cgg_label_components_i32(dev_ptr(pan, 'pan', torch.int32), H, W, int(void), dev_ptr(ws), dev_ptr(records), cap,
+                                          dev_ptr(status), stream_ptr(dev))
+    check(rc, 'cgg_label_components_i32')
+    return records[:cap], status
+
+
+def paint_panoptic_ok(img, pan, nids):
+    return (_u8_image_ok(img) and torch.is_tensor(pan) and pan.dtype == torch.int32 and pan.device == img.device
+            and tuple(pan.shape) == tuple(img.shape[:2]) and pan.is_contiguous() and 0 <= int(nids) <= PAINT_MAX_IDS)
+
+
+def paint_panoptic(img, pan, ids, colors, alpha=0.8, edges=True, out=None):
+    """img (H, W, 3) uint8, pan (H, W) int32, ids (k <= 1024) int32 strictly ascending, colors (k, 3) uint8, all on one device -> the
+    painted image, equal to `paint.paint_panoptic_host` bit for bit. One launch on the current stream, no host read."""
+    k = int(ids.numel()) if torch.is_tensor(ids) else -1
+    if k < 0 or not paint_panoptic_ok(img, pan, k):
+        raise CggError('paint_panoptic: outside the kernel gate (contiguous (H, W, 3) uint8 device image of at most 2^31 bytes, (H, W) '
+                       f'int32 map on the same device, at most {PAINT_MAX_IDS} ids)')
+    dev = img.device
+    if tuple(colors.shape) != (k, 3) or colors.device != dev or ids.device != dev:
+        raise CggError(f'paint_panoptic: ids ({k}) and colors ({k}, 3) must live on {dev}')
+    if out is None:
+        out = torch.empty_like(img)
+    elif out.shape != img.shape or out.device != dev:
+        raise CggError('paint_panoptic: out must have the image\'s shape and device')
+    H, W, _ = img.shape
+    alpha = float(alpha)
+    with _timed('paint_panoptic', bytes=float(pan.numel() * 4 + 2 * img.numel()), shape=(H, W, k)):
+        rc = _lib_().cgg_paint_panoptic_u8(dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8),
+                                           dev_ptr(pan, 'pan', torch.int32), H, W, dev_ptr(ids, 'ids', torch.int32),
+                                           dev_ptr(colors, 'colors', torch.uint8), k, alpha, 1 - alpha, int(bool(edges)),
+                                           stream_ptr(dev))
+    check(rc, 'cgg_paint_panoptic_u8')
+    return out

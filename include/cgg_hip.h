@@ -462,6 +462,56 @@ int64_t cgg_rle_strings_from_transitions(const uint32_t* positions, const int64_
 int64_t cgg_rle_encode_colmajor(const uint64_t* cols, int n, int H, int W, int threads, uint8_t* out, int64_t out_cap,
                                 int64_t* out_offsets);
 
+/* ----------------------------------------------------------------------------------------------
+ * Drawing a result over its image (csrc/paint.hip). `paint.py` states every rule in numpy (paint_instances_host,
+ * components_host, paint_panoptic_host) and the kernels equal those bit for bit. All pointers DEVICE; everything runs on
+ * `stream`; no host read, no allocation: legal under stream capture.
+ *
+ * The blend of a pixel value v (uint8) with a colour c (uint8) is the reference's numpy line
+ * ([3P] open_set/core/visualization/image.py:199) in float64: (uint8) trunc(v * one_minus_alpha + c * alpha), two rounded
+ * products and one rounded sum, no fused multiply-add. alpha and one_minus_alpha are both computed by the caller
+ * (1 - 0.8 is 0.19999999999999996, not 0.2), each in [0, 1].
+ *
+ * cgg_paint_instances_u8: img, out (H, W, 3) uint8 (out may be img); bits as cgg_rle_transitions reads them (n planes of H rows x
+ *   row_bytes, plane i at bits + i * mask_stride_bytes, pixel x = bit (x & 7) of byte (x >> 3), pad bits ignored); keep uint8[n];
+ *   colors uint8[n][3], applied to the channels in stored order; boxes int32[n][4] (x0, y0, x1, y1, already truncated; they may
+ *   reach outside the image) with box_colors uint8[n][3], or NULL for no boxes. One launch:
+ *     1. for each kept mask in index order, every pixel of the mask is blended with the mask's colour at alpha;
+ *     2. if `edges`: a pixel that lies in some kept mask i while one of its four neighbours does not (a neighbour outside the
+ *        image never does) is blended ONCE with white at alpha 0.8;
+ *     3. for each kept box in index order: the pixels of the rectangle x0..x1, y0..y1 (inclusive; empty when x1 < x0 or y1 < y0)
+ *        nearer than `thickness` pixels to one of its four sides are blended once with the box's colour at alpha 0.8; pixels
+ *        outside the image are not drawn.
+ *   CGG_EINVAL: null pointer, H, W < 1, n < 0, thickness < 0, row_bytes * 8 < W, mask_stride_bytes < H * row_bytes, alpha or
+ *   one_minus_alpha outside [0, 1]. CGG_EUNSUPPORTED: n > 1024, H * W * 3 > 2^31.
+ *
+ * cgg_label_components_i32: the 8-connected components of equal id of pan (H, W) int32, pixels equal to void_id (and negative
+ *   ids) belonging to none. records int64[capacity][5] = [root, id, area, sum_x, sum_y], root = the smallest linear index
+ *   y * W + x of the component, in NO particular order (sort by root for a canonical list); status int32[2]: [0] = the number of
+ *   components (when it exceeds capacity, `records` holds any `capacity` of them), [1] = 0, or bit 0: a union-find loop hit its
+ *   bound of H * W steps (a bug: the records are not to be used), bit 1: a negative id was met. ws: DEVICE,
+ *   cgg_label_components_workspace_bytes(H, W) bytes, 8-byte aligned. Union-find with integer atomics only (min on labels, add
+ *   on the sums), so the result does not depend on scheduling; no loop waits on another workgroup. Three memsets and four
+ *   launches. CGG_EINVAL: null pointer, H, W < 1, capacity < 0, misalignment. CGG_EUNSUPPORTED: H * W >= 2^31.
+ *
+ * cgg_paint_panoptic_u8: pan (H, W) int32; ids int32[nids] strictly ascending with colors uint8[nids][3]. A pixel whose id is in
+ *   the table is blended with that id's colour at alpha; if `edges`, such a pixel with a four-neighbour of another id, or on the
+ *   frame, is then blended with white at alpha 0.8. One launch. CGG_EINVAL: null pointer, H, W < 1, nids < 0, alpha pair outside
+ *   [0, 1]. CGG_EUNSUPPORTED: nids > 1024, H * W * 3 > 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+int cgg_paint_instances_u8(const uint8_t* img, uint8_t* out, int H, int W, const uint8_t* bits, int n, int64_t mask_stride_bytes,
+                           int row_bytes, const uint8_t* keep, const uint8_t* colors, const int32_t* boxes,
+                           const uint8_t* box_colors, double alpha, double one_minus_alpha, int thickness, int edges,
+                           cgg_stream_t stream);
+/* masks: `rows` rows of W bytes (torch.bool planes, non-zero = set) -> bits: `rows` rows of row_bytes bytes, pixel x = bit (x & 7) of
+ * byte (x >> 3), bits past W zero. CGG_EINVAL: null pointer, rows < 0, W < 1, row_bytes * 8 < W. */
+int cgg_pack_bool_rows_u8(const uint8_t* masks, int64_t rows, int W, int row_bytes, uint8_t* bits, cgg_stream_t stream);
+int64_t cgg_label_components_workspace_bytes(int H, int W);
+int cgg_label_components_i32(const int32_t* pan, int H, int W, int void_id, void* ws, int64_t* records, int capacity,
+                             int32_t* status, cgg_stream_t stream);
+int cgg_paint_panoptic_u8(const uint8_t* img, uint8_t* out, const int32_t* pan, int H, int W, const int32_t* ids,
+                          const uint8_t* colors, int nids, double alpha, double one_minus_alpha, int edges, cgg_stream_t stream);
+
 /* Throughput-mode self-attention of the query decoder ([3P] DetrTransformerDecoderLayer self_attn, no mask; S = Q <= 128):
  * q [B*Q, ldq] and kv = [k | v] [B*Q, ldkv] f32 rows (as written by the fused q|k|v projection) -> out [B*Q, H*D] f32 =
  * softmax(scale q k^T) v per head. bf16 MFMA operands, f32 accumulation and softmax; D == 32.                       */

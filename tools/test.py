@@ -69,6 +69,11 @@ def parse_args(argv=None):
                    help='keep the masks bit-packed ((n, H, W / 8) uint8, pixel x = bit x & 7 of byte x >> 3) in the results: '
                         '8x less PCIe traffic and 8x smaller result files; unpacking 315 MB of bool masks per 1024^2 image on '
                         'the host costs more than the copy it saves (28 vs 36 images/s end to end), so it is opt-in')
+    p.add_argument('--show', action='store_true', help='paints like --show-dir, into work_dirs/show when no --show-dir is given (no window is opened)')
+    p.add_argument('--show-dir', default=None,
+                   help='directory where every image of the run is written with its result painted over it (model.show_result on the '
+                        'device results the run already holds): DIR/<base name of ori_filename, or index>.png (a base name met before gets _<index> appended). Needs raw uint8 images')
+    p.add_argument('--show-score-thr', type=float, default=0.3, help='score threshold of --show-dir (default 0.3)')
     args = p.parse_args(argv)
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
@@ -183,8 +188,28 @@ def main(argv=None):
         args.mask_bits = True
         collector = RleCollector(device, fusion_class_counts(model.panoptic_fusion_head), device_rle=args.rle_device)
 
+    show_dir = args.show_dir or (os.path.join('work_dirs', 'show') if args.show else None)
+    shown = []                         # per submitted batch, in submission order: its raw images and their file names
+    n_shown = 0
+    shown_names = set()
+
+    def paint(device_results):
+        """--show-dir: the batch's images with their results painted over them, from the device results (masks are not copied)"""
+        nonlocal n_shown
+        frames = shown.pop(0)
+        for (raw, name), res in zip(frames, device_results):
+            index = n_shown * world + rank
+            stem = os.path.splitext(os.path.basename(name))[0] if name else str(index)
+            if stem in shown_names:        # the same base name from another directory (or a repeated name): keep both files
+                stem = f'{stem}_{index}'
+            shown_names.add(stem)
+            model.show_result(raw, res, score_thr=args.show_score_thr, out_file=os.path.join(show_dir, stem + '.png'))
+            n_shown += 1
+
     def emit(device_results):
         """device results of one batch -> `results` (numpy now, or a future of the RLE collector)"""
+        if show_dir is not None:
+            paint(device_results)
         if collector is None:
             results.extend(to_numpy(r) for r in device_results)
         else:
@@ -226,6 +251,11 @@ def main(argv=None):
         def run(group):
             nonlocal pipe, t0, n_img
             raw = [g[0] for g in group] if is_raw_u8(group[0][0]) else None
+            if show_dir is not None:
+                if raw is None:
+                    raise SystemExit('tools/test.py: --show-dir paints over the raw uint8 images (--synthetic-u8, or a --data stream of '
+                                     'them); prepared float tensors cannot be shown')
+                shown.append([(g[0], (g[1] or {}).get('ori_filename', (g[1] or {}).get('filename'))) for g in group])
             if raw is not None:
                 # raw uint8 images: resized, padded, normalised and collated by ONE kernel (cgg_amd.image_prep), which is launched
                 # below -- into the pipeline's own input buffer when a captured pipeline serves this batch
