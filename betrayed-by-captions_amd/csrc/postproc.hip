@@ -334,6 +334,9 @@ __global__ __launch_bounds__(256) void cgg_softmax_argmax_kernel(const float* __
     const int oi = __shfl_xor(mi, o);
     if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
   }
+  // NaN compares false both ways, so NaN entries never take part in the maximum, and a row of nothing but NaN leaves
+  // `mi` at its start value. The argmax is always an index of the row: such a row returns 0 (its maxv and prob are NaN).
+  if (mi >= n) mi = 0;
   float sum = 0.f;
   for (int i = lane; i < n; i += 64) sum += expf(xr[i] - m);
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
@@ -388,11 +391,14 @@ static bool instance_masks_dispatch(const float* logits, const int32_t* sel, con
   const long long npix = (long long)out_h * out_w;
   const long long per_block = 256LL * IM_PPT;
   const dim3 grid((unsigned)((npix + per_block - 1) / per_block), n);
-  const int S = up_h / H;
-  const bool int_path = !g.two_stage && S * H == up_h && S * W == up_w && (out_w % IM_PPT) == 0 &&
+  const int S = up_h / H;                                   // 0 when the target is smaller than the low-res logits
+  const bool int_path = S >= 1 && !g.two_stage && S * H == up_h && S * W == up_w && (out_w % IM_PPT) == 0 &&
                         (((uintptr_t)masks) & 15) == 0;
-  const long long ntile = (long long)((out_h + S - 1) / S) * (out_w / IM_PPT);   // one thread per 16 x S block
-  const dim3 tgrid((unsigned)((ntile + 255) / 256), n);
+  dim3 tgrid(1, n);
+  if (int_path) {                                           // the tile grid exists (and S divides) on the integer path only
+    const long long ntile = (long long)((out_h + S - 1) / S) * (out_w / IM_PPT);   // one thread per 16 x S block
+    tgrid.x = (unsigned)((ntile + 255) / 256);
+  }
   if (bits) {
     if (!(int_path && (S == 2 || S == 4 || S == 8))) return false;     // bit-packed output: integer-scale path only
     if (S == 4)

@@ -1237,7 +1237,8 @@ int cgg_panoptic_fuse_batched(const float* logits, const float* score, const int
 /* Row-wise softmax + max/argmax: scores = softmax(x) over the last dim, one wavefront per row
  * (MaskFormerFusionHeadOpen.get_cls_emb_scores, maskformer_fusion_head.py:297-315, and the
  * `.max(-1)` at :99).  x [rows, n] f32 -> prob [rows, n] f32 (nullable), maxv [rows] f32,
- * argmax [rows] int64 (first max wins).                                                          */
+ * argmax [rows] int64 (first max wins). argmax always lies in [0, n): NaN entries take no part in
+ * the maximum, and a row of nothing but NaN returns 0 (its maxv and prob are NaN).               */
 int cgg_rowwise_softmax_argmax(const float* x, float* prob, float* maxv, int64_t* argmax, int rows,
                                int n, cgg_stream_t stream);
 
