@@ -20,6 +20,11 @@
 //     down to 64 x 64, picked by problem shape.
 //   * conv: a 32-channel chunk lies inside one filter tap; per lane and row a tap-validity bit mask, out-of-map taps are sent to an
 //     out-of-range buffer offset, which the LDS-DMA answers with zeros (checked on MI355X, tests/test_x3s_gpu.py).
+//   * 3 x 3 / stride 1 / pad 1 convolutions of 64, 128 or 256 channels without residual have a kernel of their own,
+//     cgg_conv3x3_halo_kernel (configuration id 18): the ring kernel's implicit GEMM fetches a tile's rows from L2 once per filter
+//     tap, and these launches are bound by that L2 -> LDS operand rate (11-13 TB/s whatever the shape), not by MFMA or HBM. The
+//     halo kernel stages the input pixels of a workgroup's output patch plus a one-pixel ring in LDS ONCE, streams only the weight
+//     image and reads every tap's A fragments from the patch at shifted addresses -- same accumulation order, same epilogue.
 //   * epilogue: accumulator tile -> per-wave LDS scratch (XOR-swizzled, conflict-free) -> each lane owns 8 consecutive columns of a
 //     row: residual read (f32 or x3a), ReLU, then 32 contiguous bytes out -- 8 floats or the x3a group [8 hi | 8 lo] -- so the
 //     next GEMM's A operand is produced in the form it is consumed. |16 v| > 65504 (f16 overflow of a stored value) raises
@@ -83,6 +88,7 @@ struct XsEpi {
   __amdgpu_buffer_rsrc_t orsrc, rrsrc;
   float lo_clamp;
   int mr0;              // residual row of (tile row lane >> 3, pass 0, m-tile 0), reduced mod res_mod
+  int pb, y0, x0;       // halo kernel (TW > 0 below): first output row of the image, first pixel of the workgroup's patch
 };
 
 // mask ? b : a with mask = 0 or ~0 (v_bfi_b32)
@@ -123,7 +129,9 @@ __device__ __forceinline__ void xs_load_res(u32x4 (&rv)[4], const XsArgs& p, con
   if (p.res_mod) mres = p.res_mod >= 32 ? (mres >= p.res_mod ? mres - p.res_mod : mres) : mres % p.res_mod;
 }
 
-template <int RES, int OUT>
+// TW > 0 (the halo kernel): a tile row is a PATCH pixel -- mrow0 counts rows inside the workgroup's TH x TW patch, row R is pixel
+// (y0 + R / TW, x0 + R % TW) of the image; pixels of a patch that hangs over the right / bottom edge of the map are dropped.
+template <int RES, int OUT, int TW = 0>
 __device__ __forceinline__ float xs_finish_column(const float* scratch, int TM_, const XsArgs& p, const XsEpi& e, int mrow0, int ncol0,
                                                   int lane, float amax, const u32x4 (&rv0)[4], bool have_rv0) {
   const int r8 = lane >> 3, q = lane & 7;
@@ -177,10 +185,17 @@ __device__ __forceinline__ float xs_finish_column(const float* scratch, int TM_,
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) w[k] = fmaxf(w[k], e.lo_clamp);
-      const uint32_t oo = cok ? (uint32_t)((mrow0 + 32 * mt + rr) * p.ldc) * 4u + coff : XS_OOB;
+      uint32_t oo;
+      if constexpr (TW > 0) {
+        const int R = mrow0 + 32 * mt + rr, oy = e.y0 + R / TW, ox = e.x0 + R % TW;
+        oo = (cok && oy < p.cv.H && ox < p.cv.W) ? (uint32_t)((e.pb + oy * p.cv.W + ox) * p.ldc) * 4u + coff : XS_OOB;
+      } else {
+        oo = cok ? (uint32_t)((mrow0 + 32 * mt + rr) * p.ldc) * 4u + coff : XS_OOB;
+      }
       u32x4 o;
       if (OUT == 2) {
-        amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fmaxf(fabsf(w[0]), fabsf(w[1])), __builtin_fmaxf(fabsf(w[2]), fabsf(w[3]))));
+        const float wmax = __builtin_fmaxf(__builtin_fmaxf(fabsf(w[0]), fabsf(w[1])), __builtin_fmaxf(fabsf(w[2]), fabsf(w[3])));
+        amax = __builtin_fmaxf(amax, (TW > 0 && oo == XS_OOB) ? 0.f : wmax);      // a patch pixel past the map's edge is not a stored value
         uint2 h, l;
         cgg_x3_split2(w[0], w[1], h.x, l.x);
         cgg_x3_split2(w[2], w[3], h.y, l.y);
@@ -210,7 +225,7 @@ __device__ __forceinline__ XsEpi xs_epi_setup(const XsArgs& p, int mrow0, int la
   return e;
 }
 
-template <int TM, int TN>
+template <int TM, int TN, int TW = 0>
 __device__ __forceinline__ float xs_epilogue(const f32x16 (&acc)[TM][TN], float* scratch, const XsArgs& p, const XsEpi& e, int mrow0,
                                              int ntile0, int lane, const u32x4 (&rv0)[4]) {
   const int j = lane & 31, hi5 = lane >> 5;
@@ -231,6 +246,10 @@ __device__ __forceinline__ float xs_epilogue(const f32x16 (&acc)[TM][TN], float*
       }
     }
     const int ncol0 = (ntile0 + nt) * 32;
+    if constexpr (TW > 0) {                                     // no residual on the halo path (the host refuses it)
+      amax = fmt == 0 ? xs_finish_column<0, 1, TW>(scratch, TM, p, e, mrow0, ncol0, lane, amax, rv0, false)
+                      : xs_finish_column<0, 2, TW>(scratch, TM, p, e, mrow0, ncol0, lane, amax, rv0, false);
+    } else
     switch (fmt) {
       case 0: amax = xs_finish_column<0, 1>(scratch, TM, p, e, mrow0, ncol0, lane, amax, rv0, false); break;
       case 1: amax = xs_finish_column<0, 2>(scratch, TM, p, e, mrow0, ncol0, lane, amax, rv0, false); break;
@@ -241,6 +260,57 @@ __device__ __forceinline__ float xs_epilogue(const f32x16 (&acc)[TM][TN], float*
     }
   }
   return amax;
+}
+
+// One chunk = 2 k-steps of a wave's TM x TN MFMA tiles; MT = bytes between its consecutive m-tiles in the A image (shared by the
+// ring kernel and the halo kernel: the same MFMA order per accumulator in both). Software-pipelined in source: the B fragments of
+// k-step 1 and the A fragments of the next m-tile are requested while the current m-tile's MFMAs run (one LDS latency per chunk
+// is exposed -- behind the barrier -- instead of four)
+template <int TM, int TN, int MT>
+__device__ __forceinline__ void xs_compute_chunk(f32x16 (&acc)[TM][TN], const unsigned char* ab, const unsigned char* bb,
+                                               const int (&aoffs)[2][2]) {
+  u32x4 bh[2][TN], bl[2][TN], ah[2], al[2];
+#pragma unroll
+  for (int nt = 0; nt < TN; ++nt) {
+    bh[0][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096);
+    bl[0][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 2048);
+  }
+  ah[0] = *reinterpret_cast<const u32x4*>(ab + aoffs[0][0]);
+  al[0] = *reinterpret_cast<const u32x4*>(ab + aoffs[0][1]);
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+    for (int mt = 0; mt < TM; ++mt) {
+      const int cur = (ks * TM + mt) & 1, nxt = cur ^ 1;
+      if (mt + 1 < TM) {
+        ah[nxt] = *reinterpret_cast<const u32x4*>(ab + (mt + 1) * MT + aoffs[ks][0]);
+        al[nxt] = *reinterpret_cast<const u32x4*>(ab + (mt + 1) * MT + aoffs[ks][1]);
+      } else if (ks == 0) {
+        ah[nxt] = *reinterpret_cast<const u32x4*>(ab + aoffs[1][0]);
+        al[nxt] = *reinterpret_cast<const u32x4*>(ab + aoffs[1][1]);
+      }
+      if (ks == 0 && mt == (TM > 1 ? TM - 2 : 0)) {
+#pragma unroll
+        for (int nt = 0; nt < TN; ++nt) {
+          bh[1][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 1024);
+          bl[1][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 2048 + 1024);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);             // the prefetches issue BEFORE this m-tile's MFMAs (the scheduler sinks them to their uses otherwise)
+#pragma unroll
+      for (int nt = 0; nt < TN; ++nt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al[cur]), __builtin_bit_cast(f16x8, bh[ks][nt]),
+                                                             acc[mt][nt], 0, 0, 0);
+#pragma unroll
+      for (int nt = 0; nt < TN; ++nt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur]), __builtin_bit_cast(f16x8, bl[ks][nt]),
+                                                             acc[mt][nt], 0, 0, 0);
+#pragma unroll
+      for (int nt = 0; nt < TN; ++nt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur]), __builtin_bit_cast(f16x8, bh[ks][nt]),
+                                                             acc[mt][nt], 0, 0, 0);
+    }
+  }
 }
 
 // Workgroup = KG k-groups x (WM x WN) wavefronts; tile (32 TM WM) x (32 TN WN); every loop iteration consumes KG chunks of 32
@@ -398,53 +468,6 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) aoffs[ks][pc] = ((4 * ks + 2 * hi5 + pc) ^ sw) * 16;
 
-  // one chunk = 2 k-steps. Software-pipelined in source: the B fragments of k-step 1 and the A fragments of the next m-tile are
-  // requested while the current m-tile's MFMAs run (one LDS latency per chunk is exposed -- behind the barrier -- instead of four)
-  auto compute = [&](const unsigned char* ab, const unsigned char* bb) {
-    u32x4 bh[2][TN], bl[2][TN], ah[2], al[2];
-#pragma unroll
-    for (int nt = 0; nt < TN; ++nt) {
-      bh[0][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096);
-      bl[0][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 2048);
-    }
-    ah[0] = *reinterpret_cast<const u32x4*>(ab + aoffs[0][0]);
-    al[0] = *reinterpret_cast<const u32x4*>(ab + aoffs[0][1]);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int mt = 0; mt < TM; ++mt) {
-        const int cur = (ks * TM + mt) & 1, nxt = cur ^ 1;
-        if (mt + 1 < TM) {
-          ah[nxt] = *reinterpret_cast<const u32x4*>(ab + (mt + 1) * 4096 + aoffs[ks][0]);
-          al[nxt] = *reinterpret_cast<const u32x4*>(ab + (mt + 1) * 4096 + aoffs[ks][1]);
-        } else if (ks == 0) {
-          ah[nxt] = *reinterpret_cast<const u32x4*>(ab + aoffs[1][0]);
-          al[nxt] = *reinterpret_cast<const u32x4*>(ab + aoffs[1][1]);
-        }
-        if (ks == 0 && mt == (TM > 1 ? TM - 2 : 0)) {
-#pragma unroll
-          for (int nt = 0; nt < TN; ++nt) {
-            bh[1][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 1024);
-            bl[1][nt] = *reinterpret_cast<const u32x4*>(bb + nt * 4096 + 2048 + 1024);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);             // the prefetches issue BEFORE this m-tile's MFMAs (the scheduler sinks them to their uses otherwise)
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al[cur]), __builtin_bit_cast(f16x8, bh[ks][nt]),
-                                                               acc[mt][nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur]), __builtin_bit_cast(f16x8, bl[ks][nt]),
-                                                               acc[mt][nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah[cur]), __builtin_bit_cast(f16x8, bh[ks][nt]),
-                                                               acc[mt][nt], 0, 0, 0);
-      }
-    }
-  };
-
   // ---- main loop. Virtual iterations -DA .. -1 fill the rings; iteration it: wait until this wave's pieces of iteration it have
   //      landed (younger ones stay in flight), barrier (everyone's pieces landed AND everyone is done reading the slots of it - 1),
   //      refill those slots (B of it + DB, A of it + DA), compute ----
@@ -467,7 +490,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
     xs_barrier();
     issue_b();
     issue_a();
-    if (KG == 1 || KG * it + kg < nchunk) compute(abase + a_rd * A_SLOT, bbase + b_rd * B_SLOT);
+    if (KG == 1 || KG * it + kg < nchunk) xs_compute_chunk<TM, TN, 4096>(acc, abase + a_rd * A_SLOT, bbase + b_rd * B_SLOT, aoffs);
     a_rd = a_rd + 1 == SA ? 0 : a_rd + 1;
     b_rd = b_rd + 1 == SB ? 0 : b_rd + 1;
   }
@@ -504,6 +527,163 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
   // ---- epilogue (per wave, no further workgroup synchronisation): TM scratch tiles per wave behind the reduce buffer ----
   float* scratch = reinterpret_cast<float*>(xs_smem + (KG - 1) * NWG * TM * TN * 4096 + wg * (TM * 4096));
   const float amax = xs_epilogue<TM, TN>(acc, scratch, p, epi, m0 + wm * TM * 32, nt0 + wn * TN, lane, rv0);
+  if (p.out_fmt == 2 && p.flag && !(amax <= CGG_X3A_MAX)) atomicOr(p.flag, 1);
+}
+
+// ---- 3 x 3, stride 1, pad 1 with the A operand RESIDENT as a halo patch. The ring kernel above treats the filter tap as part of
+// K and fetches a tile's rows from L2 once per tap: nine LDS-DMA trips for bytes of which 8 / 9 are already on the chip. Here a
+// workgroup owns a TH x TW patch of output pixels of one image (BM = TH TW) and brings the (TH + 2) x (TW + 2) input pixels x C
+// channels into LDS ONCE; the K loop streams only the weight image through an SB-slot ring, and tap (ky, kx) reads its A fragments
+// from the patch at halo pixel (dy + ky, dx + kx).
+//   * LDS image of the patch: CCH = C / 32 planes (one per 32-channel chunk) of HPP halo pixels x 128 bytes, halo pixel
+//     hp = ry (TW + 2) + cx, HPP = the pixel count rounded up to the 8 pixels of one LDS-DMA instruction. Pixels outside the map
+//     (the padding ring, and patches that hang over the right / bottom edge) go to the out-of-range offset and arrive as zeros.
+//   * swizzle: the 16-byte unit index of a pixel's line is XORed with key = ((cx + (TW == 8 ? 8 ry : 0)) >> 1) & 7 -- on the
+//     source side of the DMA and on the fragment read. A ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27},
+//     {4-11, 16-19, 28-31} (+ 32); the pitch TW + 2 is even, so a pixel's half of the 256-byte bank row is cx & 1 and its slot
+//     there unit ^ key. TW = 16: a group holds columns kx + {0-3, 12-15} of one patch row and kx + {4-11} of the next: cx mod 16
+//     takes 16 different values, so (cx & 1, key) does. TW = 8: four patch rows per m-tile, a group holds columns kx + {0-3} of
+//     rows r, r + 3 and kx + {4-7} of r + 1, r + 2 (or the complement): cx + 8 ry mod 16 takes 16 different values. No conflicts
+//     for any tap.
+//   * accumulation order = the ring kernel's: tap-major, 32-channel chunks inside a tap, xs_compute_chunk per chunk; KG = 2 keeps
+//     the even and the odd chunks' sums in two accumulator sets and adds the odd one to the even one at the end, which is what the
+//     ring kernel's two k-groups compute. An instance uses the k-group count the shape rule chose for the ResNet shape it serves
+//     (layer1: 1, layer2 / layer3: 2), so those launches are bit-identical to the ring kernel's. Epilogue = xs_epilogue with the
+//     patch row map (no residual: the host keeps those launches on the ring kernel).
+//   * an iteration (one barrier) consumes CPI = 1 or 2 chunks from one ring slot.
+template <int TH, int TW, int CCH, int TM, int TN, int WM, int WN, int SB, int CPI, int KG>
+__global__ __launch_bounds__(64 * WM * WN) void cgg_conv3x3_halo_kernel(const XsArgs p) {
+  constexpr int NW = WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
+  constexpr int P = TW + 2, HP = (TH + 2) * P, HPP = (HP + 7) / 8 * 8, PLANE = HPP * 128;
+  constexpr int NAP = CCH * (HPP / 8), NAI = (NAP + NW - 1) / NW;       // LDS-DMA instructions of the patch: all / per wave
+  constexpr int B_SLOT = CPI * BN * 128, NB = CPI * BN / 8 / NW, DB = SB - 1;     // a ring slot = the CPI chunks of one iteration
+  constexpr int MT = (32 / TW) * P * 128;                              // an m-tile = 32 / TW patch rows
+  constexpr int NCHUNK = 9 * CCH, NITER = NCHUNK / CPI;
+  constexpr int WAIT = (DB - 1) * NB;                                  // the patch is older than every B piece
+  static_assert(TH * TW == BM && (TW == 8 || TW == 16) && TH % (32 / TW) == 0, "patch = the workgroup's rows, whole m-tiles");
+  static_assert(BN % (8 * NW) == 0 && SB >= 2, "B pieces split evenly over the waves");
+  static_assert(CCH % CPI == 0, "the chunks of an iteration lie inside one filter tap");
+  static_assert((CPI == 1 || CPI == 2) && (KG == 1 || KG == 2) && NCHUNK % 2 == 0, "chunk c accumulates into set c % KG");
+  static_assert(CCH * PLANE + SB * B_SLOT >= NW * TM * 4096, "LDS: patch + ring must cover the epilogue scratch");
+  static_assert(NAI + DB * NB < 64, "vmcnt counts to 63");
+  extern __shared__ __attribute__((aligned(16))) unsigned char xs_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 31, hi5 = lane >> 5;
+  const int wm = wave / WN, wn = wave - wm * WN;
+  const int H = p.cv.H, W = p.cv.W;
+  const int ptx = (W + TW - 1) / TW, pty = (H + TH - 1) / TH;
+  const int bid = cgg_xcd_remap(blockIdx.x, gridDim.x);
+  const int tile_m = bid / p.tiles_n, tile_n = bid - tile_m * p.tiles_n;
+  const int img = tile_m / (ptx * pty), pr = tile_m - img * (ptx * pty);
+  const int py = pr / ptx, px = pr - py * ptx;
+  const int y0 = py * TH, x0 = px * TW, nt0 = tile_n * (BN / 32);
+  const int KS = p.K >> 4;
+
+  // ---- the patch: piece q = wave + NW i covers halo pixels 8 (q % (HPP / 8)) .. + 7 of plane q / (HPP / 8) ----
+  const __amdgpu_buffer_rsrc_t arsrc = xs_rsrc(p.A, p.a_bytes);
+#pragma unroll
+  for (int i = 0; i < NAI; ++i) {
+    const int q = wave + NW * i;
+    if (q < NAP) {                                               // wave-uniform
+      const int c = q / (HPP / 8), hp = (q - c * (HPP / 8)) * 8 + (lane >> 3);
+      const int ry = hp / P, cx = hp - ry * P;
+      const int key = ((cx + (TW == 8 ? 8 * ry : 0)) >> 1) & 7;
+      const int iy = y0 - 1 + ry, ix = x0 - 1 + cx;
+      const bool ok = hp < HP && iy >= 0 && iy < H && ix >= 0 && ix < W;
+      const uint32_t off = ok ? (uint32_t)(((img * H + iy) * W + ix) * (CCH * 32) + c * 32) * 4u + 16u * ((lane & 7) ^ key) : XS_OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(arsrc, (xs_lds_t)(xs_smem + q * 1024), 16, (int)off, 0, 0, 0);
+    }
+  }
+  // ---- B pieces, as in the ring kernel: piece q = wave + NW i of a chunk's [n-tile][hi | lo][k-step] x 1 KiB ----
+  const __amdgpu_buffer_rsrc_t brsrc = xs_rsrc(p.w.hi, p.w_bytes);
+  uint32_t boff[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int b = (wave + NW * i) % (BN / 8);
+    const int nt = b >> 2, piece = (b >> 1) & 1, ks = b & 1;
+    const int ntc = nt0 + nt < p.n_tiles32 ? nt0 + nt : p.n_tiles32 - 1;
+    boff[i] = (uint32_t)(((piece * p.n_tiles32 + ntc) * KS + ks) * 64 + lane) * 16u;
+  }
+  int b_ld = 0, b_c = 0;
+  auto issue_b = [&]() {                                           // past the last chunk: re-read it into a slot nobody reads again
+    unsigned char* sbase = xs_smem + CCH * PLANE + b_ld * B_SLOT;
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(brsrc, (xs_lds_t)(sbase + (wave + NW * i) * 1024), 16, (int)boff[i],
+                                               (b_c + (wave + NW * i) / (BN / 8)) * 2048, 0, 0);
+    b_c = b_c + CPI < NCHUNK ? b_c + CPI : b_c;
+    b_ld = b_ld + 1 == SB ? 0 : b_ld + 1;
+  };
+#pragma unroll
+  for (int t = 0; t < DB; ++t) issue_b();
+
+  f32x16 acc[TM][TN], acc1[TM][TN];                               // acc1: the odd chunks' sums with KG = 2
+#pragma unroll
+  for (int a = 0; a < TM; ++a)
+#pragma unroll
+    for (int b = 0; b < TN; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = acc1[a][b][r] = 0.f;
+
+  // fragment reads: lane j of m-tile mt is patch pixel (dy0 + (32 / TW) mt, dx); tap (ky, kx) shifts the halo pixel by ky P + kx
+  const int r0 = wm * TM * 32 + j, dy0 = r0 / TW, dx = r0 - dy0 * TW;
+  const unsigned char* abase = xs_smem + (dy0 * P + dx) * 128;
+  const unsigned char* bbase = xs_smem + CCH * PLANE + wn * TN * 4096 + lane * 16;
+
+  XsEpi epi = xs_epi_setup(p, 0, lane);
+  epi.pb = img * H * W;
+  epi.y0 = y0;
+  epi.x0 = x0;
+  const u32x4 rv0[4] = {};
+  int cc = 0, ky = 0, kx = 0, b_rd = 0;
+  // one iteration = CPI chunks; its even / odd chunk accumulates into ae / ao
+  auto iteration = [&](f32x16 (&ae)[TM][TN], f32x16 (&ao)[TM][TN]) {
+    xs_wait_vmcnt<WAIT>();
+    xs_barrier();
+    issue_b();
+    const int key = (((dx + kx) >> 1) + (TW == 8 ? 4 * ((dy0 + ky) & 1) : 0)) & 7;
+    int aoffs[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int pc = 0; pc < 2; ++pc) aoffs[ks][pc] = ((4 * ks + 2 * hi5 + pc) ^ key) * 16;
+    xs_compute_chunk<TM, TN, MT>(ae, abase + cc * PLANE + (ky * P + kx) * 128, bbase + b_rd * B_SLOT, aoffs);
+    if constexpr (CPI == 2)
+      xs_compute_chunk<TM, TN, MT>(ao, abase + (cc + 1) * PLANE + (ky * P + kx) * 128, bbase + b_rd * B_SLOT + BN * 128, aoffs);
+    b_rd = b_rd + 1 == SB ? 0 : b_rd + 1;
+    if ((cc += CPI) == CCH) {
+      cc = 0;
+      if (++kx == 3) {
+        kx = 0;
+        ++ky;
+      }
+    }
+  };
+  for (int it = 0; it < NITER; it += (KG == 2 && CPI == 1) ? 2 : 1) {
+    if constexpr (KG == 1) {
+      iteration(acc, acc);
+    } else if constexpr (CPI == 2) {
+      iteration(acc, acc1);
+    } else {
+      iteration(acc, acc);
+      iteration(acc1, acc1);
+    }
+  }
+  // the ring kernel's two k-groups: group 0 takes the even chunks, group 1 the odd ones, and group 0 adds group 1's sums
+  if constexpr (KG == 2) {
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+      for (int b = 0; b < TN; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[a][b][r] += acc1[a][b][r];
+  }
+  xs_wait_vmcnt<0>();              // the run-ahead pieces must land before patch and ring become epilogue scratch
+  xs_barrier();
+
+  float* scratch = reinterpret_cast<float*>(xs_smem + wave * (TM * 4096));
+  const float amax = xs_epilogue<TM, TN, TW>(acc, scratch, p, epi, wm * TM * 32, nt0 + wn * TN, lane, rv0);
   if (p.out_fmt == 2 && p.flag && !(amax <= CGG_X3A_MAX)) atomicOr(p.flag, 1);
 }
 
@@ -567,6 +747,42 @@ static int xs_go(const XsArgs& a, hipStream_t stream, const char* who) {
   return CGG_OK;
 }
 
+template <int TH, int TW, int CCH, int TM, int TN, int WM, int WN, int SB, int CPI, int KG>
+static int xs_go_halo(const XsArgs& a, hipStream_t stream, const char* who) {
+  constexpr int BN = 32 * TN * WN;
+  constexpr int LDS = CCH * (((TH + 2) * (TW + 2) + 7) / 8 * 8) * 128 + SB * CPI * BN * 128;
+  CGG_RAISE_LDS((cgg_conv3x3_halo_kernel<TH, TW, CCH, TM, TN, WM, WN, SB, CPI, KG>), LDS, who);
+  XsArgs b = a;
+  b.tiles_n = (a.N + BN - 1) / BN;
+  const int images = a.M / (a.cv.H * a.cv.W);
+  const long long patches = (long long)images * ((a.cv.H + TH - 1) / TH) * ((a.cv.W + TW - 1) / TW);
+  const dim3 grid((unsigned)(patches * b.tiles_n)), block(64 * WM * WN);
+  hipLaunchKernelGGL((cgg_conv3x3_halo_kernel<TH, TW, CCH, TM, TN, WM, WN, SB, CPI, KG>), grid, block, LDS, stream, b);
+  return CGG_OK;
+}
+
+// The halo kernel's instance by channel count, 8 waves each (template arguments: TH, TW, C / 32, TM, TN, WM, WN, B slots, chunks
+// per iteration, k-groups), picked from a stand-alone sweep on MI355X of patch 4 x 16 / 8 x 16, 4 / 8 waves, 2 / 3 slots, 1 / 2 chunks per
+// iteration (all within 10 % of each other: the launch is bound by its L2 -> LDS bytes, not by the loop's shape):
+//   C =  64: 8 x 16 patch x  64 columns, waves 4 x 2 (32 x 32 each), 2 slots of 2 chunks:  46 + 32 =  78 KiB, 2 workgroups per CU
+//   C = 128: 8 x 16 patch x 128 columns, waves 2 x 4 (64 x 32 each), 2 slots of 2 chunks:  92 + 64 = 156 KiB
+//   C = 256: 8 x  8 patch x 128 columns, waves 2 x 4 (32 x 32 each), 3 slots of 1 chunk:  104 + 48 = 152 KiB
+// k-groups (order of the sums only): 1 for C = 64, 2 for C = 128 / 256 -- what the shape rule picked for layer1 / layer2 / layer3.
+static int xs_launch_halo(const XsArgs& x, hipStream_t stream, const char* who) {
+  switch (x.cv.C) {
+    case 64: return xs_go_halo<8, 16, 2, 1, 1, 4, 2, 2, 2, 1>(x, stream, who);
+    case 128: return xs_go_halo<8, 16, 4, 2, 1, 2, 4, 2, 2, 2>(x, stream, who);
+    default: return xs_go_halo<8, 8, 8, 1, 1, 2, 4, 3, 1, 2>(x, stream, who);
+  }
+}
+
+// Shapes for which the halo kernel is the default (per-launch A/B on MI355X, profiles/conv3x3_halo_launches.txt): C = 64 and 128
+// (ResNet layer1 / layer2, inside the step: 47 -> 41 us, fastest launch 44 -> 32 us; 40 -> 32 us); C = 256 only while the whole
+// problem is one round of workgroups (layer3, M = 8192: 42 -> 39.5 us). With C = 256 the patch leaves room for 64 rows only, the
+// weight stream per MFMA doubles against the 128-row patches, and from two rounds on the 256-row ring tiles win: the FPN's 3 x 3
+// at M = 32768 / 131072 takes 138 / 541 us here against 105 / 383 us there.
+static bool xs_halo_pays(int C, int N, int M) { return C < 256 || (long long)((M + 63) / 64) * ((N + 127) / 128) <= 256; }
+
 // tile configurations X(id, TM, TN, WM, WN, KG, SA, SB): workgroup tile (32 TM WM) x (32 TN WN), KG k-groups, SA / SB ring slots
 //    0: 256 x 256, 8 waves, A 3 / B 2 slots (160 KiB)     5: 64 x 128, 4 waves, 4 slots (96 KiB)          10: 128 x 128, 2 k-groups (8 waves), 2 slots (128 KiB)
 //    1: 256 x 128, 8 waves, 3 slots (144 KiB)             6: 128 x 64, 4 waves, 4 slots (96 KiB)          11: 64 x 128, 2 k-groups, 3 slots (144 KiB)
@@ -574,12 +790,15 @@ static int xs_go(const XsArgs& a, hipStream_t stream, const char* who) {
 //    3: 128 x 128, 4 waves, 4 slots (128 KiB)             8: 256 x 64, 4 waves, 3 slots (120 KiB)         13: 64 x 64, 4 waves, 2 slots (32 KiB)
 //    4: 128 x 128, 4 waves, 2 slots (64 KiB)              9: 256 x 256, 8 waves, 2 slots (128 KiB)        14: 128 x 64, 4 waves, 2 slots (48 KiB)
 //   16: 64 x 64, 2 k-groups, 2 slots (64 KiB)            17: 64 x 128, 2 k-groups, 2 slots (96 KiB)      15: 64 x 128, 4 waves, 2 slots (48 KiB)
+//   18 (XS_HALO_CFG) is not a row of this table: the halo kernel for 3 x 3 / stride 1 / pad 1, instance by channel count
+//   (xs_launch_halo above); forced for a call it does not serve it fails with CGG_EUNSUPPORTED
 #define XS_CONFIGS(X)                                                                                                              \
   X(0, 4, 2, 2, 4, 1, 3, 2) X(1, 2, 2, 4, 2, 1, 3, 3) X(2, 2, 2, 2, 4, 1, 3, 3) X(3, 2, 2, 2, 2, 1, 4, 4) X(4, 2, 2, 2, 2, 1, 2, 2)   \
   X(5, 1, 2, 2, 2, 1, 4, 4) X(6, 2, 1, 2, 2, 1, 4, 4) X(7, 1, 1, 2, 2, 1, 4, 4) X(8, 4, 1, 2, 2, 1, 3, 3) X(9, 4, 2, 2, 4, 1, 2, 2)   \
   X(10, 2, 2, 2, 2, 2, 2, 2) X(11, 1, 2, 2, 2, 2, 3, 3) X(12, 1, 1, 2, 2, 2, 4, 4) X(13, 1, 1, 2, 2, 1, 2, 2)                      \
   X(14, 2, 1, 2, 2, 1, 2, 2) X(15, 1, 2, 2, 2, 1, 2, 2) X(16, 1, 1, 2, 2, 2, 2, 2) X(17, 1, 2, 2, 2, 2, 2, 2)
 #define XS_NCFG 18
+#define XS_HALO_CFG 18           // not a ring configuration: cgg_conv3x3_halo_kernel, instance by channel count (xs_launch_halo)
 static const int xs_bm[XS_NCFG] = {256, 256, 128, 128, 128, 64, 128, 64, 256, 256, 128, 64, 64, 64, 128, 64, 64, 64};
 static const int xs_bn[XS_NCFG] = {256, 128, 256, 128, 128, 128, 64, 64, 64, 256, 128, 128, 64, 64, 64, 128, 64, 128};
 
@@ -656,8 +875,21 @@ static int xs_launch(bool conv, const char* who, const void* a, int lda, const v
   x.a_bytes = (uint32_t)a_bytes;
   x.w_bytes = (uint32_t)(2ull * ((N + 31) / 32) * (K / 16) * 64 * 16);
   x.flag = out_fmt == 2 ? cgg_x3_overflow_flag_ptr() : nullptr;
-  CGG_REQUIRE(force_cfg < XS_NCFG, CGG_EINVAL, "%s: tile configuration %d (0 .. %d, or -1 = by shape)", who, force_cfg, XS_NCFG - 1);
-  const int cfg = force_cfg >= 0 ? force_cfg : xs_pick(M, N, K, res != nullptr);
+  CGG_REQUIRE(force_cfg <= XS_HALO_CFG, CGG_EINVAL, "%s: tile configuration %d (0 .. %d, or -1 = by shape)", who, force_cfg,
+              XS_HALO_CFG);
+  // the halo kernel: 3 x 3, stride 1, pad 1, C = 64 / 128 / 256, no residual (those launches stay on the ring kernel)
+  const bool halo_ok = conv && cv.taps == 9 && cv.KW == 3 && cv.stride == 1 && cv.pad == 1 && (cv.C == 64 || cv.C == 128 || cv.C == 256) &&
+                       !res;
+  CGG_REQUIRE(force_cfg != XS_HALO_CFG || halo_ok, CGG_EUNSUPPORTED,
+              "%s: tile configuration %d (halo patch) serves 3 x 3 / stride 1 / pad 1 convolutions of 64, 128 or 256 channels without residual",
+              who, XS_HALO_CFG);
+  const int cfg = force_cfg >= 0 ? force_cfg : (halo_ok && xs_halo_pays(cv.C, N, M)) ? XS_HALO_CFG : xs_pick(M, N, K, res != nullptr);
+  if (cfg == XS_HALO_CFG) {
+    const int rc = xs_launch_halo(x, (hipStream_t)stream, who);
+    if (rc != CGG_OK) return rc;
+    CGG_CHECK_LAUNCH(who);
+    return CGG_OK;
+  }
   int rc = CGG_OK;
 #define XS_CASE(ID, TM, TN, WM, WN, KG, SA, SB)                                                 \
   case ID:                                                                                      \

@@ -692,6 +692,9 @@ int cgg_conv_x3_nhwc(const float* x, const void* w_x3, const float* bias, const 
  *   cgg_gemm_x3s_cfg / cgg_conv_x3s_nhwc_cfg: the same calls with the tile configuration (0 .. 17; -1 = by shape) as an ARGUMENT:
  *                      tests sweep every instantiation, benches compare them. (Round 4's process-global
  *                      cgg_gemm_x3s_force_config is gone: the library keeps no mutable state besides the overflow flag word.)
+ *                      Configuration 18 is the halo-patch kernel of cgg_conv_x3s_nhwc for 3 x 3 / stride 1 / pad 1 convolutions
+ *                      of 64, 128 or 256 channels without residual (the default for the ResNet's); forced for any other call
+ *                      it returns CGG_EUNSUPPORTED.
  * Same reference call sites as cgg_gemm_x3 / cgg_conv_x3_nhwc above.                                                   */
 int cgg_gemm_x3s(const void* a_x3a, int lda, const void* w_x3, const float* bias, const void* res, int ldr, int res_fmt,
                  int res_mod, void* out, int ldc, int out_fmt, int M, int N, int K, int relu, cgg_stream_t stream);
