@@ -57,10 +57,12 @@ __global__ __launch_bounds__(256) void cgg_ce_rows_fwd_kernel(const T* __restric
 #pragma unroll
     for (int e = 1; e < V; ++e) cm = fmaxf(cm, v[e]);
     const float mn = fmaxf(m, cm);
+    // every column so far is -inf: an empty contribution (s stays 0), not exp(-inf - -inf) = NaN that a later pass would keep
+    const float ms = mn == -INFINITY ? 0.f : mn;
     float add = 0.f;
 #pragma unroll
-    for (int e = 0; e < V; ++e) add += __expf(v[e] - mn);
-    s = s * __expf(m - mn) + add;
+    for (int e = 0; e < V; ++e) add += __expf(v[e] - ms);
+    s = s * __expf(m - ms) + add;
     m = mn;
   }
   // combine (m, s) over the wavefront, then over the 4 wavefronts

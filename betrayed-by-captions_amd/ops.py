@@ -802,7 +802,8 @@ def _ce_dtype(logits):
 
 
 def ce_rows_forward(logits, target, ignore_index):
-    """logits (M, N) f32 / bf16 (row stride >= N), target (M,) int64 -> (loss (M,), lse (M,)) f32."""
+    """logits (M, N) f32 / bf16 (row stride >= N), target (M,) int64 -> (loss (M,), lse (M,)) f32.
+    Columns of -inf count as probability 0, as in F.cross_entropy (a row of nothing but -inf is NaN there and here)."""
     M, N = logits.shape
     if logits.stride(1) != 1:
         raise CggError('ce_rows_forward: rows must be contiguous')
