@@ -23,10 +23,6 @@
 // build-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 #include "cgg_common.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t bn_u32x4;
-typedef __attribute__((ext_vector_type(2))) float bn_f2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bn_bf2;
-
 #define BN_TH 8                 // tile height (output pixels)
 #define BN_TW 16                // tile width
 #define BN_HW (BN_TW + 2)       // halo width 18
@@ -35,22 +31,22 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bn_bf2;
 #define BN_PF 4                 // global prefetch distance (k-steps)
 
 __device__ __forceinline__ uint32_t bn_pk(float a, float b) {
-  const bn_f2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bn_bf2));
+  const f32x2 pr = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
 }
 
 // lanes j, j ^ 1 hold neighbouring columns: they swap one value per register pair; afterwards the even lane owns row(2 rp), the odd
 // lane row(2 rp + 1), each with the bf16 pair of columns (j & ~1, (j & ~1) + 1)
 __device__ __forceinline__ uint32_t bn_pair(float v0, float v1, int odd, uint32_t rot) {
   const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-  const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));
+  const float recv = cgg_lane_xor1(sent);
   const uint32_t w = bn_pk(kept, recv);
   return __builtin_amdgcn_alignbit(w, w, rot);
 }
 
-__global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* __restrict__ x, const bn_u32x4* __restrict__ w1,
-                                                              const float* __restrict__ b1, const bn_u32x4* __restrict__ w2,
-                                                              const float* __restrict__ b2, const bn_u32x4* __restrict__ w3,
+__global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* __restrict__ x, const u32x4* __restrict__ w1,
+                                                              const float* __restrict__ b1, const u32x4* __restrict__ w2,
+                                                              const float* __restrict__ b2, const u32x4* __restrict__ w3,
                                                               const float* __restrict__ b3, uint16_t* __restrict__ y, int H, int W) {
   __shared__ __attribute__((aligned(16))) uint16_t t1[192 * BN_TS];          // 27 KiB
   __shared__ __attribute__((aligned(16))) uint16_t t2[4][32 * BN_TS];        // 18 KiB
@@ -65,7 +61,7 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
   // ---------------- phase 1: t1 on the halo ----------------
   {
     const int nt = wave & 1;
-    const bn_u32x4* wb = w1 + (size_t)nt * 16 * 64 + lane;
+    const u32x4* wb = w1 + (size_t)nt * 16 * 64 + lane;
     const uint16_t* arow[3];
     bool aval[3];
 #pragma unroll
@@ -81,12 +77,12 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
     for (int m = 0; m < 3; ++m)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
-    bn_u32x4 qa[3][BN_PF], qb[BN_PF];
+    u32x4 qa[3][BN_PF], qb[BN_PF];
 #pragma unroll
     for (int s = 0; s < BN_PF; ++s) {
       qb[s] = wb[s * 64];
 #pragma unroll
-      for (int m = 0; m < 3; ++m) qa[m][s] = *reinterpret_cast<const bn_u32x4*>(arow[m] + 16 * s);
+      for (int m = 0; m < 3; ++m) qa[m][s] = *reinterpret_cast<const u32x4*>(arow[m] + 16 * s);
     }
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
       if (s + BN_PF < 16) {
         qb[s % BN_PF] = wb[(s + BN_PF) * 64];
 #pragma unroll
-        for (int m = 0; m < 3; ++m) qa[m][s % BN_PF] = *reinterpret_cast<const bn_u32x4*>(arow[m] + 16 * (s + BN_PF));
+        for (int m = 0; m < 3; ++m) qa[m][s % BN_PF] = *reinterpret_cast<const u32x4*>(arow[m] + 16 * (s + BN_PF));
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -125,27 +121,27 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
   {
     const int r = j >> 4, c = j & 15;                                      // pixel of the m-tile this lane feeds as an A row
     const uint16_t* abase = t1 + ((2 * wave + r) * BN_HW + c) * BN_TS + 8 * hi5;
-    const bn_u32x4* wb0 = w2 + lane;
-    const bn_u32x4* wb1 = w2 + (size_t)36 * 64 + lane;
+    const u32x4* wb0 = w2 + lane;
+    const u32x4* wb1 = w2 + (size_t)36 * 64 + lane;
     f32x16 acc[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[n][q] = 0.f;
-    bn_u32x4 q0[BN_PF], q1[BN_PF];
+    u32x4 q0[BN_PF], q1[BN_PF];
 #pragma unroll
     for (int s = 0; s < BN_PF; ++s) {
       q0[s] = wb0[s * 64];
       q1[s] = wb1[s * 64];
     }
-    bn_u32x4 ua = *reinterpret_cast<const bn_u32x4*>(abase);
+    u32x4 ua = *reinterpret_cast<const u32x4*>(abase);
 #pragma unroll
     for (int s = 0; s < 36; ++s) {
       const bf16x8 va = __builtin_bit_cast(bf16x8, ua);
       const bf16x8 vb0 = __builtin_bit_cast(bf16x8, q0[s % BN_PF]), vb1 = __builtin_bit_cast(bf16x8, q1[s % BN_PF]);
       if (s + 1 < 36) {
         const int tap = (s + 1) >> 2, cb = (s + 1) & 3;
-        ua = *reinterpret_cast<const bn_u32x4*>(abase + ((tap / 3) * BN_HW + tap % 3) * BN_TS + 16 * cb);
+        ua = *reinterpret_cast<const u32x4*>(abase + ((tap / 3) * BN_HW + tap % 3) * BN_TS + 16 * cb);
       }
       if (s + BN_PF < 36) {
         q0[s % BN_PF] = wb0[(s + BN_PF) * 64];
@@ -172,9 +168,9 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
   // ---------------- phase 3: 64 -> 256, + b3 + x, ReLU ----------------
   {
     const uint16_t* abase = &t2[wave][j * BN_TS + 8 * hi5];
-    bn_u32x4 ua[4];
+    u32x4 ua[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) ua[s] = *reinterpret_cast<const bn_u32x4*>(abase + 16 * s);
+    for (int s = 0; s < 4; ++s) ua[s] = *reinterpret_cast<const u32x4*>(abase + 16 * s);
 #pragma unroll 1
     for (int h2 = 0; h2 < 2; ++h2) {
       f32x16 acc[4];
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
-      bn_u32x4 qw[4][4];
+      u32x4 qw[4][4];
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -213,8 +209,8 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
           // after the swap: even lane = row(2 rp): columns (ch, ch + 1) from tile 0 and (ch + 2, ch + 3) from tile 1
           const float k0 = odd ? a1 : a0, s0 = odd ? a0 : a1;
           const float k1 = odd ? c1 : c0, s1 = odd ? c0 : c1;
-          const float v0 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s0), 0xB1, 0xf, 0xf, true));
-          const float v1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s1), 0xB1, 0xf, 0xf, true));
+          const float v0 = cgg_lane_xor1(s0);
+          const float v1 = cgg_lane_xor1(s1);
           // even lane: (k0, v0) = columns (ch, ch + 1); odd lane: (v0, k0)
           const float e0 = odd ? v0 : k0, e1 = odd ? k0 : v0, e2 = odd ? v1 : k1, e3 = odd ? k1 : v1;
           const uint32_t o0 = bn_pk(fmaxf(e0 + r00, 0.f), fmaxf(e1 + r01, 0.f));
@@ -238,7 +234,7 @@ extern "C" int cgg_bottleneck64_bf16(const void* x, const void* w1_packed, const
   CGG_REQUIRE((long long)B * H * W * 256 < (1ll << 31), CGG_EUNSUPPORTED, "cgg_bottleneck64_bf16: activation too large");
   const int nblk = B * (H / BN_TH) * (W / BN_TW);
   hipLaunchKernelGGL(cgg_bottleneck64_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-                     (const bn_u32x4*)w1_packed, b1, (const bn_u32x4*)w2_packed, b2, (const bn_u32x4*)w3_packed, b3, (uint16_t*)y, H, W);
+                     (const u32x4*)w1_packed, b1, (const u32x4*)w2_packed, b2, (const u32x4*)w3_packed, b3, (uint16_t*)y, H, W);
   CGG_CHECK_LAUNCH("cgg_bottleneck64_bf16");
   return CGG_OK;
 }

@@ -10,8 +10,58 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;  // 4 x bf16 MFMA operand
 
 #define CGG_WAVE 64
+
+// ---- wave primitives ----------------------------------------------------------------------------
+// One DPP move: every lane reads `v` from the lane that control CTRL names within its row of 16 (all rows
+// and banks enabled; a lane whose source is invalid keeps 0). 0xB1 = quad_perm [1, 0, 3, 2].
+template <int CTRL>
+__device__ __forceinline__ int cgg_dpp(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
+template <int CTRL>
+__device__ __forceinline__ float cgg_dpp(float v) {
+  return __int_as_float(cgg_dpp<CTRL>(__float_as_int(v)));
+}
+
+// the value held by lane ^ 1, by one DPP move
+__device__ __forceinline__ float cgg_lane_xor1(float x) { return cgg_dpp<0xB1>(x); }
+__device__ __forceinline__ uint32_t cgg_lane_xor1(uint32_t x) { return (uint32_t)cgg_dpp<0xB1>((int)x); }
+
+// Sum over each row of 16 lanes by four DPP moves, in this order: lane ^ 1 (0xB1), lane ^ 2 (0x4E),
+// row_half_mirror (0x141), row_mirror (0x140). Every lane ends with its row's sum.
+__device__ __forceinline__ float cgg_row16_sum(float v) {
+  v += cgg_dpp<0xB1>(v);
+  v += cgg_dpp<0x4E>(v);
+  v += cgg_dpp<0x141>(v);
+  v += cgg_dpp<0x140>(v);
+  return v;
+}
+
+// Butterfly over each aligned group of W lanes (W = 64: the wave): __shfl_xor steps W / 2, W / 4, ..., 1.
+// Every lane ends with the sum / maximum of its group.
+template <int W = CGG_WAVE>
+__device__ __forceinline__ float cgg_wave_sum(float v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+template <int W = CGG_WAVE>
+__device__ __forceinline__ float cgg_wave_max(float v) {
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// raw buffer descriptor over [p, p + bytes): out-of-range loads return 0, out-of-range stores are dropped
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cgg_buffer_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
 
 // ---- error reporting (thread-local, no exceptions across the ABI) -------------------------------
 void cgg_set_error(const char* fmt, ...);

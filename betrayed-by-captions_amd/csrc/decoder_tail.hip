@@ -12,8 +12,6 @@
 // structure; the f32-MFMA launch chain it replaces ran 123 x 17 us per forward.
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define DT_C 256
 #define DT_STEPS (DT_C / 16)
 
@@ -249,7 +247,7 @@ __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
 // view of a packed 256-column-tile weight: bf16 image or x3 image
 static inline CggX3W dt_view(bool x3, const void* p, int N, int K) {
   if (x3) return cgg_x3_view(p, N, K);
-  return CggX3W{(const cgg_u32x4*)p, nullptr, nullptr};
+  return CggX3W{(const u32x4*)p, nullptr, nullptr};
 }
 
 static int dt_tail_launch(bool x3, const char* who, const float* planes, int nsum, int64_t plane_stride, int ld,

@@ -23,10 +23,6 @@
 //  a[0:63] around every GEMM-1 block: 384 v_accvgpr moves per chunk and wave, a third of the MFMA time.)
 #include "cgg_common.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t ef_u32x4;
-typedef __attribute__((ext_vector_type(2))) float ef_f2;
-typedef __attribute__((ext_vector_type(2))) __bf16 ef_bf2;
-
 #define EF_C 256
 #define EF_STEPS 16
 #define EF_RB 64               // rows per workgroup
@@ -37,17 +33,8 @@ typedef __attribute__((ext_vector_type(2))) __bf16 ef_bf2;
 static_assert(EF_STEPS % EF_PF == 0, "the B queue index s % EF_PF must line up across blocks");
 
 __device__ __forceinline__ uint32_t ef_pk(float a, float b) {            // v_cvt_pk_bf16_f32
-  const ef_f2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, ef_bf2));
-}
-
-// sum over the 16 lanes of a DPP row, result in every lane: quad xor 1, quad xor 2, row_half_mirror, row_mirror
-__device__ __forceinline__ float ef_row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true));
-  return v;
+  const f32x2 pr = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
 }
 
 // One 64 x 64 block of C += A B^T over 16 k-steps. A-fragment images of the two 32-row m-tiles in LDS (a0 / a1 = lane
@@ -58,14 +45,14 @@ __device__ __forceinline__ float ef_row16_sum(float v) {
 // and the L2 latency is paid at every k-step.
 // XS = true: the image is the row image, swizzled by the whole k-step (slot ^ s): a0 / a1 are the m-tile bases and xl the lane.
 template <bool XS>
-__device__ __forceinline__ void ef_block(f32x16 (&acc)[2][2], const ef_u32x4* __restrict__ a0, const ef_u32x4* __restrict__ a1,
-                                         const ef_u32x4* __restrict__ a0o, const ef_u32x4* __restrict__ a1o, int xl,
-                                         ef_u32x4 (&q0)[EF_PF], ef_u32x4 (&q1)[EF_PF], const ef_u32x4* __restrict__ b0,
-                                         const ef_u32x4* __restrict__ b1, const ef_u32x4* __restrict__ nb0,
-                                         const ef_u32x4* __restrict__ nb1) {
+__device__ __forceinline__ void ef_block(f32x16 (&acc)[2][2], const u32x4* __restrict__ a0, const u32x4* __restrict__ a1,
+                                         const u32x4* __restrict__ a0o, const u32x4* __restrict__ a1o, int xl,
+                                         u32x4 (&q0)[EF_PF], u32x4 (&q1)[EF_PF], const u32x4* __restrict__ b0,
+                                         const u32x4* __restrict__ b1, const u32x4* __restrict__ nb0,
+                                         const u32x4* __restrict__ nb1) {
   if constexpr (XS) asm volatile("" : "+v"(xl));       // keep the 15 swizzled lane offsets out of the chunk loop's live set
   // A fragments run EF_PA k-steps ahead of their MFMAs (LDS serves 8 waves: a read issued one step ahead was late under load)
-  auto load_a = [&](int s, ef_u32x4& u0, ef_u32x4& u1) {
+  auto load_a = [&](int s, u32x4& u0, u32x4& u1) {
     if constexpr (XS) {
       const int xo = xl ^ s;                            // one v_xor per k-step; the m-tile / k-step parts are immediates
       u0 = a0[s * 64 + xo];
@@ -75,7 +62,7 @@ __device__ __forceinline__ void ef_block(f32x16 (&acc)[2][2], const ef_u32x4* __
       u1 = (s & 1) ? a1o[s * 64] : a1[s * 64];
     }
   };
-  ef_u32x4 ua0[EF_PA], ua1[EF_PA];
+  u32x4 ua0[EF_PA], ua1[EF_PA];
 #pragma unroll
   for (int s = 0; s < EF_PA; ++s) load_a(s, ua0[s], ua1[s]);
 #pragma unroll
@@ -110,17 +97,17 @@ struct EfLevels { int n; int start[9]; };
 // ('self_attn' tail + first 'norm' of the layer): x1 = LN0(x + a Wo^T + bo) is computed in the workgroup from the attention
 // rows a16 (GEMM K = N = 256 on the same row image / weight-stream machinery, f32 tile, row LayerNorm with the layer-input rows
 // x16 as residual) and written straight into the row image as bf16 -- x1 never exists in memory.
-struct EfPro { const uint16_t* a16; const ef_u32x4* wo; const float* bo; const float* gamma0; const float* beta0; float eps0; };
+struct EfPro { const uint16_t* a16; const u32x4* wo; const float* bo; const float* gamma0; const float* beta0; float eps0; };
 
 template <bool KV, bool PRO>
 __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
-    const uint16_t* __restrict__ x16, const ef_u32x4* __restrict__ w1, const float* __restrict__ b1,
-    const ef_u32x4* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ gamma,
+    const uint16_t* __restrict__ x16, const u32x4* __restrict__ w1, const float* __restrict__ b1,
+    const u32x4* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, const float* __restrict__ pos, int pos_rows, uint16_t* __restrict__ y16,
     uint16_t* __restrict__ yp16, float* __restrict__ y32, int M, int F, const float* __restrict__ shift, EfLevels lv, EfPro pro) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ef_smem[];
-  ef_u32x4* xfrag = reinterpret_cast<ef_u32x4*>(ef_smem);                     // row image      [2 m-tiles][16][64]   32 KiB
-  ef_u32x4* hfrag = xfrag + (EF_RB / 32) * EF_STEPS * 64;                     // hidden chunk   [2 m-tiles][16][64]   32 KiB
+  u32x4* xfrag = reinterpret_cast<u32x4*>(ef_smem);                     // row image      [2 m-tiles][16][64]   32 KiB
+  u32x4* hfrag = xfrag + (EF_RB / 32) * EF_STEPS * 64;                     // hidden chunk   [2 m-tiles][16][64]   32 KiB
   float* tile = reinterpret_cast<float*>(ef_smem);                            // [64][EF_TS] f32 LayerNorm tile, overlays both (65 KiB)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi5 = lane >> 5;
@@ -130,8 +117,8 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
   const int KS2 = F >> 4;                                                     // k-steps of W2
 
   // weight stream: the first EF_PF k-steps of the first GEMM block are in flight while the rows are staged
-  const ef_u32x4* wfirst = PRO ? pro.wo : w1;
-  ef_u32x4 q0[EF_PF], q1[EF_PF];
+  const u32x4* wfirst = PRO ? pro.wo : w1;
+  u32x4 q0[EF_PF], q1[EF_PF];
 #pragma unroll
   for (int s = 0; s < EF_PF; ++s) {
     q0[s] = wfirst[((size_t)(2 * wn) * EF_STEPS + s) * 64 + lane];
@@ -145,12 +132,12 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
   // load / s_waitcnt vmcnt(0) / ds_write per piece -- one serial memory latency per iteration at the head of every workgroup
   {
     constexpr int NP = EF_RB * 32 / EF_NT;
-    ef_u32x4 v[NP];
+    u32x4 v[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int p = tid + i * EF_NT, row = p >> 5, k8 = p & 31;
       const int mr = m0 + row < M ? m0 + row : M - 1;
-      v[i] = *reinterpret_cast<const ef_u32x4*>(rows_in + (size_t)mr * EF_C + 8 * k8);
+      v[i] = *reinterpret_cast<const u32x4*>(rows_in + (size_t)mr * EF_C + 8 * k8);
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     __syncthreads();
-    const ef_u32x4* xb = xfrag + (2 * wm) * (EF_STEPS * 64);
+    const u32x4* xb = xfrag + (2 * wm) * (EF_STEPS * 64);
     ef_block<true>(acc, xb, xb, xb, xb, lane, q0, q1, pro.wo + ((size_t)(2 * wn) * EF_STEPS) * 64 + lane,
                    pro.wo + ((size_t)(2 * wn + 1) * EF_STEPS) * 64 + lane, w1 + ((size_t)(2 * wn) * EF_STEPS) * 64 + lane,
                    w1 + ((size_t)(2 * wn + 1) * EF_STEPS) * 64 + lane);
@@ -214,7 +201,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
         v[k][3] += __uint_as_float(xr.y & 0xffff0000u);
         sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
       }
-      sm = ef_row16_sum(sm);
+      sm = cgg_row16_sum(sm);
       const float mean = sm * (1.f / (float)EF_C);
       float q = 0.f;
 #pragma unroll
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
         v[k] = v[k] - mean;
         q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
       }
-      q = ef_row16_sum(q);
+      q = cgg_row16_sum(q);
       const float rstd = rsqrtf(q * (1.f / (float)EF_C) + pro.eps0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -266,24 +253,24 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
       const int es = j - 16 * kk - 8 * hi5;                       // B[k][n] = 1 iff 16 kk + 8 hi5 + e == j
       const uint32_t one = (es >= 0 && es < 8) ? ((es & 1) ? 0x3F800000u : 0x00003F80u) : 0u;
       const int ed = es >> 1;
-      const ef_u32x4 idv = {ed == 0 ? one : 0u, ed == 1 ? one : 0u, ed == 2 ? one : 0u, ed == 3 ? one : 0u};
+      const u32x4 idv = {ed == 0 ? one : 0u, ed == 1 ? one : 0u, ed == 2 ? one : 0u, ed == 3 ? one : 0u};
       const bf16x8 vid = __builtin_bit_cast(bf16x8, idv);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
-        const ef_u32x4 ua = xfrag[((2 * wm + mt) * EF_STEPS + ks) * 64 + (lane ^ ks)];
+        const u32x4 ua = xfrag[((2 * wm + mt) * EF_STEPS + ks) * 64 + (lane ^ ks)];
         acc2[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ua), vid, acc2[mt][nt], 0, 0, 0);
       }
     }
 
-  const ef_u32x4* xa0 = xfrag + (2 * wm) * (EF_STEPS * 64);
-  const ef_u32x4* xa1 = xfrag + (2 * wm + 1) * (EF_STEPS * 64);
+  const u32x4* xa0 = xfrag + (2 * wm) * (EF_STEPS * 64);
+  const u32x4* xa1 = xfrag + (2 * wm + 1) * (EF_STEPS * 64);
   // hidden image, bank-swizzled: slot (k-step, half, row) sits at k-step * 64 + half * 32 + (row ^ 2 (k-step & 1) ^ 8 half), so the
   // 32 stores of one instruction (2 k-steps x 2 halves x 8 (row, word) positions) fall into distinct banks
   const int hoff_e = hi5 * 32 + (j ^ (8 * hi5)), hoff_o = hi5 * 32 + (j ^ 2 ^ (8 * hi5));
-  const ef_u32x4* ha0 = hfrag + (2 * wm) * (EF_STEPS * 64) + hoff_e;
-  const ef_u32x4* ha1 = hfrag + (2 * wm + 1) * (EF_STEPS * 64) + hoff_e;
-  const ef_u32x4* ha0o = hfrag + (2 * wm) * (EF_STEPS * 64) + hoff_o;
-  const ef_u32x4* ha1o = hfrag + (2 * wm + 1) * (EF_STEPS * 64) + hoff_o;
+  const u32x4* ha0 = hfrag + (2 * wm) * (EF_STEPS * 64) + hoff_e;
+  const u32x4* ha1 = hfrag + (2 * wm + 1) * (EF_STEPS * 64) + hoff_e;
+  const u32x4* ha0o = hfrag + (2 * wm) * (EF_STEPS * 64) + hoff_o;
+  const u32x4* ha1o = hfrag + (2 * wm + 1) * (EF_STEPS * 64) + hoff_o;
   uint32_t* h32 = reinterpret_cast<uint32_t*>(hfrag);
   const int odd = j & 1, k1 = (j >> 4) & 1, half = (j >> 3) & 1;
   int hb[2][2];                                        // word index of this lane's store for (bit 1, bit 3) of the register row
@@ -303,8 +290,8 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
       for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const ef_u32x4* g2b0 = w2 + ((size_t)(2 * wn) * KS2 + 16 * c) * 64 + lane;
-    const ef_u32x4* g2b1 = w2 + ((size_t)(2 * wn + 1) * KS2 + 16 * c) * 64 + lane;
+    const u32x4* g2b0 = w2 + ((size_t)(2 * wn) * KS2 + 16 * c) * 64 + lane;
+    const u32x4* g2b1 = w2 + ((size_t)(2 * wn + 1) * KS2 + 16 * c) * 64 + lane;
     ef_block<true>(acc, xa0, xa1, xa0, xa1, lane, q0, q1, w1 + ((size_t)(8 * c + 2 * wn) * EF_STEPS) * 64 + lane,
              w1 + ((size_t)(8 * c + 2 * wn + 1) * EF_STEPS) * 64 + lane, g2b0, g2b1);
     // relu(. + b1) -> A-fragment image of the chunk; column (64 wn + 32 nt + j) of the chunk = k index of GEMM 2. Lanes j, j ^ 1 hold
@@ -319,7 +306,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
         for (int rp = 0; rp < 8; ++rp) {
           const float v0 = fmaxf(acc[mt][nt][2 * rp] + bias1, 0.f), v1 = fmaxf(acc[mt][nt][2 * rp + 1] + bias1, 0.f);
           const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-          const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));  // lane ^ 1
+          const float recv = cgg_lane_xor1(sent);  // lane ^ 1
           const uint32_t pk = ef_pk(kept, recv);
           h32[hb[rp & 1][(rp >> 1) & 1] + (((mt * EF_STEPS + 2 * nt) * 64 + 16 * (rp >> 2)) << 2)] =
               __builtin_amdgcn_alignbit(pk, pk, rot);              // odd lanes: (recv, kept)
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
       v[k] = *reinterpret_cast<const f32x4*>(&tile[row * EF_TS + 4 * sub + 64 * k]);
       sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
-    sm = ef_row16_sum(sm);
+    sm = cgg_row16_sum(sm);
     const float mean = sm * inv_n;
     float q = 0.f;
 #pragma unroll
@@ -402,7 +389,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
       v[k] = v[k] - mean;
       q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
     }
-    q = ef_row16_sum(q);
+    q = cgg_row16_sum(q);
     const float rstd = rsqrtf(q * inv_n + eps);
     if (!live) continue;
     if constexpr (KV) {
@@ -462,7 +449,7 @@ static int ef_launch(bool kv, const EfPro* prop, const void* x16, const void* w1
   do {                                                                                                                        \
     CGG_RAISE_LDS((cgg_encoder_ffn_ln_kernel<KV, PRO>), lds, who);                                                            \
     hipLaunchKernelGGL((cgg_encoder_ffn_ln_kernel<KV, PRO>), grid, block, lds, (hipStream_t)stream, (const uint16_t*)x16,     \
-                       (const ef_u32x4*)w1_packed, b1, (const ef_u32x4*)w2_packed, b2, gamma, beta, eps, pos, pos_rows,        \
+                       (const u32x4*)w1_packed, b1, (const u32x4*)w2_packed, b2, gamma, beta, eps, pos, pos_rows,        \
                        (uint16_t*)y16, (uint16_t*)yp16, y32, M, F, shift, lv, pro);                                           \
   } while (0)
   if (kv && prop) EF_LAUNCH(true, true);
@@ -529,7 +516,7 @@ extern "C" int cgg_encoder_layer_tail_bf16(const void* a16, const void* x16, con
     int rc = ef_levels(lv, level_start_host, n_levels, M, pos_rows, "cgg_encoder_layer_tail_bf16");
     if (rc != CGG_OK) return rc;
   }
-  const EfPro pro = {(const uint16_t*)a16, (const ef_u32x4*)wo_packed, bo, gamma0, beta0, eps0};
+  const EfPro pro = {(const uint16_t*)a16, (const u32x4*)wo_packed, bo, gamma0, beta0, eps0};
   int rc = ef_launch(shift != nullptr, &pro, x16, w1_packed, b1, w2_packed, b2, gamma1, beta1, eps1, pos, pos_rows, y16, yp16, y32,
                      M, C, F, shift, lv, stream, "cgg_encoder_layer_tail_bf16");
   if (rc != CGG_OK) return rc;

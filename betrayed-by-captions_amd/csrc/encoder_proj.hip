@@ -21,18 +21,14 @@
 // build-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 #include "cgg_common.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t ep_u32x4;
-typedef __attribute__((ext_vector_type(2))) float ep_f2;
-typedef __attribute__((ext_vector_type(2))) __bf16 ep_bf2;
-
 #define EP_C 256
 #define EP_STEPS 16
 #define EP_RB 64
 #define EP_PF 4
 
 __device__ __forceinline__ uint32_t ep_pk(float a, float b) {            // v_cvt_pk_bf16_f32
-  const ep_f2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, ep_bf2));
+  const f32x2 pr = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
 }
 
 // acc[2][NT] += A (two 32-row m-tiles, fragment images in LDS at a0 / a1) x B (NT consecutive n-tiles of the packed weight,
@@ -40,14 +36,14 @@ __device__ __forceinline__ uint32_t ep_pk(float a, float b) {            // v_cv
 // TR = true: the operand roles are swapped (weight fragment as A, row image as B): acc[mt][t] is the TRANSPOSED block, rows =
 // the 32 output channels of n-tile t, columns = the 32 rows of m-tile mt (fragment layouts of A and B are the same).
 template <int NT, bool TR = false>
-__device__ __forceinline__ void ep_block(f32x16 (&acc)[2][NT], const ep_u32x4* __restrict__ a0, const ep_u32x4* __restrict__ a1,
-                                         int lane, const ep_u32x4* __restrict__ b) {
-  ep_u32x4 q[NT][EP_PF];
+__device__ __forceinline__ void ep_block(f32x16 (&acc)[2][NT], const u32x4* __restrict__ a0, const u32x4* __restrict__ a1,
+                                         int lane, const u32x4* __restrict__ b) {
+  u32x4 q[NT][EP_PF];
 #pragma unroll
   for (int s = 0; s < EP_PF; ++s)
 #pragma unroll
     for (int t = 0; t < NT; ++t) q[t][s] = b[(t * EP_STEPS + s) * 64];
-  ep_u32x4 ua0 = a0[lane], ua1 = a1[lane];                      // k-step 0: lane ^ 0
+  u32x4 ua0 = a0[lane], ua1 = a1[lane];                      // k-step 0: lane ^ 0
 #pragma unroll
   for (int s = 0; s < EP_STEPS; ++s) {
     bf16x8 vb[NT];
@@ -101,7 +97,7 @@ __device__ __forceinline__ void ep_store(const f32x16 (&acc)[2][NT], const float
       for (int t = 0; t < NT; ++t) {
         const float v0 = acc[mt][t][2 * rp] + bs[t], v1 = acc[mt][t][2 * rp + 1] + bs[t];
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-        const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));  // lane ^ 1
+        const float recv = cgg_lane_xor1(sent);  // lane ^ 1
         // even lane: row(2 rp), columns (even, odd) = (kept, recv); odd lane: row(2 rp + 1), (recv, kept)
         const uint32_t w = ep_pk(kept, recv);
         pk[t] = __builtin_amdgcn_alignbit(w, w, rot);
@@ -136,7 +132,7 @@ __device__ __forceinline__ void ep_store_value_hm(const f32x16 (&acc)[2][2], con
       for (int t = 0; t < 2; ++t) {
         const float v0 = acc[mt][t][2 * rp] + bs[t], v1 = acc[mt][t][2 * rp + 1] + bs[t];
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-        const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));  // lane ^ 1
+        const float recv = cgg_lane_xor1(sent);  // lane ^ 1
         const uint32_t w = ep_pk(kept, recv);
         pk[t] = __builtin_amdgcn_alignbit(w, w, rot);
       }
@@ -157,7 +153,7 @@ __host__ __device__ __forceinline__ int ep_wave_tile0(int ntiles, int w) {
 }
 
 // weight (N x 256) f32 -> bf16 MFMA-B fragments with the column interleave above inside every wave's block
-__global__ __launch_bounds__(256) void cgg_encoder_proj_pack_kernel(const float* __restrict__ w, ep_u32x4* __restrict__ out, int ntiles,
+__global__ __launch_bounds__(256) void cgg_encoder_proj_pack_kernel(const float* __restrict__ w, u32x4* __restrict__ out, int ntiles,
                                                                    int total) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -168,14 +164,14 @@ __global__ __launch_bounds__(256) void cgg_encoder_proj_pack_kernel(const float*
   const int NT = ep_wave_nt(ntiles, wave), tile0 = ep_wave_tile0(ntiles, wave);
   const int n = 32 * tile0 + ep_col(NT, tile - tile0, lane & 31);
   const float* s = w + (size_t)n * EP_C + ks * 16 + 8 * (lane >> 5);
-  out[i] = ep_u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
+  out[i] = u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
 }
 
 __global__ __launch_bounds__(256) void cgg_encoder_proj_kernel(
-    const uint16_t* __restrict__ x16, const uint16_t* __restrict__ xp16, const ep_u32x4* __restrict__ wv,
-    const float* __restrict__ bv, const ep_u32x4* __restrict__ wc, const float* __restrict__ bc, uint16_t* __restrict__ value,
+    const uint16_t* __restrict__ x16, const uint16_t* __restrict__ xp16, const u32x4* __restrict__ wv,
+    const float* __restrict__ bv, const u32x4* __restrict__ wc, const float* __restrict__ bc, uint16_t* __restrict__ value,
     uint16_t* __restrict__ offs, int M, int NC, const uint16_t* __restrict__ pos16, int pos_rows, int hm_rows) {
-  __shared__ __attribute__((aligned(16))) ep_u32x4 frag[2][2 * EP_STEPS * 64];      // x and xp images: 2 x 32 KiB
+  __shared__ __attribute__((aligned(16))) u32x4 frag[2][2 * EP_STEPS * 64];      // x and xp images: 2 x 32 KiB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.x * EP_RB;
   // rows -> A-fragment images: 16-byte piece (row, k8) = 8 channels -> slot (row / 32, k-step = k8 / 2, (row % 32 + 32 (k8 & 1)) ^
@@ -184,22 +180,22 @@ __global__ __launch_bounds__(256) void cgg_encoder_proj_kernel(
   // (Requesting the xp rows late, to overlap them with the value block, does not help: vmcnt retires in order, so the first
   // wait on a weight fragment also waits for the older row loads.)
   {
-    ep_u32x4 v[16];
+    u32x4 v[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int p = tid + 256 * i, which = p >> 11, row = (p >> 5) & 63, k8 = p & 31;
-      v[i] = ep_u32x4{0u, 0u, 0u, 0u};
+      v[i] = u32x4{0u, 0u, 0u, 0u};
       if (m0 + row < M) {
         if (which && xp16 == nullptr) {
           // xp = bf16(x + pos) from the bf16 rows and the bf16 pos table: the (M, 256) `x + pos` rows are never stored
-          const ep_u32x4 a = *reinterpret_cast<const ep_u32x4*>(x16 + (size_t)(m0 + row) * EP_C + 8 * k8);
-          const ep_u32x4 b = *reinterpret_cast<const ep_u32x4*>(pos16 + (size_t)((m0 + row) % pos_rows) * EP_C + 8 * k8);
+          const u32x4 a = *reinterpret_cast<const u32x4*>(x16 + (size_t)(m0 + row) * EP_C + 8 * k8);
+          const u32x4 b = *reinterpret_cast<const u32x4*>(pos16 + (size_t)((m0 + row) % pos_rows) * EP_C + 8 * k8);
 #pragma unroll
           for (int d = 0; d < 4; ++d)
             v[i][d] = ep_pk(__uint_as_float(a[d] << 16) + __uint_as_float(b[d] << 16),
                             __uint_as_float(a[d] & 0xffff0000u) + __uint_as_float(b[d] & 0xffff0000u));
         } else {
-          v[i] = *reinterpret_cast<const ep_u32x4*>((which ? xp16 : x16) + (size_t)(m0 + row) * EP_C + 8 * k8);
+          v[i] = *reinterpret_cast<const u32x4*>((which ? xp16 : x16) + (size_t)(m0 + row) * EP_C + 8 * k8);
         }
       }
     }
@@ -252,7 +248,7 @@ extern "C" int cgg_encoder_proj_pack(const float* w, void* packed, int N, int K,
               "cgg_encoder_proj_pack: N=%d K=%d (N = 256 .. 384 in steps of 32, K = 256)", N, K);
   const int total = (N / 32) * EP_STEPS * 64;
   hipLaunchKernelGGL(cgg_encoder_proj_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                     (ep_u32x4*)packed, N / 32, total);
+                     (u32x4*)packed, N / 32, total);
   CGG_CHECK_LAUNCH("cgg_encoder_proj_pack");
   return CGG_OK;
 }
@@ -271,7 +267,7 @@ extern "C" int cgg_encoder_proj_bf16(const void* x16, const void* xp16, const vo
                   cgg_aligned16(value) && cgg_aligned16(offs),
               CGG_EALIGN, "cgg_encoder_proj_bf16: 16-B alignment");
   hipLaunchKernelGGL(cgg_encoder_proj_kernel, dim3((M + EP_RB - 1) / EP_RB), dim3(256), 0, (hipStream_t)stream,
-                     (const uint16_t*)x16, (const uint16_t*)xp16, (const ep_u32x4*)wv_packed, bv, (const ep_u32x4*)wc_packed, bc,
+                     (const uint16_t*)x16, (const uint16_t*)xp16, (const u32x4*)wv_packed, bv, (const u32x4*)wc_packed, bc,
                      (uint16_t*)value, (uint16_t*)offs, M, NC, (const uint16_t*)pos16, pos_rows, value_head_major_rows);
   CGG_CHECK_LAUNCH("cgg_encoder_proj_bf16");
   return CGG_OK;
@@ -305,7 +301,7 @@ __device__ __forceinline__ void ep_store_tr(const f32x16 (&acc)[2][NT], uint16_t
       for (int mt = 0; mt < 2; ++mt) {
         const float v0 = acc[mt][t][2 * rp], v1 = acc[mt][t][2 * rp + 1];
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-        const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));  // lane ^ 1
+        const float recv = cgg_lane_xor1(sent);  // lane ^ 1
         const uint32_t w = ep_pk(kept, recv);          // even lane: channel row(2 rp), pixels (j, j + 1) of m-tile mt; odd: row + 1
         pk[mt] = __builtin_amdgcn_alignbit(w, w, rot);
       }
@@ -333,20 +329,20 @@ __device__ __forceinline__ void ep_store_tr(const f32x16 (&acc)[2][NT], uint16_t
 // block of an image re-reads its last row for the missing ones (finite operands) and masks their stores
 template <bool RAGGED>
 __global__ __launch_bounds__(256) void cgg_decoder_kv_proj_kernel(
-    const uint16_t* __restrict__ m16, const uint16_t* __restrict__ mp16, const ep_u32x4* __restrict__ wk,
-    const float* __restrict__ bk, const ep_u32x4* __restrict__ wv, uint16_t* __restrict__ k, uint16_t* __restrict__ vt, int hw,
+    const uint16_t* __restrict__ m16, const uint16_t* __restrict__ mp16, const u32x4* __restrict__ wk,
+    const float* __restrict__ bk, const u32x4* __restrict__ wv, uint16_t* __restrict__ k, uint16_t* __restrict__ vt, int hw,
     int NK, int blocks_per_image) {
-  __shared__ __attribute__((aligned(16))) ep_u32x4 frag[2][2 * EP_STEPS * 64];      // m16 (row-interleaved) and mp16 images
+  __shared__ __attribute__((aligned(16))) u32x4 frag[2][2 * EP_STEPS * 64];      // m16 (row-interleaved) and mp16 images
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int img = blockIdx.x / blocks_per_image, pix0 = (blockIdx.x - img * blocks_per_image) * EP_RB;
   const int m0 = img * hw + pix0;                        // a block never straddles two images
   const int valid = RAGGED ? min(EP_RB, hw - pix0) : EP_RB;
   {
-    ep_u32x4 v[16];
+    u32x4 v[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int p = tid + 256 * i, which = p >> 11, row = (p >> 5) & 63, k8 = p & 31;
-      v[i] = *reinterpret_cast<const ep_u32x4*>((which ? mp16 : m16) + (size_t)(m0 + (RAGGED ? min(row, valid - 1) : row)) * EP_C + 8 * k8);
+      v[i] = *reinterpret_cast<const u32x4*>((which ? mp16 : m16) + (size_t)(m0 + (RAGGED ? min(row, valid - 1) : row)) * EP_C + 8 * k8);
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -386,14 +382,14 @@ __global__ __launch_bounds__(256) void cgg_decoder_kv_proj_kernel(
 }
 
 // weight (N x 256) f32, N % 64 == 0 -> bf16 B fragments for the k block: 64-column groups, the two n-tiles of a group interleaved
-__global__ __launch_bounds__(256) void cgg_decoder_kv_pack_k_kernel(const float* __restrict__ w, ep_u32x4* __restrict__ out, int total) {
+__global__ __launch_bounds__(256) void cgg_decoder_kv_pack_k_kernel(const float* __restrict__ w, u32x4* __restrict__ out, int total) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int lane = i & 63, t_all = i >> 6;
   const int ks = t_all % EP_STEPS, tile = t_all / EP_STEPS;
   const int n = 64 * (tile >> 1) + ep_col(2, tile & 1, lane & 31);
   const float* s = w + (size_t)n * EP_C + ks * 16 + 8 * (lane >> 5);
-  out[i] = ep_u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
+  out[i] = u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
 }
 
 extern "C" int cgg_decoder_kv_pack_k(const float* w, void* packed, int N, int K, cgg_stream_t stream) {
@@ -401,7 +397,7 @@ extern "C" int cgg_decoder_kv_pack_k(const float* w, void* packed, int N, int K,
   CGG_REQUIRE(K == EP_C && N > 0 && N % 256 == 0, CGG_EUNSUPPORTED, "cgg_decoder_kv_pack_k: N=%d K=%d (N %% 256, K = 256)", N, K);
   const int total = (N / 32) * EP_STEPS * 64;
   hipLaunchKernelGGL(cgg_decoder_kv_pack_k_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                     (ep_u32x4*)packed, total);
+                     (u32x4*)packed, total);
   CGG_CHECK_LAUNCH("cgg_decoder_kv_pack_k");
   return CGG_OK;
 }
@@ -420,11 +416,11 @@ extern "C" int cgg_decoder_kv_proj_bf16(const void* m16, const void* mp16, const
   const int bpi = (hw + EP_RB - 1) / EP_RB;
   if (hw % EP_RB == 0)
     hipLaunchKernelGGL(cgg_decoder_kv_proj_kernel<false>, dim3(B * bpi), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)m16,
-                       (const uint16_t*)mp16, (const ep_u32x4*)wk_packed, bk, (const ep_u32x4*)wv_packed, (uint16_t*)k, (uint16_t*)vt,
+                       (const uint16_t*)mp16, (const u32x4*)wk_packed, bk, (const u32x4*)wv_packed, (uint16_t*)k, (uint16_t*)vt,
                        hw, NK, bpi);
   else
     hipLaunchKernelGGL(cgg_decoder_kv_proj_kernel<true>, dim3(B * bpi), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)m16,
-                       (const uint16_t*)mp16, (const ep_u32x4*)wk_packed, bk, (const ep_u32x4*)wv_packed, (uint16_t*)k, (uint16_t*)vt,
+                       (const uint16_t*)mp16, (const u32x4*)wk_packed, bk, (const u32x4*)wv_packed, (uint16_t*)k, (uint16_t*)vt,
                        hw, NK, bpi);
   CGG_CHECK_LAUNCH("cgg_decoder_kv_proj_bf16");
   return CGG_OK;

@@ -22,8 +22,6 @@
 // build-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t e3_u32x4;
-
 #define E3_C 256
 #define E3_STEPS 16
 #define E3_RB 64               // rows per workgroup
@@ -32,17 +30,8 @@ typedef __attribute__((ext_vector_type(4))) uint32_t e3_u32x4;
 #define E3_PF 4                // B-fragment prefetch distance (k-steps); divides E3_STEPS (the queue rotates across blocks)
 #define E3_IMG (2 * E3_STEPS * 64)          // u32x4 slots of one 64 x 256 image piece (32 KiB)
 
-// sum over the 16 lanes of a DPP row, result in every lane: quad xor 1, quad xor 2, row_half_mirror, row_mirror
-__device__ __forceinline__ float e3_row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true));
-  return v;
-}
-
 struct E3Q {                   // rotating B-fragment queue of one n-tile: hi and lo pieces
-  e3_u32x4 h[E3_PF], l[E3_PF];
+  u32x4 h[E3_PF], l[E3_PF];
 };
 
 // One 64 x (32 TN) block of C += A B^T over 16 k-steps, x3 arithmetic. A-fragment images (hi at a, lo at a + lo_off) of the two
@@ -54,12 +43,12 @@ struct E3Q {                   // rotating B-fragment queue of one n-tile: hi an
 // columns each -- a wave issues in order, so with one wave per SIMD its LDS reads, weight loads and epilogue VALU work all ran with
 // the matrix pipe idle; with two, one wave's MFMAs cover the other's non-MFMA code (the lesson of this round's einsum kernel).
 template <bool XS, int TN>
-__device__ __forceinline__ void e3_block(f32x16 (&acc)[2][TN], const e3_u32x4* __restrict__ a0, const e3_u32x4* __restrict__ a1,
-                                         const e3_u32x4* __restrict__ a0o, const e3_u32x4* __restrict__ a1o, int lo_off, int xl,
-                                         E3Q (&q)[TN], const e3_u32x4* const (&bh)[TN], const e3_u32x4* const (&bl)[TN],
-                                         const e3_u32x4* const (&nh)[TN], const e3_u32x4* const (&nl)[TN]) {
+__device__ __forceinline__ void e3_block(f32x16 (&acc)[2][TN], const u32x4* __restrict__ a0, const u32x4* __restrict__ a1,
+                                         const u32x4* __restrict__ a0o, const u32x4* __restrict__ a1o, int lo_off, int xl,
+                                         E3Q (&q)[TN], const u32x4* const (&bh)[TN], const u32x4* const (&bl)[TN],
+                                         const u32x4* const (&nh)[TN], const u32x4* const (&nl)[TN]) {
   if constexpr (XS) asm volatile("" : "+v"(xl));
-  auto load_a = [&](int s, e3_u32x4& h0, e3_u32x4& l0, e3_u32x4& h1, e3_u32x4& l1) {
+  auto load_a = [&](int s, u32x4& h0, u32x4& l0, u32x4& h1, u32x4& l1) {
     if constexpr (XS) {
       const int xo = xl ^ s;
       h0 = a0[s * 64 + xo];
@@ -67,25 +56,25 @@ __device__ __forceinline__ void e3_block(f32x16 (&acc)[2][TN], const e3_u32x4* _
       h1 = a0[(E3_STEPS + s) * 64 + xo];
       l1 = a0[lo_off + (E3_STEPS + s) * 64 + xo];
     } else {
-      const e3_u32x4* p0 = (s & 1) ? a0o : a0;
-      const e3_u32x4* p1 = (s & 1) ? a1o : a1;
+      const u32x4* p0 = (s & 1) ? a0o : a0;
+      const u32x4* p1 = (s & 1) ? a1o : a1;
       h0 = p0[s * 64];
       l0 = p0[lo_off + s * 64];
       h1 = p1[s * 64];
       l1 = p1[lo_off + s * 64];
     }
   };
-  e3_u32x4 ah0, al0, ah1, al1;
+  u32x4 ah0, al0, ah1, al1;
   load_a(0, ah0, al0, ah1, al1);
 #pragma unroll
   for (int s = 0; s < E3_STEPS; ++s) {
-    e3_u32x4 bhv[TN], blv[TN];
+    u32x4 bhv[TN], blv[TN];
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       bhv[t] = q[t].h[s % E3_PF];
       blv[t] = q[t].l[s % E3_PF];
     }
-    const e3_u32x4 vah0 = ah0, val0 = al0, vah1 = ah1, val1 = al1;
+    const u32x4 vah0 = ah0, val0 = al0, vah1 = ah1, val1 = al1;
     if (s + 1 < E3_STEPS) load_a(s + 1, ah0, al0, ah1, al1);
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
@@ -127,8 +116,8 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
     const float* __restrict__ pos, int pos_rows, float* __restrict__ y32, float* __restrict__ yp32, int M, int F, int x3a,
     int* __restrict__ flag) {
   extern __shared__ __attribute__((aligned(16))) unsigned char e3_smem[];
-  e3_u32x4* xfrag = reinterpret_cast<e3_u32x4*>(e3_smem);                   // row image: hi [2 m-tiles][16][64] | lo    64 KiB
-  e3_u32x4* hfrag = xfrag + 2 * E3_IMG;                                      // hidden chunk: hi | lo                     64 KiB
+  u32x4* xfrag = reinterpret_cast<u32x4*>(e3_smem);                   // row image: hi [2 m-tiles][16][64] | lo    64 KiB
+  u32x4* hfrag = xfrag + 2 * E3_IMG;                                      // hidden chunk: hi | lo                     64 KiB
   float* tile = reinterpret_cast<float*>(hfrag);                             // [64][E3_TS] f32 LayerNorm tile, overlays the hidden images (65 KiB)
   constexpr int NT = 64 * NWV;                                               // threads per workgroup
   constexpr int TN = 8 / NWV;                                                // 32-column n-tiles per wave (2: four waves, 1: eight)
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int p = tid + i * NT, row = p >> 5, k8 = p & 31;
-      e3_u32x4 h, l;
+      u32x4 h, l;
       cgg_x3_split8(v0[i], v1[i], h, l);
       const int slot = ((row >> 5) * E3_STEPS + (k8 >> 1)) * 64 + (((row & 31) + 32 * (k8 & 1)) ^ (k8 >> 1));
       xfrag[slot] = h;
@@ -204,7 +193,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
   __syncthreads();
   // ---- output projection: a Wo^T (next block in the weight stream: W1's first chunk) ----
   {
-    const e3_u32x4 *bh[TN], *bl[TN], *nh[TN], *nl[TN];
+    const u32x4 *bh[TN], *bl[TN], *nh[TN], *nl[TN];
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
       const size_t o = ((size_t)(TN * wn + t) * E3_STEPS) * 64 + lane;
@@ -240,7 +229,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
         v[k] = *reinterpret_cast<const f32x4*>(&tile[row * E3_TS + 4 * sub + 64 * k]) + xr[it][k];
         sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
       }
-      sm = e3_row16_sum(sm);
+      sm = cgg_row16_sum(sm);
       const float mean = sm * inv_n;
       float q = 0.f;
 #pragma unroll
@@ -248,7 +237,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
         v[k] = v[k] - mean;
         q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
       }
-      q = e3_row16_sum(q);
+      q = cgg_row16_sum(q);
       const float rstd = rsqrtf(q * inv_n + eps0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -278,10 +267,10 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
   // hidden image, bank-swizzled: slot (k-step, half, row) sits at k-step * 64 + half * 32 + (row ^ 2 (k-step & 1) ^ 8 half), so the
   // stores of one instruction fall into distinct banks (layout of encoder_ffn.hip); hi and lo images share the addressing
   const int hoff_e = hi5 * 32 + (j ^ (8 * hi5)), hoff_o = hi5 * 32 + (j ^ 2 ^ (8 * hi5));
-  const e3_u32x4* ha0 = hfrag + hoff_e;
-  const e3_u32x4* ha1 = hfrag + E3_STEPS * 64 + hoff_e;
-  const e3_u32x4* ha0o = hfrag + hoff_o;
-  const e3_u32x4* ha1o = hfrag + E3_STEPS * 64 + hoff_o;
+  const u32x4* ha0 = hfrag + hoff_e;
+  const u32x4* ha1 = hfrag + E3_STEPS * 64 + hoff_e;
+  const u32x4* ha0o = hfrag + hoff_o;
+  const u32x4* ha1o = hfrag + E3_STEPS * 64 + hoff_o;
   uint32_t* h32 = reinterpret_cast<uint32_t*>(hfrag);
   const int odd = j & 1, k1 = (j >> 4) & 1, half = (j >> 3) & 1;
   int hb[2][2];                                        // word index of this lane's store for (bit 1, bit 3) of the register row
@@ -300,7 +289,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
       for (int b = 0; b < TN; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const e3_u32x4 *w1h[TN], *w1l[TN], *w2h[TN], *w2l[TN], *n1h[TN], *n1l[TN];
+    const u32x4 *w1h[TN], *w1l[TN], *w2h[TN], *w2l[TN], *n1h[TN], *n1l[TN];
     const int cn = c + 1 < nchunk ? c + 1 : 0;         // last chunk: the queue refills with chunk 0 again (unused)
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
           const float v0 = fmaxf(acc[mt][nt][2 * rp] * cs1 + bias1, 0.f), v1 = fmaxf(acc[mt][nt][2 * rp + 1] * cs1 + bias1, 0.f);
           hmax = fmaxf(hmax, fmaxf(v0, v1));
           const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
-          const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sent), 0xB1, 0xf, 0xf, true));  // lane ^ 1
+          const float recv = cgg_lane_xor1(sent);  // lane ^ 1
           uint32_t ph, pl;
           cgg_x3_split2(kept * CGG_X3_ASCALE, recv * CGG_X3_ASCALE, ph, pl);
           const int o = hb[rp & 1][(rp >> 1) & 1] + (((mt * E3_STEPS + 2 * nt) * 64 + 16 * (rp >> 2)) << 2);
@@ -386,7 +375,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
       v[k] = *reinterpret_cast<const f32x4*>(&tile[row * E3_TS + 4 * sub + 64 * k]) + xr[it][k];
       sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
-    sm = e3_row16_sum(sm);
+    sm = cgg_row16_sum(sm);
     const float mean = sm * inv_n;
     float q = 0.f;
 #pragma unroll
@@ -394,7 +383,7 @@ __global__ __launch_bounds__(64 * NWV) void cgg_encoder_tail_x3_kernel(
       v[k] = v[k] - mean;
       q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
     }
-    q = e3_row16_sum(q);
+    q = cgg_row16_sum(q);
     const float rstd = rsqrtf(q * inv_n + eps1);
     if (m >= M) continue;
     if (x3a) {

@@ -9,8 +9,6 @@
 // SPLIT = f32-class accuracy via 3 bf16 MFMAs on (hi, lo) operands; otherwise plain bf16.
 #include "cgg_common.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define LR_KC 256  // K chunk staged per pass (16 MFMA k-steps)
 
 __device__ __forceinline__ void lr_cvt8(const f32x4& a, const f32x4& b, u32x4& hi, u32x4& lo, bool split) {
@@ -154,14 +152,14 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_kernel(const float* __r
   const float* br = b ? b + (size_t)row * N : nullptr;
   float s = 0.f;
   for (int i = lane; i < N; i += 64) s += ar[i] + (br ? br[i] : 0.f);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = cgg_wave_sum(s);
   const float mean = s / (float)N;
   float v = 0.f;
   for (int i = lane; i < N; i += 64) {
     const float d = ar[i] + (br ? br[i] : 0.f) - mean;
     v += d * d;
   }
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = cgg_wave_sum(v);
   const float rstd = rsqrtf(v / (float)N + eps);
   for (int i = lane; i < N; i += 64) {
     const float d = ar[i] + (br ? br[i] : 0.f) - mean;
@@ -212,11 +210,11 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm256_kernel(
   f32x4 v = cgg_ln_load4(a + off);
   if (b != nullptr) v += cgg_ln_load4(b + off);
   float s = (v[0] + v[1]) + (v[2] + v[3]);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = cgg_wave_sum(s);
   const float mean = s * (1.f / 256.f);
   f32x4 d = v - mean;
   float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+  q = cgg_wave_sum(q);
   const float rstd = rsqrtf(q * (1.f / 256.f) + eps);
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + lane * 4);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + lane * 4);
@@ -253,12 +251,12 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm256_bf16x8_kernel(
     v[2 * k + 1] = __uint_as_float(wa[k] & 0xffff0000u) + __uint_as_float(wb[k] & 0xffff0000u);
   }
   float s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-  for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = cgg_wave_sum<32>(s);
   const float mean = s * (1.f / 256.f);
   float q = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) { v[k] -= mean; q += v[k] * v[k]; }
-  for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o);
+  q = cgg_wave_sum<32>(q);
   const float rstd = rsqrtf(q * (1.f / 256.f) + eps);
   const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + l * 8), g1 = *reinterpret_cast<const f32x4*>(gamma + l * 8 + 4);
   const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + l * 8), b1 = *reinterpret_cast<const f32x4*>(beta + l * 8 + 4);
@@ -336,11 +334,11 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm256_kv_kernel(
   f32x4 v = cgg_ln_load4(a + off);
   if (b != nullptr) v += cgg_ln_load4(b + off);
   float s = (v[0] + v[1]) + (v[2] + v[3]);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = cgg_wave_sum(s);
   const float mean = s * (1.f / 256.f);
   f32x4 d = v - mean;
   float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+  q = cgg_wave_sum(q);
   const float rstd = rsqrtf(q * (1.f / 256.f) + eps);
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + lane * 4);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + lane * 4);

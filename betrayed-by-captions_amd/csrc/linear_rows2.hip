@@ -19,8 +19,6 @@
 //     (17 us per call: 128 dependent v_mfma_f32_32x32x2_f32 per tile) at the bf16 kernel's launch time.
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define LR2_KC 256  // K chunk per LDS fill (16 MFMA k-steps)
 
 template <bool LN, bool X3>
@@ -343,7 +341,7 @@ static int lr2_launch(bool x3, const char* who, const float* x, int ldx, const v
   CGG_REQUIRE(ksplit == 1 || relu_cols == 0, CGG_EUNSUPPORTED, "%s: no ReLU with a K split", who);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((N + 255) / 256, (M + 31) / 32, ksplit);
-  const CggX3W w = x3 ? cgg_x3_view(w_packed, N, K) : CggX3W{(const cgg_u32x4*)w_packed, nullptr, nullptr};
+  const CggX3W w = x3 ? cgg_x3_view(w_packed, N, K) : CggX3W{(const u32x4*)w_packed, nullptr, nullptr};
 #define LR2_LAUNCH(LN, X3)                                                                                                  \
   hipLaunchKernelGGL((cgg_lr2_kernel<LN, X3>), grid, dim3(512), 0, s, x, ldx, (const u32x4*)w.hi, (const u32x4*)w.lo, w.scale, \
                      bias, res, ldr, y, ldy, ln_gamma, ln_beta, ln_eps, pos, pos_rows, yp, ldyp, M, N, K, relu_cols, x2, ldx2,  \

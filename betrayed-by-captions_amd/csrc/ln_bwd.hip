@@ -14,14 +14,6 @@
 
 #define LNB_ROWS 256          // rows per workgroup (4 wavefronts x 4 rows x 16 iterations)
 
-__device__ __forceinline__ float lnb_row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true));
-  return v;
-}
-
 __device__ __forceinline__ f32x4 lnb_load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 lnb_load4(const uint16_t* p) {
   const uint2 u = *reinterpret_cast<const uint2*>(p);
@@ -64,14 +56,14 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float*
       if (dy16b != nullptr) y[k] += lnb_load4(dy16b + off + 64 * k);
       sm += (s[k][0] + s[k][1]) + (s[k][2] + s[k][3]);
     }
-    const float mean = lnb_row16_sum(sm) * inv_n;
+    const float mean = cgg_row16_sum(sm) * inv_n;
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       s[k] = s[k] - mean;
       q += (s[k][0] * s[k][0] + s[k][1] * s[k][1]) + (s[k][2] * s[k][2] + s[k][3] * s[k][3]);
     }
-    const float rstd = rsqrtf(lnb_row16_sum(q) * inv_n + eps);
+    const float rstd = rsqrtf(cgg_row16_sum(q) * inv_n + eps);
     float c1 = 0.f, c2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -81,8 +73,8 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float*
       const f32x4 gx = g * s[k];
       c2 += (gx[0] + gx[1]) + (gx[2] + gx[3]);
     }
-    c1 = lnb_row16_sum(c1) * inv_n;
-    c2 = lnb_row16_sum(c2) * inv_n;
+    c1 = cgg_row16_sum(c1) * inv_n;
+    c2 = cgg_row16_sum(c2) * inv_n;
     if (live) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -99,8 +91,7 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float*
   }
   // max |dx| for the per-tensor pre-scale of the contractions that consume dx as grad_output (x3.h): one atomic per wavefront
   if (dx_amax) {
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, sft, 64));
+    lmax = cgg_wave_max(lmax);
     if (lane == 0 && __float_as_uint(lmax) > __hip_atomic_load(reinterpret_cast<unsigned int*>(dx_amax), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
       atomicMax(reinterpret_cast<unsigned int*>(dx_amax), __float_as_uint(lmax));      // (only when it can raise the running maximum)
   }

@@ -23,8 +23,6 @@
 // build-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t mh_u32x4;
-
 #define MH_C 256
 #define MH_STEPS 16
 #define MH_RB 64               // rows per workgroup: 8 x 8 pixels
@@ -34,8 +32,8 @@ typedef __attribute__((ext_vector_type(4))) uint32_t mh_u32x4;
 struct MhJobs {
   int n;
   int pool[4], Wp[4], npix[4], T[4];
-  mh_u32x4* hi[4];
-  mh_u32x4* lo[4];
+  u32x4* hi[4];
+  u32x4* lo[4];
 };
 
 template <int NWV>
@@ -44,7 +42,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
     float eps, const CggX3W w, const float* __restrict__ bias, float lo_clamp, const MhJobs jobs, float* __restrict__ mf, int H, int W,
     int* __restrict__ flag) {
   extern __shared__ __attribute__((aligned(16))) unsigned char mh_smem[];
-  mh_u32x4* xfrag = reinterpret_cast<mh_u32x4*>(mh_smem);                    // row image: hi [2 m-tiles][16][64] | lo    64 KiB
+  u32x4* xfrag = reinterpret_cast<u32x4*>(mh_smem);                    // row image: hi [2 m-tiles][16][64] | lo    64 KiB
   float* tile = reinterpret_cast<float*>(mh_smem);                           // [64][MH_TS] f32 output tile, overlays the image
   constexpr int NT = 64 * NWV;
   constexpr int TN = 8 / NWV;                                                // 32-column n-tiles per wave
@@ -58,8 +56,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
   const size_t HW = (size_t)H * W;
 
   // weight stream: the first MH_PF k-steps are in flight while the rows are staged
-  mh_u32x4 qh[TN][MH_PF], ql[TN][MH_PF];
-  const mh_u32x4 *bh[TN], *bl[TN];
+  u32x4 qh[TN][MH_PF], ql[TN][MH_PF];
+  const u32x4 *bh[TN], *bl[TN];
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
     const size_t o = ((size_t)(TN * wn + t) * MH_STEPS) * 64 + lane;
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
         f[k] = fmaxf(f[k], 0.f);
         am = fmaxf(am, fabsf(f[k]));
       }
-      mh_u32x4 h, l;
+      u32x4 h, l;
       cgg_x3_split8(f32x4{f[0], f[1], f[2], f[3]}, f32x4{f[4], f[5], f[6], f[7]}, h, l);
       const int slot = ((row >> 5) * MH_STEPS + (k8 >> 1)) * 64 + (((row & 31) + 32 * (k8 & 1)) ^ (k8 >> 1));
       xfrag[slot] = h;
@@ -126,24 +124,24 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
   {
     int xl = lane;
     asm volatile("" : "+v"(xl));
-    auto load_a = [&](int s, mh_u32x4& h0, mh_u32x4& l0, mh_u32x4& h1, mh_u32x4& l1) {
+    auto load_a = [&](int s, u32x4& h0, u32x4& l0, u32x4& h1, u32x4& l1) {
       const int xo = xl ^ s;
       h0 = xfrag[s * 64 + xo];
       l0 = xfrag[MH_IMG + s * 64 + xo];
       h1 = xfrag[(MH_STEPS + s) * 64 + xo];
       l1 = xfrag[MH_IMG + (MH_STEPS + s) * 64 + xo];
     };
-    mh_u32x4 ah0, al0, ah1, al1;
+    u32x4 ah0, al0, ah1, al1;
     load_a(0, ah0, al0, ah1, al1);
 #pragma unroll
     for (int s = 0; s < MH_STEPS; ++s) {
-      mh_u32x4 bhv[TN], blv[TN];
+      u32x4 bhv[TN], blv[TN];
 #pragma unroll
       for (int t = 0; t < TN; ++t) {
         bhv[t] = qh[t][s % MH_PF];
         blv[t] = ql[t][s % MH_PF];
       }
-      const mh_u32x4 vah0 = ah0, val0 = al0, vah1 = ah1, val1 = al1;
+      const u32x4 vah0 = ah0, val0 = al0, vah1 = ah1, val1 = al1;
       if (s + 1 < MH_STEPS) load_a(s + 1, ah0, al0, ah1, al1);
       if (s + MH_PF < MH_STEPS) {
 #pragma unroll
@@ -192,8 +190,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
   // ---- the images. Piece (pixel, octet kc) = 8 channels -> 16 bytes of hi and of lo at [b][p / 32][kc][p % 32]. ----
   for (int jb = 0; jb < jobs.n; ++jb) {
     const int pool = jobs.pool[jb], Wp = jobs.Wp[jb], T = jobs.T[jb];
-    mh_u32x4* __restrict__ dh = jobs.hi[jb];
-    mh_u32x4* __restrict__ dl = jobs.lo[jb];
+    u32x4* __restrict__ dh = jobs.hi[jb];
+    u32x4* __restrict__ dl = jobs.lo[jb];
     if (pool == 1) {
       // lanes (tx, kc): the 8 pixels of a tile row are 8 consecutive slots = one 128-byte run per octet (W % 8 == 0: inside one T tile)
 #pragma unroll
@@ -202,7 +200,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
         const int tx = idx & 7, kc = (idx >> 3) & 31, ty = idx >> 8;
         const float* s = tile + (ty * 8 + tx) * MH_TS + kc * 8;
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(s), v1 = *reinterpret_cast<const f32x4*>(s + 4);
-        mh_u32x4 h, l;
+        u32x4 h, l;
         cgg_x3_split8(v0, v1, h, l);
         const int p = (y0 + ty) * W + x0 + tx;
         const size_t slot = (((size_t)b * T + (p >> 5)) * 32 + kc) * 32 + (p & 31);
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
           const f32x4 d = *reinterpret_cast<const f32x4*>(s10 + 4 * h), e = *reinterpret_cast<const f32x4*>(s10 + MH_TS + 4 * h);
           m[h] = ((a + c) + (d + e)) * 0.25f;
         }
-        mh_u32x4 h, l;
+        u32x4 h, l;
         cgg_x3_split8(m[0], m[1], h, l);
         const int p = (y0 / pool + ii) * Wp + x0 / pool + jj;
         const size_t slot = (((size_t)b * T + (p >> 5)) * 32 + kc) * 32 + (p & 31);
@@ -237,7 +235,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 2) void cgg_mask_feature_head_x3_ke
     const int rag = jobs.npix[jb] & 31;
     if (rag && blockIdx.x == gridDim.x - 1) {
       const int cnt = 32 - rag;
-      const mh_u32x4 zero = {0u, 0u, 0u, 0u};
+      const u32x4 zero = {0u, 0u, 0u, 0u};
       for (int idx = tid; idx < cnt * 32; idx += NT) {
         const int kc = idx / cnt, pl = rag + (idx - kc * cnt);
         const size_t slot = (((size_t)b * T + (T - 1)) * 32 + kc) * 32 + pl;
@@ -307,8 +305,8 @@ static int mh_launch(const char* who, const float* z, const void* gn_ws, const f
     jobs.Wp[i] = Wp;
     jobs.npix[i] = Hp * Wp;
     jobs.T[i] = (Hp * Wp + 31) / 32;
-    jobs.hi[i] = (mh_u32x4*)hi_host[i];
-    jobs.lo[i] = (mh_u32x4*)lo_host[i];
+    jobs.hi[i] = (u32x4*)hi_host[i];
+    jobs.lo[i] = (u32x4*)lo_host[i];
   }
   if ((cfg < 0 ? MH_DEFAULT_CFG : cfg) == 0)
     return mh_go<4>(who, z, gn_ws, gamma, beta, eps, w_x3, bias, jobs, mf, B, H, W, (hipStream_t)stream);

@@ -14,8 +14,6 @@
 // an f32 GEMM (rounds 1-2 used a 3 x bf16 split, 8-10 x less accurate, and an exact-f32 MFMA kernel at 172 us).
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 // -------------------------------------------------------------------------------------------------
 // pack: [B, C, H, W] f32  ->  [B, T, C/8, 32, 8] bf16 (hi [+ lo residual]),  T = ceil(npix/32)
 // thread = (pixel p, channel octet kc): 8 coalesced dword loads (lanes run along p), one 16-B store.

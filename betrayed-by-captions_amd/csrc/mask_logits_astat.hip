@@ -19,8 +19,6 @@
 #include "x3.h"
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define MLA_KS 16        // C = 256
 
 __device__ __forceinline__ void mla_load_tile(u32x4 (&dst)[MLA_KS], const u32x4* __restrict__ base, int t, bool stream) {

@@ -16,20 +16,18 @@
 //   lines through L1); per-chunk partial planes are summed in a fixed order by a second kernel (no atomics).
 #include "cgg_common.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t mlb_u32x4;
-
 __device__ __forceinline__ int mlb_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
 template <bool SPLIT>
-__device__ __forceinline__ void mlb_pack8(const float (&v)[8], mlb_u32x4& h, mlb_u32x4& l) {
+__device__ __forceinline__ void mlb_pack8(const float (&v)[8], u32x4& h, u32x4& l) {
   uint16_t a[8], b[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     if (SPLIT) cgg_split_bf(v[e], a[e], b[e]);
     else a[e] = cgg_f2bf(v[e]);
   }
-  h = mlb_u32x4{cgg_pack2(a[0], a[1]), cgg_pack2(a[2], a[3]), cgg_pack2(a[4], a[5]), cgg_pack2(a[6], a[7])};
-  if (SPLIT) l = mlb_u32x4{cgg_pack2(b[0], b[1]), cgg_pack2(b[2], b[3]), cgg_pack2(b[4], b[5]), cgg_pack2(b[6], b[7])};
+  h = u32x4{cgg_pack2(a[0], a[1]), cgg_pack2(a[2], a[3]), cgg_pack2(a[4], a[5]), cgg_pack2(a[6], a[7])};
+  if (SPLIT) l = u32x4{cgg_pack2(b[0], b[1]), cgg_pack2(b[2], b[3]), cgg_pack2(b[4], b[5]), cgg_pack2(b[6], b[7])};
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -40,8 +38,8 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_feat_kernel(const fl
                                                                         int KS, int q0, int Qtot, int accumulate) {
   constexpr int C = 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  mlb_u32x4* a_hi = reinterpret_cast<mlb_u32x4*>(smem_raw);            // [8 ct][KS][64]
-  mlb_u32x4* a_lo = a_hi + 8 * KS * 64;
+  u32x4* a_hi = reinterpret_cast<u32x4*>(smem_raw);            // [8 ct][KS][64]
+  u32x4* a_lo = a_hi + 8 * KS * 64;
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 31, hi = lane >> 5;
   // ---- prologue: embed^T[b] -> A fragments: slot (ct, ks, lane) = E[q = 16 ks + 8 hi + e][c = 32 ct + j], e = 0..7 ----
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_feat_kernel(const fl
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (q0 + e < Q) ? eb[(size_t)(q0 + e) * C + c] : 0.f;
-    mlb_u32x4 h, l;
+    u32x4 h, l;
     mlb_pack8<SPLIT>(v, h, l);
     a_hi[s] = h;
     if (SPLIT) a_lo[s] = l;
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_feat_kernel(const fl
     const int p = 32 * t + j;
     const bool pin = p < npix;
     const int pc = pin ? p : npix - 1;
-    mlb_u32x4 bh[16], bl[SPLIT ? 8 : 1];
+    u32x4 bh[16], bl[SPLIT ? 8 : 1];
     // the loads of 8 k-steps (64 values per lane) are issued back to back (clamped addresses, no predication: a predicated
     // load per element serialises on its own wait); out-of-range rows / pixels are zeroed by selects afterwards
 #pragma unroll
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_feat_kernel(const fl
           const int ks = 8 * half + k8;
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[k8][e] = (pin && 16 * ks + 8 * hi + e < Q) ? v[k8][e] : 0.f;
-          mlb_u32x4 l;
+          u32x4 l;
           mlb_pack8<SPLIT>(v[k8], bh[ks], l);
           if (SPLIT) bl[ks & 7] = l;
         }
@@ -98,8 +96,8 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_feat_kernel(const fl
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const mlb_u32x4* ah = a_hi + (ct * KS) * 64 + lane;
-      const mlb_u32x4* al = a_lo + (ct * KS) * 64 + lane;
+      const u32x4* ah = a_hi + (ct * KS) * 64 + lane;
+      const u32x4* al = a_lo + (ct * KS) * 64 + lane;
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
         if (ks < KS) {
@@ -171,7 +169,7 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_embed_kernel(const f
     float v[8];
 #pragma unroll
     for (int e = 0; e < 4; ++e) { v[e] = pin ? fx[0][e] : 0.f; v[4 + e] = pin ? fx[1][e] : 0.f; }
-    mlb_u32x4 fh, fl;
+    u32x4 fh, fl;
     mlb_pack8<SPLIT>(v, fh, fl);
     const bf16x8 vfh = __builtin_bit_cast(bf16x8, fh);
 #pragma unroll
@@ -179,7 +177,7 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_embed_kernel(const f
       const bool ok = pin && qok[mt];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v[e] = ok ? gx[mt][0][e] : 0.f; v[4 + e] = ok ? gx[mt][1][e] : 0.f; }
-      mlb_u32x4 gh, gl;
+      u32x4 gh, gl;
       mlb_pack8<SPLIT>(v, gh, gl);
       const bf16x8 vgh = __builtin_bit_cast(bf16x8, gh);
       if constexpr (SPLIT) {

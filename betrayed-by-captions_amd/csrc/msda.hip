@@ -137,47 +137,33 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_kernel(
 //     (two channels per instruction): 16 packed FMAs per point instead of 40 scalar ones.
 // Same inputs / outputs; the summation order differs from the kernel above (w_p c_k folded first), so results agree to
 // rounding of the f32 accumulation (<= 1 bf16 ulp on the output), not bit for bit.
-typedef float msda_v2f __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-__device__ __forceinline__ float msda_quad_bcast(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int msda_quad_bcast(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
-}
-template <int CTRL>
-__device__ __forceinline__ float msda_quad_bcast_ctrl(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
 
 // sum over the 8 lanes of an aligned lane octet by DPP (no LDS): every lane ends up with the octet's sum
 __device__ __forceinline__ void msda_reduce8(float& v) {
-  v += msda_quad_bcast_ctrl<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-  v += msda_quad_bcast_ctrl<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-  v += msda_quad_bcast_ctrl<0x141>(v);      // row_half_mirror
+  v += cgg_dpp<0xB1>(v);       // quad_perm [1, 0, 3, 2]
+  v += cgg_dpp<0x4E>(v);       // quad_perm [2, 3, 0, 1]
+  v += cgg_dpp<0x141>(v);      // row_half_mirror
 }
 
 template <int PSEL>
-__device__ __forceinline__ void msda_point_gather(msda_v2f (&acc)[4], const uint16_t* __restrict__ vl, const int (&my_o)[4],
+__device__ __forceinline__ void msda_point_gather(f32x2 (&acc)[4], const uint16_t* __restrict__ vl, const int (&my_o)[4],
                                                   const float (&my_w)[4]) {
   constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);      // quad_perm: every lane reads lane PSEL of its quad
   uint4 u[4];
   float w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int o = msda_quad_bcast<CTRL>(my_o[k]);
-    w[k] = msda_quad_bcast<CTRL>(my_w[k]);
+    const int o = cgg_dpp<CTRL>(my_o[k]);
+    w[k] = cgg_dpp<CTRL>(my_w[k]);
     u[k] = *reinterpret_cast<const uint4*>(vl + o);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const uint32_t q[4] = {u[k].x, u[k].y, u[k].z, u[k].w};
-    const msda_v2f ww = {w[k], w[k]};
+    const f32x2 ww = {w[k], w[k]};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const msda_v2f vv = {__uint_as_float(q[c] << 16), __uint_as_float(q[c] & 0xffff0000u)};
+      const f32x2 vv = {__uint_as_float(q[c] << 16), __uint_as_float(q[c] & 0xffff0000u)};
       acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
     }
   }
@@ -246,9 +232,9 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_kernel(
   for (int l = 0; l < L; ++l)
     pw[l] = (cq == 0 ? e[4 * l] : (cq == 1 ? e[4 * l + 1] : (cq == 2 ? e[4 * l + 2] : e[4 * l + 3]))) * sinv;
 
-  msda_v2f acc[4];
+  f32x2 acc[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = msda_v2f{0.f, 0.f};
+  for (int c = 0; c < 4; ++c) acc[c] = f32x2{0.f, 0.f};
 #pragma unroll 1
   for (int l = 0; l < L; ++l) {
     const int Hl = lv.h[l], Wl = lv.w[l];
@@ -277,24 +263,24 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_kernel(
 // 8 channels per lane = two 16-byte loads per tap), same arithmetic order as the bf16 kernel with exact f32 operands; replaces
 // the generic cgg_msda_fwd_kernel<float> (one lane per 4 channels, software 64-bit divisions) in the x3 encoder stream.
 template <int PSEL>
-__device__ __forceinline__ void msda_point_gather_f32(msda_v2f (&acc)[4], const float* __restrict__ vl, const int (&my_o)[4],
+__device__ __forceinline__ void msda_point_gather_f32(f32x2 (&acc)[4], const float* __restrict__ vl, const int (&my_o)[4],
                                                       const float (&my_w)[4]) {
   constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);      // quad_perm: every lane reads lane PSEL of its quad
   f32x4 u[4][2];
   float w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int o = msda_quad_bcast<CTRL>(my_o[k]);
-    w[k] = msda_quad_bcast<CTRL>(my_w[k]);
+    const int o = cgg_dpp<CTRL>(my_o[k]);
+    w[k] = cgg_dpp<CTRL>(my_w[k]);
     u[k][0] = *reinterpret_cast<const f32x4*>(vl + o);
     u[k][1] = *reinterpret_cast<const f32x4*>(vl + o + 16);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const msda_v2f ww = {w[k], w[k]};
+    const f32x2 ww = {w[k], w[k]};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const msda_v2f vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
+      const f32x2 vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
       acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
     }
   }
@@ -303,24 +289,24 @@ __device__ __forceinline__ void msda_point_gather_f32(msda_v2f (&acc)[4], const 
 // ... with the level base in scalar registers and the taps as 32-bit BYTE offsets (T2D == 2: image and head are block-uniform): the
 // loads take the `saddr + voffset` form, no 64-bit pointer arithmetic per tap (28 + 17 of the ~200 VALU instructions per level)
 template <int PSEL>
-__device__ __forceinline__ void msda_point_gather_f32_b(msda_v2f (&acc)[4], const char* __restrict__ vlb, const uint32_t (&my_o)[4],
+__device__ __forceinline__ void msda_point_gather_f32_b(f32x2 (&acc)[4], const char* __restrict__ vlb, const uint32_t (&my_o)[4],
                                                         const float (&my_w)[4], uint32_t lane_b) {
   constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);
   f32x4 u[4][2];
   float w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const uint32_t o = (uint32_t)msda_quad_bcast<CTRL>((int)my_o[k]) + lane_b;      // (the lane's own channel offset: AFTER the broadcast)
-    w[k] = msda_quad_bcast<CTRL>(my_w[k]);
+    const uint32_t o = (uint32_t)cgg_dpp<CTRL>((int)my_o[k]) + lane_b;      // (the lane's own channel offset: AFTER the broadcast)
+    w[k] = cgg_dpp<CTRL>(my_w[k]);
     u[k][0] = *reinterpret_cast<const f32x4*>(vlb + o);
     u[k][1] = *reinterpret_cast<const f32x4*>(vlb + o + 64u);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const msda_v2f ww = {w[k], w[k]};
+    const f32x2 ww = {w[k], w[k]};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const msda_v2f vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
+      const f32x2 vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
       acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
     }
   }
@@ -405,9 +391,9 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_f32_kernel(
   for (int l = 0; l < L; ++l)
     pw[l] = (cq == 0 ? e[4 * l] : (cq == 1 ? e[4 * l + 1] : (cq == 2 ? e[4 * l + 2] : e[4 * l + 3]))) * sinv;
 
-  msda_v2f acc[4];
+  f32x2 acc[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) acc[c] = msda_v2f{0.f, 0.f};
+  for (int c = 0; c < 4; ++c) acc[c] = f32x2{0.f, 0.f};
 #pragma unroll 1
   for (int l = 0; l < L; ++l) {
     const int Hl = lv.h[l], Wl = lv.w[l];
@@ -608,7 +594,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSDA_GATHER
       ol1 = cgg_ld4(glp + 8 * l + 4);
     }
     const float xs[4] = {xy0[0], xy0[2], xy1[0], xy1[2]}, ys[4] = {xy0[1], xy0[3], xy1[1], xy1[3]};
-    const msda_v2f glo = {g[0], g[1]}, ghi = {g[2], g[3]};
+    const f32x2 glo = {g[0], g[1]}, ghi = {g[2], g[3]};
     const uint32_t rs_b = (uint32_t)rowstride * 4u, row_b = (uint32_t)Wl * rs_b;      // bytes per pixel / per pixel row of the level
     // the level's four points in two PAIRS (8 corner loads in flight each): all 16 at once needed 130+ registers = 3 waves per SIMD
     auto pair = [&](auto p0c) {
@@ -654,8 +640,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MSDA_GATHER
         // (packed: the natural register pairs of a loaded vector times (g0, g1) / (g2, g3), one horizontal add per corner -- the
         // per-channel form made the compiler pair channels of DIFFERENT corners and shuffle registers for it)
         auto dot4 = [&](const f32x4& vv) {
-          msda_v2f t = msda_v2f{vv[0], vv[1]} * glo;
-          t = __builtin_elementwise_fma(msda_v2f{vv[2], vv[3]}, ghi, t);
+          f32x2 t = f32x2{vv[0], vv[1]} * glo;
+          t = __builtin_elementwise_fma(f32x2{vv[2], vv[3]}, ghi, t);
           return t[0] + t[1];
         };
         float d00 = dot4(v00), d01 = dot4(v01), d10 = dot4(v10), d11 = dot4(v11);

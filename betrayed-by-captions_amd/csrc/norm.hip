@@ -375,10 +375,10 @@ __global__ __launch_bounds__(256) void cgg_gn_nhwc_apply_kernel(
     if (x3a & 2) {
       // the low-resolution map is stored as x3a rows (csrc/x3.h): a group of 8 channels = [8 hi | 8 lo]
       float a[8], c[8], d[8], e[8];
-      const cgg_u32x4* q00 = reinterpret_cast<const cgg_u32x4*>(r00);
-      const cgg_u32x4* q01 = reinterpret_cast<const cgg_u32x4*>(r01);
-      const cgg_u32x4* q10 = reinterpret_cast<const cgg_u32x4*>(r10);
-      const cgg_u32x4* q11 = reinterpret_cast<const cgg_u32x4*>(r11);
+      const u32x4* q00 = reinterpret_cast<const u32x4*>(r00);
+      const u32x4* q01 = reinterpret_cast<const u32x4*>(r01);
+      const u32x4* q10 = reinterpret_cast<const u32x4*>(r10);
+      const u32x4* q11 = reinterpret_cast<const u32x4*>(r11);
       cgg_x3a_decode8(q00[0], q00[1], a);
       cgg_x3a_decode8(q01[0], q01[1], c);
       cgg_x3a_decode8(q10[0], q10[1], d);
@@ -409,10 +409,10 @@ __global__ __launch_bounds__(256) void cgg_gn_nhwc_apply_kernel(
     }
     float* o = y32 + (size_t)b * y32_bstride + ov * 8;
     if (x3a & 1) {             // x3a rows: the group's hi and lo pieces
-      cgg_u32x4 h, l;
+      u32x4 h, l;
       cgg_x3a_encode8(f, h, l);
-      reinterpret_cast<cgg_u32x4*>(o)[0] = h;
-      reinterpret_cast<cgg_u32x4*>(o)[1] = l;
+      reinterpret_cast<u32x4*>(o)[0] = h;
+      reinterpret_cast<u32x4*>(o)[1] = l;
       float am = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k) am = fmaxf(am, fabsf(f[k]));
@@ -430,9 +430,9 @@ __global__ __launch_bounds__(256) void cgg_gn_nhwc_apply_kernel(
       g2[k] = f[k] + pa[k];
       g2[k + 4] = f[k + 4] + pb[k];
     }
-    cgg_u32x4 h, l;
+    u32x4 h, l;
     cgg_x3a_encode8(g2, h, l);
-    cgg_u32x4* o = reinterpret_cast<cgg_u32x4*>(yp32 + (size_t)b * y32_bstride + (size_t)i * 8);
+    u32x4* o = reinterpret_cast<u32x4*>(yp32 + (size_t)b * y32_bstride + (size_t)i * 8);
     o[0] = h;
     o[1] = l;
   }

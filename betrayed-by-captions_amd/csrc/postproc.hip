@@ -189,14 +189,13 @@ __global__ __launch_bounds__(256) void cgg_instance_masks_int_kernel(const float
         ymin = min(ymin, oy);
         ymax = max(ymax, oy);
       }
-      typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-      const u32x4_t pkv = {packed[0], packed[1], packed[2], packed[3]};
+      const u32x4 pkv = {packed[0], packed[1], packed[2], packed[3]};
       for (int d = d0; d < d1; ++d) {
         const size_t slot = dest_off != nullptr ? (size_t)dest_slot[d] : (size_t)i;
         if (BITS)
           reinterpret_cast<uint16_t*>(masks)[(slot * npix + (size_t)oy * g.out_w + ox0) >> 4] = (uint16_t)run;
         else
-          __builtin_nontemporal_store(pkv, reinterpret_cast<u32x4_t*>(masks + slot * npix + (size_t)oy * g.out_w + ox0));
+          __builtin_nontemporal_store(pkv, reinterpret_cast<u32x4*>(masks + slot * npix + (size_t)oy * g.out_w + ox0));
       }
     }
   }
@@ -339,7 +338,7 @@ __global__ __launch_bounds__(256) void cgg_softmax_argmax_kernel(const float* __
   if (mi >= n) mi = 0;
   float sum = 0.f;
   for (int i = lane; i < n; i += 64) sum += expf(xr[i] - m);
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  sum = cgg_wave_sum(sum);
   const float inv = 1.f / sum;
   if (prob != nullptr)
     for (int i = lane; i < n; i += 64) prob[(size_t)row * n + i] = expf(xr[i] - m) * inv;
@@ -497,14 +496,14 @@ __global__ __launch_bounds__(64 * CT_WAVES) void cgg_class_topk_kernel(const flo
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = lane + 64 * u < nc ? xr[lane + 64 * u] : -INFINITY;
       float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      m = cgg_wave_max(m);
       float sum = 0.f;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         v[u] = expf(v[u] - m);
         if (lane + 64 * u < nc) sum += v[u];
       }
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+      sum = cgg_wave_sum(sum);
       const float inv = 1.f / sum;
 #pragma unroll
       for (int u = 0; u < 4; ++u)
@@ -512,10 +511,10 @@ __global__ __launch_bounds__(64 * CT_WAVES) void cgg_class_topk_kernel(const flo
     } else {
       float m = -INFINITY;
       for (int i = lane; i < nc; i += 64) m = fmaxf(m, xr[i]);
-      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      m = cgg_wave_max(m);
       float sum = 0.f;
       for (int i = lane; i < nc; i += 64) sum += expf(xr[i] - m);
-      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+      sum = cgg_wave_sum(sum);
       const float inv = 1.f / sum;
       for (int i = lane; i < n; i += 64) prob[q * n + i] = __float_as_uint(expf(xr[i] - m) * inv);
     }

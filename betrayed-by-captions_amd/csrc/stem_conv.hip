@@ -15,8 +15,6 @@
 // channel-last convolution out (un-scaled in the epilogue); replaces MIOpen's f32 solver (213 us at configs[1]).
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define ST_TH 8                        // output rows per workgroup
 #define ST_TW 32                       // output columns per workgroup
 #define ST_IH (2 * ST_TH + 5)          // 21 input rows

@@ -16,17 +16,15 @@
 #include "x3.h"
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(4))) uint32_t wg_u32x4;
-typedef __attribute__((ext_vector_type(4))) short wg_s16x4;
-typedef __attribute__((address_space(3))) wg_s16x4 wg_lds_s16x4;
+typedef __attribute__((address_space(3))) s16x4 wg_lds_s16x4;
 
 template <int RS>
-__device__ __forceinline__ wg_u32x4 wg_tr_frag(const unsigned char* plane, int row0, int colbyte) {
+__device__ __forceinline__ u32x4 wg_tr_frag(const unsigned char* plane, int row0, int colbyte) {
   // rows row0 .. row0 + 3 (first half) and row0 + 4 .. row0 + 7 (second half) of this lane's column group
-  const wg_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4*)(plane + row0 * RS + colbyte));
-  const wg_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4*)(plane + (row0 + 4) * RS + colbyte));
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4*)(plane + row0 * RS + colbyte));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4*)(plane + (row0 + 4) * RS + colbyte));
   const uint2 au = __builtin_bit_cast(uint2, a), bu = __builtin_bit_cast(uint2, b);
-  return wg_u32x4{au.x, au.y, bu.x, bu.y};
+  return u32x4{au.x, au.y, bu.x, bu.y};
 }
 
 // Tile BT x BT (128: 2 x 2 waves of 2 x 2 MFMA tiles; 256: 2 x 4 waves of 4 x 2 MFMA tiles -- each operand is then read once per
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(BT == 128 ? 256 : 512) void cgg_wgrad_x3_kernel(con
   auto compute = [&](int sb) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wg_u32x4 ah[TA], al[TA], bh[TB], bl[TB];
+      u32x4 ah[TA], al[TA], bh[TB], bl[TB];
 #pragma unroll
       for (int t = 0; t < TA; ++t) {
         const int cy = 2 * (wn * 32 * TA + t * 32) + colb;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(BT == 128 ? 256 : 512) void cgg_wgrad_x3_kernel(con
   if (colfull && (size_t)N * K * 4u < 0xFFFFFF00ull) {
     // interior tile: buffer stores, the row term of the address in a scalar register (one multiply + one store per element; the
     // generic form below computes a 64-bit address and two bounds tests per element)
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(wsp, 0, (uint32_t)((size_t)N * K * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rw = cgg_buffer_rsrc(wsp, (uint32_t)((size_t)N * K * 4u));
     const int wn_u = __builtin_amdgcn_readfirstlane(wn), wk_u = __builtin_amdgcn_readfirstlane(wk);
     const uint32_t voff = (uint32_t)(4 * hi5 * K + j) * 4u;
 #pragma unroll

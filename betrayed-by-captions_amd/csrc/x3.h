@@ -26,17 +26,15 @@
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-typedef __attribute__((ext_vector_type(2))) float cgg_f32x2;
-typedef __attribute__((ext_vector_type(4))) uint32_t cgg_u32x4;
 
 #define CGG_X3_ASCALE 16.0f
 #define CGG_X3_INV_ASCALE 0.0625f
 
 // (a, b) -> packed f16 pair hi and residual pair lo of the values AS GIVEN (caller applies the pre-scale)
 __device__ __forceinline__ void cgg_x3_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  const cgg_f32x2 v = {a, b};
+  const f32x2 v = {a, b};
   const f16x2 h = __builtin_convertvector(v, f16x2);                       // v_cvt_pk_f16_f32 (RNE)
-  const cgg_f32x2 r = v - __builtin_convertvector(h, cgg_f32x2);           // exact
+  const f32x2 r = v - __builtin_convertvector(h, f32x2);                   // exact
   const f16x2 l = __builtin_convertvector(r, f16x2);
   hi = __builtin_bit_cast(uint32_t, h);
   lo = __builtin_bit_cast(uint32_t, l);
@@ -88,21 +86,21 @@ __device__ __forceinline__ void cgg_x3_split4_s(const f32x4 v, float sc, uint2& 
   cgg_x3_split2_s(v[0], v[1], sc, hi.x, lo.x);
   cgg_x3_split2_s(v[2], v[3], sc, hi.y, lo.y);
 }
-__device__ __forceinline__ void cgg_x3_split8_s(const f32x4 v0, const f32x4 v1, float sc, cgg_u32x4& hi, cgg_u32x4& lo) {
+__device__ __forceinline__ void cgg_x3_split8_s(const f32x4 v0, const f32x4 v1, float sc, u32x4& hi, u32x4& lo) {
   uint2 h0, l0, h1, l1;
   cgg_x3_split4_s(v0, sc, h0, l0);
   cgg_x3_split4_s(v1, sc, h1, l1);
-  hi = cgg_u32x4{h0.x, h0.y, h1.x, h1.y};
-  lo = cgg_u32x4{l0.x, l0.y, l1.x, l1.y};
+  hi = u32x4{h0.x, h0.y, h1.x, h1.y};
+  lo = u32x4{l0.x, l0.y, l1.x, l1.y};
 }
 
 // 8 activations -> one 16-byte A-fragment slot each
-__device__ __forceinline__ void cgg_x3_split8(const f32x4 v0, const f32x4 v1, cgg_u32x4& hi, cgg_u32x4& lo) {
+__device__ __forceinline__ void cgg_x3_split8(const f32x4 v0, const f32x4 v1, u32x4& hi, u32x4& lo) {
   uint2 h0, l0, h1, l1;
   cgg_x3_split4(v0, h0, l0);
   cgg_x3_split4(v1, h1, l1);
-  hi = cgg_u32x4{h0.x, h0.y, h1.x, h1.y};
-  lo = cgg_u32x4{l0.x, l0.y, l1.x, l1.y};
+  hi = u32x4{h0.x, h0.y, h1.x, h1.y};
+  lo = u32x4{l0.x, l0.y, l1.x, l1.y};
 }
 
 // one activation -> its two f16 pieces (element-wise fragment stores)
@@ -115,8 +113,7 @@ __device__ __forceinline__ void cgg_x3_split1(float a, uint16_t& hi, uint16_t& l
 }
 
 // acc += A B^T for one k-step, A = (ah, al), B = (bh, bl): small terms first
-__device__ __forceinline__ void cgg_x3_mfma(f32x16& acc, const cgg_u32x4 ah, const cgg_u32x4 al, const cgg_u32x4 bh,
-                                            const cgg_u32x4 bl) {
+__device__ __forceinline__ void cgg_x3_mfma(f32x16& acc, const u32x4 ah, const u32x4 al, const u32x4 bh, const u32x4 bl) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bl), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), acc, 0, 0, 0);
@@ -124,15 +121,15 @@ __device__ __forceinline__ void cgg_x3_mfma(f32x16& acc, const cgg_u32x4 ah, con
 
 // views of an x3 image
 struct CggX3W {
-  const cgg_u32x4* hi;
-  const cgg_u32x4* lo;
+  const u32x4* hi;
+  const u32x4* lo;
   const float* scale;
 };
 
 static inline CggX3W cgg_x3_view(const void* packed, int N, int K) {
   const size_t frags = (size_t)((N + 31) / 32) * (K / 16) * 64;
   CggX3W w;
-  w.hi = (const cgg_u32x4*)packed;
+  w.hi = (const u32x4*)packed;
   w.lo = packed ? w.hi + frags : nullptr;
   w.scale = packed ? (const float*)(w.hi + 2 * frags) : nullptr;
   return w;
@@ -146,43 +143,43 @@ static inline CggX3W cgg_x3_view(const void* packed, int N, int K) {
 // the GEMM loop (csrc/x3s_gemm.hip). The GEMM result is bit-identical to splitting an f32 row in the kernel (the split IS what
 // the kernel did); other consumers (residual adds, LayerNorm, up-sampling) read hi + lo, which carries 22 significant bits.
 // Range: |a| < 4094 (f16 overflow of the pre-scaled value); producers raise the overflow flag (cgg_x3_overflow_flag).
-__device__ __forceinline__ void cgg_x3a_split8_prescaled(const float* s, cgg_u32x4& hi, cgg_u32x4& lo) {
+__device__ __forceinline__ void cgg_x3a_split8_prescaled(const float* s, u32x4& hi, u32x4& lo) {
   uint32_t h[4], l[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) cgg_x3_split2(s[2 * k], s[2 * k + 1], h[k], l[k]);
-  hi = cgg_u32x4{h[0], h[1], h[2], h[3]};
-  lo = cgg_u32x4{l[0], l[1], l[2], l[3]};
+  hi = u32x4{h[0], h[1], h[2], h[3]};
+  lo = u32x4{l[0], l[1], l[2], l[3]};
 }
-__device__ __forceinline__ void cgg_x3a_encode8(const float* f, cgg_u32x4& hi, cgg_u32x4& lo) {
+__device__ __forceinline__ void cgg_x3a_encode8(const float* f, u32x4& hi, u32x4& lo) {
   float s[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) s[k] = f[k] * CGG_X3_ASCALE;
   cgg_x3a_split8_prescaled(s, hi, lo);
 }
 // -> the PRE-SCALED values 16 a (exact: hi + lo has <= 23 significant bits)
-__device__ __forceinline__ void cgg_x3a_decode8_prescaled(const cgg_u32x4 hi, const cgg_u32x4 lo, float* s) {
+__device__ __forceinline__ void cgg_x3a_decode8_prescaled(const u32x4 hi, const u32x4 lo, float* s) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     // (the element is copied to a scalar first: __builtin_bit_cast applied to the vector-element lvalue `hi[k]` read element 0
     // for every k with hipcc 7.2)
     const uint32_t hk = hi[k], lk = lo[k];
-    const cgg_f32x2 h = __builtin_convertvector(__builtin_bit_cast(f16x2, hk), cgg_f32x2);
-    const cgg_f32x2 l = __builtin_convertvector(__builtin_bit_cast(f16x2, lk), cgg_f32x2);
+    const f32x2 h = __builtin_convertvector(__builtin_bit_cast(f16x2, hk), f32x2);
+    const f32x2 l = __builtin_convertvector(__builtin_bit_cast(f16x2, lk), f32x2);
     s[2 * k] = h[0] + l[0];
     s[2 * k + 1] = h[1] + l[1];
   }
 }
-__device__ __forceinline__ void cgg_x3a_decode8(const cgg_u32x4 hi, const cgg_u32x4 lo, float* f) {
+__device__ __forceinline__ void cgg_x3a_decode8(const u32x4 hi, const u32x4 lo, float* f) {
   cgg_x3a_decode8_prescaled(hi, lo, f);
 #pragma unroll
   for (int k = 0; k < 8; ++k) f[k] *= CGG_X3_INV_ASCALE;
 }
 // 4 channels (half a group): 8-byte halves of the hi and lo pieces
 __device__ __forceinline__ void cgg_x3a_decode4(const uint2 hi, const uint2 lo, f32x4& f) {
-  const cgg_f32x2 h0 = __builtin_convertvector(__builtin_bit_cast(f16x2, hi.x), cgg_f32x2);
-  const cgg_f32x2 l0 = __builtin_convertvector(__builtin_bit_cast(f16x2, lo.x), cgg_f32x2);
-  const cgg_f32x2 h1 = __builtin_convertvector(__builtin_bit_cast(f16x2, hi.y), cgg_f32x2);
-  const cgg_f32x2 l1 = __builtin_convertvector(__builtin_bit_cast(f16x2, lo.y), cgg_f32x2);
+  const f32x2 h0 = __builtin_convertvector(__builtin_bit_cast(f16x2, hi.x), f32x2);
+  const f32x2 l0 = __builtin_convertvector(__builtin_bit_cast(f16x2, lo.x), f32x2);
+  const f32x2 h1 = __builtin_convertvector(__builtin_bit_cast(f16x2, hi.y), f32x2);
+  const f32x2 l1 = __builtin_convertvector(__builtin_bit_cast(f16x2, lo.y), f32x2);
   f = f32x4{h0[0] + l0[0], h0[1] + l0[1], h1[0] + l1[0], h1[1] + l1[1]} * CGG_X3_INV_ASCALE;
 }
 // largest finite pre-scaled magnitude: beyond it the hi piece is inf

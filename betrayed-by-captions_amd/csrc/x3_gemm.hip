@@ -30,19 +30,12 @@
 // with one wave per SIMD every LDS / memory wait is exposed; that tile needs hand-placed waits and prefetch, not a template argument.
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-
 #define XG_BK 32
 #define XG_NT 256
 
 struct XgConv {
   int H, W, C, OH, OW, KW, stride, pad;      // channel-last input [B][H][W][C]; K = KH * KW * C
 };
-
-// raw buffer descriptor over `bytes` bytes at p: loads at offsets >= bytes return 0 (the conv loader's zero padding)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xg_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 // Workgroup tile = (64 TM) x (64 TN): 2 x 2 wavefronts, each TM x TN MFMA tiles of 32 x 32. (2, 2) is the throughput shape;
 // the smaller ones keep every CU busy when the problem has few tiles (deep ResNet stages: 2048 rows) or N = 64.
@@ -74,7 +67,7 @@ __global__ __launch_bounds__(XG_NT, (TM + TN == 4) ? 2 : (TM + TN == 3) ? 3 : 4)
   //      read row M - 1 (their results are never stored); the conv form sends taps outside the map to an out-of-range
   //      offset of the buffer descriptor, which the hardware answers with zeros ----
   const int ar = tid >> 2, k8 = tid & 3;
-  const __amdgpu_buffer_rsrc_t arsrc = xg_rsrc(A, a_bytes);
+  const __amdgpu_buffer_rsrc_t arsrc = cgg_buffer_rsrc(A, a_bytes);
   uint32_t aoff[TM];                                       // byte offset of the row (GEMM) / of the image (CONV) + 32 k8
   int aiy[TM], aix[TM];                                    // CONV: top-left input coordinate of the row's receptive field
   int aslot[TM];                                           // LDS slot: m-tile (row >> 5), k-step k8 >> 1, half k8 & 1, swizzled row
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(XG_NT, (TM + TN == 4) ? 2 : (TM + TN == 3) ? 3 : 4)
   }
   // ---- B loader: unit u = q 256 + tid -> (piece, n-tile, k-step, lane) of the x3 image; n-tiles past the weight read its last
   //      tile (columns >= N are never stored) ----
-  const __amdgpu_buffer_rsrc_t brsrc = xg_rsrc(w.hi, w_bytes);
+  const __amdgpu_buffer_rsrc_t brsrc = cgg_buffer_rsrc(w.hi, w_bytes);
   uint32_t boff[NB];                                       // byte offset inside the x3 image at chunk 0; + 2 KiB per chunk
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(XG_NT, (TM + TN == 4) ? 2 : (TM + TN == 3) ? 3 : 4)
   const size_t r_span = res ? (size_t)M * (size_t)ldr * 4u : 0;
   if (full && res_mod == 0 && o_span < 0xFFFFFF00ull && o2_span < 0xFFFFFF00ull && r_span < 0xFFFFFF00ull) {
     const float floor_v = relu ? 0.f : -__builtin_inff();
-    const __amdgpu_buffer_rsrc_t rres = xg_rsrc(res ? res : out, 0xFFFFFF00u);
+    const __amdgpu_buffer_rsrc_t rres = cgg_buffer_rsrc(res ? res : out, 0xFFFFFF00u);
 #pragma unroll
     for (int nt = 0; nt < TN; ++nt) {
       const int ncol0 = __builtin_amdgcn_readfirstlane((nt0 + TN * wn + nt) * 32);      // first column of the tile (wave-uniform)
@@ -251,7 +244,7 @@ __global__ __launch_bounds__(XG_NT, (TM + TN == 4) ? 2 : (TM + TN == 3) ? 3 : 4)
       const float bs = bias ? bias[n] : 0.f;
       const bool second = out2 != nullptr && ncol0 >= col2;
       const int ldo = second ? ldc2 : ldc;
-      const __amdgpu_buffer_rsrc_t rout = xg_rsrc(second ? out2 - col2 : out, 0xFFFFFF00u);
+      const __amdgpu_buffer_rsrc_t rout = cgg_buffer_rsrc(second ? out2 - col2 : out, 0xFFFFFF00u);
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt) {
         const int mrow0 = __builtin_amdgcn_readfirstlane(m0 + 32 * (TM * wm + mt));      // wave-uniform

@@ -32,7 +32,6 @@
 #include <mutex>
 #include "x3.h"
 
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((address_space(3))) void* xs_lds_t;
 
 struct XsConv {
@@ -55,10 +54,6 @@ struct XsArgs {
   uint32_t a_bytes, w_bytes;
   int* flag;                      // overflow flag word (x3a output)
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xs_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
 
 template <int N>
 __device__ __forceinline__ void xs_wait_vmcnt() {
@@ -97,8 +92,8 @@ __device__ __forceinline__ uint32_t xs_sel(uint32_t a, uint32_t b, uint32_t mask
 // 8 bytes of lane ^ 1 (the other half of the lane pair that shares an 8-column group)
 __device__ __forceinline__ uint2 xs_pair_swap(const uint2 v) {
   uint2 r;
-  r.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.x, 0xB1, 0xf, 0xf, true);      // quad_perm [1, 0, 3, 2]
-  r.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.y, 0xB1, 0xf, 0xf, true);
+  r.x = cgg_lane_xor1(v.x);
+  r.y = cgg_lane_xor1(v.y);
   return r;
 }
 
@@ -177,10 +172,10 @@ __device__ __forceinline__ float xs_finish_column(const float* scratch, int TM_,
         const uint2 got = xs_pair_swap(send);                                                    // my columns of the partner's piece
         const uint2 hh = {xs_sel(keep.x, got.x, om), xs_sel(keep.y, got.y, om)};
         const uint2 ll = {xs_sel(got.x, keep.x, om), xs_sel(got.y, keep.y, om)};
-        const cgg_f32x2 h0 = __builtin_convertvector(__builtin_bit_cast(f16x2, hh.x), cgg_f32x2);
-        const cgg_f32x2 h1 = __builtin_convertvector(__builtin_bit_cast(f16x2, hh.y), cgg_f32x2);
-        const cgg_f32x2 l0 = __builtin_convertvector(__builtin_bit_cast(f16x2, ll.x), cgg_f32x2);
-        const cgg_f32x2 l1 = __builtin_convertvector(__builtin_bit_cast(f16x2, ll.y), cgg_f32x2);
+        const f32x2 h0 = __builtin_convertvector(__builtin_bit_cast(f16x2, hh.x), f32x2);
+        const f32x2 h1 = __builtin_convertvector(__builtin_bit_cast(f16x2, hh.y), f32x2);
+        const f32x2 l0 = __builtin_convertvector(__builtin_bit_cast(f16x2, ll.x), f32x2);
+        const f32x2 l1 = __builtin_convertvector(__builtin_bit_cast(f16x2, ll.y), f32x2);
         w += f32x4{h0[0] + l0[0], h0[1] + l0[1], h1[0] + l1[0], h1[1] + l1[1]};
       }
 #pragma unroll
@@ -216,9 +211,9 @@ __device__ __forceinline__ float xs_finish_column(const float* scratch, int TM_,
 
 __device__ __forceinline__ XsEpi xs_epi_setup(const XsArgs& p, int mrow0, int lane) {
   XsEpi e;
-  e.orsrc = xs_rsrc(p.out, (uint32_t)(((size_t)(p.M - 1) * p.ldc + p.N) * 4));
+  e.orsrc = cgg_buffer_rsrc(p.out, (uint32_t)(((size_t)(p.M - 1) * p.ldc + p.N) * 4));
   const int res_rows = p.res_mod ? p.res_mod : p.M;
-  e.rrsrc = xs_rsrc(p.res_fmt ? p.res : p.out, p.res_fmt ? (uint32_t)(((size_t)(res_rows - 1) * p.ldr + p.N) * 4) : 0u);
+  e.rrsrc = cgg_buffer_rsrc(p.res_fmt ? p.res : p.out, p.res_fmt ? (uint32_t)(((size_t)(res_rows - 1) * p.ldr + p.N) * 4) : 0u);
   e.lo_clamp = p.relu ? 0.f : -__builtin_inff();
   e.mr0 = mrow0 + (lane >> 3);
   if (p.res_fmt && p.res_mod) e.mr0 %= p.res_mod;
@@ -343,7 +338,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
   const int niter = (nchunk + KG - 1) / KG;
 
   // ---- A pieces of this lane: piece q = wave + NW i of the iteration's [k-group][BM / 8] x 1 KiB; lane -> (row, 16-byte unit) ----
-  const __amdgpu_buffer_rsrc_t arsrc = xs_rsrc(p.A, p.a_bytes);
+  const __amdgpu_buffer_rsrc_t arsrc = cgg_buffer_rsrc(p.A, p.a_bytes);
   uint32_t arow[NA];             // byte offset of the lane's unit at chunk 0 (CONV: at filter tap (0, 0); may wrap below 0)
   uint32_t amask[NA];            // CONV: bit t <=> tap t of the row's output pixel lies inside the map
   int ag[NA];                    // k-group of the piece (wave-uniform)
@@ -381,7 +376,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) void cgg_gemm_x3s_kernel(const X
   }
   // ---- B pieces: piece q = wave + NW i of the iteration's [k-group][n-tile][hi | lo][k-step] x 1 KiB; n-tiles past the weight
   //      re-read its last tile (columns >= N are never stored) ----
-  const __amdgpu_buffer_rsrc_t brsrc = xs_rsrc(p.w.hi, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t brsrc = cgg_buffer_rsrc(p.w.hi, p.w_bytes);
   uint32_t boff[NB];
   int bg[NB];
 #pragma unroll
@@ -581,7 +576,7 @@ __global__ __launch_bounds__(64 * WM * WN) void cgg_conv3x3_halo_kernel(const Xs
   const int KS = p.K >> 4;
 
   // ---- the patch: piece q = wave + NW i covers halo pixels 8 (q % (HPP / 8)) .. + 7 of plane q / (HPP / 8) ----
-  const __amdgpu_buffer_rsrc_t arsrc = xs_rsrc(p.A, p.a_bytes);
+  const __amdgpu_buffer_rsrc_t arsrc = cgg_buffer_rsrc(p.A, p.a_bytes);
 #pragma unroll
   for (int i = 0; i < NAI; ++i) {
     const int q = wave + NW * i;
@@ -596,7 +591,7 @@ __global__ __launch_bounds__(64 * WM * WN) void cgg_conv3x3_halo_kernel(const Xs
     }
   }
   // ---- B pieces, as in the ring kernel: piece q = wave + NW i of a chunk's [n-tile][hi | lo][k-step] x 1 KiB ----
-  const __amdgpu_buffer_rsrc_t brsrc = xs_rsrc(p.w.hi, p.w_bytes);
+  const __amdgpu_buffer_rsrc_t brsrc = cgg_buffer_rsrc(p.w.hi, p.w_bytes);
   uint32_t boff[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i) {

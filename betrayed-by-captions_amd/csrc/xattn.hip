@@ -26,14 +26,11 @@ __device__ __forceinline__ int xa_kswz(int key, int slot) { return slot ^ ((key 
 // BF (throughput-mode TRAINING): the same kernel with bf16 MFMA operands -- every group of four v_mfma_f32_32x32x2_f32 steps (a lane's
 // four consecutive k values) becomes ONE v_mfma_f32_32x32x8_bf16 on the converted 4-vectors; accumulators, layouts, softmax and
 // the f32 K / V rows in memory are unchanged. 1/8 of the MFMA time: the f32 pipe was this kernel's bound (0.4 of its 157-TF peak).
-typedef __attribute__((ext_vector_type(4))) short xa_s16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 xa_bf2;
-typedef __attribute__((ext_vector_type(2))) float xa_f2;
-__device__ __forceinline__ xa_s16x4 xa_cvt4(float a, float b, float c, float d) {
-  const xa_f2 lo = {a, b}, hi = {c, d};
-  const uint2 u = {__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, xa_bf2)),
-                   __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, xa_bf2))};
-  return __builtin_bit_cast(xa_s16x4, u);
+__device__ __forceinline__ s16x4 xa_cvt4(float a, float b, float c, float d) {
+  const f32x2 lo = {a, b}, hi = {c, d};
+  const uint2 u = {__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2)),
+                   __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, bf16x2))};
+  return __builtin_bit_cast(s16x4, u);
 }
 
 template <bool BF>
@@ -557,11 +554,9 @@ __global__ __launch_bounds__(256) void cgg_xattn_combine_wave(const float* __res
     if (any_firm) { mc = -INFINITY; lc = 0.f; }
     else lc = -lc;
   }
-  float M = mc;
-  for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+  const float M = cgg_wave_max(mc);
   const float f = (mc == -INFINITY) ? 0.f : (log2_domain ? __builtin_amdgcn_exp2f(mc - M) : expf(mc - M));
-  float den = f * lc;
-  for (int o = 32; o > 0; o >>= 1) den += __shfl_xor(den, o);
+  const float den = cgg_wave_sum(f * lc);
   const int d = lane & 31, half = lane >> 5;
   float num = 0.f;
   int c = half;

@@ -27,14 +27,11 @@ __device__ __forceinline__ int xb_row(int r, int hi) { return (r & 3) + 8 * (r >
 // BF (throughput-mode training, kv_dtype CGG_F32_BF16MFMA): every group of four 32x32x2 f32 steps -- a lane's four consecutive k
 // values, which is also how the accumulator rows are grouped (xb_row(4 g + e, hi) = 8 g + 4 hi + e) -- becomes one
 // v_mfma_f32_32x32x8_bf16 on the converted 4-vectors; 80 -> 20 MFMAs per (32 queries x 32 keys) at 8 x the rate, layouts unchanged.
-typedef __attribute__((ext_vector_type(4))) short xb_s16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 xb_bf2;
-typedef __attribute__((ext_vector_type(2))) float xb_f2;
-__device__ __forceinline__ xb_s16x4 xb_cvt4(float a, float b, float c, float d) {
-  const xb_f2 lo = {a, b}, hi = {c, d};
-  const uint2 u = {__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, xb_bf2)),
-                   __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, xb_bf2))};
-  return __builtin_bit_cast(xb_s16x4, u);
+__device__ __forceinline__ s16x4 xb_cvt4(float a, float b, float c, float d) {
+  const f32x2 lo = {a, b}, hi = {c, d};
+  const uint2 u = {__builtin_bit_cast(uint32_t, __builtin_convertvector(lo, bf16x2)),
+                   __builtin_bit_cast(uint32_t, __builtin_convertvector(hi, bf16x2))};
+  return __builtin_bit_cast(s16x4, u);
 }
 
 // MODE 2 (round 6, parity-mode training): the same grouping on the f32-class f16 x 3 contraction of x3.h -- every 4-vector operand is
@@ -65,11 +62,6 @@ __device__ __forceinline__ XbX3 xb_split4(float a, float b, float c, float d, fl
   r.h = __builtin_convertvector(v, xb_h4);                                  // RNE
   r.l = __builtin_convertvector(v - __builtin_convertvector(r.h, f32x4), xb_h4);   // the residual is exact in f32
   return r;
-}
-__device__ __forceinline__ float xb_wave_max(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-  return v;
 }
 // the dS pre-scale for a bound on |dS|: 2^(14 - floor(log2 bound)); a zero / denormal / non-finite bound keeps 1
 __device__ __forceinline__ float xb_ds_scale(float bound) {
@@ -145,7 +137,7 @@ __global__ __launch_bounds__(256) void cgg_xattn_bwd_kernel(
   }
   __syncthreads();
   float dmax = 0.f;                                    // x3: max_q |delta_q|, the second term of the dS bound
-  if constexpr (X3) dmax = xb_wave_max(fmaxf(fabsf(Ds[lane]), fabsf(Ds[lane + 64])));
+  if constexpr (X3) dmax = cgg_wave_max(fmaxf(fabsf(Ds[lane]), fabsf(Ds[lane + 64])));
 
   f32x16 dq[4];
 #pragma unroll
@@ -189,7 +181,7 @@ __global__ __launch_bounds__(256) void cgg_xattn_bwd_kernel(
 #pragma unroll
       for (int e = 0; e < 16; ++e) l1 += fabsf(vf[e]);
       l1 += __shfl_xor(l1, 32);
-      const float st = xb_ds_scale(gmax * xb_wave_max(l1) + dmax);
+      const float st = xb_ds_scale(gmax * cgg_wave_max(l1) + dmax);
       if (st < ss) {                                    // wave-uniform
         const float down = st / ss;                     // a power of two <= 1/2
 #pragma unroll

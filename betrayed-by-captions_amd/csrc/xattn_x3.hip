@@ -8,9 +8,7 @@
 #include "x3.h"
 
 #define XA_TK 64  // keys per LDS tile
-typedef __attribute__((ext_vector_type(4))) uint32_t x3_u32x4;
-typedef __attribute__((ext_vector_type(4))) short xa_s16x4;
-typedef __attribute__((address_space(3))) xa_s16x4 xa_lds_s16x4;
+typedef __attribute__((address_space(3))) s16x4 xa_lds_s16x4;
 
 __global__ __launch_bounds__(256) void cgg_xattn_partial_x3(
     const float* __restrict__ q, const float* __restrict__ kv, const uint32_t* __restrict__ bits,
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(256) void cgg_xattn_partial_x3(
   // ---- this wave's queries (pre-scaled), B operand of S^T: lane (j, hi) holds d = 16*hi + s ----
   const int qi = wave * 32 + j;
   const bool wave_live = wave < nmt;
-  x3_u32x4 qh[2], ql[2];      // k-step s: dims 16 s + 8 hi .. + 7 of query qi, pre-scaled by `scale` (and by 16: x3.h)
+  u32x4 qh[2], ql[2];      // k-step s: dims 16 s + 8 hi .. + 7 of query qi, pre-scaled by `scale` (and by 16: x3.h)
   {
     const bool ok = qi < Q;
     const float* qp = q + ((size_t)b * Q + (ok ? qi : 0)) * HD + h * D + 8 * hi;
@@ -117,8 +115,8 @@ __global__ __launch_bounds__(256) void cgg_xattn_partial_x3(
         const unsigned char* kr = Kx + krow * 128;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const x3_u32x4 kh_ = *reinterpret_cast<const x3_u32x4*>(kr + 16 * ((2 * s + hi) ^ sw));
-          const x3_u32x4 kl_ = *reinterpret_cast<const x3_u32x4*>(kr + 16 * ((4 + 2 * s + hi) ^ sw));
+          const u32x4 kh_ = *reinterpret_cast<const u32x4*>(kr + 16 * ((2 * s + hi) ^ sw));
+          const u32x4 kl_ = *reinterpret_cast<const u32x4*>(kr + 16 * ((4 + 2 * s + hi) ^ sw));
           cgg_x3_mfma(sc, kh_, kl_, qh[s], ql[s]);
         }
       }
@@ -158,18 +156,18 @@ __global__ __launch_bounds__(256) void cgg_xattn_partial_x3(
         const int g = lane >> 4, u = g >> 1, d0 = 16 * (g & 1), i16 = lane & 15;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          x3_u32x4 ph, pl;
+          u32x4 ph, pl;
           cgg_x3a_split8_prescaled(p16 + 8 * t, ph, pl);
           // chunk i16 of the transpose read = 4 dims d0 + 4 (i16 & 3) .. of key row (i16 >> 2)
           const int k0 = kt + 8 * (2 * t) + 4 * u + (i16 >> 2), k1 = k0 + 8;
           const int co = 2 * (d0 + 4 * (i16 & 3));
-          const xa_s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vh + k0 * 64 + co));
-          const xa_s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vh + k1 * 64 + co));
-          const xa_s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vl + k0 * 64 + co));
-          const xa_s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vl + k1 * 64 + co));
+          const s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vh + k0 * 64 + co));
+          const s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vh + k1 * 64 + co));
+          const s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vl + k0 * 64 + co));
+          const s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((xa_lds_s16x4*)(Vl + k1 * 64 + co));
           const uint2 h0u = __builtin_bit_cast(uint2, h0), h1u = __builtin_bit_cast(uint2, h1);
           const uint2 l0u = __builtin_bit_cast(uint2, l0), l1u = __builtin_bit_cast(uint2, l1);
-          const x3_u32x4 vh_ = {h0u.x, h0u.y, h1u.x, h1u.y}, vl_ = {l0u.x, l0u.y, l1u.x, l1u.y};
+          const u32x4 vh_ = {h0u.x, h0u.y, h1u.x, h1u.y}, vl_ = {l0u.x, l0u.y, l1u.x, l1u.y};
           cgg_x3_mfma(o, vh_, vl_, ph, pl);
         }
       }
