@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import CGG_BF16, CGG_F32, CggError, check, dev_ptr, stream_ptr
+from ._lib import CGG_BF16, CGG_F32, CGG_F32_BF16MFMA, CGG_F32_X3, CONSTANTS, CggError, check, dev_ptr, host_ptr, stream_ptr
 
 _WS_CACHE = {}
 
@@ -45,11 +45,35 @@ class _timed:
 
 
 def _lib_():
-    return _lib.load()
+    return _lib._lib or _lib.load()       # (the loaded handle without a second frame: this runs once per launch)
+
+
+def _call(symbol, *args, total=False):
+    """The one call path of the status-returning entry points: `symbol` is looked up only now, after Python has evaluated (and
+    `dev_ptr` has checked) every argument, and a non-zero status raises under the name of the symbol that ran. total=True: the
+    entry point answers a byte count (the host RLE functions), only a negative value is a status. Returns what the symbol returned."""
+    rc = getattr(_lib_(), symbol)(*args)
+    if rc < 0 or (rc and not total):
+        check(rc, symbol)
+    return rc
+
+
+def _ptr_at(t, elem_offset, name, dtype):
+    """Device address `elem_offset` elements into tensor `t` (None -> NULL): the one place an offset address is formed. `t` passes
+    the dtype and device tests of `dev_ptr`; what lies at the offset (a column block, a destination inside a larger tensor) is the
+    caller's statement, so density is not tested."""
+    if t is None:
+        return None
+    return ctypes.c_void_p(dev_ptr(t, name, dtype, dense=False).value + int(elem_offset) * t.element_size())
 
 
 def _int_array(vals):
     return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
+
+
+def _levels(level_hw, level_start):
+    """host level table of the MSDeformAttn entries: (int32 [L, 2] = (H_l, W_l), int32 [L] first pixel)"""
+    return _int_array([v for pair in level_hw for v in pair]), _int_array(level_start)
 
 
 _F32_BF16 = (torch.float32, torch.bfloat16)
@@ -83,13 +107,11 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_locations, a
     B, Nv, H, D, L, Nq, P = _msda_dims(value, sampling_locations)
     vdt = _f32_bf16_tag(value, 'msda_forward: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
-    rc = _lib_().cgg_msda_forward(
-        dev_ptr(value, 'value', _F32_BF16), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
-        dev_ptr(level_start_index, 'level_start_index', torch.int64),
-        dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
-        dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(out), B, Nv, H, D, L,
-        Nq, P, vdt, stream_ptr(value.device))
-    check(rc, 'cgg_msda_forward')
+    _call('cgg_msda_forward', dev_ptr(value, 'value', _F32_BF16), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
+          dev_ptr(level_start_index, 'level_start_index', torch.int64),
+          dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
+          dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(out), B, Nv, H, D, L, Nq, P, vdt,
+          stream_ptr(value.device))
     return out
 
 
@@ -98,13 +120,11 @@ def msda_forward_hostlevels(value, level_hw, level_start, sampling_locations, at
     B, Nv, H, D, L, Nq, P = _msda_dims(value, sampling_locations)
     vdt = _f32_bf16_tag(value, 'msda_forward_hostlevels: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
-    hw = _int_array([v for pair in level_hw for v in pair])
-    st = _int_array(level_start)
-    rc = _lib_().cgg_msda_forward_hostlevels(
-        dev_ptr(value, 'value', _F32_BF16), hw, st, dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
-        dev_ptr(attention_weights, 'attention_weights', torch.float32), None, 0, dev_ptr(out), B, Nv,
-        H, D, L, Nq, P, vdt, 0, stream_ptr(value.device))
-    check(rc, 'cgg_msda_forward_hostlevels')
+    hw, st = _levels(level_hw, level_start)
+    _call('cgg_msda_forward_hostlevels', dev_ptr(value, 'value', _F32_BF16), hw, st,
+          dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
+          dev_ptr(attention_weights, 'attention_weights', torch.float32), None, 0, dev_ptr(out), B, Nv, H, D, L, Nq, P, vdt, 0,
+          stream_ptr(value.device))
     return out
 
 
@@ -117,23 +137,18 @@ def msda_forward_fused(value, level_hw, level_start, offs_logits, ref_points, nu
     P = int(num_points)
     vdt = _f32_bf16_tag(value, 'msda_forward_fused: value')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=value.device)
-    hw = _int_array([v for pair in level_hw for v in pair])
-    st = _int_array(level_start)
+    hw, st = _levels(level_hw, level_start)
     vld = _value_row_stride(value)
     if vld != H * D:                        # padded value rows (`padded_value_rows`): the strided-value form of the f32 kernel
         with _timed('msda_fused'):
-            rc = _lib_().cgg_msda_forward_fused_vld(ctypes.c_void_p(value.data_ptr()), vld, hw, st,
-                                                    dev_ptr(offs_logits, 'offs_logits', torch.float32), ld,
-                                                    dev_ptr(ref_points, 'ref_points', torch.float32), dev_ptr(out), B, Nv, H, D, L, Nq, P,
-                                                    stream_ptr(value.device))
-        check(rc, 'cgg_msda_forward_fused_vld')
+            _call('cgg_msda_forward_fused_vld', dev_ptr(value, 'value', torch.float32, dense=False), vld, hw, st,
+                  dev_ptr(offs_logits, 'offs_logits', torch.float32), ld, dev_ptr(ref_points, 'ref_points', torch.float32),
+                  dev_ptr(out), B, Nv, H, D, L, Nq, P, stream_ptr(value.device))
         return out
     with _timed('msda_fused'):
-        rc = _lib_().cgg_msda_forward_hostlevels(
-            dev_ptr(value, 'value', _F32_BF16), hw, st, dev_ptr(offs_logits, 'offs_logits', torch.float32), None,
-            dev_ptr(ref_points, 'ref_points', torch.float32), ld, dev_ptr(out), B, Nv, H, D, L, Nq, P, vdt,
-            1, stream_ptr(value.device))
-    check(rc, 'cgg_msda_forward_hostlevels(fused)')
+        _call('cgg_msda_forward_hostlevels', dev_ptr(value, 'value', _F32_BF16), hw, st,
+              dev_ptr(offs_logits, 'offs_logits', torch.float32), None, dev_ptr(ref_points, 'ref_points', torch.float32), ld,
+              dev_ptr(out), B, Nv, H, D, L, Nq, P, vdt, 1, stream_ptr(value.device))
     return out
 
 
@@ -175,14 +190,11 @@ def msda_forward_fused_rows(rows_all, level_hw, level_start, ref_points, num_poi
     if rows_all.dtype != torch.float32 or not rows_all.is_contiguous() or ldr != H * D + 3 * H * L * P or ldr % 32:
         raise CggError(f'msda_forward_fused_rows: rows {tuple(rows_all.shape)} for H={H} D={D} L={L} P={P}')
     out = torch.empty((B, Nq, H * D), dtype=torch.float32, device=rows_all.device)
-    hw = _int_array([v for pair in level_hw for v in pair])
-    st = _int_array(level_start)
-    base = dev_ptr(rows_all, 'rows_all', torch.float32)
-    offs = ctypes.c_void_p(rows_all.data_ptr() + H * D * 4)
+    hw, st = _levels(level_hw, level_start)
     with _timed('msda_fused'):
-        rc = _lib_().cgg_msda_forward_fused_vld(base, ldr, hw, st, offs, ldr, dev_ptr(ref_points, 'ref_points', torch.float32),
-                                                dev_ptr(out), B, Nq, H, D, L, Nq, P, stream_ptr(rows_all.device))
-    check(rc, 'cgg_msda_forward_fused_vld')
+        _call('cgg_msda_forward_fused_vld', dev_ptr(rows_all, 'rows_all', torch.float32), ldr, hw, st,
+              _ptr_at(rows_all, H * D, 'rows_all', torch.float32), ldr, dev_ptr(ref_points, 'ref_points', torch.float32), dev_ptr(out),
+              B, Nq, H, D, L, Nq, P, stream_ptr(rows_all.device))
     return out
 
 
@@ -195,14 +207,11 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_locations, 
     # algorithmic bytes: value + locations + weights + grad_output in, the three gradients out
     nbytes = 4.0 * (2 * value.numel() + 2 * sampling_locations.numel() + 2 * attention_weights.numel() + grad_output.numel())
     with _timed('msda_backward', bytes=nbytes, flops=0.0, shape=(B, Nq, H, D, L, P)):
-        rc = _lib_().cgg_msda_backward(
-            dev_ptr(value, 'value', torch.float32), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
-            dev_ptr(level_start_index, 'level_start_index', torch.int64),
-            dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
-            dev_ptr(attention_weights, 'attention_weights', torch.float32),
-            dev_ptr(grad_output, 'grad_output', torch.float32), dev_ptr(gv), dev_ptr(gl), dev_ptr(gw), B,
-            Nv, H, D, L, Nq, P, stream_ptr(value.device))
-    check(rc, 'cgg_msda_backward')
+        _call('cgg_msda_backward', dev_ptr(value, 'value', torch.float32), dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
+              dev_ptr(level_start_index, 'level_start_index', torch.int64),
+              dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
+              dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(grad_output, 'grad_output', torch.float32),
+              dev_ptr(gv), dev_ptr(gl), dev_ptr(gw), B, Nv, H, D, L, Nq, P, stream_ptr(value.device))
     return gv, gl, gw
 
 
@@ -210,8 +219,7 @@ def msda_backward_hostlevels(value, level_hw, level_start, sampling_locations, a
     """`msda_backward` with the level table as host integers: no device tensors for the shapes, no read-back / stream
     synchronisation inside the call (csrc/msda.hip `cgg_msda_backward_hostlevels`)."""
     B, Nv, H, D, L, Nq, P = _msda_dims(value, sampling_locations)
-    hw = _int_array([v for pair in level_hw for v in pair])
-    st = _int_array(level_start)
+    hw, st = _levels(level_hw, level_start)
     # split backward on a tileable pyramid: grad_loc / grad_attn are written by the gather kernel (no zero-fill, no read of old values)
     ow = bool(_lib_().cgg_msda_backward_overwrites(hw, st, B, Nv, H, D, L, Nq, P)) and \
         sampling_locations.data_ptr() % 16 == 0 and attention_weights.data_ptr() % 16 == 0
@@ -234,13 +242,12 @@ def msda_backward_hostlevels(value, level_hw, level_start, sampling_locations, a
     wsb = int(_lib_().cgg_msda_backward_workspace_bytes(hw, st, B, Nv, H, D, L, Nq, P)) if MSDA_BWD_2P else 0
     ws = _workspace(wsb, value.device) if wsb > 0 else None
     with _timed('msda_backward', bytes=nbytes, flops=0.0, shape=(B, Nq, H, D, L, P)):
-        rc = _lib_().cgg_msda_backward_hostlevels_ws(
-            ctypes.c_void_p(value.data_ptr()), vld, hw, st, dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
-            dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(grad_output, 'grad_output', torch.float32),
-            ctypes.c_void_p(gv.data_ptr()), dev_ptr(gl), dev_ptr(gw), B, Nv, H, D, L, Nq, P, int(ow),
-            dev_ptr(ws) if ws is not None else None, wsb,
-            stream_ptr(value.device), ctypes.c_void_p(side.cuda_stream) if side is not None else None)
-    check(rc, 'cgg_msda_backward_hostlevels_ws')
+        _call('cgg_msda_backward_hostlevels_ws', dev_ptr(value, 'value', torch.float32, dense=False), vld, hw, st,
+              dev_ptr(sampling_locations, 'sampling_locations', torch.float32),
+              dev_ptr(attention_weights, 'attention_weights', torch.float32), dev_ptr(grad_output, 'grad_output', torch.float32),
+              dev_ptr(gv, 'grad_value', dense=False), dev_ptr(gl), dev_ptr(gw), B, Nv, H, D, L, Nq, P, int(ow),
+              dev_ptr(ws) if ws is not None else None, wsb, stream_ptr(value.device),
+              ctypes.c_void_p(side.cuda_stream) if side is not None else None)
     return gv, gl, gw
 
 
@@ -267,10 +274,8 @@ def msda_read_levels(spatial_shapes, level_start_index, Nv):
         return hit[1], hit[2]
     L = int(spatial_shapes.shape[0])
     hw, st = (ctypes.c_int32 * (2 * L))(), (ctypes.c_int32 * L)()
-    rc = _lib_().cgg_msda_read_levels(dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
-                                      dev_ptr(level_start_index, 'level_start_index', torch.int64), L, int(Nv), hw, st,
-                                      stream_ptr(spatial_shapes.device))
-    check(rc, 'cgg_msda_read_levels')
+    _call('cgg_msda_read_levels', dev_ptr(spatial_shapes, 'spatial_shapes', torch.int64),
+          dev_ptr(level_start_index, 'level_start_index', torch.int64), L, int(Nv), hw, st, stream_ptr(spatial_shapes.device))
     level_hw = tuple((int(hw[2 * l]), int(hw[2 * l + 1])) for l in range(L))
     level_start = tuple(int(st[l]) for l in range(L))
     try:
@@ -335,15 +340,15 @@ def msda_rows_backward(value, rows, ref_points, level_hw, level_start, P, grad_o
     B, Nv, H, D = value.shape
     _, Nq, ld = rows.shape
     L = len(level_hw)
-    hw = _int_array([v for pair in level_hw for v in pair])
+    hw, _ = _levels(level_hw, level_start)
     loc = torch.empty((B, Nq, H, L, P, 2), dtype=torch.float32, device=value.device)
     aw = torch.empty((B, Nq, H, L, P), dtype=torch.float32, device=value.device)
-    check(_lib_().cgg_msda_prologue(dev_ptr(rows, 'rows', torch.float32), ld, dev_ptr(ref_points, 'ref', torch.float32), hw,
-                                    dev_ptr(loc), dev_ptr(aw), B, Nq, H, L, P, stream_ptr(value.device)), 'cgg_msda_prologue')
+    _call('cgg_msda_prologue', dev_ptr(rows, 'rows', torch.float32), ld, dev_ptr(ref_points, 'ref', torch.float32), hw, dev_ptr(loc),
+          dev_ptr(aw), B, Nq, H, L, P, stream_ptr(value.device))
     gv, gl, gw = msda_backward_hostlevels(value, level_hw, level_start, loc, aw, grad_out.contiguous())
     grows = torch.empty_like(rows)
-    check(_lib_().cgg_msda_prologue_backward(dev_ptr(gl), dev_ptr(gw), dev_ptr(rows), ld, hw, dev_ptr(grows), B, Nq, H, L, P,
-                                             stream_ptr(value.device)), 'cgg_msda_prologue_backward')
+    _call('cgg_msda_prologue_backward', dev_ptr(gl), dev_ptr(gw), dev_ptr(rows), ld, hw, dev_ptr(grows), B, Nq, H, L, P,
+          stream_ptr(value.device))
     return gv, grows
 
 
@@ -382,9 +387,8 @@ def pack_mask_feature(feat, pool=1, split=True):
     T = (h * w + 31) // 32
     hi = torch.empty((B, T, C // 8, 32, 8), dtype=torch.bfloat16, device=feat.device)
     lo = torch.empty_like(hi) if split else None
-    rc = _lib_().cgg_pack_mask_feature(dev_ptr(feat, 'mask_feature', torch.float32), dev_ptr(hi),
-                                       dev_ptr(lo), B, C, H, W, pool, stream_ptr(feat.device))
-    check(rc, 'cgg_pack_mask_feature')
+    _call('cgg_pack_mask_feature', dev_ptr(feat, 'mask_feature', torch.float32), dev_ptr(hi), dev_ptr(lo), B, C, H, W, pool,
+          stream_ptr(feat.device))
     f32 = None
     from . import runtime
     if split and C == 256 and EXACT_F32_LOGITS and not runtime.x3_enabled():
@@ -416,10 +420,9 @@ def mask_logits(embed, packed, want_logits=True, want_bits=False, out=None):
         out = torch.empty((B, Q, packed.h, packed.w), dtype=torch.float32, device=embed.device) if want_logits else None
         bits = torch.empty((B, Q, packed.words), dtype=torch.int32, device=embed.device) if want_bits else None
         with _timed('mask_logits_full' if want_logits else 'mask_logits_bits'):
-            rc = _lib_().cgg_mask_logits_f32(dev_ptr(embed, 'mask_embed', torch.float32),
-                                             dev_ptr(packed.f32.contiguous(), 'mask_feature', torch.float32), dev_ptr(out),
-                                             dev_ptr(bits), B, Q, C, packed.npix, stream_ptr(embed.device))
-        check(rc, 'cgg_mask_logits_f32')
+            _call('cgg_mask_logits_f32', dev_ptr(embed, 'mask_embed', torch.float32),
+                  dev_ptr(packed.f32.contiguous(), 'mask_feature', torch.float32), dev_ptr(out), dev_ptr(bits), B, Q, C, packed.npix,
+                  stream_ptr(embed.device))
         return out, bits
     if out is not None:
         out = out.view(B, Q, packed.h, packed.w)
@@ -429,10 +432,8 @@ def mask_logits(embed, packed, want_logits=True, want_bits=False, out=None):
         if want_bits else None
     tag = 'mask_logits_full' if want_logits else 'mask_logits_bits'
     with _timed(tag):
-        rc = _lib_().cgg_mask_logits(dev_ptr(embed, 'mask_embed', torch.float32), dev_ptr(packed.hi),
-                                     dev_ptr(packed.lo), dev_ptr(out), dev_ptr(bits), B, Q, C, packed.npix,
-                                     stream_ptr(embed.device))
-    check(rc, 'cgg_mask_logits')
+        _call('cgg_mask_logits', dev_ptr(embed, 'mask_embed', torch.float32), dev_ptr(packed.hi), dev_ptr(packed.lo), dev_ptr(out),
+              dev_ptr(bits), B, Q, C, packed.npix, stream_ptr(embed.device))
     return out, bits
 
 
@@ -456,9 +457,8 @@ def mask_logits_bits_astat(embed, packed):
         raise CggError('mask_logits_bits_astat: bf16 PackedFeature of the same batch / channels expected')
     bits = torch.empty((B, Q, packed.words), dtype=torch.int32, device=embed.device)
     with _timed('mask_logits_bits_astat'):
-        rc = _lib_().cgg_mask_logits_bits_astat(dev_ptr(embed, 'mask_embed', torch.float32), dev_ptr(packed.hi), dev_ptr(bits), B, Q, C,
-                                                packed.npix, stream_ptr(embed.device))
-    check(rc, 'cgg_mask_logits_bits_astat')
+        _call('cgg_mask_logits_bits_astat', dev_ptr(embed, 'mask_embed', torch.float32), dev_ptr(packed.hi), dev_ptr(bits), B, Q, C,
+              packed.npix, stream_ptr(embed.device))
     return bits
 
 
@@ -479,23 +479,19 @@ def mask_logits_backward(embed, feat, grad_out, split, need_embed=True, need_fea
     feat = feat.contiguous()
     go = grad_out.contiguous()
     embed = embed.contiguous()
-    lib = _lib_()
     ge = torch.empty((B, Q, C), dtype=torch.float32, device=embed.device) if need_embed else None
     gf = torch.empty((B, C, h, w), dtype=torch.float32, device=embed.device) if need_feat else None
-    ws = _workspace(lib.cgg_mask_logits_backward_workspace_bytes(B, min(Q, 128), C, npix), embed.device)
-    rc = lib.cgg_mask_logits_backward(dev_ptr(embed, 'embed', torch.float32), dev_ptr(feat, 'feat', torch.float32),
-                                      dev_ptr(go, 'grad_out', torch.float32), dev_ptr(ge), dev_ptr(gf), dev_ptr(ws), B, Q, C, npix,
-                                      int(bool(split)), stream_ptr(embed.device))
-    check(rc, 'cgg_mask_logits_backward')
+    ws = _workspace(_lib_().cgg_mask_logits_backward_workspace_bytes(B, min(Q, 128), C, npix), embed.device)
+    _call('cgg_mask_logits_backward', dev_ptr(embed, 'embed', torch.float32), dev_ptr(feat, 'feat', torch.float32),
+          dev_ptr(go, 'grad_out', torch.float32), dev_ptr(ge), dev_ptr(gf), dev_ptr(ws), B, Q, C, npix, int(bool(split)),
+          stream_ptr(embed.device))
     return ge, gf
 
 
 def attn_mask_fix_full_rows(bits, npix):
     """In place: rows of the bit mask that block all `npix` keys are cleared."""
     rows = bits.numel() // bits.shape[-1]
-    rc = _lib_().cgg_attn_mask_fix_full_rows(dev_ptr(bits, 'bits', torch.int32), rows, npix,
-                                             stream_ptr(bits.device))
-    check(rc, 'cgg_attn_mask_fix_full_rows')
+    _call('cgg_attn_mask_fix_full_rows', dev_ptr(bits, 'bits', torch.int32), rows, npix, stream_ptr(bits.device))
     return bits
 
 
@@ -505,9 +501,8 @@ def attn_mask_from_logits(logits, size):
     h, w = int(size[0]), int(size[1])
     words = (h * w + 31) // 32
     bits = torch.empty((B, Q, words), dtype=torch.int32, device=logits.device)
-    rc = _lib_().cgg_attn_mask_from_logits(dev_ptr(logits, 'logits', torch.float32), dev_ptr(bits),
-                                           B * Q, H, W, h, w, stream_ptr(logits.device))
-    check(rc, 'cgg_attn_mask_from_logits')
+    _call('cgg_attn_mask_from_logits', dev_ptr(logits, 'logits', torch.float32), dev_ptr(bits), B * Q, H, W, h, w,
+          stream_ptr(logits.device))
     return bits
 
 
@@ -554,45 +549,37 @@ def masked_xattn(q, kv, bits, num_heads, scale=None, return_lse=False):
         raise CggError(f'masked_xattn: kv last dim {kv.shape[2]} != 2*{E}')
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    lib = _lib_()
-    ws = _xattn_ws(lib.cgg_masked_xattn_workspace_bytes, q, B, Q, H, D, S)
+    ws = _xattn_ws(_lib_().cgg_masked_xattn_workspace_bytes, q, B, Q, H, D, S)
     out = torch.empty((B, Q, E), dtype=torch.float32, device=q.device)
     from . import runtime
     if XATTN_X3 and not return_lse and runtime.x3_enabled() and kv.is_cuda and kv.dtype == torch.float32 \
             and kv.stride(2) == 1 and kv.stride(1) % 4 == 0 and kv.stride(0) % 4 == 0:
         # parity mode, inference: both products on the f32-class f16 x 3 contraction (csrc/xattn_x3.hip); kv may be a column
         # slice of a merged projection (rows / images at their strides)
-        rc = lib.cgg_masked_xattn_forward_x3(dev_ptr(q, 'q', torch.float32), ctypes.c_void_p(kv.data_ptr()), kv.stride(1), kv.stride(0),
-                                             dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q, H, D, S, float(scale),
-                                             stream_ptr(q.device))
-        check(rc, 'cgg_masked_xattn_forward_x3')
+        _call('cgg_masked_xattn_forward_x3', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32, dense=False),
+              kv.stride(1), kv.stride(0), dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q, H, D, S, float(scale),
+              stream_ptr(q.device))
         return out
     if not kv.is_contiguous() and not return_lse:
         # a column slice of the merged [K | V] projection of the layers that read one level: rows / images at their strides
-        if not kv.is_cuda or kv.dtype != torch.float32 or kv.stride(2) != 1:
-            raise CggError('masked_xattn: a strided kv must be a float32 ROCm tensor with a contiguous last dim')
-        rc = lib.cgg_masked_xattn_forward_strided(dev_ptr(q, 'q', torch.float32), ctypes.c_void_p(kv.data_ptr()), kv.stride(1),
-                                                  kv.stride(0), dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q,
-                                                  H, D, S, float(scale), stream_ptr(q.device))
-        check(rc, 'cgg_masked_xattn_forward_strided')
+        if kv.stride(2) != 1:
+            raise CggError('masked_xattn: a strided kv must have a contiguous last dim')
+        _call('cgg_masked_xattn_forward_strided', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32, dense=False),
+              kv.stride(1), kv.stride(0), dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q, H, D, S, float(scale),
+              stream_ptr(q.device))
         return out
     dev_ptr(kv, 'kv', torch.float32)
     if return_lse:
         lse = torch.empty((B, H, Q), dtype=torch.float32, device=q.device)
-        rc = lib.cgg_masked_xattn_forward_lse(dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
-                                              dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(lse), dev_ptr(ws),
-                                              B, Q, H, D, S, float(scale), _xattn_train_dtype(forward=True), stream_ptr(q.device))
-        check(rc, 'cgg_masked_xattn_forward_lse')
+        _call('cgg_masked_xattn_forward_lse', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
+              dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(lse), dev_ptr(ws), B, Q, H, D, S, float(scale),
+              _xattn_train_dtype(forward=True), stream_ptr(q.device))
         return out, lse
-    rc = lib.cgg_masked_xattn_forward(dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
-                                      dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B,
-                                      Q, H, D, S, float(scale), CGG_F32, stream_ptr(q.device))
-    check(rc, 'cgg_masked_xattn_forward')
+    _call('cgg_masked_xattn_forward', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
+          dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q, H, D, S, float(scale), CGG_F32, stream_ptr(q.device))
     return out
 
 
-CGG_F32_BF16MFMA = 2                 # include/cgg_hip.h: f32 rows in memory, bf16 MFMA operands (training kernels of throughput mode)
-CGG_F32_X3 = 3                       # cgg_masked_xattn_forward_lse only: the forward on the f32-class f16 x 3 contraction
 XATTN_X3_TRAIN = os.environ.get('CGG_XATTN_X3_TRAIN', '1') != '0'
 XATTN_X3_BWD = os.environ.get('CGG_XATTN_X3_BWD', '1') != '0'       # parity-mode training: the cross-attention backward on f16 x 3 (0: f32 MFMA)
 
@@ -627,8 +614,7 @@ def masked_xattn_backward(q, kv, bits, out, lse, grad_out, num_heads, scale=None
             gq.append(a)
             gkv = b if gkv is None else gkv.add_(b)
         return torch.cat(gq, 1), gkv
-    lib = _lib_()
-    ws = _xattn_ws(lib.cgg_masked_xattn_backward_workspace_bytes, q, B, Q, H, D, S)
+    ws = _xattn_ws(_lib_().cgg_masked_xattn_backward_workspace_bytes, q, B, Q, H, D, S)
     gq = torch.empty_like(q)
     gkv = torch.empty_like(kv)
     from . import runtime
@@ -636,19 +622,15 @@ def masked_xattn_backward(q, kv, bits, out, lse, grad_out, num_heads, scale=None
         # parity mode: the f16 x 3 form of the kernel (f32-class, 2.7 x less matrix-pipe time than the f32 MFMA); the gradient operands
         # take their pre-scale from max |grad_out|
         amax = absmax(grad_out.view(-1, E))
-        rc = lib.cgg_masked_xattn_backward_x3(dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
-                                              dev_ptr(bits, 'bits', torch.int32), dev_ptr(out, 'out', torch.float32),
-                                              dev_ptr(lse, 'lse', torch.float32), dev_ptr(grad_out, 'grad_out', torch.float32),
-                                              dev_ptr(amax), dev_ptr(gq), dev_ptr(gkv), dev_ptr(ws), B, Q, H, D, S, float(scale),
-                                              stream_ptr(q.device))
-        check(rc, 'cgg_masked_xattn_backward_x3')
+        _call('cgg_masked_xattn_backward_x3', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
+              dev_ptr(bits, 'bits', torch.int32), dev_ptr(out, 'out', torch.float32), dev_ptr(lse, 'lse', torch.float32),
+              dev_ptr(grad_out, 'grad_out', torch.float32), dev_ptr(amax), dev_ptr(gq), dev_ptr(gkv), dev_ptr(ws), B, Q, H, D, S,
+              float(scale), stream_ptr(q.device))
         return gq, gkv
-    rc = lib.cgg_masked_xattn_backward(dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
-                                       dev_ptr(bits, 'bits', torch.int32), dev_ptr(out, 'out', torch.float32),
-                                       dev_ptr(lse, 'lse', torch.float32), dev_ptr(grad_out, 'grad_out', torch.float32),
-                                       dev_ptr(gq), dev_ptr(gkv), dev_ptr(ws), B, Q, H, D, S, float(scale), _xattn_train_dtype(),
-                                       stream_ptr(q.device))
-    check(rc, 'cgg_masked_xattn_backward')
+    _call('cgg_masked_xattn_backward', dev_ptr(q, 'q', torch.float32), dev_ptr(kv, 'kv', torch.float32),
+          dev_ptr(bits, 'bits', torch.int32), dev_ptr(out, 'out', torch.float32), dev_ptr(lse, 'lse', torch.float32),
+          dev_ptr(grad_out, 'grad_out', torch.float32), dev_ptr(gq), dev_ptr(gkv), dev_ptr(ws), B, Q, H, D, S, float(scale),
+          _xattn_train_dtype(), stream_ptr(q.device))
     return gq, gkv
 
 
@@ -709,9 +691,8 @@ def window_attention(qkv, table, hw, ws, shift, num_heads, scale=None, return_ls
     out = torch.empty((B, Hp * Wp, C), dtype=torch.float32, device=qkv.device)
     lse = torch.empty((B, H, Hp * Wp), dtype=torch.float32, device=qkv.device)
     with _timed('window_attn_fwd'):
-        rc = _lib_().cgg_window_attn_forward(dev_ptr(qkv), dev_ptr(table), dev_ptr(out), dev_ptr(lse), B, Hp, Wp, C, H, ws, shift,
-                                             scale, stream_ptr(qkv.device))
-    check(rc, 'cgg_window_attn_forward')
+        _call('cgg_window_attn_forward', dev_ptr(qkv), dev_ptr(table), dev_ptr(out), dev_ptr(lse), B, Hp, Wp, C, H, ws, shift, scale,
+              stream_ptr(qkv.device))
     return (out, lse) if return_lse else out
 
 
@@ -725,14 +706,12 @@ def window_attention_backward(qkv, table, lse, grad_out, hw, ws, shift, num_head
     if tuple(lse.shape) != (B, H, Hp * Wp) or tuple(grad_out.shape) != (B, Hp * Wp, C):
         raise CggError(f'window_attention_backward: lse {tuple(lse.shape)} / grad_out {tuple(grad_out.shape)} do not match '
                        f'qkv {tuple(qkv.shape)}')
-    lib = _lib_()
-    wsb = _workspace(lib.cgg_window_attn_backward_workspace_bytes(B, Hp, Wp, H, ws), qkv.device)
+    wsb = _workspace(_lib_().cgg_window_attn_backward_workspace_bytes(B, Hp, Wp, H, ws), qkv.device)
     gqkv = torch.empty_like(qkv)
     gtab = torch.empty_like(table)
     with _timed('window_attn_bwd'):
-        rc = lib.cgg_window_attn_backward(dev_ptr(qkv), dev_ptr(table), dev_ptr(lse), dev_ptr(grad_out), dev_ptr(gqkv), dev_ptr(gtab),
-                                          dev_ptr(wsb), B, Hp, Wp, C, H, ws, shift, scale, stream_ptr(qkv.device))
-    check(rc, 'cgg_window_attn_backward')
+        _call('cgg_window_attn_backward', dev_ptr(qkv), dev_ptr(table), dev_ptr(lse), dev_ptr(grad_out), dev_ptr(gqkv), dev_ptr(gtab),
+              dev_ptr(wsb), B, Hp, Wp, C, H, ws, shift, scale, stream_ptr(qkv.device))
     return gqkv, gtab
 
 
@@ -770,10 +749,8 @@ def grounding_pair_costs(pred, cap, cap_mask, inv_temperature):
     Bp, Q, d = pred.shape
     Bc, T, _ = cap.shape
     cost = torch.empty((2, Bc, Bp), dtype=torch.float32, device=pred.device)
-    rc = _lib_().cgg_grounding_pair_costs(dev_ptr(pred, 'pred', torch.float32), dev_ptr(cap, 'cap', torch.float32),
-                                          dev_ptr(cap_mask, 'cap_mask', torch.int32), dev_ptr(cost), Bp, Bc, Q, T, d,
-                                          float(inv_temperature), stream_ptr(pred.device))
-    check(rc, 'cgg_grounding_pair_costs')
+    _call('cgg_grounding_pair_costs', dev_ptr(pred, 'pred', torch.float32), dev_ptr(cap, 'cap', torch.float32),
+          dev_ptr(cap_mask, 'cap_mask', torch.int32), dev_ptr(cost), Bp, Bc, Q, T, d, float(inv_temperature), stream_ptr(pred.device))
     return cost
 
 
@@ -782,11 +759,9 @@ def grounding_pair_costs_backward(pred, cap, cap_mask, grad_cost, inv_temperatur
     Bp, Q, d = pred.shape
     Bc, T, _ = cap.shape
     dsim = torch.empty((Bp, Bc * T, Q), dtype=torch.float32, device=pred.device)
-    rc = _lib_().cgg_grounding_pair_costs_backward(
-        dev_ptr(pred, 'pred', torch.float32), dev_ptr(cap, 'cap', torch.float32),
-        dev_ptr(cap_mask, 'cap_mask', torch.int32), dev_ptr(grad_cost.contiguous(), 'grad_cost', torch.float32),
-        dev_ptr(dsim), Bp, Bc, Q, T, d, float(inv_temperature), stream_ptr(pred.device))
-    check(rc, 'cgg_grounding_pair_costs_backward')
+    _call('cgg_grounding_pair_costs_backward', dev_ptr(pred, 'pred', torch.float32), dev_ptr(cap, 'cap', torch.float32),
+          dev_ptr(cap_mask, 'cap_mask', torch.int32), dev_ptr(grad_cost.contiguous(), 'grad_cost', torch.float32), dev_ptr(dsim), Bp,
+          Bc, Q, T, d, float(inv_temperature), stream_ptr(pred.device))
     return dsim
 
 
@@ -809,10 +784,9 @@ def ce_rows_forward(logits, target, ignore_index):
         raise CggError('ce_rows_forward: rows must be contiguous')
     loss = torch.empty(M, dtype=torch.float32, device=logits.device)
     lse = torch.empty(M, dtype=torch.float32, device=logits.device)
-    rc = _lib_().cgg_ce_rows_forward(ctypes.c_void_p(logits.data_ptr()), dev_ptr(target, 'target', torch.int64), dev_ptr(loss),
-                                     dev_ptr(lse), M, N, int(logits.stride(0)), int(-100 if ignore_index is None else ignore_index),
-                                     _ce_dtype(logits), stream_ptr(logits.device))
-    check(rc, 'cgg_ce_rows_forward')
+    _call('cgg_ce_rows_forward', dev_ptr(logits, 'logits', _F32_BF16, dense=False), dev_ptr(target, 'target', torch.int64),
+          dev_ptr(loss), dev_ptr(lse), M, N, int(logits.stride(0)), int(-100 if ignore_index is None else ignore_index),
+          _ce_dtype(logits), stream_ptr(logits.device))
     return loss, lse
 
 
@@ -827,20 +801,17 @@ def match_cost_rows(x, square=False):
     sig = torch.empty_like(x)
     sp = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
     ss = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    rc = _lib_().cgg_match_cost_rows(dev_ptr(x, 'x', torch.float32), dev_ptr(sig), dev_ptr(sp), dev_ptr(ss), rows, P, int(bool(square)),
-                                     stream_ptr(x.device))
-    check(rc, 'cgg_match_cost_rows')
+    _call('cgg_match_cost_rows', dev_ptr(x, 'x', torch.float32), dev_ptr(sig), dev_ptr(sp), dev_ptr(ss), rows, P, int(bool(square)),
+          stream_ptr(x.device))
     return sig, sp, ss
 
 
 def ce_rows_backward_(logits, target, lse, grad_rows, ignore_index):
     """logits (M, N) -> d loss / d logits IN PLACE: grad_rows[row] * (softmax - onehot); returns `logits`."""
     M, N = logits.shape
-    rc = _lib_().cgg_ce_rows_backward(ctypes.c_void_p(logits.data_ptr()), dev_ptr(target, 'target', torch.int64),
-                                      dev_ptr(lse, 'lse', torch.float32), dev_ptr(grad_rows.contiguous(), 'grad_rows', torch.float32),
-                                      M, N, int(logits.stride(0)), int(-100 if ignore_index is None else ignore_index),
-                                      _ce_dtype(logits), stream_ptr(logits.device))
-    check(rc, 'cgg_ce_rows_backward')
+    _call('cgg_ce_rows_backward', dev_ptr(logits, 'logits', _F32_BF16, dense=False), dev_ptr(target, 'target', torch.int64),
+          dev_ptr(lse, 'lse', torch.float32), dev_ptr(grad_rows.contiguous(), 'grad_rows', torch.float32), M, N, int(logits.stride(0)),
+          int(-100 if ignore_index is None else ignore_index), _ce_dtype(logits), stream_ptr(logits.device))
     return logits
 
 
@@ -854,9 +825,7 @@ def upsample_bilinear(x, size):
     h, w = int(size[0]), int(size[1])
     n = x.numel() // (H * W)
     y = torch.empty(tuple(shp[:-2]) + (h, w), dtype=torch.float32, device=x.device)
-    rc = _lib_().cgg_upsample_bilinear(dev_ptr(x, 'x', torch.float32), dev_ptr(y), n, H, W, h, w,
-                                       stream_ptr(x.device))
-    check(rc, 'cgg_upsample_bilinear')
+    _call('cgg_upsample_bilinear', dev_ptr(x, 'x', torch.float32), dev_ptr(y), n, H, W, h, w, stream_ptr(x.device))
     return y
 
 
@@ -871,12 +840,9 @@ def instance_masks(logits, sel, up_size, crop_size, out_size):
     if n == 0:
         return masks.bool(), score, bbox
     ws = torch.empty((n, 8), dtype=torch.int32, device=logits.device)
-    rc = _lib_().cgg_instance_masks(dev_ptr(logits, 'logits', torch.float32),
-                                    dev_ptr(sel, 'sel', torch.int32), dev_ptr(masks), dev_ptr(score),
-                                    dev_ptr(bbox), dev_ptr(ws), Q, H, W, int(up_size[0]),
-                                    int(up_size[1]), int(crop_size[0]), int(crop_size[1]), oh, ow, n,
-                                    stream_ptr(logits.device))
-    check(rc, 'cgg_instance_masks')
+    _call('cgg_instance_masks', dev_ptr(logits, 'logits', torch.float32), dev_ptr(sel, 'sel', torch.int32), dev_ptr(masks),
+          dev_ptr(score), dev_ptr(bbox), dev_ptr(ws), Q, H, W, int(up_size[0]), int(up_size[1]), int(crop_size[0]), int(crop_size[1]),
+          oh, ow, n, stream_ptr(logits.device))
     return masks.view(torch.bool), score, bbox
 
 
@@ -888,23 +854,17 @@ def panoptic_argmax(logits, keep, score, up_size, crop_size, out_size):
     ids = torch.empty((oh, ow), dtype=torch.int32, device=logits.device)
     half = torch.empty((oh, ow), dtype=torch.uint8, device=logits.device)
     counts = torch.empty((n, 3), dtype=torch.int32, device=logits.device)
-    rc = _lib_().cgg_panoptic_argmax(dev_ptr(logits, 'logits', torch.float32),
-                                     dev_ptr(keep, 'keep', torch.int32),
-                                     dev_ptr(score, 'score', torch.float32), dev_ptr(ids), dev_ptr(half),
-                                     dev_ptr(counts), Q, H, W, int(up_size[0]), int(up_size[1]),
-                                     int(crop_size[0]), int(crop_size[1]), oh, ow, n,
-                                     stream_ptr(logits.device))
-    check(rc, 'cgg_panoptic_argmax')
+    _call('cgg_panoptic_argmax', dev_ptr(logits, 'logits', torch.float32), dev_ptr(keep, 'keep', torch.int32),
+          dev_ptr(score, 'score', torch.float32), dev_ptr(ids), dev_ptr(half), dev_ptr(counts), Q, H, W, int(up_size[0]),
+          int(up_size[1]), int(crop_size[0]), int(crop_size[1]), oh, ow, n, stream_ptr(logits.device))
     return ids, half, counts
 
 
 def panoptic_paint(ids, win_half, lut_val, lut_half, void_label):
     seg = torch.empty_like(ids)
-    rc = _lib_().cgg_panoptic_paint(dev_ptr(ids, 'ids', torch.int32), dev_ptr(win_half, 'win_half', torch.uint8),
-                                    dev_ptr(lut_val, 'lut_val', torch.int32),
-                                    dev_ptr(lut_half, 'lut_half', torch.int32), dev_ptr(seg),
-                                    ids.numel(), int(void_label), stream_ptr(ids.device))
-    check(rc, 'cgg_panoptic_paint')
+    _call('cgg_panoptic_paint', dev_ptr(ids, 'ids', torch.int32), dev_ptr(win_half, 'win_half', torch.uint8),
+          dev_ptr(lut_val, 'lut_val', torch.int32), dev_ptr(lut_half, 'lut_half', torch.int32), dev_ptr(seg), ids.numel(),
+          int(void_label), stream_ptr(ids.device))
     return seg
 
 
@@ -941,13 +901,11 @@ def panoptic_fuse_batched(logits, score, label, geometry, up_size, num_classes, 
     kscore = torch.empty((B, Q), dtype=torch.float32, device=dev)
     nbytes = int(_lib_().cgg_panoptic_fuse_batched_workspace_bytes(B, Q, total))
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
-    rc = _lib_().cgg_panoptic_fuse_batched(dev_ptr(logits, 'logits', torch.float32), dev_ptr(score, 'score', torch.float32),
-                                           dev_ptr(label, 'label', torch.int64), dev_ptr(table, 'geometry', torch.int64),
-                                           dev_ptr(seg), dev_ptr(n_kept), dev_ptr(segments), dev_ptr(kscore), dev_ptr(ws), nbytes,
-                                           B, Q, H, W, int(up_size[0]), int(up_size[1]), moh, mow, total, int(num_classes),
-                                           int(num_things), float(object_mask_thr), float(iou_thr), int(bool(filter_low_score)),
-                                           int(math.ceil(stuff_area_limit)), int(bool(defer_stuff)), stream_ptr(dev))
-    check(rc, 'cgg_panoptic_fuse_batched')
+    _call('cgg_panoptic_fuse_batched', dev_ptr(logits, 'logits', torch.float32), dev_ptr(score, 'score', torch.float32),
+          dev_ptr(label, 'label', torch.int64), dev_ptr(table, 'geometry', torch.int64), dev_ptr(seg), dev_ptr(n_kept),
+          dev_ptr(segments), dev_ptr(kscore), dev_ptr(ws), nbytes, B, Q, H, W, int(up_size[0]), int(up_size[1]), moh, mow, total,
+          int(num_classes), int(num_things), float(object_mask_thr), float(iou_thr), int(bool(filter_low_score)),
+          int(math.ceil(stuff_area_limit)), int(bool(defer_stuff)), stream_ptr(dev))
     if debug:
         return seg, n_kept, segments, kscore, ws[:2 * B].view(B, 2)
     return seg, n_kept, segments, kscore
@@ -959,9 +917,8 @@ def rowwise_softmax_argmax(x, want_prob=True):
     prob = torch.empty_like(x) if want_prob else None
     maxv = torch.empty((rows,), dtype=torch.float32, device=x.device)
     arg = torch.empty((rows,), dtype=torch.int64, device=x.device)
-    rc = _lib_().cgg_rowwise_softmax_argmax(dev_ptr(x, 'x', torch.float32), dev_ptr(prob), dev_ptr(maxv),
-                                            dev_ptr(arg), rows, n, stream_ptr(x.device))
-    check(rc, 'cgg_rowwise_softmax_argmax')
+    _call('cgg_rowwise_softmax_argmax', dev_ptr(x, 'x', torch.float32), dev_ptr(prob), dev_ptr(maxv), dev_ptr(arg), rows, n,
+          stream_ptr(x.device))
     return prob, maxv, arg
 
 
@@ -987,19 +944,12 @@ def linear_rows(x, weight, bias=None, relu=False, res=None, split=True, out=None
         r2 = res.reshape(-1, N)
         if r2.stride(-1) != 1:
             r2 = r2.contiguous()
-    for t, nm in ((x2, 'x'), (weight, 'weight')):
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise CggError(f'linear_rows: {nm} must be a float32 ROCm tensor')
     if not weight.is_contiguous():
         weight = weight.contiguous()
-    rc = _lib_().cgg_linear_rows(ctypes.c_void_p(x2.data_ptr()), x2.stride(0), dev_ptr(weight),
-                                 dev_ptr(bias, 'bias', torch.float32),
-                                 ctypes.c_void_p(r2.data_ptr()) if r2 is not None else None,
-                                 r2.stride(0) if r2 is not None else 0, ctypes.c_void_p(y.data_ptr()),
-                                 y.stride(0), M, N, K,
-                                 1 if relu else 0, (2 if EXACT_F32_LOGITS and not _throughput_mode() else 1) if split else 0,
-                                 stream_ptr(x.device))
-    check(rc, 'cgg_linear_rows')
+    _call('cgg_linear_rows', dev_ptr(x2, 'x', torch.float32, dense=False), x2.stride(0), dev_ptr(weight, 'weight', torch.float32),
+          dev_ptr(bias, 'bias', torch.float32), dev_ptr(r2, 'res', torch.float32, dense=False), r2.stride(0) if r2 is not None else 0,
+          dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), M, N, K, 1 if relu else 0,
+          (2 if EXACT_F32_LOGITS and not _throughput_mode() else 1) if split else 0, stream_ptr(x.device))
     return y.view(*x.shape[:-1], N) if out is None else out
 
 
@@ -1009,10 +959,8 @@ def add_layernorm(a, b, gamma, beta, eps=1e-5):
     a2 = a.contiguous()
     b2 = b.contiguous() if b is not None else None
     y = torch.empty_like(a2)
-    rc = _lib_().cgg_add_layernorm(dev_ptr(a2, 'a', torch.float32), dev_ptr(b2, 'b', torch.float32),
-                                   dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
-                                   dev_ptr(y), a2.numel() // N, N, float(eps), stream_ptr(a.device))
-    check(rc, 'cgg_add_layernorm')
+    _call('cgg_add_layernorm', dev_ptr(a2, 'a', torch.float32), dev_ptr(b2, 'b', torch.float32), dev_ptr(gamma, 'gamma', torch.float32),
+          dev_ptr(beta, 'beta', torch.float32), dev_ptr(y), a2.numel() // N, N, float(eps), stream_ptr(a.device))
     return y
 
 
@@ -1020,14 +968,12 @@ def group_norm(x, gamma, beta, groups, eps=1e-5, relu=False):
     """x (B,C,H,W) f32 NCHW -> GroupNorm(groups)(x) (* gamma + beta) (+ ReLU)."""
     B, C, H, W = x.shape
     x = x.contiguous()
-    lib = _lib_()
-    nbytes = lib.cgg_group_norm_workspace_bytes(B, C, H, W, int(groups))
+    nbytes = _lib_().cgg_group_norm_workspace_bytes(B, C, H, W, int(groups))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
     y = torch.empty_like(x)
-    rc = lib.cgg_group_norm(dev_ptr(x, 'x', torch.float32), dev_ptr(gamma, 'gamma', torch.float32),
-                            dev_ptr(beta, 'beta', torch.float32), dev_ptr(y), dev_ptr(ws), B, C, H, W,
-                            int(groups), float(eps), 1 if relu else 0, stream_ptr(x.device))
-    check(rc, 'cgg_group_norm')
+    _call('cgg_group_norm', dev_ptr(x, 'x', torch.float32), dev_ptr(gamma, 'gamma', torch.float32),
+          dev_ptr(beta, 'beta', torch.float32), dev_ptr(y), dev_ptr(ws), B, C, H, W, int(groups), float(eps), 1 if relu else 0,
+          stream_ptr(x.device))
     return y
 
 
@@ -1043,14 +989,12 @@ def msda_forward_fused_bf16(value, level_hw, level_start, offs_logits, ref_point
         B, Nv, H, D = value.shape
     _, Nq, ld = offs_logits.shape
     out = torch.empty((B, Nq, H * D), dtype=torch.bfloat16, device=value.device)
-    hw = _int_array([v for pair in level_hw for v in pair])
-    st = _int_array(level_start)
-    fn = _lib_().cgg_msda_forward_fused_bf16_hm if head_major else _lib_().cgg_msda_forward_fused_bf16
+    hw, st = _levels(level_hw, level_start)
     with _timed('msda_fused'):
-        rc = fn(dev_ptr(value, 'value', torch.bfloat16), hw, st, dev_ptr(offs_logits, 'offs_logits', torch.bfloat16),
-                ld, dev_ptr(ref_points, 'ref_points', torch.float32), dev_ptr(out), B, Nv, H, D, len(level_start), Nq,
-                int(num_points), stream_ptr(value.device))
-    check(rc, 'cgg_msda_forward_fused_bf16')
+        _call('cgg_msda_forward_fused_bf16_hm' if head_major else 'cgg_msda_forward_fused_bf16',
+              dev_ptr(value, 'value', torch.bfloat16), hw, st, dev_ptr(offs_logits, 'offs_logits', torch.bfloat16), ld,
+              dev_ptr(ref_points, 'ref_points', torch.float32), dev_ptr(out), B, Nv, H, D, len(level_start), Nq, int(num_points),
+              stream_ptr(value.device))
     return out
 
 
@@ -1064,12 +1008,9 @@ def add_layernorm_stream(a, b, gamma, beta, eps=1e-5, pos=None, want_f32=True, w
     yp16 = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if want_pos else None
     adt = _f32_bf16_tag(a, 'add_layernorm_stream: a')
     bdt = _f32_bf16_tag(b, 'add_layernorm_stream: b')
-    rc = _lib_().cgg_add_layernorm_ex(
-        dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32),
-        dev_ptr(beta, 'beta', torch.float32), dev_ptr(pos, 'pos', torch.float32),
-        pos.shape[0] if pos is not None else 0, dev_ptr(y32), dev_ptr(y16), dev_ptr(yp16), rows, N, float(eps),
-        stream_ptr(a.device))
-    check(rc, 'cgg_add_layernorm_ex')
+    _call('cgg_add_layernorm_ex', dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt,
+          dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32), dev_ptr(pos, 'pos', torch.float32),
+          pos.shape[0] if pos is not None else 0, dev_ptr(y32), dev_ptr(y16), dev_ptr(yp16), rows, N, float(eps), stream_ptr(a.device))
     return y32, y16, yp16
 
 
@@ -1098,10 +1039,9 @@ def bottleneck64(x, packed):
     y = torch.empty_like(x)
     w1p, b1, w2p, b2, w3p, b3 = packed
     with _timed('bottleneck64'):
-        rc = _lib_().cgg_bottleneck64_bf16(dev_ptr(x, 'x', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32),
-                                           dev_ptr(w2p), dev_ptr(b2, 'b2', torch.float32), dev_ptr(w3p),
-                                           dev_ptr(b3, 'b3', torch.float32), dev_ptr(y), B, H, W, C, 64, stream_ptr(x.device))
-    check(rc, 'cgg_bottleneck64_bf16')
+        _call('cgg_bottleneck64_bf16', dev_ptr(x, 'x', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2p),
+              dev_ptr(b2, 'b2', torch.float32), dev_ptr(w3p), dev_ptr(b3, 'b3', torch.float32), dev_ptr(y), B, H, W, C, 64,
+              stream_ptr(x.device))
     return y
 
 
@@ -1110,8 +1050,7 @@ def pack_decoder_k_weight(weight):
     N, K = weight.shape
     out = torch.empty((_lib_().cgg_linear_rows_packed_bytes(N, K),), dtype=torch.uint8, device=weight.device)
     w = weight.detach().float().contiguous()
-    check(_lib_().cgg_decoder_kv_pack_k(dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device)),
-          'cgg_decoder_kv_pack_k')
+    _call('cgg_decoder_kv_pack_k', dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device))
     return out
 
 
@@ -1123,10 +1062,8 @@ def decoder_kv_proj(m16, mp16, wkp, bk, wvp):
     k = torch.empty((B, hw, NK), dtype=torch.bfloat16, device=m16.device)
     vt = torch.empty((B, NK, hw), dtype=torch.bfloat16, device=m16.device)
     with _timed('decoder_kv_proj'):
-        rc = _lib_().cgg_decoder_kv_proj_bf16(dev_ptr(m16, 'm16', torch.bfloat16), dev_ptr(mp16, 'mp16', torch.bfloat16),
-                                              dev_ptr(wkp), dev_ptr(bk, 'bk', torch.float32), dev_ptr(wvp), dev_ptr(k),
-                                              dev_ptr(vt), B, hw, C, NK, stream_ptr(m16.device))
-    check(rc, 'cgg_decoder_kv_proj_bf16')
+        _call('cgg_decoder_kv_proj_bf16', dev_ptr(m16, 'm16', torch.bfloat16), dev_ptr(mp16, 'mp16', torch.bfloat16), dev_ptr(wkp),
+              dev_ptr(bk, 'bk', torch.float32), dev_ptr(wvp), dev_ptr(k), dev_ptr(vt), B, hw, C, NK, stream_ptr(m16.device))
     return k, vt
 
 
@@ -1135,8 +1072,7 @@ def pack_encoder_proj_weight(weight):
     N, K = weight.shape
     out = torch.empty((_lib_().cgg_linear_rows_packed_bytes(N, K),), dtype=torch.uint8, device=weight.device)
     w = weight.detach().float().contiguous()
-    check(_lib_().cgg_encoder_proj_pack(dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device)),
-          'cgg_encoder_proj_pack')
+    _call('cgg_encoder_proj_pack', dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device))
     return out
 
 
@@ -1156,12 +1092,10 @@ def encoder_proj(x16, xp16, wvp, bv, wcp, bc, pos16=None, value_head_major=False
         value = torch.empty(x16.shape[:-1] + (bv.numel(),), dtype=torch.bfloat16, device=x16.device)
     offs = torch.empty(x16.shape[:-1] + (bc.numel(),), dtype=torch.bfloat16, device=x16.device)
     with _timed('encoder_proj'):
-        rc = _lib_().cgg_encoder_proj_bf16(
-            dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(xp16, 'xp16', torch.bfloat16), dev_ptr(pos16, 'pos16', torch.bfloat16),
-            pos16.shape[0] if pos16 is not None else 0, dev_ptr(wvp), dev_ptr(bv, 'bv', torch.float32), dev_ptr(wcp),
-            dev_ptr(bc, 'bc', torch.float32), dev_ptr(value), dev_ptr(offs), M, C, bv.numel(), bc.numel(), hm_rows,
-            stream_ptr(x16.device))
-    check(rc, 'cgg_encoder_proj_bf16')
+        _call('cgg_encoder_proj_bf16', dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(xp16, 'xp16', torch.bfloat16),
+              dev_ptr(pos16, 'pos16', torch.bfloat16), pos16.shape[0] if pos16 is not None else 0, dev_ptr(wvp),
+              dev_ptr(bv, 'bv', torch.float32), dev_ptr(wcp), dev_ptr(bc, 'bc', torch.float32), dev_ptr(value), dev_ptr(offs), M, C,
+              bv.numel(), bc.numel(), hm_rows, stream_ptr(x16.device))
     return value, offs
 
 
@@ -1174,12 +1108,10 @@ def encoder_ffn_ln(x16, w1p, b1, w2p, b2, gamma, beta, eps=1e-5, pos=None, want_
     y32 = torch.empty(x16.shape, dtype=torch.float32, device=x16.device) if want_f32 else None
     y16 = torch.empty(x16.shape, dtype=torch.bfloat16, device=x16.device) if want_bf16 else None
     yp16 = torch.empty(x16.shape, dtype=torch.bfloat16, device=x16.device) if want_pos else None
-    rc = _lib_().cgg_encoder_ffn_ln_bf16(
-        dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2p),
-        dev_ptr(b2, 'b2', torch.float32), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
-        float(eps), dev_ptr(pos, 'pos', torch.float32), pos.shape[0] if pos is not None else 0, dev_ptr(y16), dev_ptr(yp16),
-        dev_ptr(y32), M, C, F_, stream_ptr(x16.device))
-    check(rc, 'cgg_encoder_ffn_ln_bf16')
+    _call('cgg_encoder_ffn_ln_bf16', dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2p),
+          dev_ptr(b2, 'b2', torch.float32), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32), float(eps),
+          dev_ptr(pos, 'pos', torch.float32), pos.shape[0] if pos is not None else 0, dev_ptr(y16), dev_ptr(yp16), dev_ptr(y32), M, C,
+          F_, stream_ptr(x16.device))
     return y32, y16, yp16
 
 
@@ -1190,12 +1122,10 @@ def encoder_ffn_ln_kv(x16, w1p, b1, w2p, b2, gamma, beta, eps, shift, pos, level
     y32 = torch.empty(x16.shape, dtype=torch.float32, device=x16.device) if want_f32 else None
     m16 = torch.empty((B * S, C), dtype=torch.bfloat16, device=x16.device)
     mp16 = torch.empty((B * S, C), dtype=torch.bfloat16, device=x16.device)
-    rc = _lib_().cgg_encoder_ffn_ln_kv_bf16(
-        dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2p),
-        dev_ptr(b2, 'b2', torch.float32), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
-        float(eps), dev_ptr(shift, 'shift', torch.float32), dev_ptr(pos, 'pos', torch.float32), S, _int_array(level_start),
-        len(level_start), dev_ptr(y32), dev_ptr(m16), dev_ptr(mp16), B * S, C, b1.numel(), stream_ptr(x16.device))
-    check(rc, 'cgg_encoder_ffn_ln_kv_bf16')
+    _call('cgg_encoder_ffn_ln_kv_bf16', dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32),
+          dev_ptr(w2p), dev_ptr(b2, 'b2', torch.float32), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
+          float(eps), dev_ptr(shift, 'shift', torch.float32), dev_ptr(pos, 'pos', torch.float32), S, _int_array(level_start),
+          len(level_start), dev_ptr(y32), dev_ptr(m16), dev_ptr(mp16), B * S, C, b1.numel(), stream_ptr(x16.device))
     return y32, m16, mp16
 
 
@@ -1221,15 +1151,12 @@ def encoder_layer_tail(a16, x16, wop, bo, norm0, w1p, b1, w2p, b2, norm1, pos=No
         yp16 = torch.empty(x16.shape, dtype=torch.bfloat16, device=dev) if want_pos else None
         pos_rows = pos.shape[0] if pos is not None else 0
     with _timed('encoder_tail_kv' if kv is not None else 'encoder_tail'):
-        rc = _lib_().cgg_encoder_layer_tail_bf16(
-            dev_ptr(a16, 'a16', torch.bfloat16), dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(wop),
-            dev_ptr(bo, 'bo', torch.float32), dev_ptr(norm0[0], 'gamma0', torch.float32),
-            dev_ptr(norm0[1], 'beta0', torch.float32), float(norm0[2]), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32),
-            dev_ptr(w2p), dev_ptr(b2, 'b2', torch.float32), dev_ptr(norm1[0], 'gamma1', torch.float32),
-            dev_ptr(norm1[1], 'beta1', torch.float32), float(norm1[2]), dev_ptr(pos, 'pos', torch.float32), pos_rows,
-            dev_ptr(shift, 'shift', torch.float32), ls, nl, dev_ptr(y16), dev_ptr(yp16), dev_ptr(y32), M, C, b1.numel(),
-            stream_ptr(dev))
-    check(rc, 'cgg_encoder_layer_tail_bf16')
+        _call('cgg_encoder_layer_tail_bf16', dev_ptr(a16, 'a16', torch.bfloat16), dev_ptr(x16, 'x16', torch.bfloat16), dev_ptr(wop),
+              dev_ptr(bo, 'bo', torch.float32), dev_ptr(norm0[0], 'gamma0', torch.float32), dev_ptr(norm0[1], 'beta0', torch.float32),
+              float(norm0[2]), dev_ptr(w1p), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2p), dev_ptr(b2, 'b2', torch.float32),
+              dev_ptr(norm1[0], 'gamma1', torch.float32), dev_ptr(norm1[1], 'beta1', torch.float32), float(norm1[2]),
+              dev_ptr(pos, 'pos', torch.float32), pos_rows, dev_ptr(shift, 'shift', torch.float32), ls, nl, dev_ptr(y16), dev_ptr(yp16),
+              dev_ptr(y32), M, C, b1.numel(), stream_ptr(dev))
     return y32, y16, yp16
 
 
@@ -1246,19 +1173,16 @@ def add_layernorm_backward(dy, a, b, gamma, eps, want_bf16=False, dy16a=None, dy
     partial = torch.empty((nb, 2 * N), dtype=torch.float32, device=a.device)
     if want_amax:
         amax = torch.empty(1, dtype=torch.float32, device=a.device)
-        rc = _lib_().cgg_add_layernorm_backward_amax(dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
-                                                     dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32),
-                                                     dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
-                                                     dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), dev_ptr(amax), rows, N,
-                                                     stream_ptr(a.device))
-        check(rc, 'cgg_add_layernorm_backward_amax')
+        _call('cgg_add_layernorm_backward_amax', dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
+              dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32), dev_ptr(b, 'b', _F32_BF16), bdt,
+              dev_ptr(gamma, 'gamma', torch.float32), float(eps), dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), dev_ptr(amax), rows, N,
+              stream_ptr(a.device))
         sums = partial.sum(0)
         return dx, dx16, sums[:N], sums[N:], amax
-    rc = _lib_().cgg_add_layernorm_backward(dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
-                                            dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32),
-                                            dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32), float(eps),
-                                            dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), rows, N, stream_ptr(a.device))
-    check(rc, 'cgg_add_layernorm_backward')
+    _call('cgg_add_layernorm_backward', dev_ptr(dy, 'dy', torch.float32), dev_ptr(dy16a, 'dy16a', torch.bfloat16),
+          dev_ptr(dy16b, 'dy16b', torch.bfloat16), dev_ptr(a, 'a', torch.float32), dev_ptr(b, 'b', _F32_BF16), bdt,
+          dev_ptr(gamma, 'gamma', torch.float32), float(eps), dev_ptr(dx), dev_ptr(dx16), dev_ptr(partial), rows, N,
+          stream_ptr(a.device))
     sums = partial.sum(0)
     return dx, dx16, sums[:N], sums[N:]
 
@@ -1322,32 +1246,19 @@ def add_layernorm_kv(a, b, gamma, beta, eps, shift, pos, level_start, want_f32=T
     mp16 = torch.empty((B * S, N), dtype=torch.bfloat16, device=a.device)
     adt = _f32_bf16_tag(a, 'add_layernorm_kv: a')
     bdt = _f32_bf16_tag(b, 'add_layernorm_kv: b')
-    rc = _lib_().cgg_add_layernorm_kv(
-        dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt, dev_ptr(gamma, 'gamma', torch.float32),
-        dev_ptr(beta, 'beta', torch.float32), dev_ptr(shift, 'shift', torch.float32), dev_ptr(pos, 'pos', torch.float32),
-        S, _int_array(level_start), len(level_start), dev_ptr(y32), dev_ptr(m16), dev_ptr(mp16), B * S, N, float(eps),
-        stream_ptr(a.device))
-    check(rc, 'cgg_add_layernorm_kv')
+    _call('cgg_add_layernorm_kv', dev_ptr(a, 'a', _F32_BF16), adt, dev_ptr(b, 'b', _F32_BF16), bdt,
+          dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32), dev_ptr(shift, 'shift', torch.float32),
+          dev_ptr(pos, 'pos', torch.float32), S, _int_array(level_start), len(level_start), dev_ptr(y32), dev_ptr(m16), dev_ptr(mp16),
+          B * S, N, float(eps), stream_ptr(a.device))
     return y32, m16, mp16
 
 
 def bias_act_nhwc_(y, bias=None, res=None, relu=True):
     """In place on a channel-last bf16 activation `y` (..., C): y <- act(y + bias[C] + res)."""
     C = y.shape[-1]
-    rc = _lib_().cgg_bias_act_nhwc(dev_ptr(y, 'y', torch.bfloat16), dev_ptr(bias, 'bias', torch.bfloat16),
-                                   dev_ptr(res, 'res', torch.bfloat16), y.numel() // C, C, int(bool(relu)),
-                                   stream_ptr(y.device))
-    check(rc, 'cgg_bias_act_nhwc')
+    _call('cgg_bias_act_nhwc', dev_ptr(y, 'y', torch.bfloat16), dev_ptr(bias, 'bias', torch.bfloat16),
+          dev_ptr(res, 'res', torch.bfloat16), y.numel() // C, C, int(bool(relu)), stream_ptr(y.device))
     return y
-
-
-def _ptr_at(t, elem_offset=0):
-    """Raw device address `elem_offset` elements into tensor `t` (None -> NULL)."""
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise CggError(f'tensor must live on a ROCm device (got {t.device})')
-    return ctypes.c_void_p(t.data_ptr() + int(elem_offset) * t.element_size())
 
 
 def group_norm_nhwc_workspace(B, HW, groups, device):
@@ -1368,23 +1279,20 @@ def group_norm_nhwc(x, gamma, beta, groups, eps, ws, relu=False, up=None, W=0, o
     B, HW, C = x.shape
     if x.dtype not in (torch.bfloat16, torch.float32):
         raise CggError(f'group_norm_nhwc: x dtype {x.dtype}')
-    fn = _lib_().cgg_group_norm_nhwc if x.dtype == torch.bfloat16 else _lib_().cgg_group_norm_nhwc_f32
     need = _lib_().cgg_group_norm_nhwc_workspace_bytes(B, HW, int(groups))
     if ws is None or ws.numel() * ws.element_size() < need:
         raise CggError(f'group_norm_nhwc: workspace too small ({need} bytes needed; see group_norm_nhwc_workspace)')
     b16 = out16[2] if out16 is not None else (outp16[2] if outp16 is not None else 0)
     if out16 is not None and outp16 is not None and out16[2] != outp16[2]:
         raise CggError('group_norm_nhwc: out16 and outp16 must share the batch stride')
-    rc = fn(
-        dev_ptr(x, 'x', x.dtype), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
-        dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups), float(eps), int(bool(relu)),
-        _ptr_at(up[0], up[1]) if up is not None else None, up[3] if up is not None else 0,
-        up[4] if up is not None else 0, up[2] if up is not None else 0, int(W),
-        _ptr_at(out32[0], out32[1]) if out32 is not None else None, out32[2] if out32 is not None else 0,
-        _ptr_at(out16[0], out16[1]) if out16 is not None else None,
-        _ptr_at(pos[0], pos[1]) if pos is not None else None,
-        _ptr_at(outp16[0], outp16[1]) if outp16 is not None else None, b16, stream_ptr(x.device))
-    check(rc, 'cgg_group_norm_nhwc')
+    _call('cgg_group_norm_nhwc' if x.dtype == torch.bfloat16 else 'cgg_group_norm_nhwc_f32', dev_ptr(x, 'x', x.dtype),
+          dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32), dev_ptr(ws, 'ws', torch.float32), B, HW, C,
+          int(groups), float(eps), int(bool(relu)), _ptr_at(*up[:2], 'up', torch.float32) if up is not None else None,
+          up[3] if up is not None else 0, up[4] if up is not None else 0, up[2] if up is not None else 0, int(W),
+          _ptr_at(*out32[:2], 'out32', torch.float32) if out32 is not None else None, out32[2] if out32 is not None else 0,
+          _ptr_at(*out16[:2], 'out16', torch.bfloat16) if out16 is not None else None,
+          _ptr_at(*pos[:2], 'pos', torch.float32) if pos is not None else None,
+          _ptr_at(*outp16[:2], 'outp16', torch.bfloat16) if outp16 is not None else None, b16, stream_ptr(x.device))
 
 
 def group_norm_nhwc_x3a(x, gamma, beta, groups, eps, ws, out, relu=False, up=None, W=0, pos=None, outp=None):
@@ -1398,14 +1306,12 @@ def group_norm_nhwc_x3a(x, gamma, beta, groups, eps, ws, out, relu=False, up=Non
     need = _lib_().cgg_group_norm_nhwc_workspace_bytes(B, HW, int(groups))
     if ws is None or ws.numel() * ws.element_size() < need:
         raise CggError(f'group_norm_nhwc_x3a: workspace too small ({need} bytes needed; see group_norm_nhwc_workspace)')
-    rc = _lib_().cgg_group_norm_nhwc_f32_x3a(
-        dev_ptr(x, 'x', torch.float32), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
-        dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups), float(eps), int(bool(relu)),
-        _ptr_at(up[0], up[1]) if up is not None else None, up[3] if up is not None else 0,
-        up[4] if up is not None else 0, up[2] if up is not None else 0, int(W),
-        _ptr_at(out[0], out[1]), out[2], _ptr_at(pos[0], pos[1]) if pos is not None else None,
-        _ptr_at(outp[0], outp[1]) if outp is not None else None, stream_ptr(x.device))
-    check(rc, 'cgg_group_norm_nhwc_f32_x3a')
+    _call('cgg_group_norm_nhwc_f32_x3a', dev_ptr(x, 'x', torch.float32), dev_ptr(gamma, 'gamma', torch.float32),
+          dev_ptr(beta, 'beta', torch.float32), dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups), float(eps), int(bool(relu)),
+          _ptr_at(*up[:2], 'up', None) if up is not None else None, up[3] if up is not None else 0, up[4] if up is not None else 0,
+          up[2] if up is not None else 0, int(W), _ptr_at(*out[:2], 'out', None), out[2],
+          _ptr_at(*pos[:2], 'pos', torch.float32) if pos is not None else None,
+          _ptr_at(*outp[:2], 'outp', None) if outp is not None else None, stream_ptr(x.device))
 
 
 def group_norm_nhwc_stats(x, groups, ws):
@@ -1417,8 +1323,8 @@ def group_norm_nhwc_stats(x, groups, ws):
     need = _lib_().cgg_group_norm_nhwc_workspace_bytes(B, HW, int(groups))
     if ws is None or ws.dtype != torch.float32 or ws.numel() * ws.element_size() < need:
         raise CggError(f'group_norm_nhwc_stats: workspace too small ({need} bytes needed; see group_norm_nhwc_workspace)')
-    check(_lib_().cgg_group_norm_nhwc_f32_stats(dev_ptr(x, 'x', torch.float32), dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups),
-                                                stream_ptr(x.device)), 'cgg_group_norm_nhwc_f32_stats')
+    _call('cgg_group_norm_nhwc_f32_stats', dev_ptr(x, 'x', torch.float32), dev_ptr(ws, 'ws', torch.float32), B, HW, C, int(groups),
+          stream_ptr(x.device))
 
 
 def zero_border_map(B, H, W, C, device):
@@ -1440,11 +1346,10 @@ def group_norm_nhwc_padout(x, gamma, beta, groups, eps, ws, hw, y_padded, relu=F
         raise CggError('group_norm_nhwc_padout: x (B, HW, C) float32 contiguous and y_padded (B, H + 2, W + 2, C) expected')
     if lo is not None and (not lo.is_contiguous() or lo.dtype != torch.float32):
         raise CggError('group_norm_nhwc_padout: lo must be contiguous float32 rows')
-    check(_lib_().cgg_group_norm_nhwc_f32_padout(
-        dev_ptr(x), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32), dev_ptr(ws), B, HW, C, int(groups),
-        float(eps), int(bool(relu)), dev_ptr(lo) if lo is not None else None, int(lo_hw[0]) if lo is not None else 0,
-        int(lo_hw[1]) if lo is not None else 0, int(lo.shape[1]) * C if lo is not None else 0, W, dev_ptr(y_padded),
-        stream_ptr(x.device)), 'cgg_group_norm_nhwc_f32_padout')
+    _call('cgg_group_norm_nhwc_f32_padout', dev_ptr(x), dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(beta, 'beta', torch.float32),
+          dev_ptr(ws), B, HW, C, int(groups), float(eps), int(bool(relu)), dev_ptr(lo) if lo is not None else None,
+          int(lo_hw[0]) if lo is not None else 0, int(lo_hw[1]) if lo is not None else 0, int(lo.shape[1]) * C if lo is not None else 0,
+          W, dev_ptr(y_padded), stream_ptr(x.device))
 
 
 def group_norm_nhwc_backward(x, y, dy, stats, gamma, groups, eps, relu, hw, lo_hw=None, dx_padded=None):
@@ -1452,16 +1357,14 @@ def group_norm_nhwc_backward(x, y, dy, stats, gamma, groups, eps, relu, hw, lo_h
     (B * groups * 2) = the forward workspace's head. -> (dx, dgamma, dbeta, dlo | None); dx_padded: a `zero_border_map` that receives
     dx in its interior (then returned as dx)."""
     B, HW, C = x.shape
-    lib = _lib_()
-    ws = torch.empty(max(lib.cgg_group_norm_nhwc_backward_workspace_bytes(B, HW, int(groups)) // 4, 1), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(_lib_().cgg_group_norm_nhwc_backward_workspace_bytes(B, HW, int(groups)) // 4, 1), dtype=torch.float32, device=x.device)
     dx = dx_padded if dx_padded is not None else torch.empty_like(x)
     tot = torch.empty((B, int(groups), 16), dtype=torch.float32, device=x.device)
     dlo = torch.empty((B, lo_hw[0] * lo_hw[1], C), dtype=torch.float32, device=x.device) if lo_hw is not None else None
-    check(lib.cgg_group_norm_nhwc_f32_backward(dev_ptr(x), dev_ptr(y) if relu else None, dev_ptr(dy), dev_ptr(stats),
-                                               dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(ws), B, HW, C, int(groups), float(eps),
-                                               int(bool(relu)), dev_ptr(dx), dev_ptr(tot), dev_ptr(dlo) if dlo is not None else None,
-                                               lo_hw[0] if lo_hw else 0, lo_hw[1] if lo_hw else 0, int(hw[1]),
-                                               int(dx_padded is not None), stream_ptr(x.device)), 'cgg_group_norm_nhwc_f32_backward')
+    _call('cgg_group_norm_nhwc_f32_backward', dev_ptr(x), dev_ptr(y) if relu else None, dev_ptr(dy), dev_ptr(stats),
+          dev_ptr(gamma, 'gamma', torch.float32), dev_ptr(ws), B, HW, C, int(groups), float(eps), int(bool(relu)), dev_ptr(dx),
+          dev_ptr(tot), dev_ptr(dlo) if dlo is not None else None, lo_hw[0] if lo_hw else 0, lo_hw[1] if lo_hw else 0, int(hw[1]),
+          int(dx_padded is not None), stream_ptr(x.device))
     t = tot.sum(0)                                        # (groups, 16)
     return dx, t[:, :8].reshape(C), t[:, 8:].reshape(C), dlo
 
@@ -1503,9 +1406,8 @@ def pack_mask_feature_nhwc(feat, pool=1):
     h, w = H // pool, W // pool
     T = (h * w + 31) // 32
     hi = torch.empty((B, T, C // 8, 32, 8), dtype=torch.bfloat16, device=feat.device)
-    rc = _lib_().cgg_pack_mask_feature_nhwc(dev_ptr(feat, 'mask_feature', torch.bfloat16), dev_ptr(hi), B, C, H, W,
-                                            int(pool), stream_ptr(feat.device))
-    check(rc, 'cgg_pack_mask_feature_nhwc')
+    _call('cgg_pack_mask_feature_nhwc', dev_ptr(feat, 'mask_feature', torch.bfloat16), dev_ptr(hi), B, C, H, W, int(pool),
+          stream_ptr(feat.device))
     return PackedFeature(hi, None, B, C, h, w)
 
 
@@ -1526,10 +1428,8 @@ def pack_mask_feature_nhwc_x3(feat, pools):
         hp.append(hi.data_ptr())
         lp.append(lo.data_ptr())
     n = len(pools)
-    rc = _lib_().cgg_pack_mask_feature_nhwc_f32_x3(dev_ptr(feat, 'mask_feature', torch.float32), (ctypes.c_void_p * n)(*hp),
-                                                   (ctypes.c_void_p * n)(*lp), _int_array([int(p) for p in pools]), n,
-                                                   B, C, H, W, stream_ptr(feat.device))
-    check(rc, 'cgg_pack_mask_feature_nhwc_f32_x3')
+    _call('cgg_pack_mask_feature_nhwc_f32_x3', dev_ptr(feat, 'mask_feature', torch.float32), (ctypes.c_void_p * n)(*hp),
+          (ctypes.c_void_p * n)(*lp), _int_array([int(p) for p in pools]), n, B, C, H, W, stream_ptr(feat.device))
     return outs
 
 
@@ -1603,11 +1503,9 @@ def mask_feature_head_x3(z, ws, gn, weight_x3, bias, pools, want_f32=False, cfg=
     n = len(pools)
     with _timed('mask_feature_head_x3', flops=2.0 * B * H * W * C * C, bytes=4.0 * B * H * W * C * (2.4 + (1 if want_f32 else 0)),
                 shape=(B * H * W, C, C)):
-        rc = _lib_().cgg_mask_feature_head_x3_cfg(
-            dev_ptr(z), dev_ptr(ws), dev_ptr(gamma), dev_ptr(beta), float(eps), int(groups), dev_ptr(weight_x3),
-            dev_ptr(bias) if bias is not None else None, (ctypes.c_void_p * n)(*hp), (ctypes.c_void_p * n)(*lp), _int_array(pools), n,
-            dev_ptr(mf) if mf is not None else None, B, H, W, C, C, int(cfg), stream_ptr(z.device))
-    check(rc, 'cgg_mask_feature_head_x3')
+        _call('cgg_mask_feature_head_x3_cfg', dev_ptr(z), dev_ptr(ws), dev_ptr(gamma), dev_ptr(beta), float(eps), int(groups),
+              dev_ptr(weight_x3), dev_ptr(bias) if bias is not None else None, (ctypes.c_void_p * n)(*hp), (ctypes.c_void_p * n)(*lp),
+              _int_array(pools), n, dev_ptr(mf) if mf is not None else None, B, H, W, C, C, int(cfg), stream_ptr(z.device))
     return (outs, mf) if want_f32 else outs
 
 
@@ -1623,10 +1521,8 @@ def pack_mask_feature_nhwc_multi(feat, pools):
         outs.append(PackedFeature(hi, None, B, C, h, w))
         ptrs.append(hi.data_ptr())
     n = len(pools)
-    rc = _lib_().cgg_pack_mask_feature_nhwc_multi(dev_ptr(feat, 'mask_feature', torch.bfloat16),
-                                                  (ctypes.c_void_p * n)(*ptrs), _int_array([int(p) for p in pools]), n,
-                                                  B, C, H, W, stream_ptr(feat.device))
-    check(rc, 'cgg_pack_mask_feature_nhwc_multi')
+    _call('cgg_pack_mask_feature_nhwc_multi', dev_ptr(feat, 'mask_feature', torch.bfloat16), (ctypes.c_void_p * n)(*ptrs),
+          _int_array([int(p) for p in pools]), n, B, C, H, W, stream_ptr(feat.device))
     return outs
 
 
@@ -1654,11 +1550,12 @@ def _x3_check(packed, N, K, who):
 
 
 def _x3_fn(name, *packed):
-    """C entry point `cgg_<name>_bf16` or its f32-class twin `cgg_<name>_x3`; all packed operands must be of one kind."""
+    """Symbol of the C entry point `cgg_<name>_bf16` or of its f32-class twin `cgg_<name>_x3`; all packed operands must be of one
+    kind."""
     kinds = {is_x3(p) for p in packed if p is not None}
     if len(kinds) > 1:
         raise CggError(f'{name}: bf16 and x3 packed weights mixed in one call')
-    return getattr(_lib_(), f'cgg_{name}_x3' if True in kinds else f'cgg_{name}_bf16'), ('x3' if True in kinds else 'bf16')
+    return f'cgg_{name}_x3' if True in kinds else f'cgg_{name}_bf16'
 
 
 def pack_linear_weight_x3(weight):
@@ -1669,8 +1566,7 @@ def pack_linear_weight_x3(weight):
         raise CggError(f'pack_linear_weight_x3: unsupported shape {tuple(weight.shape)} (K % 16)')
     out = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
     w = weight.detach().float().contiguous()
-    rc = _lib_().cgg_x3_pack(dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device))
-    check(rc, 'cgg_x3_pack')
+    _call('cgg_x3_pack', dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device))
     return out.as_subclass(X3Image)
 
 
@@ -1683,13 +1579,13 @@ def pack_conv_weight_x3(weight):
 def topk_select(x, k):
     """x (rows, N) float32 ROCm (last dim contiguous) -> (rows, k) int64: the indices of each row's k largest values as a SET
     (no order, ties at the threshold arbitrary) -- csrc/topk_select.hip, a radix select instead of torch.topk's sort."""
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.stride(1) != 1 or not 0 < k <= x.shape[1]:
-        raise CggError('topk_select: (rows, N) float32 ROCm matrix with a contiguous last dim and 0 < k <= N expected')
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1 or not 0 < k <= x.shape[1]:
+        raise CggError('topk_select: (rows, N) float32 matrix with a contiguous last dim and 0 < k <= N expected')
     rows, N = x.shape
+    px = dev_ptr(x, 'x', torch.float32, dense=False)
     out = torch.empty((rows, k), dtype=torch.int64, device=x.device)
     if rows:
-        check(_lib_().cgg_topk_select(ctypes.c_void_p(x.data_ptr()), int(x.stride(0)), rows, N, int(k), dev_ptr(out),
-                                      stream_ptr(x.device)), 'cgg_topk_select')
+        _call('cgg_topk_select', px, int(x.stride(0)), rows, N, int(k), dev_ptr(out), stream_ptr(x.device))
     return out
 
 
@@ -1697,8 +1593,6 @@ def absmax(x):
     """max |x| of a float32 ROCm matrix / tensor (last dim contiguous, % 4) -> device scalar (1,) f32: the per-tensor pre-scale
     of the x3 contractions' grad_output operands (`gemm_x3(..., amax=)`, `wgrad_x3(..., amax=)`; csrc/x3.h). Exact: one streaming
     pass over the tensor (a sampled maximum is NOT safe for gradients -- they are sparse, see runtime._X3LinearFn.backward)."""
-    if x.dtype != torch.float32 or not x.is_cuda:
-        raise CggError('absmax: float32 ROCm tensor expected')
     x2 = x.reshape(-1, x.shape[-1]) if x.is_contiguous() else x
     if x2.dim() != 2 or x2.stride(1) != 1:
         raise CggError('absmax: a 2-D view with a contiguous last dim expected')
@@ -1706,8 +1600,8 @@ def absmax(x):
         x2 = x2.view(1, -1)                       # dense: one long row
     out = torch.empty(1, dtype=torch.float32, device=x.device)
     M, N = x2.shape
-    check(_lib_().cgg_absmax_f32(ctypes.c_void_p(x2.data_ptr()), int(x2.stride(0)) if M > 1 else N, M, N, dev_ptr(out),
-                                 stream_ptr(x.device)), 'cgg_absmax_f32')
+    _call('cgg_absmax_f32', dev_ptr(x2, 'x', torch.float32, dense=False), int(x2.stride(0)) if M > 1 else N, M, N, dev_ptr(out),
+          stream_ptr(x.device))
     return out
 
 
@@ -1719,8 +1613,7 @@ def relu_backward_absmax(gy, y):
         raise CggError('relu_backward_absmax: two contiguous float32 ROCm tensors of one shape with numel % 4 == 0 expected')
     g = torch.empty_like(gy)
     amax = torch.empty(1, dtype=torch.float32, device=gy.device)
-    check(_lib_().cgg_relu_bwd_absmax_f32(dev_ptr(gy), dev_ptr(y), dev_ptr(g), gy.numel(), dev_ptr(amax), stream_ptr(gy.device)),
-          'cgg_relu_bwd_absmax_f32')
+    _call('cgg_relu_bwd_absmax_f32', dev_ptr(gy), dev_ptr(y), dev_ptr(g), gy.numel(), dev_ptr(amax), stream_ptr(gy.device))
     return g, amax
 
 
@@ -1728,8 +1621,8 @@ def gemm_x3(a, packed, N, bias=None, res=None, relu=False, out=None, amax=None):
     """a (M, K) f32 rows (row stride free, last dim contiguous) x x3 image -> act(a W^T + bias (+ res)) (M, N) f32:
     parity mode's large linear (csrc/x3_gemm.hip). amax: device scalar max |a| (`absmax`) -> a is pre-scaled per tensor instead
     of by the fixed 2^4 (operands that are not unit scale: gradients)."""
-    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not a.is_cuda or not is_x3(packed):
-        raise CggError('gemm_x3: a must be a 2-D float32 ROCm tensor with a contiguous last dim, packed an x3 image')
+    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not is_x3(packed):
+        raise CggError('gemm_x3: a must be a 2-D float32 tensor with a contiguous last dim, packed an x3 image')
     M, K = a.shape
     _x3_check(packed, N, K, 'gemm_x3')
     y = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=a.device)
@@ -1740,17 +1633,15 @@ def gemm_x3(a, packed, N, bias=None, res=None, relu=False, out=None, amax=None):
     with _timed('gemm_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * K + M * N * (2 if res is not None else 1)) + 4.0 * N * K,
                 shape=(M, N, K)):
         if amax is not None:
-            rc = _lib_().cgg_gemm_x3_scaled(ctypes.c_void_p(a.data_ptr()), a.stride(0), dev_ptr(amax, 'amax', torch.float32),
-                                            dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-                                            ctypes.c_void_p(res.data_ptr()) if res is not None else None,
-                                            res.stride(0) if res is not None else 0, ctypes.c_void_p(y.data_ptr()), y.stride(0), M, N,
-                                            K, int(bool(relu)), stream_ptr(a.device))
+            _call('cgg_gemm_x3_scaled', dev_ptr(a, 'a', torch.float32, dense=False), a.stride(0), dev_ptr(amax, 'amax', torch.float32),
+                  dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res, 'res', torch.float32, dense=False),
+                  res.stride(0) if res is not None else 0, dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), M, N, K,
+                  int(bool(relu)), stream_ptr(a.device))
         else:
-            rc = _lib_().cgg_gemm_x3(ctypes.c_void_p(a.data_ptr()), a.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-                                     ctypes.c_void_p(res.data_ptr()) if res is not None else None,
-                                     res.stride(0) if res is not None else 0, ctypes.c_void_p(y.data_ptr()), y.stride(0), M, N, K,
-                                     int(bool(relu)), stream_ptr(a.device))
-    check(rc, 'cgg_gemm_x3')
+            _call('cgg_gemm_x3', dev_ptr(a, 'a', torch.float32, dense=False), a.stride(0), dev_ptr(packed),
+                  dev_ptr(bias, 'bias', torch.float32), dev_ptr(res, 'res', torch.float32, dense=False),
+                  res.stride(0) if res is not None else 0, dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), M, N, K,
+                  int(bool(relu)), stream_ptr(a.device))
     return y
 
 
@@ -1758,8 +1649,8 @@ def gemm_x3_bwd(g, packed, N, amax=None, mask=None, out=None, want_amax=False):
     """Backward-side x3 GEMM (csrc/x3_gemm.hip `cgg_gemm_x3_bwd`): out (M, N) = g (M, K) W^T with g pre-scaled per tensor (`amax`),
     the result zeroed where `mask` (M, N) <= 0 (ReLU backward of the layer whose output `mask` is) and, with want_amax, max |out|
     from the epilogue as a device scalar -> (out, out_amax | None)."""
-    if g.dim() != 2 or g.stride(1) != 1 or g.dtype != torch.float32 or not g.is_cuda or not is_x3(packed):
-        raise CggError('gemm_x3_bwd: g must be a 2-D float32 ROCm tensor with a contiguous last dim, packed an x3 image')
+    if g.dim() != 2 or g.stride(1) != 1 or g.dtype != torch.float32 or not is_x3(packed):
+        raise CggError('gemm_x3_bwd: g must be a 2-D float32 tensor with a contiguous last dim, packed an x3 image')
     M, K = g.shape
     _x3_check(packed, N, K, 'gemm_x3_bwd')
     y = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=g.device)
@@ -1770,11 +1661,9 @@ def gemm_x3_bwd(g, packed, N, amax=None, mask=None, out=None, want_amax=False):
     oa = torch.empty(1, dtype=torch.float32, device=g.device) if want_amax else None
     with _timed('gemm_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * K + M * N * (2 if mask is not None else 1)) + 4.0 * N * K,
                 shape=(M, N, K)):
-        rc = _lib_().cgg_gemm_x3_bwd(ctypes.c_void_p(g.data_ptr()), g.stride(0), dev_ptr(amax, 'amax', torch.float32), dev_ptr(packed),
-                                     ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                     mask.stride(0) if mask is not None else 0, ctypes.c_void_p(y.data_ptr()), y.stride(0),
-                                     dev_ptr(oa), M, N, K, stream_ptr(g.device))
-    check(rc, 'cgg_gemm_x3_bwd')
+        _call('cgg_gemm_x3_bwd', dev_ptr(g, 'g', torch.float32, dense=False), g.stride(0), dev_ptr(amax, 'amax', torch.float32),
+              dev_ptr(packed), dev_ptr(mask, 'mask', torch.float32, dense=False), mask.stride(0) if mask is not None else 0,
+              dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), dev_ptr(oa), M, N, K, stream_ptr(g.device))
     return y, oa
 
 
@@ -1794,14 +1683,12 @@ def encoder_layer_tail_x3(a, x, wo, bo, norm0, w1, b1, w2, b2, norm1, pos=None, 
     yp = torch.empty_like(a) if want_pos else None
     with _timed('encoder_tail_x3', flops=2.0 * M * (C * C + 2 * C * F), bytes=4.0 * M * C * (3 + (1 if want_pos else 0)),
                 shape=(M, C, F)):
-        fn = _lib_().cgg_encoder_layer_tail_x3a if x3a else _lib_().cgg_encoder_layer_tail_x3
-        rc = fn(
-            dev_ptr(a), dev_ptr(x), dev_ptr(wo), dev_ptr(bo, 'bo', torch.float32), dev_ptr(norm0[0], 'gamma0', torch.float32),
-            dev_ptr(norm0[1], 'beta0', torch.float32), float(norm0[2]), dev_ptr(w1), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2),
-            dev_ptr(b2, 'b2', torch.float32), dev_ptr(norm1[0], 'gamma1', torch.float32), dev_ptr(norm1[1], 'beta1', torch.float32),
-            float(norm1[2]), dev_ptr(pos, 'pos', torch.float32) if want_pos else None, pos.shape[0] if want_pos else 0, dev_ptr(y),
-            dev_ptr(yp), M, C, int(F), stream_ptr(a.device))
-    check(rc, 'cgg_encoder_layer_tail_x3')
+        _call('cgg_encoder_layer_tail_x3a' if x3a else 'cgg_encoder_layer_tail_x3', dev_ptr(a), dev_ptr(x), dev_ptr(wo),
+              dev_ptr(bo, 'bo', torch.float32), dev_ptr(norm0[0], 'gamma0', torch.float32), dev_ptr(norm0[1], 'beta0', torch.float32),
+              float(norm0[2]), dev_ptr(w1), dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2), dev_ptr(b2, 'b2', torch.float32),
+              dev_ptr(norm1[0], 'gamma1', torch.float32), dev_ptr(norm1[1], 'beta1', torch.float32), float(norm1[2]),
+              dev_ptr(pos, 'pos', torch.float32) if want_pos else None, pos.shape[0] if want_pos else 0, dev_ptr(y), dev_ptr(yp), M, C,
+              int(F), stream_ptr(a.device))
     return y, yp
 
 
@@ -1812,7 +1699,7 @@ def transpose_f32(x):
         raise CggError('transpose_f32: contiguous (B, R, C) float32 ROCm tensor expected')
     B, R, C = x.shape
     y = torch.empty((B, C, R), dtype=torch.float32, device=x.device)
-    check(_lib_().cgg_transpose_f32(dev_ptr(x), dev_ptr(y), B, R, C, stream_ptr(x.device)), 'cgg_transpose_f32')
+    _call('cgg_transpose_f32', dev_ptr(x), dev_ptr(y), B, R, C, stream_ptr(x.device))
     return y
 
 
@@ -1832,7 +1719,7 @@ def nchw_to_nhwc_pad1(x):
     B, C, H, W = x.shape
     x = x.contiguous()
     y = zero_border_map(B, H, W, C, x.device)
-    check(_lib_().cgg_nchw_to_nhwc_pad1_f32(dev_ptr(x), dev_ptr(y), B, C, H, W, stream_ptr(x.device)), 'cgg_nchw_to_nhwc_pad1_f32')
+    _call('cgg_nchw_to_nhwc_pad1_f32', dev_ptr(x), dev_ptr(y), B, C, H, W, stream_ptr(x.device))
     return y
 
 
@@ -1848,27 +1735,24 @@ def wgrad_x3(dy, x, want_bias=False, amax=None):
     want_bias: -> (dW, db) with db (N) = dy.sum(0) from the same pass over dy. amax: device scalar max |dy| (`absmax`) -> dy is
     pre-scaled per tensor instead of by the fixed 2^4 (gradients are not unit scale, csrc/x3.h)."""
     if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or dy.dtype != torch.float32 or x.dtype != torch.float32 \
-            or not dy.is_cuda or dy.stride(1) != 1 or x.stride(1) != 1:
-        raise CggError('wgrad_x3: dy (M, N) and x (M, K) must be float32 ROCm matrices with contiguous rows')
+            or dy.stride(1) != 1 or x.stride(1) != 1:
+        raise CggError('wgrad_x3: dy (M, N) and x (M, K) must be float32 matrices with contiguous rows')
     M, N = dy.shape
     K = x.shape[1]
-    lib = _lib_()
-    nbytes = lib.cgg_wgrad_x3_workspace_bytes(M, N, K)
+    pdy, px = dev_ptr(dy, 'dy', torch.float32, dense=False), dev_ptr(x, 'x', torch.float32, dense=False)
+    nbytes = _lib_().cgg_wgrad_x3_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
     splits = ctypes.c_int(0)
     wsb = torch.empty((nbytes // (4 * N * K)) * N, dtype=torch.float32, device=dy.device) if want_bias else None
     with _timed('wgrad_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * N + M * K + N * K), shape=(M, N, K)):
         if amax is not None:
-            rc = lib.cgg_wgrad_x3_scaled(ctypes.c_void_p(dy.data_ptr()), dy.stride(0), dev_ptr(amax, 'amax', torch.float32),
-                                         ctypes.c_void_p(x.data_ptr()), x.stride(0), dev_ptr(ws), dev_ptr(wsb), ctypes.byref(splits),
-                                         M, N, K, stream_ptr(dy.device))
+            _call('cgg_wgrad_x3_scaled', pdy, dy.stride(0), dev_ptr(amax, 'amax', torch.float32), px, x.stride(0), dev_ptr(ws),
+                  dev_ptr(wsb), ctypes.byref(splits), M, N, K, stream_ptr(dy.device))
         elif want_bias:
-            rc = lib.cgg_wgrad_bias_x3(ctypes.c_void_p(dy.data_ptr()), dy.stride(0), ctypes.c_void_p(x.data_ptr()), x.stride(0),
-                                       dev_ptr(ws), dev_ptr(wsb), ctypes.byref(splits), M, N, K, stream_ptr(dy.device))
+            _call('cgg_wgrad_bias_x3', pdy, dy.stride(0), px, x.stride(0), dev_ptr(ws), dev_ptr(wsb), ctypes.byref(splits), M, N, K,
+                  stream_ptr(dy.device))
         else:
-            rc = lib.cgg_wgrad_x3(ctypes.c_void_p(dy.data_ptr()), dy.stride(0), ctypes.c_void_p(x.data_ptr()), x.stride(0), dev_ptr(ws),
-                                  ctypes.byref(splits), M, N, K, stream_ptr(dy.device))
-    check(rc, 'cgg_wgrad_x3')
+            _call('cgg_wgrad_x3', pdy, dy.stride(0), px, x.stride(0), dev_ptr(ws), ctypes.byref(splits), M, N, K, stream_ptr(dy.device))
     gw = ws.view(splits.value, N, K).sum(0) if splits.value > 1 else ws.view(N, K).clone()
     if want_bias:
         return gw, wsb.view(-1, N)[:splits.value].sum(0)
@@ -1878,8 +1762,8 @@ def wgrad_x3(dy, x, want_bias=False, amax=None):
 def gemm_x3_split(a, packed, N, col2, bias=None, res_table=None):
     """a (M, K) f32 rows x x3 image of an (N, K) weight -> (y1 (M, col2), y2 (M, N - col2)) = column blocks of
     a W^T + bias + res_table[row % len(res_table)] (res_table (R, N) f32 | None), one launch (`cgg_gemm_x3_ex`)."""
-    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not a.is_cuda or not is_x3(packed):
-        raise CggError('gemm_x3_split: a must be a 2-D float32 ROCm tensor with a contiguous last dim, packed an x3 image')
+    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not is_x3(packed):
+        raise CggError('gemm_x3_split: a must be a 2-D float32 tensor with a contiguous last dim, packed an x3 image')
     M, K = a.shape
     _x3_check(packed, N, K, 'gemm_x3_split')
     y1 = torch.empty((M, col2), dtype=torch.float32, device=a.device)
@@ -1888,19 +1772,18 @@ def gemm_x3_split(a, packed, N, col2, bias=None, res_table=None):
                                   or res_table.dtype != torch.float32):
         raise CggError('gemm_x3_split: res_table must be a contiguous (R, N) float32 tensor')
     with _timed('gemm_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * K + M * N + N * K), shape=(M, N, K)):
-        rc = _lib_().cgg_gemm_x3_ex(ctypes.c_void_p(a.data_ptr()), a.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-                                    dev_ptr(res_table), N if res_table is not None else 0,
-                                    res_table.shape[0] if res_table is not None else 0, dev_ptr(y1), col2, dev_ptr(y2), N - col2,
-                                    int(col2), M, N, K, 0, stream_ptr(a.device))
-    check(rc, 'cgg_gemm_x3_ex')
+        _call('cgg_gemm_x3_ex', dev_ptr(a, 'a', torch.float32, dense=False), a.stride(0), dev_ptr(packed),
+              dev_ptr(bias, 'bias', torch.float32), dev_ptr(res_table), N if res_table is not None else 0,
+              res_table.shape[0] if res_table is not None else 0, dev_ptr(y1), col2, dev_ptr(y2), N - col2, int(col2), M, N, K, 0,
+              stream_ptr(a.device))
     return y1, y2
 
 
 def gemm_x3_table(a, packed, N, res_table, bias=None, out=None):
     """a (M, K) f32 rows x x3 image of an (N, K) weight -> a W^T + bias + res_table[row % len(res_table)] (M, N) f32, one launch
     (`cgg_gemm_x3_ex` with a row-periodic residual): a linear layer whose bias is a per-token table shared by the images of a batch."""
-    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not a.is_cuda or not is_x3(packed):
-        raise CggError('gemm_x3_table: a must be a 2-D float32 ROCm tensor with a contiguous last dim, packed an x3 image')
+    if a.dim() != 2 or a.stride(1) != 1 or a.dtype != torch.float32 or not is_x3(packed):
+        raise CggError('gemm_x3_table: a must be a 2-D float32 tensor with a contiguous last dim, packed an x3 image')
     M, K = a.shape
     _x3_check(packed, N, K, 'gemm_x3_table')
     if res_table.dim() != 2 or res_table.shape[1] != N or not res_table.is_contiguous() or res_table.dtype != torch.float32 \
@@ -1910,10 +1793,9 @@ def gemm_x3_table(a, packed, N, res_table, bias=None, out=None):
     if y.shape != (M, N) or not y.is_contiguous() or y.dtype != torch.float32:
         raise CggError('gemm_x3_table: bad `out`')
     with _timed('gemm_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * K + M * N + N * K), shape=(M, N, K)):
-        rc = _lib_().cgg_gemm_x3_ex(ctypes.c_void_p(a.data_ptr()), a.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-                                    dev_ptr(res_table), N, res_table.shape[0], dev_ptr(y), N, None, 0, 0, M, N, K, 0,
-                                    stream_ptr(a.device))
-    check(rc, 'cgg_gemm_x3_ex')
+        _call('cgg_gemm_x3_ex', dev_ptr(a, 'a', torch.float32, dense=False), a.stride(0), dev_ptr(packed),
+              dev_ptr(bias, 'bias', torch.float32), dev_ptr(res_table), N, res_table.shape[0], dev_ptr(y), N, None, 0, 0, M, N, K, 0,
+              stream_ptr(a.device))
     return y
 
 
@@ -1933,13 +1815,12 @@ def conv_x3_nhwc(x, packed, N, kernel, stride=1, pad=0, bias=None, res=None, rel
                 bytes=4.0 * (B * H * W * C + B * OH * OW * N * (2 if res is not None else 1) + N * C * KH * KW),
                 shape=(B * OH * OW, N, C * KH * KW)):
         if amax is not None:
-            rc = _lib_().cgg_conv_x3_nhwc_scaled(dev_ptr(x), dev_ptr(amax, 'amax', torch.float32), dev_ptr(packed),
-                                                 dev_ptr(bias, 'bias', torch.float32), dev_ptr(res), dev_ptr(y), B, H, W, C, N, KH, KW,
-                                                 int(stride), int(pad), int(bool(relu)), stream_ptr(x.device))
+            _call('cgg_conv_x3_nhwc_scaled', dev_ptr(x), dev_ptr(amax, 'amax', torch.float32), dev_ptr(packed),
+                  dev_ptr(bias, 'bias', torch.float32), dev_ptr(res), dev_ptr(y), B, H, W, C, N, KH, KW, int(stride), int(pad),
+                  int(bool(relu)), stream_ptr(x.device))
         else:
-            rc = _lib_().cgg_conv_x3_nhwc(dev_ptr(x), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res), dev_ptr(y),
-                                          B, H, W, C, N, KH, KW, int(stride), int(pad), int(bool(relu)), stream_ptr(x.device))
-    check(rc, 'cgg_conv_x3_nhwc')
+            _call('cgg_conv_x3_nhwc', dev_ptr(x), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res), dev_ptr(y), B, H,
+                  W, C, N, KH, KW, int(stride), int(pad), int(bool(relu)), stream_ptr(x.device))
     return y
 
 
@@ -1976,7 +1857,7 @@ def x3a_encode(x):
     if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.numel() % 8:
         raise CggError('x3a_encode: contiguous float32 ROCm tensor with numel % 8 == 0 expected')
     y = torch.empty_like(x)
-    check(_lib_().cgg_x3a_encode(dev_ptr(x), dev_ptr(y), x.numel(), stream_ptr(x.device)), 'cgg_x3a_encode')
+    _call('cgg_x3a_encode', dev_ptr(x), dev_ptr(y), x.numel(), stream_ptr(x.device))
     return y
 
 
@@ -1985,7 +1866,7 @@ def x3a_decode(x):
     if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.numel() % 8:
         raise CggError('x3a_decode: contiguous float32-tagged ROCm tensor with numel % 8 == 0 expected')
     y = torch.empty_like(x)
-    check(_lib_().cgg_x3a_decode(dev_ptr(x), dev_ptr(y), x.numel(), stream_ptr(x.device)), 'cgg_x3a_decode')
+    _call('cgg_x3a_decode', dev_ptr(x), dev_ptr(y), x.numel(), stream_ptr(x.device))
     return y
 
 
@@ -1994,7 +1875,7 @@ def x3_overflow_check(device, reset=True):
     Synchronises the current stream."""
     v = ctypes.c_int(0)
     with torch.cuda.device(device):
-        check(_lib_().cgg_x3_overflow_check(int(bool(reset)), ctypes.byref(v), stream_ptr(device)), 'cgg_x3_overflow_check')
+        _call('cgg_x3_overflow_check', int(bool(reset)), ctypes.byref(v), stream_ptr(device))
     return v.value != 0
 
 
@@ -2005,8 +1886,8 @@ def _x3s_fmt(split):
 def gemm_x3s(a, packed, N, bias=None, res=None, res_split=False, res_mod=0, relu=False, out=None, out_split=False, cfg=-1):
     """a (M, K) x3a rows (row stride free, multiples of 8) x x3 image -> act(a W^T + bias (+ res)) (M, N), f32 or x3a
     (`out_split`); res (M, N) | (res_mod, N) in f32 or x3a (`res_split`). csrc/x3s_gemm.hip."""
-    if a.dim() not in (2, 3) or a.stride(-1) != 1 or a.dtype != torch.float32 or not a.is_cuda or not is_x3(packed):
-        raise CggError('gemm_x3s: a must be a 2-D / 3-D float32-tagged ROCm tensor with a contiguous last dim, packed an x3 image')
+    if a.dim() not in (2, 3) or a.stride(-1) != 1 or a.dtype != torch.float32 or not is_x3(packed):
+        raise CggError('gemm_x3s: a must be a 2-D / 3-D float32-tagged tensor with a contiguous last dim, packed an x3 image')
     rpb, bstride = 0, 0
     if a.dim() == 3:                    # (B, R, K) view of a stack of images (row stride and image stride free): rows = B * R
         rpb, bstride = int(a.shape[1]), int(a.stride(0))
@@ -2021,19 +1902,15 @@ def gemm_x3s(a, packed, N, bias=None, res=None, res_split=False, res_mod=0, relu
         raise CggError('gemm_x3s: bad `res` view')
     with _timed('gemm_x3', flops=2.0 * M * N * K, bytes=4.0 * (M * K + M * N * (2 if res is not None and not res_mod else 1)) +
                 4.0 * N * K, shape=(M, N, K)):
-        rc = _lib_().cgg_gemm_x3s_batched(ctypes.c_void_p(a.data_ptr()), lda, rpb, bstride, dev_ptr(packed),
-                                          dev_ptr(bias, 'bias', torch.float32),
-                                          ctypes.c_void_p(res.data_ptr()) if res is not None else None,
-                                          res.stride(0) if res is not None else 0,
-                                          0 if res is None else _x3s_fmt(res_split), int(res_mod), ctypes.c_void_p(y.data_ptr()),
-                                          y.stride(0), _x3s_fmt(out_split), M, N, K, int(bool(relu)), stream_ptr(a.device)) \
-            if rpb else \
-            _lib_().cgg_gemm_x3s_cfg(ctypes.c_void_p(a.data_ptr()), lda, dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-                                     ctypes.c_void_p(res.data_ptr()) if res is not None else None,
-                                     res.stride(0) if res is not None else 0,
-                                     0 if res is None else _x3s_fmt(res_split), int(res_mod), ctypes.c_void_p(y.data_ptr()),
-                                     y.stride(0), _x3s_fmt(out_split), M, N, K, int(bool(relu)), int(cfg), stream_ptr(a.device))
-    check(rc, 'cgg_gemm_x3s')
+        pa = dev_ptr(a, 'a', torch.float32, dense=False)
+        # the operands after a and its image geometry are those of both entry points
+        rest = (dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res, 'res', torch.float32, dense=False),
+                res.stride(0) if res is not None else 0, 0 if res is None else _x3s_fmt(res_split), int(res_mod),
+                dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), _x3s_fmt(out_split), M, N, K, int(bool(relu)))
+        if rpb:
+            _call('cgg_gemm_x3s_batched', pa, lda, rpb, bstride, *rest, stream_ptr(a.device))
+        else:
+            _call('cgg_gemm_x3s_cfg', pa, lda, *rest, int(cfg), stream_ptr(a.device))
     return y
 
 
@@ -2052,10 +1929,9 @@ def conv_x3s_nhwc(x, packed, N, kernel, stride=1, pad=0, bias=None, res=None, re
     with _timed('gemm_x3', flops=2.0 * B * OH * OW * N * C * KH * KW,
                 bytes=4.0 * (B * H * W * C + B * OH * OW * N * (2 if res is not None else 1) + N * C * KH * KW),
                 shape=(B * OH * OW, N, C * KH * KW)):
-        rc = _lib_().cgg_conv_x3s_nhwc_cfg(dev_ptr(x), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res),
-                                           0 if res is None else _x3s_fmt(res_split), dev_ptr(y), _x3s_fmt(out_split), B, H, W, C, N,
-                                           KH, KW, int(stride), int(pad), int(bool(relu)), int(cfg), stream_ptr(x.device))
-    check(rc, 'cgg_conv_x3s_nhwc')
+        _call('cgg_conv_x3s_nhwc_cfg', dev_ptr(x), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), dev_ptr(res),
+              0 if res is None else _x3s_fmt(res_split), dev_ptr(y), _x3s_fmt(out_split), B, H, W, C, N, KH, KW, int(stride), int(pad),
+              int(bool(relu)), int(cfg), stream_ptr(x.device))
     return y
 
 
@@ -2067,9 +1943,7 @@ def pack_linear_weight(weight):
         raise CggError(f'pack_linear_weight: unsupported shape {tuple(weight.shape)} (K % 16)')
     out = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
     w = weight.detach().float().contiguous()
-    rc = _lib_().cgg_linear_rows_pack(dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K,
-                                      stream_ptr(weight.device))
-    check(rc, 'cgg_linear_rows_pack')
+    _call('cgg_linear_rows_pack', dev_ptr(w, 'weight', torch.float32), dev_ptr(out), N, K, stream_ptr(weight.device))
     return out
 
 
@@ -2079,20 +1953,17 @@ def linear_rows_bf16(x, packed, N, bias=None, res=None, relu_cols=0, ln=None, po
     ln = (gamma, beta, eps) fuses a LayerNorm over the N <= 256 outputs; pos (rows, N) with want_pos returns
     (y, y + pos[row % rows]). `out` may be a 2-D view with its own row stride. ksplit > 1 returns the (ksplit, M, N)
     split-K partial planes (bias / res in plane 0) for `layernorm_chain` to add."""
-    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32 or not x.is_cuda:
-        raise CggError('linear_rows_bf16: x must be a 2-D float32 ROCm tensor with a contiguous last dim')
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+        raise CggError('linear_rows_bf16: x must be a 2-D float32 tensor with a contiguous last dim')
     M, K = x.shape
-    fn, _ = _x3_fn('linear_rows', packed)
+    symbol = _x3_fn('linear_rows', packed)
     if ksplit > 1:
         if out is not None or want_pos or ln is not None or relu_cols:
             raise CggError('linear_rows_bf16: split-K returns (ksplit, M, N) partial planes; no out / ln / pos / relu')
         y = torch.empty((int(ksplit), M, N), dtype=torch.float32, device=x.device)
-        rc = fn(
-            ctypes.c_void_p(x.data_ptr()), x.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-            ctypes.c_void_p(res.data_ptr()) if res is not None else None, res.stride(0) if res is not None else 0,
-            dev_ptr(y), N, None, None, 0.0, None, 0, None, 0, M, N, K, 0, int(ksplit), None, 0, 0, None, 0, 0,
-            stream_ptr(x.device))
-        check(rc, 'cgg_linear_rows_bf16(split-K)')
+        _call(symbol, dev_ptr(x, 'x', torch.float32, dense=False), x.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
+              dev_ptr(res, 'res', torch.float32, dense=False), res.stride(0) if res is not None else 0, dev_ptr(y), N, None, None, 0.0,
+              None, 0, None, 0, M, N, K, 0, int(ksplit), None, 0, 0, None, 0, 0, stream_ptr(x.device))
         return y
     y = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=x.device)
     if y.dim() != 2 or y.stride(1) != 1 or y.shape != (M, N) or y.dtype != torch.float32:
@@ -2101,14 +1972,12 @@ def linear_rows_bf16(x, packed, N, bias=None, res=None, relu_cols=0, ln=None, po
         raise CggError('linear_rows_bf16: bad `res` view')
     yp = torch.empty((M, N), dtype=torch.float32, device=x.device) if want_pos else None
     g, b, eps = ln if ln is not None else (None, None, 0.0)
-    rc = fn(
-        ctypes.c_void_p(x.data_ptr()), x.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
-        ctypes.c_void_p(res.data_ptr()) if res is not None else None, res.stride(0) if res is not None else 0,
-        ctypes.c_void_p(y.data_ptr()), y.stride(0), dev_ptr(g, 'gamma', torch.float32),
-        dev_ptr(b, 'beta', torch.float32), float(eps), dev_ptr(pos, 'pos', torch.float32) if want_pos else None,
-        pos.shape[0] if want_pos else 0, dev_ptr(yp), N if want_pos else 0, M, N, K, int(relu_cols), int(ksplit),
-        None, 0, 0, None, 0, 0, stream_ptr(x.device))
-    check(rc, 'cgg_linear_rows_bf16')
+    _call(symbol, dev_ptr(x, 'x', torch.float32, dense=False), x.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32),
+          dev_ptr(res, 'res', torch.float32, dense=False), res.stride(0) if res is not None else 0,
+          dev_ptr(y, 'out', torch.float32, dense=False), y.stride(0), dev_ptr(g, 'gamma', torch.float32),
+          dev_ptr(b, 'beta', torch.float32), float(eps), dev_ptr(pos, 'pos', torch.float32) if want_pos else None,
+          pos.shape[0] if want_pos else 0, dev_ptr(yp), N if want_pos else 0, M, N, K, int(relu_cols), int(ksplit), None, 0, 0, None, 0,
+          0, stream_ptr(x.device))
     return (y, yp) if want_pos else y
 
 
@@ -2117,17 +1986,15 @@ def linear_rows_bf16_qkv(xqk, xv, packed, bias, E):
     q, k from xqk (= query + query_pos), v from xv (= query); all (M, E) f32 rows -> (q (M, E), kv (M, 2E))."""
     M, K = xqk.shape
     for t in (xqk, xv):
-        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float32 or not t.is_cuda or t.shape != (M, K):
-            raise CggError('linear_rows_bf16_qkv: inputs must be matching 2-D float32 ROCm tensors')
+        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float32 or t.shape != (M, K):
+            raise CggError('linear_rows_bf16_qkv: inputs must be matching 2-D float32 tensors')
     if E % 256:
         raise CggError('linear_rows_bf16_qkv: E must be a multiple of 256')
     q = torch.empty((M, E), dtype=torch.float32, device=xqk.device)
     kv = torch.empty((M, 2 * E), dtype=torch.float32, device=xqk.device)
-    rc = _x3_fn('linear_rows', packed)[0](
-        ctypes.c_void_p(xqk.data_ptr()), xqk.stride(0), dev_ptr(packed), dev_ptr(bias, 'bias', torch.float32), None, 0,
-        dev_ptr(q), E, None, None, 0.0, None, 0, None, 0, M, 3 * E, K, 0, 1,
-        ctypes.c_void_p(xv.data_ptr()), xv.stride(0), 2 * E, dev_ptr(kv), 2 * E, E, stream_ptr(xqk.device))
-    check(rc, 'cgg_linear_rows_bf16(qkv)')
+    _call(_x3_fn('linear_rows', packed), dev_ptr(xqk, 'xqk', torch.float32, dense=False), xqk.stride(0), dev_ptr(packed),
+          dev_ptr(bias, 'bias', torch.float32), None, 0, dev_ptr(q), E, None, None, 0.0, None, 0, None, 0, M, 3 * E, K, 0, 1,
+          dev_ptr(xv, 'xv', torch.float32, dense=False), xv.stride(0), 2 * E, dev_ptr(kv), 2 * E, E, stream_ptr(xqk.device))
     return q, kv
 
 
@@ -2147,13 +2014,10 @@ def layernorm_chain(a, norm_a, pos=None, norm_b=None):
     yp = torch.empty_like(y) if pos is not None else None
     z = torch.empty_like(y) if norm_b is not None else None
     gb, bb, eb = norm_b if norm_b is not None else (None, None, 0.0)
-    rc = _lib_().cgg_layernorm_chain(
-        ctypes.c_void_p(a.data_ptr()), a.stride(0), dev_ptr(norm_a[0], 'gamma', torch.float32),
-        dev_ptr(norm_a[1], 'beta', torch.float32), float(norm_a[2]), dev_ptr(pos, 'pos', torch.float32),
-        pos.shape[0] if pos is not None else 0, dev_ptr(gb, 'gamma_b', torch.float32),
-        dev_ptr(bb, 'beta_b', torch.float32), float(eb), dev_ptr(y), dev_ptr(yp), dev_ptr(z), M, N, int(nsum),
-        int(plane), stream_ptr(a.device))
-    check(rc, 'cgg_layernorm_chain')
+    _call('cgg_layernorm_chain', dev_ptr(a, 'a', torch.float32, dense=False), a.stride(0), dev_ptr(norm_a[0], 'gamma', torch.float32),
+          dev_ptr(norm_a[1], 'beta', torch.float32), float(norm_a[2]), dev_ptr(pos, 'pos', torch.float32),
+          pos.shape[0] if pos is not None else 0, dev_ptr(gb, 'gamma_b', torch.float32), dev_ptr(bb, 'beta_b', torch.float32),
+          float(eb), dev_ptr(y), dev_ptr(yp), dev_ptr(z), M, N, int(nsum), int(plane), stream_ptr(a.device))
     return y, yp, z
 
 
@@ -2172,13 +2036,11 @@ def decoder_mid(core, wo, bo, res, norm, pos=None, qkv=None):
         wqkv, bqkv = qkv
         q = torch.empty((M, C), dtype=torch.float32, device=dev)
         kv = torch.empty((M, 2 * C), dtype=torch.float32, device=dev)
-    rc = _x3_fn('decoder_mid', wo, wqkv)[0](
-        ctypes.c_void_p(core.data_ptr()), core.stride(0), dev_ptr(wo), dev_ptr(bo, 'bo', torch.float32),
-        ctypes.c_void_p(res.data_ptr()), res.stride(0), dev_ptr(norm[0], 'gamma', torch.float32),
-        dev_ptr(norm[1], 'beta', torch.float32), float(norm[2]), dev_ptr(pos, 'pos', torch.float32),
-        pos.shape[0] if pos is not None else 0, dev_ptr(wqkv), dev_ptr(bqkv, 'bqkv', torch.float32), dev_ptr(x1),
-        dev_ptr(q), dev_ptr(kv), M, C, stream_ptr(dev))
-    check(rc, 'cgg_decoder_mid_bf16')
+    _call(_x3_fn('decoder_mid', wo, wqkv), dev_ptr(core, 'core', torch.float32, dense=False), core.stride(0), dev_ptr(wo),
+          dev_ptr(bo, 'bo', torch.float32), dev_ptr(res, 'res', torch.float32, dense=False), res.stride(0),
+          dev_ptr(norm[0], 'gamma', torch.float32), dev_ptr(norm[1], 'beta', torch.float32), float(norm[2]),
+          dev_ptr(pos, 'pos', torch.float32), pos.shape[0] if pos is not None else 0, dev_ptr(wqkv),
+          dev_ptr(bqkv, 'bqkv', torch.float32), dev_ptr(x1), dev_ptr(q), dev_ptr(kv), M, C, stream_ptr(dev))
     return x1, q, kv
 
 
@@ -2189,10 +2051,9 @@ def decoder_ffn(x, w1, b1, w2, b2, F):
     if x.stride(1) != 1 or x.dtype != torch.float32 or F % 256:
         raise CggError('decoder_ffn: x must be (M, C) float32 rows and F a multiple of 256')
     planes = torch.empty((F // 256, M, C), dtype=torch.float32, device=x.device)
-    rc = _x3_fn('decoder_ffn', w1, w2)[0](ctypes.c_void_p(x.data_ptr()), x.stride(0), dev_ptr(w1),
-                                      dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2), dev_ptr(b2, 'b2', torch.float32),
-                                      dev_ptr(planes), M, C, int(F), stream_ptr(x.device))
-    check(rc, 'cgg_decoder_ffn_bf16')
+    _call(_x3_fn('decoder_ffn', w1, w2), dev_ptr(x, 'x', torch.float32, dense=False), x.stride(0), dev_ptr(w1),
+          dev_ptr(b1, 'b1', torch.float32), dev_ptr(w2), dev_ptr(b2, 'b2', torch.float32), dev_ptr(planes), M, C, int(F),
+          stream_ptr(x.device))
     return planes
 
 
@@ -2203,10 +2064,9 @@ def self_attn_rows_bf16(q, kv, B, num_heads, scale=None):
     if q.stride(1) != 1 or kv.stride(1) != 1 or kv.shape != (M, 2 * E) or q.dtype != torch.float32 or kv.dtype != torch.float32:
         raise CggError('self_attn_rows_bf16: q (M, E) / kv (M, 2E) float32 rows expected')
     out = torch.empty((M, E), dtype=torch.float32, device=q.device)
-    rc = _lib_().cgg_self_attn_rows_bf16(ctypes.c_void_p(q.data_ptr()), q.stride(0), ctypes.c_void_p(kv.data_ptr()),
-                                         kv.stride(0), dev_ptr(out), B, M // B, num_heads, D,
-                                         float(scale if scale is not None else D ** -0.5), stream_ptr(q.device))
-    check(rc, 'cgg_self_attn_rows_bf16')
+    _call('cgg_self_attn_rows_bf16', dev_ptr(q, 'q', torch.float32, dense=False), q.stride(0),
+          dev_ptr(kv, 'kv', torch.float32, dense=False), kv.stride(0), dev_ptr(out), B, M // B, num_heads, D,
+          float(scale if scale is not None else D ** -0.5), stream_ptr(q.device))
     return out
 
 
@@ -2223,14 +2083,12 @@ def decoder_tail(planes, norm_a, pos, norm_b, mlp, qproj=None, want_pos=False):
     me = torch.empty_like(y)
     qn = torch.empty_like(y) if qproj is not None else None
     wq, bq = qproj if qproj is not None else (None, None)
-    rc = _x3_fn('decoder_tail', mlp[0], mlp[2], mlp[4], wq)[0](
-        dev_ptr(planes), nsum, M * C, C, dev_ptr(norm_a[0], 'gamma_a', torch.float32),
-        dev_ptr(norm_a[1], 'beta_a', torch.float32), float(norm_a[2]), dev_ptr(pos, 'pos', torch.float32), pos.shape[0],
-        dev_ptr(norm_b[0], 'gamma_b', torch.float32), dev_ptr(norm_b[1], 'beta_b', torch.float32), float(norm_b[2]),
-        dev_ptr(mlp[0]), dev_ptr(mlp[1], 'b1', torch.float32), dev_ptr(mlp[2]), dev_ptr(mlp[3], 'b2', torch.float32),
-        dev_ptr(mlp[4]), dev_ptr(mlp[5], 'b3', torch.float32), dev_ptr(wq), dev_ptr(bq, 'bq', torch.float32),
-        dev_ptr(y), dev_ptr(yp), dev_ptr(me), dev_ptr(qn), M, C, stream_ptr(dev))
-    check(rc, 'cgg_decoder_tail_bf16')
+    _call(_x3_fn('decoder_tail', mlp[0], mlp[2], mlp[4], wq), dev_ptr(planes), nsum, M * C, C,
+          dev_ptr(norm_a[0], 'gamma_a', torch.float32), dev_ptr(norm_a[1], 'beta_a', torch.float32), float(norm_a[2]),
+          dev_ptr(pos, 'pos', torch.float32), pos.shape[0], dev_ptr(norm_b[0], 'gamma_b', torch.float32),
+          dev_ptr(norm_b[1], 'beta_b', torch.float32), float(norm_b[2]), dev_ptr(mlp[0]), dev_ptr(mlp[1], 'b1', torch.float32),
+          dev_ptr(mlp[2]), dev_ptr(mlp[3], 'b2', torch.float32), dev_ptr(mlp[4]), dev_ptr(mlp[5], 'b3', torch.float32), dev_ptr(wq),
+          dev_ptr(bq, 'bq', torch.float32), dev_ptr(y), dev_ptr(yp), dev_ptr(me), dev_ptr(qn), M, C, stream_ptr(dev))
     return y, yp, me, qn
 
 
@@ -2255,19 +2113,12 @@ def masked_xattn_bf16(q, k, vt, bits, num_heads, scale=None, fix_full_rows=False
     ldk, vtb = k.stride(1), vt.stride(0)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
-    lib = _lib_()
-    nbytes = lib.cgg_masked_xattn_workspace_bytes(B, Q, H, D, S)
-    key = (q.device.index, stream_ptr(q.device).value)
-    ws = _WS_CACHE.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=q.device)
-        _WS_CACHE[key] = ws
+    pq = dev_ptr(q, 'q', torch.float32)       # refuses CPU tensors before any torch.cuda call
+    ws = _xattn_ws(_lib_().cgg_masked_xattn_workspace_bytes, q, B, Q, H, D, S)
     out = torch.empty((B, Q, E), dtype=torch.float32, device=q.device)
-    rc = lib.cgg_masked_xattn_forward_bf16(dev_ptr(q, 'q', torch.float32), ctypes.c_void_p(k.data_ptr()),
-                                           ctypes.c_void_p(vt.data_ptr()), dev_ptr(bits, 'bits', torch.int32),
-                                           dev_ptr(out), dev_ptr(ws), B, Q, H, D, S, float(scale), int(ldk), int(vtb),
-                                           int(bool(fix_full_rows)), stream_ptr(q.device))
-    check(rc, 'cgg_masked_xattn_forward_bf16')
+    _call('cgg_masked_xattn_forward_bf16', pq, dev_ptr(k, 'k', torch.bfloat16, dense=False),
+          dev_ptr(vt, 'vt', torch.bfloat16, dense=False), dev_ptr(bits, 'bits', torch.int32), dev_ptr(out), dev_ptr(ws), B, Q, H, D, S,
+          float(scale), int(ldk), int(vtb), int(bool(fix_full_rows)), stream_ptr(q.device))
     return out
 
 
@@ -2293,11 +2144,9 @@ def instance_masks_multi(logits, index_lists, up_size, crop_size, out_size):
     off = torch.zeros((Q + 1,), dtype=torch.int32, device=dev)
     off[1:] = torch.cumsum(counts, 0)
     ws = torch.empty((Q, 8), dtype=torch.int32, device=dev)
-    rc = _lib_().cgg_instance_masks_multi(dev_ptr(logits, 'logits', torch.float32), dev_ptr(off), dev_ptr(order),
-                                          dev_ptr(masks), dev_ptr(score), dev_ptr(bbox), dev_ptr(ws), Q, H, W,
-                                          int(up_size[0]), int(up_size[1]), int(crop_size[0]), int(crop_size[1]), oh,
-                                          ow, stream_ptr(dev))
-    check(rc, 'cgg_instance_masks_multi')
+    _call('cgg_instance_masks_multi', dev_ptr(logits, 'logits', torch.float32), dev_ptr(off), dev_ptr(order), dev_ptr(masks),
+          dev_ptr(score), dev_ptr(bbox), dev_ptr(ws), Q, H, W, int(up_size[0]), int(up_size[1]), int(crop_size[0]), int(crop_size[1]),
+          oh, ow, stream_ptr(dev))
     out, o = [], 0
     for n in sizes:
         out.append(masks[o:o + n].view(torch.bool))
@@ -2315,9 +2164,8 @@ def class_topk(dots, B, col0, ncols, k):
     labels = torch.empty((B, T, k), dtype=torch.int64, device=dev)
     qidx = torch.empty((B, T, k), dtype=torch.int64, device=dev)
     scores = torch.empty((B, T, k), dtype=torch.float32, device=dev)
-    rc = _lib_().cgg_class_topk(dev_ptr(dots, 'dots', torch.float32), ld, B, Q, T, _int_array(col0), _int_array(ncols),
-                                int(k), dev_ptr(labels), dev_ptr(scores), dev_ptr(qidx), stream_ptr(dev))
-    check(rc, 'cgg_class_topk')
+    _call('cgg_class_topk', dev_ptr(dots, 'dots', torch.float32), ld, B, Q, T, _int_array(col0), _int_array(ncols), int(k),
+          dev_ptr(labels), dev_ptr(scores), dev_ptr(qidx), stream_ptr(dev))
     return labels, scores, qidx
 
 
@@ -2338,11 +2186,9 @@ def instance_masks_picks(logits, qidx, cls_scores, up_size, crop_size, out_size,
     masks = torch.empty((n, oh, ow // 8 if bitpack else ow), dtype=torch.uint8, device=dev)
     bboxes = torch.empty((n, 5), dtype=torch.float32, device=dev)
     ws = torch.empty((int(_lib_().cgg_instance_masks_picks_workspace_bytes(Q, n)) + 3) // 4, dtype=torch.int32, device=dev)
-    rc = _lib_().cgg_instance_masks_picks(dev_ptr(logits, 'logits', torch.float32), dev_ptr(qidx, 'qidx', torch.int64),
-                                          dev_ptr(cls_scores, 'cls_scores', torch.float32), n, dev_ptr(masks),
-                                          dev_ptr(bboxes), dev_ptr(ws), Q, H, W, int(up_size[0]), int(up_size[1]),
-                                          int(crop_size[0]), int(crop_size[1]), oh, ow, int(bool(bitpack)), stream_ptr(dev))
-    check(rc, 'cgg_instance_masks_picks')
+    _call('cgg_instance_masks_picks', dev_ptr(logits, 'logits', torch.float32), dev_ptr(qidx, 'qidx', torch.int64),
+          dev_ptr(cls_scores, 'cls_scores', torch.float32), n, dev_ptr(masks), dev_ptr(bboxes), dev_ptr(ws), Q, H, W, int(up_size[0]),
+          int(up_size[1]), int(crop_size[0]), int(crop_size[1]), oh, ow, int(bool(bitpack)), stream_ptr(dev))
     return (masks if bitpack else masks.view(torch.bool)), bboxes
 
 
@@ -2359,9 +2205,8 @@ def bias_relu_maxpool_nhwc(x, bias):
     B, H, W, C = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
-    rc = _lib_().cgg_bias_relu_maxpool_nhwc(dev_ptr(x, 'x', torch.bfloat16), dev_ptr(bias, 'bias', torch.bfloat16),
-                                            dev_ptr(y), B, H, W, C, stream_ptr(x.device))
-    check(rc, 'cgg_bias_relu_maxpool_nhwc')
+    _call('cgg_bias_relu_maxpool_nhwc', dev_ptr(x, 'x', torch.bfloat16), dev_ptr(bias, 'bias', torch.bfloat16), dev_ptr(y), B, H, W, C,
+          stream_ptr(x.device))
     return y
 
 
@@ -2375,8 +2220,8 @@ def _blaslt_init():
         import os
         cand = os.path.join(os.path.dirname(torch.__file__), 'lib', 'libhipblaslt.so')
         path = cand if os.path.exists(cand) else 'libhipblaslt.so'
-        check(_lib_().cgg_blaslt_init(path.encode()), 'cgg_blaslt_init')
-        check(_lib_().cgg_blaslt_set_tuning(int(os.environ.get('CGG_GEMM_TUNE', '16'))), 'cgg_blaslt_set_tuning')
+        _call('cgg_blaslt_init', path.encode())
+        _call('cgg_blaslt_set_tuning', int(os.environ.get('CGG_GEMM_TUNE', '16')))
         _BLASLT_READY = True
 
 
@@ -2396,10 +2241,8 @@ def gemm_bias_res_act_bf16(x, w, bias, res=None, relu=True):
         if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous()):
             raise CggError('gemm_bias_res_act_bf16: %s must be a contiguous bfloat16 tensor' % n)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    rc = _lib_().cgg_gemm_bias_res_act_bf16(dev_ptr(x, 'x', torch.bfloat16), dev_ptr(w, 'w', torch.bfloat16),
-                                            dev_ptr(bias), dev_ptr(res), dev_ptr(y), M, N, K,
-                                            int(bool(relu)), stream_ptr(x.device))
-    check(rc, 'cgg_gemm_bias_res_act_bf16')
+    _call('cgg_gemm_bias_res_act_bf16', dev_ptr(x, 'x', torch.bfloat16), dev_ptr(w, 'w', torch.bfloat16), dev_ptr(bias), dev_ptr(res),
+          dev_ptr(y), M, N, K, int(bool(relu)), stream_ptr(x.device))
     return y
 
 
@@ -2411,8 +2254,7 @@ def im2col3x3_nhwc(x, stride=1):
         raise CggError('im2col3x3_nhwc: x must be a contiguous (B, H, W, C) bfloat16 tensor')
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((B * Ho * Wo, 9 * C), dtype=torch.bfloat16, device=x.device)
-    check(_lib_().cgg_im2col3x3_nhwc(dev_ptr(x), dev_ptr(y), B, H, W, C, int(stride), stream_ptr(x.device)),
-          'cgg_im2col3x3_nhwc')
+    _call('cgg_im2col3x3_nhwc', dev_ptr(x), dev_ptr(y), B, H, W, C, int(stride), stream_ptr(x.device))
     return y, Ho, Wo
 
 
@@ -2436,8 +2278,7 @@ def stem_conv7x7(img, packed):
         raise CggError('stem_conv7x7: img must be a contiguous (B, 3, H, W) float32 tensor')
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((B, Ho, Wo, 64), dtype=torch.bfloat16, device=img.device)
-    check(_lib_().cgg_stem_conv7x7_nchw(dev_ptr(img), dev_ptr(packed), dev_ptr(y), B, H, W, stream_ptr(img.device)),
-          'cgg_stem_conv7x7_nchw')
+    _call('cgg_stem_conv7x7_nchw', dev_ptr(img), dev_ptr(packed), dev_ptr(y), B, H, W, stream_ptr(img.device))
     return y
 
 
@@ -2468,8 +2309,8 @@ def stem_conv7x7_x3(img, packed, wscale):
         raise CggError('stem_conv7x7_x3: img must be a contiguous (B, 3, H, W) float32 tensor')
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((B, Ho, Wo, 64), dtype=torch.float32, device=img.device)
-    check(_lib_().cgg_stem_conv7x7_x3_nchw(dev_ptr(img), dev_ptr(packed), dev_ptr(wscale, 'wscale', torch.float32), dev_ptr(y), B, H, W,
-                                           stream_ptr(img.device)), 'cgg_stem_conv7x7_x3_nchw')
+    _call('cgg_stem_conv7x7_x3_nchw', dev_ptr(img), dev_ptr(packed), dev_ptr(wscale, 'wscale', torch.float32), dev_ptr(y), B, H, W,
+          stream_ptr(img.device))
     return y
 
 
@@ -2479,9 +2320,8 @@ def bias_relu_maxpool_nhwc_f32(x, bias, x3a=False):
     B, H, W, C = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
-    fn = _lib_().cgg_bias_relu_maxpool_nhwc_f32_x3a if x3a else _lib_().cgg_bias_relu_maxpool_nhwc_f32
-    rc = fn(dev_ptr(x, 'x', torch.float32), dev_ptr(bias, 'bias', torch.float32), dev_ptr(y), B, H, W, C, stream_ptr(x.device))
-    check(rc, 'cgg_bias_relu_maxpool_nhwc_f32')
+    _call('cgg_bias_relu_maxpool_nhwc_f32_x3a' if x3a else 'cgg_bias_relu_maxpool_nhwc_f32', dev_ptr(x, 'x', torch.float32),
+          dev_ptr(bias, 'bias', torch.float32), dev_ptr(y), B, H, W, C, stream_ptr(x.device))
     return y
 
 
@@ -2498,10 +2338,8 @@ def linear_sum_assignment_batch(costs):
     total = sum(sizes)
     rows = torch.empty((max(total, 1),), dtype=torch.int64)
     cols = torch.empty((max(total, 1),), dtype=torch.int64)
-    rc = _lib_().cgg_linear_sum_assignment_f32(ctypes.c_void_p(flat.data_ptr()) if flat.numel() else None, len(costs),
-                                               _int_array(nr), _int_array(nc), ctypes.c_void_p(rows.data_ptr()),
-                                               ctypes.c_void_p(cols.data_ptr()))
-    check(rc, 'cgg_linear_sum_assignment_f32')
+    _call('cgg_linear_sum_assignment_f32', host_ptr(flat, 'costs', torch.float32) if flat.numel() else None, len(costs), _int_array(nr),
+          _int_array(nc), host_ptr(rows, 'rows', torch.int64), host_ptr(cols, 'cols', torch.int64))
     out, o = [], 0
     for n in sizes:
         out.append((rows[o:o + n], cols[o:o + n]))
@@ -2540,13 +2378,11 @@ def lsap_device_launch(cost_flat, desc, lds_bytes, q_out, g_out, status, gt_labe
         raise CggError('lsap_device_launch: the epilogue needs gt_labels, labels and weights together')
     if labels is not None and labels.numel() != weights.numel():
         raise CggError('lsap_device_launch: labels and weights must have one size')
-    rc = _lib_().cgg_lsap_device_f32(
-        dev_ptr(cost_flat, 'cost_flat', torch.float32), cost_flat.numel(), dev_ptr(desc, 'desc', torch.int64), P, int(lds_bytes),
-        dev_ptr(q_out, 'q_out', torch.int64), dev_ptr(g_out, 'g_out', torch.int64), q_out.numel(),
-        dev_ptr(gt_labels, 'gt_labels', torch.int64), 0 if gt_labels is None else gt_labels.numel(),
-        dev_ptr(labels, 'labels', torch.int64), dev_ptr(weights, 'weights', torch.float32), 0 if labels is None else labels.numel(),
-        dev_ptr(status, 'status', torch.int32), stream_ptr(cost_flat.device))
-    check(rc, 'cgg_lsap_device_f32')
+    _call('cgg_lsap_device_f32', dev_ptr(cost_flat, 'cost_flat', torch.float32), cost_flat.numel(), dev_ptr(desc, 'desc', torch.int64),
+          P, int(lds_bytes), dev_ptr(q_out, 'q_out', torch.int64), dev_ptr(g_out, 'g_out', torch.int64), q_out.numel(),
+          dev_ptr(gt_labels, 'gt_labels', torch.int64), 0 if gt_labels is None else gt_labels.numel(),
+          dev_ptr(labels, 'labels', torch.int64), dev_ptr(weights, 'weights', torch.float32), 0 if labels is None else labels.numel(),
+          dev_ptr(status, 'status', torch.int32), stream_ptr(cost_flat.device))
 
 
 def linear_sum_assignment_device(cost_flat, nr, nc):
@@ -2596,9 +2432,8 @@ def point_sample_planes(planes, index, points):
     out = torch.empty((rows, P), dtype=torch.float32, device=planes.device)
     if rows == 0:
         return out
-    check(_lib_().cgg_point_sample_planes(dev_ptr(planes, 'planes', torch.float32), dev_ptr(index, 'index', torch.int32),
-                                          dev_ptr(points.contiguous(), 'points', torch.float32), dev_ptr(out), N, H, W, rows, P,
-                                          stream_ptr(planes.device)), 'cgg_point_sample_planes')
+    _call('cgg_point_sample_planes', dev_ptr(planes, 'planes', torch.float32), dev_ptr(index, 'index', torch.int32),
+          dev_ptr(points.contiguous(), 'points', torch.float32), dev_ptr(out), N, H, W, rows, P, stream_ptr(planes.device))
     return out
 
 
@@ -2623,17 +2458,13 @@ class _PointSampleRowsFn(torch.autograd.Function):
         if rows and rows <= 65535 and W <= 16384:
             # every row has its own plane: band-stationary LDS accumulation, planes written once (no zero-fill, no global atomics)
             gp = torch.empty((rows, H, W), dtype=torch.float32, device=gout.device)
-            check(_lib_().cgg_point_sample_planes_backward_rows(dev_ptr(gout.contiguous().float(), 'grad', torch.float32),
-                                                                dev_ptr(points, 'points', torch.float32), dev_ptr(gp), H, W, rows,
-                                                                points.shape[1], stream_ptr(gout.device)),
-                  'cgg_point_sample_planes_backward_rows')
+            _call('cgg_point_sample_planes_backward_rows', dev_ptr(gout.contiguous().float(), 'grad', torch.float32),
+                  dev_ptr(points, 'points', torch.float32), dev_ptr(gp), H, W, rows, points.shape[1], stream_ptr(gout.device))
             return gp, None
         gp = torch.zeros((rows, H, W), dtype=torch.float32, device=gout.device)
         if rows:
-            check(_lib_().cgg_point_sample_planes_backward(dev_ptr(gout.contiguous().float(), 'grad', torch.float32), None,
-                                                           dev_ptr(points, 'points', torch.float32), dev_ptr(gp), rows, H, W, rows,
-                                                           points.shape[1], stream_ptr(gout.device)),
-                  'cgg_point_sample_planes_backward')
+            _call('cgg_point_sample_planes_backward', dev_ptr(gout.contiguous().float(), 'grad', torch.float32), None,
+                  dev_ptr(points, 'points', torch.float32), dev_ptr(gp), rows, H, W, rows, points.shape[1], stream_ptr(gout.device))
         return gp, None
 
 
@@ -2657,8 +2488,7 @@ def point_sample_nhwc(feat, points):
         raise CggError('point_sample_nhwc: feat (B, H, W, C) contiguous float32, points (B, P, 2) float32 expected')
     pts = points.contiguous()
     out = torch.empty((B, P, C), dtype=torch.float32, device=feat.device)
-    check(_lib_().cgg_point_sample_nhwc(dev_ptr(feat), dev_ptr(pts), dev_ptr(out), B, H, W, C, P, stream_ptr(feat.device)),
-          'cgg_point_sample_nhwc')
+    _call('cgg_point_sample_nhwc', dev_ptr(feat), dev_ptr(pts), dev_ptr(out), B, H, W, C, P, stream_ptr(feat.device))
     return out
 
 
@@ -2684,8 +2514,7 @@ def point_sample_nhwc_x3(feat, points, groups):
     pts = points.contiguous()
     hi = torch.empty((groups * B, P // 32, C // 8, 32, 8), dtype=torch.bfloat16, device=feat.device)     # (16-bit pieces: f16 bits)
     lo = torch.empty_like(hi)
-    check(_lib_().cgg_point_sample_nhwc_x3(dev_ptr(feat), dev_ptr(pts), dev_ptr(hi), dev_ptr(lo), B, H, W, C, Pt, P,
-                                           stream_ptr(feat.device)), 'cgg_point_sample_nhwc_x3')
+    _call('cgg_point_sample_nhwc_x3', dev_ptr(feat), dev_ptr(pts), dev_ptr(hi), dev_ptr(lo), B, H, W, C, Pt, P, stream_ptr(feat.device))
     return [PackedFeature(hi[g * B:(g + 1) * B], lo[g * B:(g + 1) * B], B, C, 1, P) for g in range(groups)]
 
 
@@ -2696,7 +2525,7 @@ def subsample_nhwc(x, stride):
         return x[:, ::stride, ::stride, :].contiguous()
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
-    check(_lib_().cgg_subsample_nhwc(dev_ptr(x), dev_ptr(y), B, H, W, C, int(stride), stream_ptr(x.device)), 'cgg_subsample_nhwc')
+    _call('cgg_subsample_nhwc', dev_ptr(x), dev_ptr(y), B, H, W, C, int(stride), stream_ptr(x.device))
     return y
 
 
@@ -2743,9 +2572,8 @@ def image_prep_u8(staged, table, out, mean, std, pad_val=0.0, to_rgb=True, pad_b
     m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'image_prep_u8: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
     Hb, Wb = int(out.shape[2]), int(out.shape[3])
     with _timed('image_prep_u8', bytes=float(nbytes + out.numel() * 4), shape=(B, Hb, Wb)):
-        rc = _lib_().cgg_image_prep_u8(sp, nbytes, int(table_offset), ctypes.c_void_p(table.data_ptr()), B, m, s, p, int(bool(to_rgb)),
-                                       int(bool(pad_before_norm)), op, Hb, Wb, stream_ptr(out.device))
-    check(rc, 'cgg_image_prep_u8')
+        _call('cgg_image_prep_u8', sp, nbytes, int(table_offset), host_ptr(table, 'table', torch.int32), B, m, s, p, int(bool(to_rgb)),
+              int(bool(pad_before_norm)), op, Hb, Wb, stream_ptr(out.device))
     return out
 
 
@@ -2800,16 +2628,15 @@ def train_prep_u8(staged, img_table, inst_table, img, masks, seg, stats, mean, s
         inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
     with _timed('train_prep_u8', bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)),
                 shape=(B, N, H, W)):
-        rc = _lib_().cgg_train_prep_u8(sp, nbytes, int(img_table_offset), int(inst_table_offset), ctypes.c_void_p(img_table.data_ptr()),
-                                       ctypes.c_void_p(inst_table.data_ptr()) if N else None, B, N, m, s, p, int(bool(to_rgb)),
-                                       int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
-    check(rc, 'cgg_train_prep_u8')
+        _call('cgg_train_prep_u8', sp, nbytes, int(img_table_offset), int(inst_table_offset),
+              host_ptr(img_table, 'img_table', torch.int32), host_ptr(inst_table, 'inst_table', torch.int32) if N else None, B, N, m, s,
+              p, int(bool(to_rgb)), int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
     return img, masks, seg, stats
 
 
 TRAIN_PREP_PAN_COLS = 5       # byte offset of the id map, row pitch, format (0: int32 ids, 1: R, G, B bytes), first segment row, segment rows
 TRAIN_PREP_SEG_COLS = 2       # id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t
-TRAIN_PREP_MAX_SEGMENTS = 256  # CGG_TRAIN_PREP_MAX_SEGMENTS
+TRAIN_PREP_MAX_SEGMENTS = CONSTANTS['CGG_TRAIN_PREP_MAX_SEGMENTS']
 
 
 def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, seg, stats, mean, std, pad_val=0.0, to_rgb=True,
@@ -2870,19 +2697,18 @@ def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, 
     if seg_table_offset is None:
         seg_table_offset = int(pan_table_offset) + 4 * TRAIN_PREP_PAN_COLS * B
     with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)), shape=(B, N, H, W)):
-        rc = _lib_().cgg_train_prep_panoptic_u8(sp, nbytes, int(img_table_offset), int(pan_table_offset), int(seg_table_offset),
-                                                ctypes.c_void_p(img_table.data_ptr()), ctypes.c_void_p(pan_table.data_ptr()),
-                                                ctypes.c_void_p(seg_table.data_ptr()) if S else None, B, N, S, m, s, p,
-                                                int(bool(to_rgb)), int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
-    check(rc, 'cgg_train_prep_panoptic_u8')
+        _call('cgg_train_prep_panoptic_u8', sp, nbytes, int(img_table_offset), int(pan_table_offset), int(seg_table_offset),
+              host_ptr(img_table, 'img_table', torch.int32), host_ptr(pan_table, 'pan_table', torch.int32),
+              host_ptr(seg_table, 'seg_table', torch.int32) if S else None, B, N, S, m, s, p, int(bool(to_rgb)), int(seg_pad), ch, cw,
+              ip, mp, gp, tp, H, W, stream_ptr(img.device))
     return img, masks, seg, stats
 
 
 # ------------------------------------------------------------------------------------------------
 # caption search: one beam-search step for a whole batch, decided on the device (caption_search.py states the rule)
 # ------------------------------------------------------------------------------------------------
-BEAM_STEP_MAX_BEAM = 8        # CGG_BEAM_STEP_MAX_BEAM
-BEAM_STEP_MAX_LEN = 256       # CGG_BEAM_STEP_MAX_LEN
+BEAM_STEP_MAX_BEAM = CONSTANTS['CGG_BEAM_STEP_MAX_BEAM']
+BEAM_STEP_MAX_LEN = CONSTANTS['CGG_BEAM_STEP_MAX_LEN']
 
 
 class BeamState:
@@ -2959,9 +2785,8 @@ def beam_step(logits, state, length, alpha, max_len, first=False, passes=3):
     if state.ws is None or state.ws.numel() < need or state.ws.device != logits.device:
         state.ws = torch.empty(max(need, 4), dtype=torch.uint8, device=logits.device)
     with _timed('beam_step', bytes=float(logits.numel() * 4), shape=(L, B, beam, V)):
-        rc = _lib_().cgg_beam_step_passes(lp, L, B, beam, V, *ptrs, dev_ptr(state.ws), int(length), float(alpha), state.EOS,
-                                          int(max_len), state.max_len, int(bool(first)), int(passes), stream_ptr(logits.device))
-    check(rc, 'cgg_beam_step')
+        _call('cgg_beam_step_passes', lp, L, B, beam, V, *ptrs, dev_ptr(state.ws), int(length), float(alpha), state.EOS, int(max_len),
+              state.max_len, int(bool(first)), int(passes), stream_ptr(logits.device))
     return state
 
 
@@ -2979,21 +2804,9 @@ def rle_encode_bitmasks(bits, width, threads=8):
     W = int(width)
     if n == 0:
         return []
-    lib = _lib_()
-    offs = np.empty(n + 1, dtype=np.int64)
-    cap = max(1 << 16, n * 4096)          # ~2 KB per mask at 1024^2 with this benchmark's noisy masks: a too-small buffer encodes twice
-    while True:
-        out = np.empty(cap, dtype=np.uint8)
-        total = lib.cgg_rle_encode_bitmasks(ctypes.c_void_p(arr.ctypes.data), n, H, W, H * rb, rb, int(threads),
-                                            ctypes.c_void_p(out.ctypes.data), cap, ctypes.c_void_p(offs.ctypes.data))
-        if total < 0:
-            check(int(-total), 'cgg_rle_encode_bitmasks')
-        if total <= cap:
-            break
-        cap = int(total)
-    raw = out[:total].tobytes()
-    o = offs.tolist()
-    return [dict(size=[H, W], counts=raw[o[i]:o[i + 1]]) for i in range(n)]
+    # ~2 KB per mask at 1024^2 with this benchmark's noisy masks: a too-small buffer encodes twice
+    return _rle_strings('cgg_rle_encode_bitmasks', (ctypes.c_void_p(arr.ctypes.data), n, H, W, H * rb, rb, int(threads)),
+                        n, H, W, max(1 << 16, n * 4096))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3013,13 +2826,11 @@ def rle_transitions(bits, width, capacity=None, positions=None, offsets=None, ws
     positions / offsets / ws may be handed in (reused buffers); no host read, no allocation then."""
     if not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 3:
         raise CggError('rle_transitions: (n, H, row_bytes) uint8 device tensor expected')
-    if not bits.is_cuda:
-        raise CggError(f'rle_transitions: bits must live on a ROCm device (got {bits.device})')
+    pbits = dev_ptr(bits, 'rle_transitions: bits', torch.uint8, dense=False)
     n, H, rb = bits.shape
     W = int(width)
     if n > 0 and (bits.stride(2) != 1 or bits.stride(1) != rb or bits.stride(0) < H * rb):
         raise CggError(f'rle_transitions: rows must be contiguous and planes at least H * row_bytes apart (strides {bits.stride()})')
-    lib = _lib_()
     dev = bits.device
     if positions is None:
         if capacity is None:
@@ -3032,7 +2843,7 @@ def rle_transitions(bits, width, capacity=None, positions=None, offsets=None, ws
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
     if offsets.numel() < n + 1:
         raise CggError(f'rle_transitions: offsets has {offsets.numel()} elements, n + 1 = {n + 1} needed')
-    need = int(lib.cgg_rle_transitions_workspace_bytes(n, H, W))
+    need = int(_lib_().cgg_rle_transitions_workspace_bytes(n, H, W))
     if ws is None:
         ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
     if ws.numel() < need:
@@ -3042,21 +2853,19 @@ def rle_transitions(bits, width, capacity=None, positions=None, offsets=None, ws
             raise CggError(f'rle_transitions: {name} ({t.device}) and bits ({dev}) live on different devices')
     stride = bits.stride(0) if n > 0 else H * rb
     with _timed('rle_transitions', bytes=float(n * H * rb), shape=(n, H, W)):
-        rc = lib.cgg_rle_transitions(ctypes.c_void_p(bits.data_ptr()), n, H, W, int(stride), rb, dev_ptr(ws, 'ws', torch.uint8),
-                                     dev_ptr(positions, 'positions', torch.int32), cap,
-                                     dev_ptr(offsets, 'offsets', torch.int64), stream_ptr(dev))
-    check(rc, 'cgg_rle_transitions')
+        _call('cgg_rle_transitions', pbits, n, H, W, int(stride), rb, dev_ptr(ws, 'ws', torch.uint8),
+              dev_ptr(positions, 'positions', torch.int32), cap, dev_ptr(offsets, 'offsets', torch.int64), stream_ptr(dev))
     return positions, offsets, ws
 
 
-def _rle_strings(call, what, n, H, W, cap):
+def _rle_strings(symbol, head, n, H, W, cap):
+    """the n COCO RLE dicts of a host RLE entry point `symbol(*head, out, out_cap, out_offsets)`, called again with a buffer of the
+    size it asked for when the first was too small"""
     import numpy as np
     offs = np.empty(n + 1, dtype=np.int64)
     while True:
         out = np.empty(cap, dtype=np.uint8)
-        total = call(ctypes.c_void_p(out.ctypes.data), cap, ctypes.c_void_p(offs.ctypes.data))
-        if total < 0:
-            check(int(total), what)
+        total = _call(symbol, *head, ctypes.c_void_p(out.ctypes.data), cap, ctypes.c_void_p(offs.ctypes.data), total=True)
         if total <= cap:
             break
         cap = int(total)
@@ -3080,11 +2889,9 @@ def rle_strings_from_transitions(positions, offsets, H, width):
         return []
     if int(off.max()) > pos.size:
         raise CggError(f'rle_strings_from_transitions: offsets reach {int(off.max())}, {pos.size} positions given')
-    lib = _lib_()
     H, W = int(H), int(width)
-    return _rle_strings(lambda out, cap, oo: lib.cgg_rle_strings_from_transitions(
-        ctypes.c_void_p(pos.ctypes.data), ctypes.c_void_p(off.ctypes.data), n, H, W, out, cap, oo),
-        'cgg_rle_strings_from_transitions', n, H, W, max(1 << 12, 2 * int(off[-1] - off[0]) + 8 * n))
+    return _rle_strings('cgg_rle_strings_from_transitions', (ctypes.c_void_p(pos.ctypes.data), ctypes.c_void_p(off.ctypes.data), n, H, W),
+                        n, H, W, max(1 << 12, 2 * int(off[-1] - off[0]) + 8 * n))
 
 
 def rle_encode_colmajor(cols, H, width, threads=8):
@@ -3101,10 +2908,8 @@ def rle_encode_colmajor(cols, H, width, threads=8):
     n = arr.shape[0]
     if n == 0:
         return []
-    lib = _lib_()
-    return _rle_strings(lambda out, cap, oo: lib.cgg_rle_encode_colmajor(
-        ctypes.c_void_p(arr.ctypes.data), n, H, W, int(threads), out, cap, oo),
-        'cgg_rle_encode_colmajor', n, H, W, max(1 << 16, n * 4096))
+    return _rle_strings('cgg_rle_encode_colmajor', (ctypes.c_void_p(arr.ctypes.data), n, H, W, int(threads)),
+                        n, H, W, max(1 << 16, n * 4096))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3129,9 +2934,8 @@ def pack_bool_masks(masks):
     rb = (W + 7) // 8
     bits = torch.empty((n, H, rb), dtype=torch.uint8, device=masks.device)
     if n * H > 0:
-        rc = _lib_().cgg_pack_bool_rows_u8(dev_ptr(masks.view(torch.uint8), 'masks', torch.uint8), n * H, W, rb, dev_ptr(bits),
-                                           stream_ptr(masks.device))
-        check(rc, 'cgg_pack_bool_rows_u8')
+        _call('cgg_pack_bool_rows_u8', dev_ptr(masks.view(torch.uint8), 'masks', torch.uint8), n * H, W, rb, dev_ptr(bits),
+              stream_ptr(masks.device))
     return bits
 
 
@@ -3168,12 +2972,10 @@ def paint_instances(img, bits, keep, colors, boxes=None, box_colors=None, alpha=
     alpha = float(alpha)
     stride = bits.stride(0) if n > 0 else H * rb
     with _timed('paint_instances', bytes=float(n * H * rb + 2 * img.numel()), shape=(n, H, W)):
-        rc = _lib_().cgg_paint_instances_u8(dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8), H, W,
-                                            ctypes.c_void_p(bits.data_ptr()) if n > 0 else None, n, int(stride), rb,
-                                            dev_ptr(keep, 'keep', torch.uint8), dev_ptr(colors, 'colors', torch.uint8),
-                                            dev_ptr(boxes, 'boxes', torch.int32), dev_ptr(box_colors, 'box_colors', torch.uint8),
-                                            alpha, 1 - alpha, int(thickness), int(bool(edges)), stream_ptr(dev))
-    check(rc, 'cgg_paint_instances_u8')
+        _call('cgg_paint_instances_u8', dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8), H, W,
+              dev_ptr(bits, 'bits', torch.uint8, dense=False) if n > 0 else None, n, int(stride), rb,
+              dev_ptr(keep, 'keep', torch.uint8), dev_ptr(colors, 'colors', torch.uint8), dev_ptr(boxes, 'boxes', torch.int32),
+              dev_ptr(box_colors, 'box_colors', torch.uint8), alpha, 1 - alpha, int(thickness), int(bool(edges)), stream_ptr(dev))
     return out
 
 
@@ -3193,15 +2995,13 @@ def label_components(pan, void, capacity=4096):
         raise CggError('label_components: contiguous (H, W) int32 device tensor with H * W < 2^31 expected')
     H, W = pan.shape
     dev = pan.device
-    lib = _lib_()
     cap = int(capacity)
-    ws = torch.empty(max(int(lib.cgg_label_components_workspace_bytes(H, W)), 8), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(int(_lib_().cgg_label_components_workspace_bytes(H, W)), 8), dtype=torch.uint8, device=dev)
     records = torch.empty((max(cap, 1), 5), dtype=torch.int64, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
     with _timed('label_components', bytes=float(pan.numel() * 4), shape=(H, W)):
-        rc = lib.cgg_label_components_i32(dev_ptr(pan, 'pan', torch.int32), H, W, int(void), dev_ptr(ws), dev_ptr(records), cap,
-                                          dev_ptr(status), stream_ptr(dev))
-    check(rc, 'cgg_label_components_i32')
+        _call('cgg_label_components_i32', dev_ptr(pan, 'pan', torch.int32), H, W, int(void), dev_ptr(ws), dev_ptr(records), cap,
+              dev_ptr(status), stream_ptr(dev))
     return records[:cap], status
 
 
@@ -3227,9 +3027,7 @@ def paint_panoptic(img, pan, ids, colors, alpha=0.8, edges=True, out=None):
     H, W, _ = img.shape
     alpha = float(alpha)
     with _timed('paint_panoptic', bytes=float(pan.numel() * 4 + 2 * img.numel()), shape=(H, W, k)):
-        rc = _lib_().cgg_paint_panoptic_u8(dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8),
-                                           dev_ptr(pan, 'pan', torch.int32), H, W, dev_ptr(ids, 'ids', torch.int32),
-                                           dev_ptr(colors, 'colors', torch.uint8), k, alpha, 1 - alpha, int(bool(edges)),
-                                           stream_ptr(dev))
-    check(rc, 'cgg_paint_panoptic_u8')
+        _call('cgg_paint_panoptic_u8', dev_ptr(img, 'img', torch.uint8), dev_ptr(out, 'out', torch.uint8),
+              dev_ptr(pan, 'pan', torch.int32), H, W, dev_ptr(ids, 'ids', torch.int32), dev_ptr(colors, 'colors', torch.uint8), k,
+              alpha, 1 - alpha, int(bool(edges)), stream_ptr(dev))
     return out

@@ -4,6 +4,10 @@ An `ops.py` wrapper that tells the library "this buffer is f32" or "bf16" by a t
 other type must be refused in Python, by argument name and dtype, before a pointer is taken -- the callee would read the buffer as
 one of the two. The tensors here live on the CPU, so a wrapper that let the dtype through would report the DEVICE instead (or, with
 a device, launch): the message tells the two apart, and a spy on `ops._lib_` shows that the library was never reached."""
+import ast
+import ctypes
+from types import SimpleNamespace
+
 import pytest
 import torch
 
@@ -89,14 +93,23 @@ TAGGED = [
 ]
 
 
-class _NoLibrary:
-    """Stands in for the loaded library: any entry point looked up on it is recorded (and fails the call)."""
+def _is_size_query(name):
+    """the entry points that answer a size or a yes / no about a geometry and touch no operand"""
+    return name.endswith(('_bytes', '_partials')) or name in ('cgg_dynamic_lds_limit', 'cgg_msda_backward_overwrites')
 
-    def __init__(self):
+
+class _NoLibrary:
+    """Stands in for the loaded library: any entry point looked up on it is recorded (and fails the call). sizes=True: a size query
+    is recorded and answers 1, for the wrappers that size a workspace or check an x3 image before their first pointer."""
+
+    def __init__(self, sizes=False):
         self.reached = []
+        self.sizes = sizes
 
     def __getattr__(self, name):
         self.reached.append(name)
+        if self.sizes and _is_size_query(name):
+            return lambda *a: 1
         raise AssertionError(f'the library entry {name} was reached')
 
 
@@ -149,3 +162,140 @@ def test_dev_ptr_tests_dtype_before_device_and_takes_a_tuple():
         fake = SimpleNamespace(dtype=dt, is_cuda=True, device='cuda:0', is_contiguous=lambda: True, data_ptr=lambda: 4096)
         assert _lib.dev_ptr(fake, 'x', (torch.float32, torch.bfloat16)).value == 4096
         assert _lib.dev_ptr(fake, 'x', dt).value == 4096
+
+
+def test_dev_ptr_dense_false_skips_only_the_contiguity_test():
+    view = torch.zeros(4, 8)[:, :4]
+    assert not view.is_contiguous()
+    with pytest.raises(_lib.CggError, match=r'x must live on a ROCm device'):
+        _lib.dev_ptr(view, 'x', torch.float32, dense=False)
+    with pytest.raises(_lib.CggError, match=r'x must be torch\.float32 \(got torch\.float16\)'):
+        _lib.dev_ptr(view.half(), 'x', torch.float32, dense=False)
+    fake = SimpleNamespace(dtype=torch.float32, is_cuda=True, device='cuda:0', is_contiguous=lambda: False, data_ptr=lambda: 4096)
+    assert _lib.dev_ptr(fake, 'x', torch.float32, dense=False).value == 4096
+    with pytest.raises(_lib.CggError, match='x must be contiguous'):
+        _lib.dev_ptr(fake, 'x', torch.float32)
+    assert _lib.dev_ptr(None, 'x', torch.float32, dense=False) is None
+
+
+def test_ptr_at_checks_the_tensor_and_adds_elements():
+    fake = SimpleNamespace(dtype=torch.float32, is_cuda=True, device='cuda:0', is_contiguous=lambda: False, data_ptr=lambda: 4096,
+                           element_size=lambda: 4)
+    assert ops._ptr_at(fake, 256, 'rows', torch.float32).value == 4096 + 1024
+    assert ops._ptr_at(None, 256, 'rows', torch.float32) is None
+    with pytest.raises(_lib.CggError, match='rows must live on a ROCm device'):
+        ops._ptr_at(torch.zeros(8), 4, 'rows', torch.float32)
+    with pytest.raises(_lib.CggError, match=r'rows must be torch\.bfloat16'):
+        ops._ptr_at(torch.zeros(8), 4, 'rows', torch.bfloat16)
+
+
+def test_host_ptr_is_dev_ptr_with_the_device_test_inverted():
+    t = torch.zeros(4, dtype=torch.int32)
+    assert _lib.host_ptr(t, 'table', torch.int32).value == t.data_ptr()
+    assert _lib.host_ptr(None, 'table') is None
+    with pytest.raises(_lib.CggError, match=r'table must be torch\.int32 \(got torch\.int64\)'):
+        _lib.host_ptr(t.long(), 'table', torch.int32)
+    with pytest.raises(_lib.CggError, match='table must be contiguous'):
+        _lib.host_ptr(torch.zeros(4, 2, dtype=torch.int32)[:, 0], 'table', torch.int32)
+    fake = SimpleNamespace(dtype=torch.int32, is_cuda=True, device='cuda:0', is_contiguous=lambda: True, data_ptr=lambda: 4096)
+    with pytest.raises(_lib.CggError, match='table must live in host memory'):
+        _lib.host_ptr(fake, 'table', torch.int32)
+
+
+def _enclosing_functions(tree):
+    """(node, name of the top-level function or class it lies in | None) for every node of the module"""
+    for top in tree.body:
+        name = top.name if isinstance(top, (ast.FunctionDef, ast.ClassDef)) else None
+        for node in ast.walk(top):
+            yield node, name
+
+
+def test_ops_has_one_pointer_path_and_one_call_path():
+    """Structure of ops.py: a tensor's address is taken by `dev_ptr` / `host_ptr` (offsets by `_ptr_at`), never by a cast of
+    `data_ptr()`; a status is checked in `_call` alone."""
+    tree = ast.parse(open(ops.__file__).read())
+    raw, checks = [], []
+    for node, where in _enclosing_functions(tree):
+        if not isinstance(node, ast.Call):
+            continue
+        f = node.func
+        if isinstance(f, ast.Attribute) and f.attr == 'c_void_p' and where != '_ptr_at':
+            inner = [n for a in node.args for n in ast.walk(a)]
+            if any(isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == 'data_ptr' for n in inner):
+                raw.append((where, node.lineno))
+        if (isinstance(f, ast.Name) and f.id == 'check' or isinstance(f, ast.Attribute) and f.attr == 'check') and where != '_call':
+            checks.append((where, node.lineno))
+    assert raw == [], f'raw tensor addresses: {raw}'
+    assert checks == [], f'status checks outside _call: {checks}'
+
+
+M, E = 8, 256
+
+
+def _rows(*shape, dt=torch.float32):
+    return torch.zeros(*shape, dtype=dt)
+
+
+def _packed():
+    return torch.zeros(64, dtype=torch.uint8)
+
+
+def _x3_image():
+    return torch.zeros(1, dtype=torch.uint8).as_subclass(ops.X3Image)       # 1 byte: what the spy's cgg_x3_packed_bytes answers
+
+
+def _norm():
+    return torch.ones(E), torch.zeros(E), 1e-5
+
+
+# wrappers whose tensor operands all went past `dev_ptr` as raw casts, with legal CPU operands, by their first operand
+RAW_CAST_WRAPPERS = {
+    'decoder_ffn': ('x', lambda: ops.decoder_ffn(_rows(M, E), _packed(), _rows(E), _packed(), _rows(E), 256)),
+    'decoder_mid': ('core', lambda: ops.decoder_mid(_rows(M, E), _packed(), _rows(E), _rows(M, E), _norm())),
+    'self_attn_rows_bf16': ('q', lambda: ops.self_attn_rows_bf16(_rows(M, E), _rows(M, 2 * E), 1, 8)),
+    'layernorm_chain': ('a', lambda: ops.layernorm_chain(_rows(M, E), _norm())),
+    'linear_rows_bf16': ('x', lambda: ops.linear_rows_bf16(_rows(M, E), _packed(), E)),
+    'linear_rows_bf16_qkv': ('xqk', lambda: ops.linear_rows_bf16_qkv(_rows(M, E), _rows(M, E), _packed(), _rows(3 * E), E)),
+    'gemm_x3': ('a', lambda: ops.gemm_x3(_rows(M, E), _x3_image(), E)),
+    'gemm_x3s': ('a', lambda: ops.gemm_x3s(_rows(M, E), _x3_image(), E)),
+    'gemm_x3s_batched': ('a', lambda: ops.gemm_x3s(_rows(2, M, E), _x3_image(), E)),
+    'gemm_x3_bwd': ('g', lambda: ops.gemm_x3_bwd(_rows(M, E), _x3_image(), E, amax=_rows(1))),
+    'wgrad_x3': ('dy', lambda: ops.wgrad_x3(_rows(M, E), _rows(M, E))),
+    'topk_select': ('x', lambda: ops.topk_select(_rows(4, 16), 3)),
+    'absmax': ('x', lambda: ops.absmax(_rows(M, E))),
+    'masked_xattn_bf16': ('q', lambda: ops.masked_xattn_bf16(_rows(1, M, E), _rows(1, 16, E, dt=torch.bfloat16),
+                                                             _rows(1, E, 16, dt=torch.bfloat16), None, 8)),
+}
+
+
+@pytest.mark.parametrize('wrapper', sorted(RAW_CAST_WRAPPERS))
+def test_raw_cast_wrapper_refuses_cpu_operands_before_the_library(monkeypatch, wrapper):
+    """Legal shapes and dtypes on the CPU: the first operand is refused for its device, by name, and no entry point other than a size
+    query was looked up -- for the _bf16 / _x3 twins: the symbol is no longer fetched before the pointers are checked."""
+    arg, call = RAW_CAST_WRAPPERS[wrapper]
+    spy = _NoLibrary(sizes=True)
+    monkeypatch.setattr(ops, '_lib_', lambda: spy)
+    with pytest.raises(_lib.CggError, match='ROCm device') as e:
+        call()
+    assert str(e.value).startswith(f'{arg} must live on a ROCm device'), str(e.value)
+    assert [n for n in spy.reached if not _is_size_query(n)] == []
+
+
+def test_a_failed_call_is_reported_under_the_symbol_that_ran(monkeypatch):
+    """`gemm_x3s` on a (B, R, K) stack runs cgg_gemm_x3s_batched: its status is reported under that name."""
+    ran = []
+
+    class _Fails:
+        def cgg_x3_packed_bytes(self, N, K):
+            return 1
+
+        def cgg_gemm_x3s_batched(self, *args):
+            ran.append(len(args))
+            return -2
+
+    monkeypatch.setattr(ops, '_lib_', lambda: _Fails())
+    monkeypatch.setattr(ops, 'dev_ptr', lambda t, *a, **k: None if t is None else ctypes.c_void_p(4096))
+    monkeypatch.setattr(ops, 'stream_ptr', lambda device=None: None)
+    with pytest.raises(_lib.CggError, match=r'cgg_gemm_x3s_batched failed \(rc=-2\)'):
+        ops.gemm_x3s(_rows(2, M, E), _x3_image(), E)
+    assert ran == [len(_lib.PROTOTYPES['cgg_gemm_x3s_batched'][1])]

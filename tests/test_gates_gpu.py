@@ -456,3 +456,51 @@ def test_grounding_gate(dev, Q, T, d, inside, monkeypatch):
     print(f'Q {Q} T {T} d {d}: loss err {abs(lg - lw):.2e}, grad err {err:.2e} of scale {scale:.2e}, kernel {inside}')
     assert abs(lg - lw) <= 1e-5 * (1 + abs(lw)), (lg, lw)
     assert err <= 1e-4 * scale + 1e-9, (err, scale)
+
+
+# ------------------------------------------------------------------------------------------------
+# F. one operand on the CPU among device operands (the case the CPU suite cannot build)
+# ------------------------------------------------------------------------------------------------
+class _SizesOnlyReal:
+    """Stands in for the loaded library: a `*_bytes` query goes to the real one, any other entry point raises when it is looked up --
+    whatever the wrapper under test does, it cannot launch a kernel."""
+
+    def __init__(self, real):
+        self.real = real
+        self.refused = []
+
+    def __getattr__(self, name):
+        if name.endswith('_bytes'):
+            return getattr(self.real, name)
+        self.refused.append(name)
+        raise AssertionError(f'the library entry {name} was reached')
+
+
+def _mixed_device_calls(dev, real):
+    M, K, N = 8, 256, 256
+    a, on_dev, on_cpu = torch.zeros(M, K, device=dev), torch.zeros(M, N, device=dev), torch.zeros(M, N)
+    x3 = torch.zeros(real.cgg_x3_packed_bytes(N, K), dtype=torch.uint8, device=dev).as_subclass(ops.X3Image)
+    bf16 = torch.zeros(real.cgg_linear_rows_packed_bytes(N, K), dtype=torch.uint8, device=dev)
+    bias = torch.zeros(N, device=dev)
+    norm = (torch.ones(N, device=dev), torch.zeros(N, device=dev), 1e-5)
+    return [
+        ('gemm_x3', 'res', lambda: ops.gemm_x3(a, x3, N, bias=bias, res=on_cpu)),
+        ('gemm_x3', 'out', lambda: ops.gemm_x3(a, x3, N, bias=bias, res=on_dev, out=on_cpu)),
+        ('linear_rows_bf16', 'res', lambda: ops.linear_rows_bf16(a, bf16, N, bias=bias, res=on_cpu)),
+        ('linear_rows_bf16', 'out', lambda: ops.linear_rows_bf16(a, bf16, N, bias=bias, res=on_dev, out=on_cpu)),
+        ('decoder_mid', 'res', lambda: ops.decoder_mid(a, bf16, bias, on_cpu, norm)),
+    ]
+
+
+def test_one_cpu_operand_among_device_operands_is_refused_by_name(dev, monkeypatch):
+    """M = 8, K = N = 256, every operand on the device except `res` (or a caller's `out`): these went to the kernel as raw addresses
+    -- a host pointer in a device launch. Now a CggError names the operand and no entry point but a size query was looked up."""
+    real = ops._lib_()
+    calls = _mixed_device_calls(dev, real)
+    guard = _SizesOnlyReal(real)
+    monkeypatch.setattr(ops, '_lib_', lambda: guard)
+    for wrapper, arg, call in calls:
+        with pytest.raises(ops.CggError, match='ROCm device') as e:
+            call()
+        assert str(e.value).startswith(f'{arg} must live on a ROCm device (got cpu)'), (wrapper, arg, str(e.value))
+    assert guard.refused == []
