@@ -3031,3 +3031,105 @@ def paint_panoptic(img, pan, ids, colors, alpha=0.8, edges=True, out=None):
               dev_ptr(pan, 'pan', torch.int32), H, W, dev_ptr(ids, 'ids', torch.int32), dev_ptr(colors, 'colors', torch.uint8), k,
               alpha, 1 - alpha, int(bool(edges)), stream_ptr(dev))
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# COCO mask evaluation on the device (csrc/mask_eval.hip; mask_eval.py states the rules in numpy)
+# ------------------------------------------------------------------------------------------------
+MASK_EVAL_MAX_MASKS = 1024
+MASK_EVAL_MAX_THRS = 64
+MASK_EVAL_MAX_AREAS = 8
+MASK_EVAL_MAX_CATS = 1024
+
+
+def mask_eval_ok(D, G, H, W):
+    """The gate of `mask_intersections` / `coco_match`: at most 1024 masks on each side and H * W < 2^31 (the sums are int32).
+    Shapes outside it take the host rule (`mask_eval.mask_intersections_host`, `mask_eval.evaluate_img_host`)."""
+    return 0 <= int(D) <= MASK_EVAL_MAX_MASKS and 0 <= int(G) <= MASK_EVAL_MAX_MASKS and int(H) > 0 and int(W) > 0 \
+        and int(H) * int(W) < (1 << 31)
+
+
+def _bit_planes(bits, name):
+    """(n, H, row_bytes, plane stride) of bit-packed device masks with contiguous rows"""
+    if not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 3:
+        raise CggError(f'{name}: (n, H, row_bytes) uint8 device tensor expected')
+    n, H, rb = bits.shape
+    if n > 0 and (bits.stride(2) != 1 or bits.stride(1) != rb or bits.stride(0) < H * rb):
+        raise CggError(f'{name}: rows must be contiguous and planes at least H * row_bytes apart (strides {bits.stride()})')
+    return n, H, rb, int(bits.stride(0)) if n > 0 else H * rb
+
+
+def mask_intersections(det_bits, gt_bits, width, ws=None):
+    """det_bits (D, H, row_bytes), gt_bits (G, H, row_bytes) DEVICE uint8 bit planes (rows contiguous, stride(0) may exceed
+    H * row_bytes; pixel x in bit (x & 7) of byte (x >> 3), pad bits may hold anything) -> (inter int32 (D, G), area_d int32 (D,),
+    area_g int32 (G,)) on the device, equal to `mask_eval.mask_intersections_host`. Two launches on the current stream, no host
+    read; `ws` (uint8, cgg_mask_intersections_workspace_bytes) may be handed in."""
+    D, H, rb, dstride = _bit_planes(det_bits, 'mask_intersections: det_bits')
+    G, Hg, rbg, gstride = _bit_planes(gt_bits, 'mask_intersections: gt_bits')
+    W = int(width)
+    if Hg != H or rbg != rb or gt_bits.device != det_bits.device:
+        raise CggError(f'mask_intersections: det_bits {tuple(det_bits.shape)} on {det_bits.device} and gt_bits {tuple(gt_bits.shape)} '
+                       f'on {gt_bits.device} must share H, row_bytes and the device')
+    if not mask_eval_ok(D, G, H, W):
+        raise CggError(f'mask_intersections: outside the kernel gate (D={D}, G={G} <= {MASK_EVAL_MAX_MASKS}, H * W < 2^31)')
+    dev = det_bits.device
+    pd = dev_ptr(det_bits, 'mask_intersections: det_bits', torch.uint8, dense=False)
+    pg = dev_ptr(gt_bits, 'mask_intersections: gt_bits', torch.uint8, dense=False)
+    inter = torch.empty((D, G), dtype=torch.int32, device=dev)
+    area_d = torch.empty(D, dtype=torch.int32, device=dev)
+    area_g = torch.empty(G, dtype=torch.int32, device=dev)
+    need = int(_lib_().cgg_mask_intersections_workspace_bytes(D, G, H, W))
+    if ws is None:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    if ws.numel() < need or ws.device != dev:
+        raise CggError(f'mask_intersections: workspace of {ws.numel()} bytes on {ws.device}, {need} on {dev} needed')
+    with _timed('mask_intersections', bytes=float((D + G) * H * rb), shape=(D, G, H, W)):
+        _call('cgg_mask_intersections_bits', pd if D else None, D, dstride, pg if G else None, G, gstride, H, W, rb,
+              dev_ptr(ws, 'ws', torch.uint8), dev_ptr(inter, 'inter') if D * G else None, dev_ptr(area_d, 'area_d') if D else None,
+              dev_ptr(area_g, 'area_g') if G else None, stream_ptr(dev))
+    return inter, area_d, area_g
+
+
+def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt_area, cat_ids, area_rngs, iou_thrs, max_det,
+               class_agnostic, out=None):
+    """The matching of `mask_eval.evaluate_img_host` for one image on the device, from the outputs of `mask_intersections`:
+    det_order int32 (D,) (stable descending score order: `torch.sort(scores, descending=True, stable=True).indices`), det_cats
+    int32 (D,), gt_cats int32 (G,), gt_crowd uint8 (G,), gt_area float64 (G,), cat_ids int32 (K,), area_rngs float64 (A, 2),
+    iou_thrs float64 (T,) -> (dt_match int32 (K, A, T, D), dt_ignore uint8 (K, A, T, D), gt_ignore uint8 (K, A, G), counts int32
+    (K, 2) = (D_k, G_k)); row (k, a, t) holds the category's D_k detections in score order, 0 past them. One launch on the current
+    stream, no host read. `out`: the four tensors, preallocated."""
+    D, G = int(area_d.numel()), int(area_g.numel())
+    K, A, T = int(cat_ids.numel()), int(area_rngs.shape[0]), int(iou_thrs.numel())
+    dev = area_d.device
+    if tuple(inter.shape) != (D, G) or tuple(area_rngs.shape) != (A, 2):
+        raise CggError(f'coco_match: inter {tuple(inter.shape)} / area_rngs {tuple(area_rngs.shape)} do not match D={D}, G={G}')
+    if D > MASK_EVAL_MAX_MASKS or G > MASK_EVAL_MAX_MASKS or T > MASK_EVAL_MAX_THRS or A > MASK_EVAL_MAX_AREAS or K > MASK_EVAL_MAX_CATS \
+            or min(K, A, T) < 1:
+        raise CggError(f'coco_match: outside the kernel gate (D={D}, G={G} <= {MASK_EVAL_MAX_MASKS}, 1 <= T={T} <= {MASK_EVAL_MAX_THRS}, '
+                       f'1 <= A={A} <= {MASK_EVAL_MAX_AREAS}, 1 <= K={K} <= {MASK_EVAL_MAX_CATS})')
+    for t, name, n in ((det_order, 'det_order', D), (det_cats, 'det_cats', D), (gt_cats, 'gt_cats', G), (gt_crowd, 'gt_crowd', G),
+                       (gt_area, 'gt_area', G)):
+        if t.numel() != n or t.device != dev:
+            raise CggError(f'coco_match: {name} must have {n} elements on {dev} (got {t.numel()} on {t.device})')
+    if out is None:
+        out = (torch.empty((K, A, T, D), dtype=torch.int32, device=dev), torch.empty((K, A, T, D), dtype=torch.uint8, device=dev),
+               torch.empty((K, A, G), dtype=torch.uint8, device=dev), torch.empty((K, 2), dtype=torch.int32, device=dev))
+    dt_match, dt_ignore, gt_ignore, counts = out
+    for t, name, shape in ((dt_match, 'dt_match', (K, A, T, D)), (dt_ignore, 'dt_ignore', (K, A, T, D)),
+                           (gt_ignore, 'gt_ignore', (K, A, G)), (counts, 'counts', (K, 2))):
+        if tuple(t.shape) != shape or t.device != dev:
+            raise CggError(f'coco_match: {name} must be {shape} on {dev} (got {tuple(t.shape)} on {t.device})')
+
+    def opt(t, name, dtype, n):
+        return dev_ptr(t, f'coco_match: {name}', dtype) if n else None
+
+    with _timed('coco_match', shape=(D, G, K, A, T)):
+        _call('cgg_coco_match', opt(inter, 'inter', torch.int32, D * G), opt(area_d, 'area_d', torch.int32, D),
+              opt(area_g, 'area_g', torch.int32, G), opt(det_order, 'det_order', torch.int32, D),
+              opt(det_cats, 'det_cats', torch.int32, D), opt(gt_cats, 'gt_cats', torch.int32, G),
+              opt(gt_crowd, 'gt_crowd', torch.uint8, G), opt(gt_area, 'gt_area', torch.float64, G),
+              dev_ptr(cat_ids, 'coco_match: cat_ids', torch.int32), K, dev_ptr(area_rngs, 'coco_match: area_rngs', torch.float64), A,
+              dev_ptr(iou_thrs, 'coco_match: iou_thrs', torch.float64), T, D, G, int(max_det), int(bool(class_agnostic)),
+              opt(dt_match, 'dt_match', torch.int32, D), opt(dt_ignore, 'dt_ignore', torch.uint8, D),
+              opt(gt_ignore, 'gt_ignore', torch.uint8, G), dev_ptr(counts, 'coco_match: counts', torch.int32), stream_ptr(dev))
+    return dt_match, dt_ignore, gt_ignore, counts

@@ -1245,6 +1245,49 @@ int cgg_panoptic_fuse_batched(const float* logits, const float* score, const int
 int cgg_rowwise_softmax_argmax(const float* x, float* prob, float* maxv, int64_t* argmax, int rows,
                                int n, cgg_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * COCO mask evaluation on the device (csrc/mask_eval.hip). `mask_eval.py` states the rules in numpy
+ * (mask_intersections_host, mask_iou_host, evaluate_img_host) and the kernels equal them exactly: integers, and IEEE double
+ * operations in a fixed order. All pointers DEVICE; everything runs on `stream`; no host read, no allocation, no atomics:
+ * legal under stream capture.
+ *
+ * cgg_mask_intersections_bits: inter[d][g] = set pixels of det plane d AND gt plane g, area_d[d], area_g[g] = set pixels of
+ *   each plane. Planes as cgg_rle_transitions reads them: H rows x row_bytes bytes, plane i at bits + i * stride_bytes, pixel x
+ *   of a row = bit (x & 7) of byte (x >> 3); only the first W pixels of a row count, pad bits may hold anything. Both sides share
+ *   H, W and row_bytes. A workgroup stages a slab of rows of up to 64 + 64 planes in LDS (16-byte loads when pointer, stride
+ *   and row_bytes are multiples of 16, 4-byte or byte loads otherwise; the pad bits are masked there, once) and each thread keeps
+ *   a 4 x 4 register tile of pairs: one AND and one count-add per 32 pixels and pair. Slab groups write int32 partials to ws, a
+ *   second launch adds them. ws: cgg_mask_intersections_workspace_bytes(D, G, H, W) bytes, 4-byte aligned.
+ *   D = 0 or G = 0 is legal (the areas of the other side are still written; both 0: nothing is launched).
+ *   CGG_EINVAL: null pointer, D, G < 0, H, W < 1, row_bytes * 8 < W, a stride below H * row_bytes, misaligned ws / outputs.
+ *   CGG_EUNSUPPORTED: D > 1024, G > 1024, H * W >= 2^31.
+ *
+ * cgg_coco_match: COCOeval.evaluateImg for every (category k, area range a, threshold t) of one image, one thread each.
+ *   inter / area_d / area_g as written above; det_order int32[D] = the detections in stable descending score order; det_cats
+ *   int32[D], gt_cats int32[G], gt_crowd uint8[G], gt_area double[G] (the annotation's own area); cat_ids int32[K]; area_rngs
+ *   double[A][2] = (lo, hi); iou_thrs double[T]. IoU = (double)inter / (double)(area_d + area_g - inter), for a crowd
+ *   (double)inter / (double)area_d, 0 where the denominator is 0. Detections of category k (every detection when
+ *   class_agnostic) in det_order, cut to max_det; ground truths of category k, those that count first, the ignored ones (crowd,
+ *   or gt_area < lo or > hi) after them, original order within each group; greedy scan with best = min(t, 1 - 1e-10): a
+ *   matched non-crowd ground truth is skipped, the ignored ones are not scanned once one that counts has matched, `iou < best`
+ *   continues (a later equal IoU wins).
+ *   dt_match int32[K][A][T][D]: row (k, a, t) holds, for the D_k detections in that order, 0 or 1 + the matched ground truth's
+ *   index in the image; dt_ignore uint8[K][A][T][D]: the match is an ignored ground truth, or unmatched with area_d outside
+ *   (lo, hi); gt_ignore uint8[K][A][G]: the G_k ground truths in scan order; counts int32[K][2] = (D_k, G_k). Entries past D_k /
+ *   G_k are written as 0.
+ *   CGG_EINVAL: null pointer, K, A, T < 1, D, G, max_det < 0, misaligned doubles. CGG_EUNSUPPORTED: T > 64, A > 8, K > 1024,
+ *   D > 1024, G > 1024.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t cgg_mask_intersections_workspace_bytes(int D, int G, int H, int W);
+int cgg_mask_intersections_bits(const uint8_t* det_bits, int D, int64_t det_stride_bytes, const uint8_t* gt_bits, int G,
+                                int64_t gt_stride_bytes, int H, int W, int row_bytes, void* ws, int32_t* inter, int32_t* area_d,
+                                int32_t* area_g, cgg_stream_t stream);
+int cgg_coco_match(const int32_t* inter, const int32_t* area_d, const int32_t* area_g, const int32_t* det_order,
+                   const int32_t* det_cats, const int32_t* gt_cats, const uint8_t* gt_crowd, const double* gt_area,
+                   const int32_t* cat_ids, int K, const double* area_rngs, int A, const double* iou_thrs, int T, int D, int G,
+                   int max_det, int class_agnostic, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, int32_t* counts,
+                   cgg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

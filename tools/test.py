@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Minimal inference driver with the command line of the reference's tools/test.py: config + checkpoint -> detector from
 the registry -> `simple_test` over a stream of images -> results pickle (`--out`), one process per GPU under
-`--launcher pytorch` (images are sharded by rank, results gathered on rank 0). COCO evaluation (`--eval`) needs the
-dataset classes, which are out of this build's scope: the option is accepted and reported as unavailable.
+`--launcher pytorch` (images are sharded by rank, results gathered on rank 0). `--eval segm` computes COCO mask AP (and base /
+novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`); the other
+metrics need the dataset classes, which are out of this build's scope: they are accepted and reported as unavailable.
 
 Both precision modes serve through `pipeline.StagePipeline` (hipGraph per stage, encode of batch k+1 overlapped with decode of
 batch k): `--precision fp32` (default) is parity mode -- the reference's f32 semantics on the f32-class x3 kernels --,
@@ -39,7 +40,13 @@ def parse_args(argv=None):
     p.add_argument('--out', help='output result file in pickle format')
     p.add_argument('--fuse-conv-bn', action='store_true', help='accepted: the bf16 path always folds BN into the convs')
     p.add_argument('--gpu-id', type=int, default=0)
-    p.add_argument('--eval', type=str, nargs='+', help='evaluation metrics (needs the dataset classes: unavailable here)')
+    p.add_argument('--eval', type=str, nargs='+',
+                   help='evaluation metrics. segm: COCO mask AP of every result type the head returns, evaluated on the device from the '
+                        'bit-packed masks; needs a --data stream whose metas carry gt_masks (n, h, w) and gt_labels (category ids) at the '
+                        'original size (gt_crowd, gt_area optional), and sets --mask-bits. The config may hold segm_eval = dict(all_results='
+                        '[category id per label], base_results=[...], novel_results=[...], unknown_cat_ids=[...], all_cat_ids=[...], '
+                        'class_agnostic=False, max_dets=(100, 300, 1000)); a type without a list takes label + 1 as the category id. '
+                        'Other metrics need the dataset classes: unavailable here')
     p.add_argument('--cfg-options', nargs='+', default=None, help='key=value overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none')
     p.add_argument('--local_rank', type=int, default=0)
@@ -131,6 +138,34 @@ def interleave_rank_results(parts):
     return out[:total]
 
 
+def segm_summary(cfg, model, evaluators, eval_records, device, work_dir):
+    """--eval segm on rank 0: accumulate every type's image records (this rank's and the gathered ones), print the summary and write
+    it to WORK_DIR/segm_eval.json. Without ground truth in the stream nothing was recorded: today's message."""
+    from cgg_amd.mask_eval import SegmEvaluator, format_summary
+    if not eval_records:
+        print('--eval segm: the stream carries no ground truth (metas with gt_masks and gt_labels come from a --data stream); dataset '
+              'classes / COCO evaluation are outside this build', flush=True)
+        return None
+    opts = dict(cfg.get('segm_eval') or {})
+    summary = {}
+    for key in sorted(eval_records):
+        ev = evaluators.get(key)
+        if ev is None:                  # a type only other ranks saw: the same evaluator, without records of its own
+            n_cls = getattr(model.panoptic_fusion_head, key.replace('_results', '_classes'), None) or model.num_classes
+            ev = SegmEvaluator(opts.get(key) or list(range(1, int(n_cls) + 1)), opts.get('unknown_cat_ids'), opts.get('all_cat_ids'),
+                               max_dets=tuple(opts.get('max_dets', (100, 300, 1000))), class_agnostic=bool(opts.get('class_agnostic', False)))
+        ev.records = list(eval_records[key])
+        res = ev.summarize()
+        print(format_summary(key, res), flush=True)
+        summary[key] = dict(images=res['images'], stats=res['stats'], base_ap50=res['base_ap50'], novel_ap50=res['novel_ap50'],
+                            all_ap50=res['all_ap50'])
+    if work_dir:
+        os.makedirs(work_dir, exist_ok=True)
+        with open(os.path.join(work_dir, 'segm_eval.json'), 'w') as f:
+            json.dump(summary, f, indent=1)
+    return summary
+
+
 def _test_stages():
     """CGG_TEST_STAGES (pipeline stage split of the serving loop): validated up front, 2..5 as `pipeline.detector_pipeline` names them
     (4 and 5 add a separate post-processing stage to the 2- / 3-stage split)."""
@@ -163,8 +198,14 @@ def main(argv=None):
     if 'CLASSES' in meta:
         model.CLASSES = meta['CLASSES']
     model = model.to(device).eval()
-    if args.eval:
+    eval_segm = bool(args.eval) and 'segm' in args.eval
+    if args.eval and [m for m in args.eval if m != 'segm']:
         print('--eval: dataset classes / COCO evaluation are outside this build; results are written with --out', flush=True)
+    if eval_segm:
+        args.mask_bits = True
+    evaluators = {}                    # --eval segm: result type -> SegmEvaluator, made when the first ground truth arrives
+    eval_metas = []                    # per submitted batch, in submission order: the metas of its images
+    evaluated = [None]                 # event after the newest batch's evaluator launches
 
     if args.data:
         mod, fn = args.data.split(':')
@@ -206,8 +247,32 @@ def main(argv=None):
             model.show_result(raw, res, score_thr=args.show_score_thr, out_file=os.path.join(show_dir, stem + '.png'))
             n_shown += 1
 
+    def evaluate(device_results):
+        """--eval segm: every image's result of each type the head returns goes to that type's evaluator (masks stay on the device)"""
+        from cgg_amd.mask_eval import SegmEvaluator
+        opts = dict(cfg.get('segm_eval') or {})
+        for m, res in zip(eval_metas.pop(0), device_results):
+            if m.get('gt_masks') is None or m.get('gt_labels') is None:
+                continue
+            for key, val in res.items():
+                if not (key.endswith('_results') and isinstance(val, (tuple, list)) and len(val) == 3):
+                    continue
+                if key not in evaluators:
+                    n_cls = getattr(model.panoptic_fusion_head, key.replace('_results', '_classes'), None) or model.num_classes
+                    agnostic = bool(opts.get('class_agnostic', False))
+                    evaluators[key] = SegmEvaluator(opts.get(key) or list(range(1, int(n_cls) + 1)), opts.get('unknown_cat_ids'),
+                                                    opts.get('all_cat_ids'), max_dets=tuple(opts.get('max_dets', (100, 300, 1000))),
+                                                    class_agnostic=agnostic, device=device, skip_images_without_gt=not agnostic)
+                evaluators[key].add(val[0], val[1], val[2], m['gt_masks'], m['gt_labels'], m.get('gt_crowd'), m.get('gt_area'))
+
     def emit(device_results):
         """device results of one batch -> `results` (numpy now, or a future of the RLE collector)"""
+        if eval_segm:
+            evaluate(device_results)
+            # the evaluator's kernels read the result buffers on THIS stream: the pipeline's last stage waits for them before it
+            # writes a slot again (a wait on the GPU; without the RLE collector the copies below end in a host wait anyway)
+            evaluated[0] = torch.cuda.Event()
+            evaluated[0].record()
         if show_dir is not None:
             paint(device_results)
         if collector is None:
@@ -269,6 +334,8 @@ def main(argv=None):
                     imgs[k].copy_(g[0], non_blocking=True)
                 metas = [dict(g[1], batch_input_shape=tuple(imgs.shape[-2:])) for g in group]
                 shape = tuple(imgs.shape)
+            if eval_segm:
+                eval_metas.append(metas)
             use_pipe = (not args.no_pipeline and len(group) == B
                         and all(m['img_shape'] == metas[0]['img_shape'] and m['ori_shape'] == metas[0]['ori_shape'] for m in metas))
             if use_pipe:
@@ -294,6 +361,8 @@ def main(argv=None):
                     ev = slot_copied.pop((id(pipe), pipe._n % pipe.slots), None)
                     if ev is not None:
                         pipe.streams[-1].wait_event(ev)
+                if evaluated[0] is not None:
+                    pipe.streams[-1].wait_event(evaluated[0])
                 if imgs is None:
                     # the kernel writes the static input of the slot this submit takes, once stage 0 of the slot's previous batch
                     # has read it (a wait on the GPU; an event that was never recorded does not wait)
@@ -364,13 +433,23 @@ def main(argv=None):
             results = flat
             collector.close()
     dt = time.perf_counter() - (t0 or time.perf_counter())
+    eval_records = {key: ev.image_records() for key, ev in evaluators.items()}     # per image a few KB of match records, no masks
     if distributed:
         import torch.distributed as dist
         gathered = [None] * world if rank == 0 else None
         dist.gather_object(results, gathered, dst=0)
         if rank == 0:
             results = interleave_rank_results(gathered)
+        if eval_segm:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(eval_records, parts, dst=0)
+            if rank == 0:
+                for part in parts[1:]:
+                    for key, recs in part.items():
+                        eval_records.setdefault(key, []).extend(recs)
         dist.destroy_process_group()
+    if eval_segm and rank == 0:
+        segm_summary(cfg, model, evaluators, eval_records, device, args.work_dir)
     if rank == 0:
         print(json.dumps(dict(images=len(results), images_per_sec_this_rank=round(n_img / max(dt, 1e-9), 1),
                               precision=args.precision, pipeline=pipe is not None,
