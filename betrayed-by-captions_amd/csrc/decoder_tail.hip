@@ -16,6 +16,7 @@
 #define DT_STEPS (DT_C / 16)
 
 #define DT_FRAG (DT_STEPS * 64)     // u32x4 slots of one 32 x 256 A-fragment image (16 KiB)
+#define DT_MAX_PLANES 8             // split-K planes cgg_decoder_tail_kernel holds in registers per row (2048 / 256)
 
 // a 32 x 256 A-fragment image: one 16-KiB half (bf16) or a hi and a lo half (x3: f16 pieces)
 template <bool X3>
@@ -139,12 +140,12 @@ __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
   // lane l the columns 4l .. 4l+3; all 4 x nsum plane loads of a wave are in flight together
   f32x4 acc4[4];
   {
-    f32x4 ld4[4][8];
+    f32x4 ld4[4][DT_MAX_PLANES];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int m = m0 + 4 * wave + rr;
 #pragma unroll
-      for (int p = 0; p < 8; ++p) {
+      for (int p = 0; p < DT_MAX_PLANES; ++p) {
         // clamped (row M - 1 / plane nsum - 1: lines this wave reads anyway), zeroed after: predicated loads compile to
         // branch / load / s_waitcnt vmcnt(0) chains, one memory latency per row at the head of the kernel
         const f32x4 pv = *reinterpret_cast<const f32x4*>(planes + (size_t)(p < nsum ? p : nsum - 1) * plane_stride +
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
     for (int rr = 0; rr < 4; ++rr) {
       acc4[rr] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int p = 0; p < 8; ++p) acc4[rr] += ld4[rr][p];          // fixed order (adding the zero planes is exact)
+      for (int p = 0; p < DT_MAX_PLANES; ++p) acc4[rr] += ld4[rr][p];   // fixed order (adding the zero planes is exact)
     }
   }
   u32x4 bf[DT_STEPS], bl[X3 ? DT_STEPS : 1];
@@ -260,6 +261,8 @@ static int dt_tail_launch(bool x3, const char* who, const float* planes, int nsu
               CGG_EINVAL, "%s: null pointer", who);
   CGG_REQUIRE(C == DT_C, CGG_EUNSUPPORTED, "%s: C=%d (only 256 is built)", who, C);
   CGG_REQUIRE(M > 0 && nsum >= 1 && pos_rows > 0 && ld >= C, CGG_EINVAL, "%s: bad sizes", who);
+  CGG_REQUIRE(nsum <= DT_MAX_PLANES, CGG_EUNSUPPORTED, "%s: nsum=%d planes (at most %d are summed; cgg_layernorm_chain takes any)",
+              who, nsum, DT_MAX_PLANES);
   CGG_REQUIRE(!wq || (bq && qn), CGG_EINVAL, "%s: wq needs bq and qn", who);
   CGG_REQUIRE(cgg_aligned16(w1) && cgg_aligned16(w2) && cgg_aligned16(w3) && cgg_aligned16(wq), CGG_EALIGN,
               "%s: packed weights must be 16-B aligned", who);

@@ -505,7 +505,9 @@ class Mask2FormerHeadOpen(nn.Module):
         layers = self.transformer_decoder.layers
         return (C == 256 and self.attn_mask_hook is None and len(me) == 5
                 and all(tuple(m.weight.shape) == (C, C) for m in (me[0], me[2], me[4]))
-                and all(l.attentions[0].embed_dims == C for l in layers))
+                and all(l.attentions[0].embed_dims == C for l in layers)
+                # `ops.decoder_tail` sums at most that many FFN planes; a wider FFN takes `_decode_stream` (`layernorm_chain`)
+                and all(l.ffn_planes() <= ops.DECODER_TAIL_MAX_PLANES for l in layers))
 
     def _decode_stream_lean(self, B, kvs, sizes, packed_full, pooled):
         """Inference-only decode (`all_masks=False`): the intermediate layers' class / caption-embedding predictions

@@ -2070,10 +2070,13 @@ def self_attn_rows_bf16(q, kv, B, num_heads, scale=None):
     return out
 
 
+DECODER_TAIL_MAX_PLANES = 8          # csrc/decoder_tail.hip DT_MAX_PLANES: more planes are refused (CGG_EUNSUPPORTED), not dropped
+
+
 def decoder_tail(planes, norm_a, pos, norm_b, mlp, qproj=None, want_pos=False):
-    """planes (nsum, M, 256) f32 (FFN split-K partials, bias + residual in plane 0) -> (y = LN_a(sum), y + pos | None,
-    mask_embed = MLP3(LN_b(y)), qn = Wq (y + pos) + bq | None). norm_* = (gamma, beta, eps); mlp = (w1, b1, w2, b2, w3, b3)
-    and qproj = (wq, bq) with weights packed by `pack_linear_weight` (256 x 256)."""
+    """planes (nsum, M, 256) f32 (FFN split-K partials, bias + residual in plane 0), nsum <= DECODER_TAIL_MAX_PLANES ->
+    (y = LN_a(sum), y + pos | None, mask_embed = MLP3(LN_b(y)), qn = Wq (y + pos) + bq | None). norm_* = (gamma, beta, eps);
+    mlp = (w1, b1, w2, b2, w3, b3) and qproj = (wq, bq) with weights packed by `pack_linear_weight` (256 x 256)."""
     if planes.dim() != 3 or not planes.is_contiguous() or planes.dtype != torch.float32:
         raise CggError('decoder_tail: planes must be a contiguous (nsum, M, C) float32 tensor')
     nsum, M, C = planes.shape

@@ -260,6 +260,17 @@ class DetrTransformerDecoderLayer(BaseTransformerLayer):
                 and len(ffn.layers) == 3 and isinstance(ffn.layers[0][1], nn.ReLU) and ffn.add_identity
                 and self.embed_dims <= 256 and self.embed_dims % 32 == 0)
 
+    def ffn_fused(self):
+        """whether `forward_stream` runs the FFN as `ops.decoder_ffn` (one plane per 256 hidden columns)"""
+        return self.embed_dims == 256 and self.ffns[0].layers[0][0].weight.shape[0] % 256 == 0
+
+    def ffn_planes(self):
+        """how many split-K planes `forward_stream(raw=True)` returns: the fused FFN's F / 256, else the split of the second linear"""
+        F1 = self.ffns[0].layers[0][0].weight.shape[0]
+        if self.ffn_fused():
+            return F1 // 256
+        return 8 if F1 >= 1024 else 1
+
     def forward_stream(self, x, xp, pos, kv, bits, post_norm=None, q=None, raw=False, fix_rows=False):
         """Throughput-mode layer on 2-D rows: x, xp = x + pos (M = B*Q, C) f32; pos (Q, C). Every projection is
         `cgg_linear_rows_bf16` on pre-packed bf16 weights; the three post-norm LayerNorms, the residual adds and the
@@ -325,11 +336,11 @@ class DetrTransformerDecoderLayer(BaseTransformerLayer):
         ffn = self.ffns[0]
         w1, b1, F1 = pk((ffn.layers[0][0].weight,), (ffn.layers[0][0].bias,))
         w2, b2, _ = pk((ffn.layers[1].weight,), (ffn.layers[1].bias,))
-        if E == 256 and F1 % 256 == 0 and x2.stride(1) == 1:
+        if self.ffn_fused():
             t = ops.decoder_ffn(x2, w1, b1, w2, b2, F1)          # both projections, hidden block in LDS
         else:
             h = lr(x2, w1, F1, b1, relu_cols=F1)
-            t = lr(h, w2, E, b2, res=x2, ksplit=8 if F1 >= 1024 else 1)
+            t = lr(h, w2, E, b2, res=x2, ksplit=self.ffn_planes())
         if raw:
             return t if t.dim() == 3 else t.unsqueeze(0)
         return ops.layernorm_chain(t, (n2.weight, n2.bias, n2.eps), pos,

@@ -568,7 +568,8 @@ int cgg_layernorm_chain(const float* a, int lda, const float* gamma_a, const flo
  * yp = y + pos[row % pos_rows] (nullable), z = LN_b(y) (decoder post_norm, mask2former_head.py:734),
  * mask_embed = W3 relu(W2 relu(W1 z + b1) + b2) + b3 (:741-746) and, when wq != NULL, qn = Wq (y + pos) + bq -- the next
  * layer's cross-attention query projection (:829). w1 / w2 / w3 / wq: 256 x 256 weights packed by cgg_linear_rows_pack.
- * Same arithmetic per stage as cgg_layernorm_chain + 4 x cgg_linear_rows_bf16 (bf16 operands, f32 accumulate).     */
+ * Same arithmetic per stage as cgg_layernorm_chain + 4 x cgg_linear_rows_bf16 (bf16 operands, f32 accumulate).
+ * nsum <= 8 (F = 2048): more planes are CGG_EUNSUPPORTED -- cgg_layernorm_chain sums any number.                      */
 int cgg_decoder_tail_bf16(const float* planes, int nsum, int64_t plane_stride, int ld, const float* gamma_a,
                           const float* beta_a, float eps_a, const float* pos, int pos_rows, const float* gamma_b,
                           const float* beta_b, float eps_b, const void* w1, const float* b1, const void* w2,

@@ -299,3 +299,41 @@ def test_a_failed_call_is_reported_under_the_symbol_that_ran(monkeypatch):
     with pytest.raises(_lib.CggError, match=r'cgg_gemm_x3s_batched failed \(rc=-2\)'):
         ops.gemm_x3s(_rows(2, M, E), _x3_image(), E)
     assert ran == [len(_lib.PROTOTYPES['cgg_gemm_x3s_batched'][1])]
+
+
+# ---- the decoder tail's plane cap: refused by name, never summed short ---------------------------------------------------------------
+@pytest.mark.skipif(torch.cuda.is_available(), reason='hands host pointers to the entry: only where no launch can follow a missed check')
+def test_cgg_decoder_tail_refuses_more_planes_than_it_sums_without_a_launch():
+    """`cgg_decoder_tail_{bf16,x3}` hold DT_MAX_PLANES = 8 planes per row; nsum = 9 is CGG_EUNSUPPORTED with `nsum` in the message
+    (it was summed as 8), before any launch: there is no device here, and the pointers are host memory."""
+    lib = _lib.load()
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for fn in (lib.cgg_decoder_tail_bf16, lib.cgg_decoder_tail_x3):
+        def call(nsum, C=256):
+            return fn(p, nsum, 4 * 256, 256, p, p, 1e-5, p, 1, p, p, 1e-5, p, p, p, p, p, p, None, None, p, None, p, None, 4, C, None)
+        assert call(ops.DECODER_TAIL_MAX_PLANES + 1) == -2                     # CGG_EUNSUPPORTED
+        msg = lib.cgg_last_error_string()
+        assert b'nsum=%d' % (ops.DECODER_TAIL_MAX_PLANES + 1) in msg and b'decoder_tail' in msg, msg
+        assert b'at most %d are summed' % ops.DECODER_TAIL_MAX_PLANES in msg, msg        # DT_MAX_PLANES itself, by the C side's own word
+        assert call(16) == -2
+        assert call(0) == -1 and b'bad sizes' in lib.cgg_last_error_string()  # CGG_EINVAL, as before
+        assert call(8, C=128) == -2 and b'C=128' in lib.cgg_last_error_string()
+
+
+@pytest.mark.parametrize('width,planes,inside', [(2048, 8, True), (2304, 9, False), (1000, 1, True), (1100, 8, True)])
+def test_lean_decode_gate_looks_at_the_ffn_width(width, planes, inside):
+    """`Mask2FormerHeadOpen._lean_decode_ok`: the lean inference decode hands the FFN's planes to `ops.decoder_tail`, so it is taken
+    only while every layer produces at most DECODER_TAIL_MAX_PLANES of them: 2048 / 256 = 8 inside, 2304 / 256 = 9 outside; a width
+    that is no multiple of 256 goes through the split-K linear (1 or 8 planes)."""
+    import util
+    cfg = util.small_cfg()
+    tl = cfg['panoptic_head']['transformer_decoder']['transformerlayers']
+    tl['feedforward_channels'] = width
+    tl['ffn_cfgs']['feedforward_channels'] = width
+    prod, _ = util.build_heads(cfg)
+    layers = prod.transformer_decoder.layers
+    assert all(l.ffns[0].layers[0][0].weight.shape[0] == width and l.ffn_planes() == planes for l in layers)
+    assert prod._lean_decode_ok(256) == inside
+    prod.attn_mask_hook = lambda i, bits: bits
+    assert not prod._lean_decode_ok(256)

@@ -458,6 +458,62 @@ def test_grounding_gate(dev, Q, T, d, inside, monkeypatch):
     assert err <= 1e-4 * scale + 1e-9, (err, scale)
 
 
+def _decoder_ffn_head(dev, width):
+    import warnings
+    import util
+    cfg = util.small_cfg()
+    tl = cfg['panoptic_head']['transformer_decoder']['transformerlayers']
+    tl['feedforward_channels'] = width
+    tl['ffn_cfgs']['feedforward_channels'] = width
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        prod, _ = util.build_heads(cfg)
+    return prod.to(dev)
+
+
+@pytest.mark.parametrize('mode', ['bf16', 'fp32'])
+@pytest.mark.parametrize('width,inside', [(2048, True), (2304, False)])
+def test_lean_decode_gate_at_the_decoder_tail_plane_cap(dev, width, inside, mode, monkeypatch):
+    """`Mask2FormerHeadOpen._lean_decode_ok` at the plane cap of `ops.decoder_tail` (DECODER_TAIL_MAX_PLANES = 8 planes of 256 FFN
+    columns), in both precision modes. Inside (2048): the lean inference decode hands the FFN planes to `ops.decoder_tail`. Outside
+    (2304 = 9 planes, which the kernel used to sum as 8): `ops.decoder_tail` is not called, `ops.layernorm_chain` adds all 9, and
+    the inference outputs equal, bit for bit, those with `_lean_decode_ok` forced to False."""
+    from cgg_amd import synthetic
+    from cgg_amd.mask2former_head import Mask2FormerHeadOpen
+    prod = _decoder_ffn_head(dev, width)
+    B, H, W = 2, 64, 96
+    feats = [f.to(dev) for f in synthetic.backbone_feats(B, H, W, channels=(64, 128, 256, 512), seed=21)]
+    if mode == 'bf16':
+        feats = [f.bfloat16().contiguous(memory_format=torch.channels_last) for f in feats]
+    metas = synthetic.img_metas(B, H, W)
+    tail, chain = _Spy(monkeypatch, ops, 'decoder_tail'), _Spy(monkeypatch, ops, 'layernorm_chain')
+    assert prod._lean_decode_ok(256) == inside
+    with torch.no_grad(), runtime.precision_scope(mode):
+        got = prod._forward(feats, metas, all_masks=False)
+        planes = [a[0].shape[0] for a, _ in chain.calls if a[0].dim() == 3]
+        assert len(tail.calls) == (prod.num_transformer_decoder_layers - 1 if inside else 0)
+        assert planes == ([8] if inside else [9] * prod.num_transformer_decoder_layers), planes
+        monkeypatch.setattr(Mask2FormerHeadOpen, '_lean_decode_ok', lambda self, C: False)
+        want = prod._forward(feats, metas, all_masks=False)
+    for g, w in zip(got, want):
+        assert torch.isfinite(g[-1]).all()
+        if not inside:
+            assert torch.equal(g[-1], w[-1])
+
+
+@pytest.mark.parametrize('x3', [False, True], ids=['bf16', 'x3'])
+def test_decoder_tail_refuses_nine_planes(dev, x3):
+    pack = ops.pack_linear_weight_x3 if x3 else ops.pack_linear_weight
+    w = pack(torch.eye(256, device=dev))
+    v = torch.ones(256, device=dev)
+    norm = (v, v, 1e-5)
+    mlp = (w, v, w, v, w, v)
+    for nsum in (9, 16):
+        with pytest.raises(ops.CggError, match=f'nsum={nsum} planes .at most {ops.DECODER_TAIL_MAX_PLANES} '):
+            ops.decoder_tail(torch.zeros(nsum, 4, 256, device=dev), norm, torch.zeros(2, 256, device=dev), norm, mlp, (w, v))
+    assert ops.decoder_tail(torch.zeros(8, 4, 256, device=dev), norm, torch.zeros(2, 256, device=dev), norm, mlp, (w, v))[0].shape == (4, 256)
+
+
 # ------------------------------------------------------------------------------------------------
 # F. one operand on the CPU among device operands (the case the CPU suite cannot build)
 # ------------------------------------------------------------------------------------------------

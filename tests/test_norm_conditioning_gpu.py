@@ -23,6 +23,7 @@ import cgg_amd  # noqa: F401
 from cgg_amd import ops
 
 import norm_cases as NC
+from layer_cases import bf16_rounding as _bf16_rounding          # the rule lives with the layer cases now; unchanged
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +40,6 @@ def _cached(key, make):
 def _affine(C, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(C, generator=g), torch.randn(C, generator=g)
-
-
-def _bf16_rounding(want):
-    """half a bf16 ulp at |want| (0 at 0)"""
-    w = want.double().abs()
-    e = torch.floor(torch.log2(w.clamp_min(2.0 ** -126)))
-    return torch.where(w > 0, torch.exp2(e - 8), torch.zeros_like(w))
 
 
 def _interp(lo, size, dt):
