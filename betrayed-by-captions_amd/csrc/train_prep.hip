@@ -34,6 +34,10 @@
 // Panoptic samples (cgg_train_prep_panoptic_u8): the image kernel, then ONE kernel that gathers one id of the panoptic id map per output
 // pixel and derives every thing mask, the semantic plane and the statistics from it (stated at the kernel).
 //
+// Polygon samples (cgg_train_prep_polygons_u8): the image kernel, then a fill kernel that rasterises every instance's COCO polygons
+// into a column-major bit plane at source resolution (rule 6 of train_prep.py, stated at the kernel), then the plane kernel's body
+// over those bits instead of staged bytes.
+//
 // build-flags: -ffp-contract=off
 #include "cgg_common.h"
 
@@ -219,21 +223,25 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
   }
 }
 
-__global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
-                                                                    const int32_t* __restrict__ itable, uint8_t* __restrict__ masks,
-                                                                    uint8_t* __restrict__ seg, int32_t* __restrict__ stats, int N,
-                                                                    int H, int W, int ch, int cw, int seg_pad) {
-  __shared__ int red[4][5];
+// The plane kernel's body, over the reader of an instance's source pixels: BITS false = the staged row-major bytes (non-zero = set),
+// BITS true = the column-major bit plane the polygon fill kernel left in the workspace (plane z at word z * pw; pixel (r, c) of an
+// h x w source is bit c * h + r). Rule 3 and the statistics are this one piece of code for both.
+template <bool BITS>
+__device__ __forceinline__ void tp_plane_body(int (*red)[5], const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                              const int32_t* __restrict__ itable, const uint32_t* __restrict__ bits, int pw,
+                                              uint8_t* __restrict__ masks, uint8_t* __restrict__ seg, int32_t* __restrict__ stats,
+                                              int N, int H, int W, int ch, int cw, int seg_pad) {
   const int z = blockIdx.z;
-  const bool is_seg = z >= N;                                  // workgroup-uniform: planes N .. N + B - 1 are the semantic maps
+  const bool is_seg = !BITS && z >= N;                         // workgroup-uniform: planes N .. N + B - 1 are the semantic maps
   int b, moff = -1, mpitch = 0;
   if (is_seg) {
     b = z - N;
   } else {
     b = itable[TP_INST_COLS * z];
-    moff = itable[TP_INST_COLS * z + 1];
-    mpitch = itable[TP_INST_COLS * z + 2];
+    moff = BITS ? 0 : itable[TP_INST_COLS * z + 1];            // a polygon instance row: image index, first part, parts
+    mpitch = BITS ? 0 : itable[TP_INST_COLS * z + 2];
   }
+  const uint32_t* ib = BITS ? bits + (size_t)z * pw : nullptr;
   const int32_t* d = table + TP_IMG_COLS * b;
   const int h = d[1], w = d[2], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8];
   if (is_seg) {
@@ -267,14 +275,19 @@ __global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t
     const int y = y0 + 4 * wv + r;                             // wavefront-uniform
     if (y >= H) break;
     const bool yin = y < eh;
-    const int rowbase = yin ? moff + tp_nearest(y + oy, h, sy) * mpitch : 0;
+    const int rowbase = yin ? (BITS ? tp_nearest(y + oy, h, sy) : moff + tp_nearest(y + oy, h, sy) * mpitch) : 0;
     int v[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       v[c] = fill;
       if (yin && xl + c < ew) {
-        const int p = src[rowbase + rx[c]];
-        v[c] = is_seg ? p : (p != 0);
+        if (BITS) {
+          const uint32_t q = (uint32_t)rx[c] * (uint32_t)h + (uint32_t)rowbase;   // < h * w <= 2^31 - 32
+          v[c] = (int)((ib[q >> 5] >> (q & 31)) & 1u);
+        } else {
+          const int p = src[rowbase + rx[c]];
+          v[c] = is_seg ? p : (p != 0);
+        }
       }
     }
     if (!is_seg) {
@@ -338,6 +351,24 @@ __global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void cgg_train_prep_plane_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
+                                                                    const int32_t* __restrict__ itable, uint8_t* __restrict__ masks,
+                                                                    uint8_t* __restrict__ seg, int32_t* __restrict__ stats, int N,
+                                                                    int H, int W, int ch, int cw, int seg_pad) {
+  __shared__ int red[4][5];
+  tp_plane_body<false>(red, src, table, itable, nullptr, 0, masks, seg, stats, N, H, W, ch, cw, seg_pad);
+}
+
+// the same planes from the polygon fill kernel's bit planes (no semantic plane: polygon samples carry none)
+__global__ __launch_bounds__(256) void cgg_train_prep_plane_bits_kernel(const int32_t* __restrict__ table,
+                                                                         const int32_t* __restrict__ itable,
+                                                                         const uint32_t* __restrict__ bits, int pw,
+                                                                         uint8_t* __restrict__ masks, int32_t* __restrict__ stats, int N,
+                                                                         int H, int W, int ch, int cw) {
+  __shared__ int red[4][5];
+  tp_plane_body<true>(red, nullptr, table, itable, bits, pw, masks, nullptr, stats, N, H, W, ch, cw, 0);
 }
 
 // ---- panoptic samples: every plane from ONE gather of the id map -------------------------------------------------------------------
@@ -597,7 +628,7 @@ static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int
                 "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
                 (long long)first, (long long)(first + n), (long long)next, N);
     CGG_REQUIRE(!panoptic || soff == -1, CGG_EINVAL,
-                "%s: image %d: the semantic-map offset must be -1 (got %lld): the semantic plane comes from the id map", me, b,
+                "%s: image %d: the semantic-map offset must be -1 (got %lld): no semantic map is staged", me, b,
                 (long long)soff);
     CGG_REQUIRE(!seg || soff == -1 || (soff >= 0 && soff + h * w <= staged_bytes), CGG_EINVAL,
                 "%s: image %d: the semantic map at byte %lld extends past the %lld staged bytes", me, b, (long long)soff,
@@ -728,6 +759,325 @@ extern "C" int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_
     hipLaunchKernelGGL(cgg_train_prep_panoptic_kernel, dim3(gx, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, staged, table,
                        reinterpret_cast<const int32_t*>(staged + pan_table_offset),
                        reinterpret_cast<const int32_t*>(staged + seg_table_offset), masks, seg, stats, H, W, crop_h, crop_w, seg_pad);
+    CGG_CHECK_LAUNCH(me);
+  }
+  return CGG_OK;
+}
+
+// ---- polygon samples: the masks rasterised on the device (rule 6 of train_prep.py) ------------------------------------------------
+#define TP_POLY_INST_COLS 3 /* image index, first part, parts */
+#define TP_POLY_PART_COLS 2 /* byte offset of the part's 2 k float64 (a multiple of 8), vertex count k */
+#define PF_LDS_WORDS (CGG_POLY_LDS_BITS / 32)
+#define PF_SCAN_WORDS (CGG_POLY_SCAN_BITS / 32)
+static_assert(PF_SCAN_WORDS == 256, "one word per thread of the fill kernel's workgroup");
+
+// one edge of a part as rleFrPoly walks it: the start after the optional swap, the number of steps m = max(dx, dy), the slope
+struct PfEdge {
+  int xs, ys, m, flip, steep;
+  double s;
+};
+
+__device__ __forceinline__ int pf_vertex(double c) { return (int)(5.0 * c + 0.5); }   // product and sum rounded on their own
+
+__device__ __forceinline__ PfEdge pf_edge(const double* __restrict__ xy, int k, int j) {
+  const int j1 = j + 1 == k ? 0 : j + 1;
+  int xs = pf_vertex(xy[2 * j]), ys = pf_vertex(xy[2 * j + 1]), xe = pf_vertex(xy[2 * j1]), ye = pf_vertex(xy[2 * j1 + 1]);
+  const int dx = abs(xe - xs), dy = abs(ys - ye);
+  PfEdge e;
+  e.steep = dx < dy;
+  e.flip = e.steep ? ys > ye : xs > xe;
+  if (e.flip) {
+    int t = xs;
+    xs = xe;
+    xe = t;
+    t = ys;
+    ys = ye;
+    ye = t;
+  }
+  e.xs = xs;
+  e.ys = ys;
+  e.m = max(dx, dy);
+  e.s = e.m == 0 ? 0.0 : (e.steep ? (double)(xe - xs) / (double)dy : (double)(ye - ys) / (double)dx);
+  return e;
+}
+
+// point d (0 .. m) of an edge; an edge of one point (dx == dy == 0) is its vertex
+__device__ __forceinline__ void pf_point(const PfEdge& e, int d, int& u, int& v) {
+  const int t = e.flip ? e.m - d : d;
+  if (e.m == 0) {
+    u = e.xs;
+    v = e.ys;
+  } else if (!e.steep) {
+    u = t + e.xs;
+    v = (int)(((double)e.ys + e.s * (double)t) + 0.5);
+  } else {
+    v = t + e.ys;
+    u = (int)(((double)e.xs + e.s * (double)t) + 0.5);
+  }
+}
+
+// Fill kernel: one workgroup of 4 wavefronts per instance, the instance's parts in turn. Per part: (1) crossings -- wavefront wv
+// takes edges wv, wv + 4, ..., its lanes stride over the edge's points d; a point and its predecessor (d - 1, or the previous edge's
+// last point) are closed-form, and a change of column toggles bit a = xd * h + yd of the toggle plane (atomic XOR: LDS, or the
+// workspace for a plane of more than CGG_POLY_LDS_BITS pixels); (2) fill -- pixel p is set iff the number of crossings <= p is odd:
+// blocks of 256 words, one per thread; an inclusive prefix XOR inside the word by shift-XOR, the parity of the words before it in
+// the wavefront from one ballot, the wavefronts before it and the blocks before it through LDS; a set carry inverts the word. The
+// part's plane is OR-ed into the instance's (the first part stores: nothing is read that this workgroup did not write). Reading a
+// toggle word clears it for the next part. Every word of the bit plane is written, an instance without parts as zeros.
+__global__ __launch_bounds__(256) void cgg_poly_fill_kernel(const uint8_t* __restrict__ staged, const int32_t* __restrict__ table,
+                                                             const int32_t* __restrict__ itable, const int32_t* __restrict__ ptable,
+                                                             uint32_t* __restrict__ ws, int pw, int N, int force_ws) {
+  __shared__ uint32_t s_tog[PF_LDS_WORDS];
+  __shared__ int s_par[2][4];
+  const int z = blockIdx.x;
+  const int b = itable[TP_POLY_INST_COLS * z], p0 = itable[TP_POLY_INST_COLS * z + 1], parts = itable[TP_POLY_INST_COLS * z + 2];
+  const int h = table[TP_IMG_COLS * b + 1], w = table[TP_IMG_COLS * b + 2];
+  const int hw = h * w, nwords = (hw + 31) >> 5;               // hw <= 2^31 - 32, nwords <= pw
+  const bool glob = force_ws || hw > CGG_POLY_LDS_BITS;        // workgroup-uniform
+  uint32_t* out = ws + (size_t)z * pw;
+  uint32_t* gt = ws + ((size_t)N + z) * pw;                    // this instance's toggle plane on the workspace route
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+
+  for (int i = tid; i < nwords; i += 256) {
+    if (glob)
+      atomicExch(gt + i, 0u);
+    else
+      s_tog[i] = 0u;
+    if (parts == 0) out[i] = 0u;
+  }
+  __threadfence();
+  __syncthreads();
+
+#pragma unroll 1
+  for (int part = 0; part < parts; ++part) {
+    const int32_t* row = ptable + TP_POLY_PART_COLS * (p0 + part);
+    const double* xy = reinterpret_cast<const double*>(staged + row[0]);
+    const int k = row[1];
+    // ---- (1) crossings
+#pragma unroll 1
+    for (int j = wv; j < k; j += 4) {
+      const PfEdge e = pf_edge(xy, k, j);
+#pragma unroll 1
+      for (int d = lane; d <= e.m; d += 64) {
+        if (j == 0 && d == 0) continue;                        // the sequence's first point has no predecessor
+        int u0, v0, u1, v1;
+        pf_point(e, d, u1, v1);
+        if (d > 0) {
+          pf_point(e, d - 1, u0, v0);
+        } else {
+          const PfEdge q = pf_edge(xy, k, j - 1);
+          pf_point(q, q.m, u0, v0);
+        }
+        if (u1 == u0) continue;
+        const double xd = ((double)(u1 < u0 ? u1 : u1 - 1) + 0.5) / 5.0 - 0.5;
+        if (floor(xd) != xd || xd < 0.0 || xd > (double)(w - 1)) continue;
+        double yd = ((double)min(v0, v1) + 0.5) / 5.0 - 0.5;
+        yd = yd < 0.0 ? 0.0 : (yd > (double)h ? (double)h : yd);
+        const int a = (int)xd * h + (int)ceil(yd);             // <= h * w; a == h * w lies past the last pixel
+        if (a < hw) {
+          if (glob)
+            atomicXor(gt + (a >> 5), 1u << (a & 31));
+          else
+            atomicXor(&s_tog[a >> 5], 1u << (a & 31));
+        }
+      }
+    }
+    __threadfence();
+    __syncthreads();
+    // ---- (2) fill
+    int carry = 0, par = 0;                                    // workgroup-uniform
+#pragma unroll 1
+    for (int base = 0; base < nwords; base += PF_SCAN_WORDS) {
+      const int i = base + tid;
+      uint32_t x = 0u;
+      if (i < nwords) {
+        if (glob) {
+          x = atomicExch(gt + i, 0u);
+        } else {
+          x = s_tog[i];
+          s_tog[i] = 0u;
+        }
+      }
+      x ^= x << 1;
+      x ^= x << 2;
+      x ^= x << 4;
+      x ^= x << 8;
+      x ^= x << 16;
+      const unsigned long long m = __ballot((x >> 31) != 0u);  // bit 31 of the inclusive scan = the word's parity
+      if (lane == 0) s_par[par][wv] = __popcll(m) & 1;
+      __syncthreads();
+      // s_par[par] is written again two blocks on: a wavefront gets there only after the next barrier, which every wavefront
+      // reaches after it has read this one
+      int before = (__popcll(m & ((1ull << lane) - 1ull)) & 1) ^ carry;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int t = s_par[par][q];
+        if (q < wv) before ^= t;
+        carry ^= t;
+      }
+      if (before) x = ~x;
+      if (i < nwords) {
+        if (i == nwords - 1 && (hw & 31)) x &= (1u << (hw & 31)) - 1u;
+        out[i] = part ? (out[i] | x) : x;                      // word i is this thread's in every part
+      }
+      par ^= 1;
+    }
+    __threadfence();
+    __syncthreads();
+  }
+}
+
+// h, w, first instance, instances of the image rows, as the polygon entry points need them: sizes, and ranges that tile 0 .. N
+static int pf_validate_images(const char* me, const int32_t* img_table_host, int B, int N, int force_ws, int64_t* pw, int* any_ws) {
+  CGG_REQUIRE(img_table_host, CGG_EINVAL, "%s: null pointer (img_table_host)", me);
+  CGG_REQUIRE(B >= 1 && N >= 0, CGG_EINVAL, "%s: B must be >= 1 and N >= 0 (got %d, %d)", me, B, N);
+  CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && (int64_t)N + B <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+              "%s: B + N must be <= %d (got %d + %d)", me, CGG_IMAGE_PREP_MAX_DIM, B, N);
+  int64_t next = 0, words = 0;
+  int ws = 0;
+  for (int b = 0; b < B; ++b) {
+    const int32_t* d = img_table_host + TP_IMG_COLS * b;
+    const int64_t h = d[1], w = d[2], first = d[9], n = d[10];
+    CGG_REQUIRE(h >= 1 && w >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld)", me, b, (long long)h, (long long)w);
+    CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM && h * w <= (int64_t)INT32_MAX - 31, CGG_EUNSUPPORTED,
+                "%s: image %d is %lld x %lld: larger than %d on a side, or more than 2^31 - 32 pixels", me, b, (long long)h,
+                (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+    CGG_REQUIRE(n >= 0 && first == next && first + n <= N, CGG_EINVAL,
+                "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
+                (long long)first, (long long)(first + n), (long long)next, N);
+    if (n > 0) {
+      words = words > (h * w + 31) / 32 ? words : (h * w + 31) / 32;
+      if (h * w > CGG_POLY_LDS_BITS) ws = 1;
+    }
+    next = first + n;
+  }
+  CGG_REQUIRE(next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)next, N);
+  *pw = words;
+  *any_ws = (ws || force_ws) && N > 0;
+  return CGG_OK;
+}
+
+extern "C" int64_t cgg_train_prep_polygons_workspace_bytes(const int32_t* img_table_host, int B, int N, int force_workspace) {
+  int64_t pw = 0;
+  int any_ws = 0;
+  const int rc = pf_validate_images("cgg_train_prep_polygons_workspace_bytes", img_table_host, B, N, force_workspace, &pw, &any_ws);
+  if (rc != CGG_OK) return rc;
+  return (int64_t)N * pw * 4 * (any_ws ? 2 : 1);
+}
+
+// everything the fill kernel relies on, checked on the host: the tables, the coordinates, the workspace
+static int pf_validate(const char* me, const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                       int64_t part_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host,
+                       const int32_t* part_table_host, const uint8_t* staged_host, int B, int N, int P, const uint32_t* workspace,
+                       int64_t workspace_bytes, int force_ws, int64_t* pw_out) {
+  CGG_REQUIRE(staged && img_table_host && P >= 0 && (N <= 0 || (inst_table_host && workspace)) &&
+                  (P == 0 || (part_table_host && staged_host)),
+              CGG_EINVAL, "%s: null pointer (staged, img_table_host; inst_table_host, workspace with N = %d; part_table_host, "
+              "staged_host with P = %d)", me, N, P);
+  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
+              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
+  int64_t pw = 0;
+  int any_ws = 0;
+  const int rc = pf_validate_images(me, img_table_host, B, N, force_ws, &pw, &any_ws);
+  if (rc != CGG_OK) return rc;
+  const struct {
+    const char* name;
+    int64_t off, rows, cols;
+  } tabs[3] = {{"image", img_table_offset, B, TP_IMG_COLS},
+               {"instance", inst_table_offset, N, TP_POLY_INST_COLS},
+               {"part", part_table_offset, P, TP_POLY_PART_COLS}};
+  for (int t = 0; t < 3; ++t)
+    CGG_REQUIRE(tabs[t].off >= 0 && (tabs[t].off & 3) == 0 && tabs[t].off + tabs[t].rows * tabs[t].cols * 4 <= staged_bytes, CGG_EINVAL,
+                "%s: the %s table (%lld rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, tabs[t].name,
+                (long long)tabs[t].rows, (long long)tabs[t].off, (long long)staged_bytes);
+  CGG_REQUIRE((((uintptr_t)staged) & 7u) == 0 && (((uintptr_t)workspace) & 3u) == 0, CGG_EALIGN,
+              "%s: staged must be 8-byte and workspace 4-byte aligned", me);
+  int64_t next = 0;
+  for (int b = 0; b < B; ++b) {                                // every instance inside its image's range names that image
+    const int32_t* d = img_table_host + TP_IMG_COLS * b;
+    for (int64_t i = d[9]; i < (int64_t)d[9] + d[10]; ++i) {
+      const int32_t* t = inst_table_host + TP_POLY_INST_COLS * i;
+      const int64_t ib = t[0], first = t[1], n = t[2];
+      CGG_REQUIRE(ib == b, CGG_EINVAL, "%s: instance %lld belongs to image %lld but lies in image %d's range", me, (long long)i,
+                  (long long)ib, b);
+      CGG_REQUIRE(n >= 0 && first == next && first + n <= P, CGG_EINVAL,
+                  "%s: instance %lld: parts %lld .. %lld must follow the previous instance's (%lld) and stay below P = %d", me,
+                  (long long)i, (long long)first, (long long)(first + n), (long long)next, P);
+      next = first + n;
+    }
+  }
+  CGG_REQUIRE(next == P, CGG_EINVAL, "%s: the instances own %lld parts, P = %d", me, (long long)next, P);
+  for (int64_t p = 0; p < P; ++p) {
+    const int64_t off = part_table_host[TP_POLY_PART_COLS * p], k = part_table_host[TP_POLY_PART_COLS * p + 1];
+    CGG_REQUIRE(k >= 1, CGG_EINVAL, "%s: part %lld has %lld vertices (one or more expected)", me, (long long)p, (long long)k);
+    CGG_REQUIRE(off >= 0 && (off & 7) == 0, CGG_EINVAL, "%s: part %lld: byte offset %lld must be a non-negative multiple of 8", me,
+                (long long)p, (long long)off);
+    CGG_REQUIRE(off + 16 * k <= staged_bytes, CGG_EINVAL, "%s: part %lld (bytes %lld .. %lld) extends past the %lld staged bytes", me,
+                (long long)p, (long long)off, (long long)(off + 16 * k), (long long)staged_bytes);
+    for (int64_t c = 0; c < 2 * k; ++c) {
+      double v;
+      __builtin_memcpy(&v, staged_host + off + 8 * c, 8);
+      CGG_REQUIRE(v - v == 0.0, CGG_EINVAL, "%s: part %lld: coordinate %lld is not finite", me, (long long)p, (long long)c);
+      CGG_REQUIRE(fabs(v) <= (double)CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+                  "%s: part %lld: coordinate %lld is %g, beyond +-%d (the bound of the edge walk)", me, (long long)p, (long long)c, v,
+                  CGG_IMAGE_PREP_MAX_DIM);
+    }
+  }
+  const int64_t need = (int64_t)N * pw * 4 * (any_ws ? 2 : 1);
+  CGG_REQUIRE(workspace_bytes >= need, CGG_EUNSUPPORTED, "%s: the workspace holds %lld bytes, %lld are needed", me,
+              (long long)workspace_bytes, (long long)need);
+  *pw_out = pw;
+  return CGG_OK;
+}
+
+static int pf_launch(const char* me, const uint8_t* staged, int64_t img_table_offset, int64_t inst_table_offset, int64_t part_table_offset,
+                     int N, uint32_t* workspace, int pw, int force_ws, cgg_stream_t stream) {
+  if (N > 0) {
+    hipLaunchKernelGGL(cgg_poly_fill_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, staged,
+                       reinterpret_cast<const int32_t*>(staged + img_table_offset),
+                       reinterpret_cast<const int32_t*>(staged + inst_table_offset),
+                       reinterpret_cast<const int32_t*>(staged + part_table_offset), workspace, pw, N, force_ws ? 1 : 0);
+    CGG_CHECK_LAUNCH(me);
+  }
+  return CGG_OK;
+}
+
+extern "C" int cgg_polygon_fill_bits(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                                     int64_t part_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host,
+                                     const int32_t* part_table_host, const uint8_t* staged_host, int B, int N, int P,
+                                     uint32_t* workspace, int64_t workspace_bytes, int force_workspace, cgg_stream_t stream) {
+  const char* me = "cgg_polygon_fill_bits";
+  int64_t pw = 0;
+  const int rc = pf_validate(me, staged, staged_bytes, img_table_offset, inst_table_offset, part_table_offset, img_table_host,
+                             inst_table_host, part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, &pw);
+  if (rc != CGG_OK) return rc;
+  return pf_launch(me, staged, img_table_offset, inst_table_offset, part_table_offset, N, workspace, (int)pw, force_workspace, stream);
+}
+
+extern "C" int cgg_train_prep_polygons_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset,
+                                          int64_t inst_table_offset, int64_t part_table_offset, const int32_t* img_table_host,
+                                          const int32_t* inst_table_host, const int32_t* part_table_host, const uint8_t* staged_host,
+                                          int B, int N, int P, const float* mean, const float* std_, const float* pad_val, int to_rgb,
+                                          int crop_h, int crop_w, float* img, uint8_t* masks, int32_t* stats, int H, int W,
+                                          uint32_t* workspace, int64_t workspace_bytes, int force_workspace, cgg_stream_t stream) {
+  const char* me = "cgg_train_prep_polygons_u8";
+  int rc = tp_validate(me, true, staged, staged_bytes, img_table_offset, 0, img_table_host, nullptr, B, N, mean, std_, pad_val, 0, crop_h,
+                       crop_w, img, masks, nullptr, stats, H, W);
+  if (rc != CGG_OK) return rc;
+  int64_t pw = 0;
+  rc = pf_validate(me, staged, staged_bytes, img_table_offset, inst_table_offset, part_table_offset, img_table_host, inst_table_host,
+                   part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, &pw);
+  if (rc != CGG_OK) return rc;
+  const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
+  rc = tp_launch_image(me, staged, table, B, mean, std_, pad_val, to_rgb, crop_h, crop_w, img, stats, H, W, stream);
+  if (rc != CGG_OK) return rc;
+  rc = pf_launch(me, staged, img_table_offset, inst_table_offset, part_table_offset, N, workspace, (int)pw, force_workspace, stream);
+  if (rc != CGG_OK) return rc;
+  if (N > 0) {
+    const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
+    hipLaunchKernelGGL(cgg_train_prep_plane_bits_kernel, dim3(gx, gy, (unsigned)N), dim3(256), 0, (hipStream_t)stream, table,
+                       reinterpret_cast<const int32_t*>(staged + inst_table_offset), workspace, (int)pw, masks, stats, N, H, W, crop_h,
+                       crop_w);
     CGG_CHECK_LAUNCH(me);
   }
   return CGG_OK;

@@ -2707,6 +2707,121 @@ def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, 
     return img, masks, seg, stats
 
 
+TRAIN_PREP_POLY_INST_COLS = 3  # image index, first part, parts
+TRAIN_PREP_POLY_PART_COLS = 2  # byte offset of the part's float64 coordinates (a multiple of 8), vertex count
+TRAIN_PREP_MAX_COORD = CONSTANTS['CGG_IMAGE_PREP_MAX_DIM']      # |coordinate| of a polygon vertex: it bounds the edge walk
+POLY_LDS_BITS = CONSTANTS['CGG_POLY_LDS_BITS']                  # a plane of more pixels keeps its toggle plane in the workspace
+POLY_SCAN_BITS = CONSTANTS['CGG_POLY_SCAN_BITS']                # pixels of one scan block of the fill kernel
+
+
+def _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace):
+    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
+        raise CggError(f'{me}: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
+    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_POLY_INST_COLS),
+                          ('part_table', part_table, TRAIN_PREP_POLY_PART_COLS)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
+            raise CggError(f'{me}: {name} must be a (rows, {cols}) torch.int32 tensor '
+                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
+        if t.is_cuda or not t.is_contiguous():
+            raise CggError(f'{me}: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
+    if not torch.is_tensor(staged_host) or staged_host.dtype != torch.uint8 or staged_host.dim() != 1 or staged_host.is_cuda:
+        raise CggError(f'{me}: staged_host must be a 1-D torch.uint8 HOST tensor, the copy of the staged bytes')
+    if not torch.is_tensor(workspace) or workspace.dtype != torch.int32 or workspace.dim() != 1:
+        raise CggError(f'{me}: workspace must be a 1-D torch.int32 tensor (got {getattr(workspace, "dtype", type(workspace))})')
+    if workspace.device != staged.device:
+        raise CggError(f'{me}: workspace ({workspace.device}) and staged ({staged.device}) live on different devices')
+    if int(img_table.shape[0]) < 1:
+        raise CggError(f'{me}: an empty batch')
+    return int(img_table.shape[0]), int(inst_table.shape[0]), int(part_table.shape[0])
+
+
+def train_prep_polygons_workspace_bytes(img_table, N, force_workspace=False):
+    """bytes of workspace `train_prep_polygons_u8` / `polygon_fill_bits` need for these (B, 12) HOST image rows and N instances"""
+    if not torch.is_tensor(img_table) or img_table.dtype != torch.int32 or img_table.dim() != 2 or img_table.shape[1] != TRAIN_PREP_IMG_COLS:
+        raise CggError(f'train_prep_polygons_workspace_bytes: img_table must be a (B, {TRAIN_PREP_IMG_COLS}) torch.int32 HOST tensor')
+    return int(_call('cgg_train_prep_polygons_workspace_bytes', host_ptr(img_table, 'img_table', torch.int32), int(img_table.shape[0]),
+                     int(N), int(bool(force_workspace)), total=True))
+
+
+def polygon_fill_bits(staged, img_table, inst_table, part_table, staged_host, workspace, img_table_offset=0, inst_table_offset=None,
+                      part_table_offset=None, staged_bytes=None, force_workspace=False):
+    """The polygon fill kernel alone (`cgg_polygon_fill_bits`, one launch, no synchronisation): every instance's parts -> its
+    column-major bit plane at source resolution, plane i at word i * plane_words of `workspace` (rule 6 of train_prep.py). Arguments
+    as for `train_prep_polygons_u8`; of an image row only h, w, first instance, instances are used. force_workspace (tests): toggle
+    planes in the workspace whatever their size. Returns (workspace, plane_words); `polygon_bits_to_mask` unpacks a plane."""
+    me = 'polygon_fill_bits'
+    B, N, P = _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace)
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if nbytes > staged.numel() or nbytes > staged_host.numel():
+        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the bytes of staged ({staged.numel()}) or staged_host ({staged_host.numel()})')
+    if inst_table_offset is None:
+        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
+    if part_table_offset is None:
+        part_table_offset = int(inst_table_offset) + 4 * TRAIN_PREP_POLY_INST_COLS * N
+    with _timed(me, bytes=float(nbytes), shape=(B, N, P)):
+        _call('cgg_polygon_fill_bits', dev_ptr(staged, f'{me}: staged'), nbytes, int(img_table_offset), int(inst_table_offset),
+              int(part_table_offset), host_ptr(img_table, 'img_table', torch.int32),
+              host_ptr(inst_table, 'inst_table', torch.int32) if N else None,
+              host_ptr(part_table, 'part_table', torch.int32) if P else None, host_ptr(staged_host, 'staged_host', torch.uint8), B, N,
+              P, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(), int(bool(force_workspace)),
+              stream_ptr(staged.device))
+    hw = [int(r[1]) * int(r[2]) for r in img_table.tolist() if r[10] > 0]
+    return workspace, (max(hw) + 31) // 32 if hw else 0
+
+
+def polygon_bits_to_mask(workspace, plane_words, i, h, w):
+    """plane i of `polygon_fill_bits`' workspace as an (h, w) uint8 tensor on its device (torch ops; test-facing)"""
+    words = workspace[i * plane_words:i * plane_words + (h * w + 31) // 32]
+    bits = (words.view(-1, 1) >> torch.arange(32, device=workspace.device, dtype=torch.int32)) & 1
+    return bits.reshape(-1)[:h * w].to(torch.uint8).view(w, h).t().contiguous()
+
+
+def train_prep_polygons_u8(staged, img_table, inst_table, part_table, staged_host, img, masks, stats, workspace, mean, std, pad_val=0.0,
+                           to_rgb=True, crop_size=None, img_table_offset=0, inst_table_offset=None, part_table_offset=None,
+                           staged_bytes=None, force_workspace=False):
+    """`train_prep_u8` for instance samples whose masks are COCO polygons, rasterised on the device (`cgg_train_prep_polygons_u8`:
+    image kernel, polygon fill kernel, plane kernel over the bit planes; no synchronisation; train_prep.py states the rule, rule 6
+    for the raster). staged: DEVICE uint8 (n,) -- the three tables at bytes `img_table_offset` / `inst_table_offset` /
+    `part_table_offset` (by default back to back), the images and the float64 coordinates; img_table (B, 12) with -1 for the
+    semantic-map offset, inst_table (N, 3) = image index, first part, parts, part_table (P, 2) = byte offset (a multiple of 8),
+    vertices: HOST int32 copies; staged_host: HOST uint8 copy of the staged bytes (the coordinates are validated from it); img
+    (B, 3, H, W) f32, masks (N, H, W) u8, stats (N, 5) i32, workspace 1-D int32 of `train_prep_polygons_workspace_bytes` or more:
+    DEVICE, contiguous; the caller clears nothing. Returns (img, masks, stats)."""
+    me = 'train_prep_polygons_u8'
+    B, N, P = _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace)
+    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
+        raise CggError(f'{me}: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
+                       f'shape {tuple(getattr(img, "shape", ()))})')
+    H, W = int(img.shape[2]), int(img.shape[3])
+    for name, t, shape, dt in (('masks', masks, (N, H, W), torch.uint8), ('stats', stats, (N, 5), torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise CggError(f'{me}: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
+                           f'shape {tuple(getattr(t, "shape", ()))})')
+        if t.device != img.device:
+            raise CggError(f'{me}: {name} ({t.device}) and img ({img.device}) live on different devices')
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if nbytes > staged.numel() or nbytes > staged_host.numel():
+        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the bytes of staged ({staged.numel()}) or staged_host ({staged_host.numel()})')
+    sp, ip = dev_ptr(staged, f'{me}: staged'), dev_ptr(img, f'{me}: img')
+    if staged.device != img.device:
+        raise CggError(f'{me}: staged ({staged.device}) and img ({img.device}) live on different devices')
+    mp = dev_ptr(masks, f'{me}: masks') if N else None
+    tp = dev_ptr(stats, f'{me}: stats') if N else None
+    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'{me}: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
+    if inst_table_offset is None:
+        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
+    if part_table_offset is None:
+        part_table_offset = int(inst_table_offset) + 4 * TRAIN_PREP_POLY_INST_COLS * N
+    with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W), shape=(B, N, H, W)):
+        _call('cgg_train_prep_polygons_u8', sp, nbytes, int(img_table_offset), int(inst_table_offset), int(part_table_offset),
+              host_ptr(img_table, 'img_table', torch.int32), host_ptr(inst_table, 'inst_table', torch.int32) if N else None,
+              host_ptr(part_table, 'part_table', torch.int32) if P else None, host_ptr(staged_host, 'staged_host', torch.uint8), B, N,
+              P, m, s, p, int(bool(to_rgb)), ch, cw, ip, mp, tp, H, W, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(),
+              int(bool(force_workspace)), stream_ptr(img.device))
+    return img, masks, stats
+
+
 # ------------------------------------------------------------------------------------------------
 # caption search: one beam-search step for a whole batch, decided on the device (caption_search.py states the rule)
 # ------------------------------------------------------------------------------------------------

@@ -260,3 +260,52 @@ def panoptic_samples(hw, num_things, num_stuff, seed=0, vocab=30522, blocks=(4, 
     while True:
         yield panoptic_sample(hw, num_things, num_stuff, seed=seed + i, vocab=vocab, blocks=blocks)
         i += 1
+
+
+def _star_polygon(r, cy, cx, ry, rx, k):
+    """a flat x0, y0, x1, y1, ... star-shaped polygon of k vertices around (cx, cy), radii jittered, coordinates with fractions"""
+    ang = np.sort(r.uniform(0.0, 2.0 * np.pi, size=k))
+    rad = r.uniform(0.55, 1.0, size=k)
+    xy = np.stack([cx + rx * rad * np.cos(ang), cy + ry * rad * np.sin(ang)], axis=1)
+    return np.round(xy, 2).reshape(-1).tolist()
+
+
+def polygon_sample(hw, num_classes, seed=0, vocab=30522, extra=4, vertices=(6, 40)):
+    """One RAW polygon sample as the dataset holds it before LoadOpenAnnotations(poly2mask=True) (train_prep.py, rule 6): a uint8 BGR
+    image, `gt_polygons` = `ann_info['masks']` (per instance a list of parts, per part a flat x0, y0, x1, y1, ... list), `gt_labels`
+    and the caption fields. The instances, in this order (`POLYGON_KINDS` names the first four): one of three parts; one that lies
+    partly outside the image; one with a degenerate two-vertex part next to a proper one; one wholly outside the image, which no
+    crop keeps; then `extra` star-shaped instances of 1 to 3 parts."""
+    h, w = int(hw[0]), int(hw[1])
+    r = np.random.default_rng(seed)
+
+    def star(cy, cx, ry, rx):
+        return _star_polygon(r, cy, cx, max(ry, 1.0), max(rx, 1.0), int(r.integers(vertices[0], vertices[1] + 1)))
+
+    polys = [
+        [star(r.uniform(0.2, 0.8) * h, r.uniform(0.2, 0.8) * w, 0.15 * h, 0.15 * w) for _ in range(3)],
+        [star(r.uniform(0.3, 0.7) * h, w - 1.0, 0.3 * h, 0.3 * w)],
+        [star(0.5 * h, 0.5 * w, 0.2 * h, 0.2 * w), [round(0.1 * w, 2), round(0.1 * h, 2), round(0.6 * w, 2), round(0.7 * h, 2)]],
+        [star(0.5 * h, w + 0.4 * w + 8.0, 0.2 * h, 0.2 * w)],
+    ]
+    for _ in range(extra):
+        polys.append([star(r.uniform(0.0, 1.0) * h, r.uniform(0.0, 1.0) * w, r.uniform(0.03, 0.3) * h, r.uniform(0.03, 0.3) * w)
+                      for _ in range(int(r.integers(1, 4)))])
+    labels = r.integers(0, max(num_classes, 1), size=len(polys)).astype(np.int64)
+    cap = train_batch(1, 8, 8, num_classes=max(num_classes, 1), max_inst=1, vocab=vocab, seed=seed)
+    out = dict(img=r.integers(0, 256, size=(h, w, 3), dtype=np.uint8), gt_polygons=polys, gt_labels=labels,
+               filename=f'synthetic_polygons_{seed}.jpg', ori_filename=f'synthetic_polygons_{seed}.jpg')
+    for k in ('gt_caption_ids', 'gt_caption_mask', 'gt_caption_nouns_ids', 'gt_caption_nouns_mask'):
+        out[k] = cap[k][0].numpy()
+    return out
+
+
+POLYGON_KINDS = ('multi_part', 'partly_outside', 'two_vertex_part', 'never_kept')   # instances 0 .. 3 of every `polygon_sample`
+
+
+def polygon_samples(hw, num_classes, seed=0, vocab=30522, extra=4, vertices=(6, 40)):
+    """Endless seeded stream of `polygon_sample`s."""
+    i = 0
+    while True:
+        yield polygon_sample(hw, num_classes, seed=seed + i, vocab=vocab, extra=extra, vertices=vertices)
+        i += 1

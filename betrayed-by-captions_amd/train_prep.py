@@ -37,8 +37,9 @@ This restates the [3P] steps (mmdet RandomFlip / Resize / RandomCrop / FilterAnn
 imrescale bilinear on float32 / nearest for masks) from their published behaviour. mmdet, mmcv and cv2 are not available offline,
 so equality with a particular build is NOT claimed; what is pinned is this rule (tests/test_train_prep.py). Nor is equality claimed
 with mmdet's use of the global `np.random` stream: the random decisions are drawn by `draw_train_params` in a documented order and
-are an argument of the rule, so a caller may supply its own. PhotoMetricDistortion, multi-scale value lists and polygon masks are
-not restated and are refused by name.
+are an argument of the rule, so a caller may supply its own. PhotoMetricDistortion and multi-scale value lists are not restated and
+are refused by name; so is poly2mask=False (polygon-form gt_masks through the pipeline). Polygons that the loader rasterises
+(poly2mask=True, the reference's setting) are rule 6 below.
 
 PANOPTIC SAMPLES. The panoptic configs start from `LoadOpenPanopticAnnotations(with_mask=True, with_seg=True)`, which turns the
 panoptic PNG into one bitmap per thing and a semantic map on the host (open_set/datasets/pipelines/loading.py:317-341). A raw
@@ -54,6 +55,33 @@ is_thing) and `gt_labels`, one per record with is_thing true. `load_panoptic_hos
 gather, which commutes with "compare the id": (pan[ry, rx] == id) is the resized bitmap and category_of(pan[ry, rx]) the resized
 semantic map, so `TrainPrep` stages the id map (3 or 4 bytes per pixel, against 1 + n_things bytes for the planes) and a table of
 the records, and one gather per output pixel yields every plane, bit for bit. With with_seg=False only the thing planes are made.
+
+POLYGON SAMPLES. The instance configs start from `LoadOpenAnnotations(with_mask=True, poly2mask=True)`: the dataset hands over the raw
+`segmentation` lists and the loader rasterises them on the host with pycocotools (`frPyObjects` -> `merge` -> `decode`,
+open_set/datasets/pipelines/loading.py:105-129). A raw polygon sample carries the lists themselves: `gt_polygons`, a list over
+instances of lists over parts of flat x0, y0, x1, y1, ... sequences (`ann_info['masks']`), and `gt_labels`, one per instance.
+`polygon_mask_host(parts, h, w)` is the loader's rule, restated from the published maskApi.c (rleFrPoly):
+
+6. per part with k vertices, in double precision, every product and sum rounded on its own (no fused multiply-add), (int) = C
+   truncation: X[j] = (int)(5 x_j + 0.5), Y[j] likewise, vertex k = vertex 0. Edge j with dx = |X[j+1] - X[j]|, dy = |Y[j] - Y[j+1]|:
+   flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye) swaps its ends; s = (ye - ys) / dx if dx >= dy else (xe - xs) / dy; its
+   points are d = 0 .. max(dx, dy) with t = max - d under flip, else d: (u, v) = (t + xs, (int)(ys + s t + 0.5)), x and y exchanged when
+   dx < dy; dx == dy == 0 gives the one point (xs, ys). All edges' points form one sequence. Every point i >= 1 with u[i] != u[i-1]
+   is a crossing when xd = ((u[i] if u[i] < u[i-1] else u[i] - 1) + 0.5) / 5 - 0.5 is an integer in [0, w - 1]: with yd =
+   ceil(clamp((min(v[i], v[i-1]) + 0.5) / 5 - 0.5, 0, h)) it lies at the COLUMN-MAJOR index a = xd h + yd (yd == h is legal: row 0 of
+   the next column). Pixel p = x h + y is set iff the number of crossings <= p is odd -- ONE prefix parity over the whole plane,
+   carried across columns (crossings per column are not always even in number). `_polygon_mask_literal` spells the same out as
+   rleFrPoly does: sorted crossings, h w appended, differences, zero-length runs merged, runs alternating 0, 1. An instance is the OR
+   of its parts (`merge`, intersect = 0); one without parts is empty and falls to "area >= 1".
+
+pycocotools is not available offline, so equality with a particular build is NOT claimed; what is pinned is this rule
+(tests/test_train_prep_polygons.py holds the two forms equal). `prepare_train_host` of polygon samples is DEFINED as
+`prepare_train_host` of the bitmap samples rule 6 makes (`polygons_to_bitmap_sample`). `TrainPrep` stages the coordinates as float64
+(a few hundred bytes per instance against h w) and three small tables; `cgg_train_prep_polygons_u8` rasterises every instance into a
+column-major bit plane at source resolution (crossings as atomic XORs into a toggle plane, then a prefix XOR), and the plane kernel
+of the bitmap route gathers from those bits: rule 3 and rule 4 are the same code. Refused by name: an RLE dict (a crowd; the
+reference dataset sends those to bboxes_ignore), an odd coordinate count, an empty part, non-finite coordinates, |coordinate| >
+CGG_IMAGE_PREP_MAX_DIM (it bounds the edge walk), gt_masks next to gt_polygons, a pipeline with with_seg.
 """
 from dataclasses import dataclass
 from typing import NamedTuple, Tuple
@@ -63,8 +91,8 @@ import torch
 
 from ._lib import CggError
 from .image_prep import ImagePrep, PrepSpec, _as_hwc_u8, norm_constants, rescale_size
-from .ops import (TRAIN_PREP_IMG_COLS, TRAIN_PREP_INST_COLS, TRAIN_PREP_MAX_SEGMENTS, TRAIN_PREP_PAN_COLS, TRAIN_PREP_SEG_COLS,
-                  three_floats)
+from .ops import (TRAIN_PREP_IMG_COLS, TRAIN_PREP_INST_COLS, TRAIN_PREP_MAX_SEGMENTS, TRAIN_PREP_PAN_COLS, TRAIN_PREP_POLY_INST_COLS,
+                  TRAIN_PREP_POLY_PART_COLS, TRAIN_PREP_SEG_COLS, three_floats)
 
 CAPTION_FIELDS = ('gt_caption_ids', 'gt_caption_mask', 'gt_caption_nouns_ids', 'gt_caption_nouns_mask')
 
@@ -129,7 +157,7 @@ def parse_train_pipeline(pipeline):
                 raise _unsupported(t, 'to_float32 is missing or false (the 8-bit resize is the test pipeline\'s rule, image_prep.py)')
         elif t in _ANNOTATIONS:
             if step.get('poly2mask', True) is False:
-                raise _unsupported(t, 'poly2mask=False (polygon masks are out of scope)')
+                raise _unsupported(t, 'poly2mask=False (polygons are rasterised, rule 6: polygon-form gt_masks are out of scope)')
             if not step.get('with_mask', t != 'LoadAnnotations'):
                 raise _unsupported(t, 'with_mask=False' + (' (the thing masks are what the panoptic rule yields)' if 'Panoptic' in t else ''))
             # the panoptic loaders' with_mask_based_bbox (either value) and with_seg=False are accepted: neither makes the result differ
@@ -302,7 +330,7 @@ def _check_sample(s, spec):
         masks = masks.view(np.uint8)
     if masks.dtype != np.uint8 or masks.ndim != 3 or (masks.shape[0] and masks.shape[1:] != (h, w)):
         raise CggError(f'train_prep: gt_masks must be (n, {h}, {w}) uint8 or bool bitmaps (got {masks.dtype}, shape {masks.shape}; '
-                       'polygon masks are out of scope)')
+                       'polygons go in gt_polygons, rule 6)')
     labels = s.get('gt_labels')
     labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
     if labels.shape != (masks.shape[0],):
@@ -421,6 +449,218 @@ def panoptic_to_bitmap_sample(s):
     return out
 
 
+# ---- rule 6: COCO polygons -> bitmaps ---------------------------------------------------------------------------------------------
+POLY_SCALE = 5                                               # rleFrPoly walks the outline on a grid of 1 / 5 pixel
+
+
+def _as_part(part):
+    """one part as a float64 array x0, y0, x1, y1, ... (no checks: `_check_polygons` is the checked door)"""
+    return np.asarray(part, dtype=np.float64).reshape(-1)
+
+
+def _polygon_mask_literal(parts, h, w):
+    """Rule 6 in its LITERAL form, plain loops over Python floats (IEEE doubles, every operation rounded on its own; int() truncates
+    toward zero like a C cast): per part the vertices, the edge walk, the crossings, then the sorted crossings as run lengths with
+    zero-length runs merged as rleFrPoly does, decoded column-major; the parts OR-ed (`merge` with intersect = 0). Test-facing: it is
+    what `polygon_mask_host` is held equal to."""
+    h, w = int(h), int(w)
+    out = np.zeros(h * w, dtype=np.uint8)
+    for part in parts:
+        xy = [float(c) for c in _as_part(part)]
+        k = len(xy) // 2
+        X = [int(POLY_SCALE * xy[2 * j] + 0.5) for j in range(k)]
+        Y = [int(POLY_SCALE * xy[2 * j + 1] + 0.5) for j in range(k)]
+        X.append(X[0])
+        Y.append(Y[0])
+        u, v = [], []
+        for j in range(k):
+            xs, xe, ys, ye = X[j], X[j + 1], Y[j], Y[j + 1]
+            dx, dy = abs(xe - xs), abs(ys - ye)
+            flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+            if flip:
+                xs, xe, ys, ye = xe, xs, ye, ys
+            if dx == 0 and dy == 0:                          # one point; the slope 0 / 0 is never used
+                u.append(xs)
+                v.append(ys)
+            elif dx >= dy:
+                s = float(ye - ys) / dx
+                for d in range(dx + 1):
+                    t = dx - d if flip else d
+                    u.append(t + xs)
+                    v.append(int(ys + s * t + 0.5))
+            else:
+                s = float(xe - xs) / dy
+                for d in range(dy + 1):
+                    t = dy - d if flip else d
+                    v.append(t + ys)
+                    u.append(int(xs + s * t + 0.5))
+        a = []
+        for i in range(1, len(u)):
+            if u[i] == u[i - 1]:
+                continue
+            xd = float(u[i] if u[i] < u[i - 1] else u[i] - 1)
+            xd = (xd + 0.5) / POLY_SCALE - 0.5
+            if np.floor(xd) != xd or xd < 0 or xd > w - 1:
+                continue
+            yd = float(min(v[i], v[i - 1]))
+            yd = (yd + 0.5) / POLY_SCALE - 0.5
+            yd = 0.0 if yd < 0 else float(h) if yd > h else yd
+            a.append(int(xd) * h + int(np.ceil(yd)))
+        a.sort()
+        a.append(h * w)
+        p = 0
+        for j in range(len(a)):                              # differences
+            a[j], p = a[j] - p, a[j]
+        runs = [a[0]]
+        j = 1
+        while j < len(a):                                    # zero-length runs merge their neighbours
+            if a[j] > 0:
+                runs.append(a[j])
+                j += 1
+            else:
+                j += 1
+                if j < len(a):
+                    runs[-1] += a[j]
+                    j += 1
+        pos, val = 0, 0
+        for r in runs:                                       # the runs alternate 0, 1, ... over the column-major pixels
+            if val:
+                out[pos:pos + r] = 1
+            pos += r
+            val ^= 1
+    return np.ascontiguousarray(out.reshape(w, h).T)
+
+
+def _part_crossings(part, h, w):
+    """steps 1 to 3 of rule 6 for one part, vectorised per edge: the column-major indices of its crossings (int64, unsorted)"""
+    xy = _as_part(part)
+    X = (POLY_SCALE * xy[0::2] + 0.5).astype(np.int64)       # the cast truncates toward zero
+    Y = (POLY_SCALE * xy[1::2] + 0.5).astype(np.int64)
+    k = X.size
+    us, vs = [], []
+    for j in range(k):
+        xs, xe, ys, ye = int(X[j]), int(X[(j + 1) % k]), int(Y[j]), int(Y[(j + 1) % k])
+        dx, dy = abs(xe - xs), abs(ys - ye)
+        flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+        if flip:
+            xs, xe, ys, ye = xe, xs, ye, ys
+        m = max(dx, dy)
+        if m == 0:
+            us.append(np.array([xs], dtype=np.int64))
+            vs.append(np.array([ys], dtype=np.int64))
+            continue
+        t = np.arange(m, -1, -1, dtype=np.int64) if flip else np.arange(m + 1, dtype=np.int64)
+        tf = t.astype(np.float64)
+        if dx >= dy:
+            s = np.float64(ye - ys) / np.float64(dx)
+            us.append(t + xs)
+            vs.append(((np.float64(ys) + s * tf) + 0.5).astype(np.int64))
+        else:
+            s = np.float64(xe - xs) / np.float64(dy)
+            vs.append(t + ys)
+            us.append(((np.float64(xs) + s * tf) + 0.5).astype(np.int64))
+    u, v = np.concatenate(us), np.concatenate(vs)
+    u0, u1, v0, v1 = u[:-1], u[1:], v[:-1], v[1:]
+    xd = (np.where(u1 < u0, u1, u1 - 1).astype(np.float64) + 0.5) / POLY_SCALE - 0.5
+    ok = (u1 != u0) & (np.floor(xd) == xd) & (xd >= 0) & (xd <= w - 1)
+    yd = (np.minimum(v0, v1).astype(np.float64) + 0.5) / POLY_SCALE - 0.5
+    yd = np.ceil(np.clip(yd, 0.0, float(h)))
+    return xd[ok].astype(np.int64) * h + yd[ok].astype(np.int64)
+
+
+def polygon_mask_host(parts, h, w):
+    """Rule 6: the (h, w) uint8 bitmap of one instance given as a list of polygons (`parts`, each a flat x0, y0, x1, y1, ...
+    sequence) -- what pycocotools' `frPyObjects` -> `merge` -> `decode` is published to yield, restated from maskApi.c (rleFrPoly):
+    vertices on a grid of 1 / 5 pixel, the outline walked point by point, a crossing at every change of column, and a pixel set iff
+    the number of crossings at or before its column-major index is odd (one prefix parity over the whole plane: it does not restart
+    at a column); the parts OR-ed. This is the PARITY form, the one csrc/train_prep.hip computes; `_polygon_mask_literal` is the
+    run-length form the C code spells out, and tests/test_train_prep_polygons.py holds the two equal. pycocotools is not available
+    offline, so equality with a particular build is NOT claimed; what is pinned is this rule. No input checks here."""
+    h, w = int(h), int(w)
+    out = np.zeros((h, w), dtype=np.uint8)
+    for part in parts:
+        a = _part_crossings(part, h, w)
+        tog = np.bincount(a, minlength=h * w + 1)[:h * w] & 1        # a == h * w lies past the last pixel
+        out |= (np.cumsum(tog) & 1).astype(np.uint8).reshape(w, h).T
+    return out
+
+
+def _check_polygons(polys, where='gt_polygons'):
+    """`ann_info['masks']` of one image -> [[float64 array per part] per instance]; anything outside rule 6 raises naming it"""
+    from .ops import TRAIN_PREP_MAX_COORD
+    if polys is None or isinstance(polys, (str, bytes, dict)) or not hasattr(polys, '__iter__'):
+        raise CggError(f"train_prep: {where} must be a list over instances of lists of polygons (ann_info['masks'])")
+    out = []
+    for i, inst in enumerate(polys):
+        if isinstance(inst, dict):
+            raise CggError(f'train_prep: {where}[{i}] is an RLE dict segmentation (a crowd; the dataset sends those to bboxes_ignore): '
+                           'only polygon lists are rasterised')
+        if isinstance(inst, (str, bytes)) or not hasattr(inst, '__iter__'):
+            raise CggError(f'train_prep: {where}[{i}] must be a list of polygons (got {type(inst).__name__})')
+        parts = []
+        for j, part in enumerate(inst):
+            try:
+                xy = np.asarray(part, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise CggError(f'train_prep: {where}[{i}][{j}] must be a flat sequence of numbers x0, y0, x1, y1, ...') from None
+            if xy.ndim != 1:
+                raise CggError(f'train_prep: {where}[{i}][{j}] must be a flat sequence x0, y0, x1, y1, ... (got shape {xy.shape})')
+            if xy.size == 0:
+                raise CggError(f'train_prep: {where}[{i}][{j}] is an empty part')
+            if xy.size % 2:
+                raise CggError(f'train_prep: {where}[{i}][{j}] has an odd coordinate count ({xy.size})')
+            if not np.isfinite(xy).all():
+                raise CggError(f'train_prep: {where}[{i}][{j}] holds non-finite coordinates')
+            if np.abs(xy).max() > TRAIN_PREP_MAX_COORD:
+                raise CggError(f'train_prep: {where}[{i}][{j}] holds a coordinate beyond +-{TRAIN_PREP_MAX_COORD} '
+                               f'({xy[np.abs(xy).argmax()]!r}); CGG_IMAGE_PREP_MAX_DIM bounds the edge walk')
+            parts.append(np.ascontiguousarray(xy))
+        out.append(parts)
+    return out
+
+
+def _check_poly_sample(s, spec):
+    """(img, [[part arrays] per instance], labels) of one raw polygon sample"""
+    if not hasattr(s, 'get') or s.get('img') is None:
+        raise CggError('train_prep: a polygon sample is a dict with img, gt_polygons, gt_labels')
+    if s.get('gt_masks') is not None:
+        raise CggError('train_prep: a sample with both gt_masks and gt_polygons (bitmaps or polygons, not both)')
+    if spec is not None and spec.with_seg:
+        raise CggError('train_prep: the pipeline loads a semantic map (with_seg) and gt_polygons samples have none')
+    img = _as_hwc_u8(s['img'])
+    h, w = img.shape[:2]
+    if h < 1 or w < 1:
+        raise CggError(f'train_prep: a zero-sized image ({h} x {w})')
+    polys = _check_polygons(s['gt_polygons'])
+    labels = s.get('gt_labels')
+    labels = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if labels.shape != (len(polys),):
+        raise CggError(f'train_prep: gt_labels must be ({len(polys)},), one per instance of gt_polygons (got shape {labels.shape})')
+    return img, polys, labels
+
+
+def _is_polygons(s):
+    return hasattr(s, 'get') and s.get('gt_polygons') is not None
+
+
+def _batch_is_polygons(samples):
+    poly = [_is_polygons(s) for s in samples]
+    if any(poly) and not all(poly):
+        raise CggError('train_prep: a batch that mixes polygon samples (gt_polygons) with bitmap or panoptic samples')
+    return poly[0]
+
+
+def polygons_to_bitmap_sample(s, spec=None):
+    """the bitmap sample rule 6 makes of a raw polygon one: gt_polygons replaced by gt_masks (n, h, w) uint8 (with `spec`, a
+    pipeline that loads a semantic map is refused: polygon samples have none)"""
+    img, polys, _ = _check_poly_sample(s, spec)
+    h, w = img.shape[:2]
+    out = {k: v for k, v in s.items() if k != 'gt_polygons'}
+    out['gt_masks'] = (np.stack([polygon_mask_host(parts, h, w) for parts in polys]) if polys
+                       else np.zeros((0, h, w), dtype=np.uint8))
+    return out
+
+
 def _check_batch(samples, params):
     if not isinstance(samples, (list, tuple)) or not samples:
         raise CggError('train_prep: expected a non-empty list of samples')
@@ -445,13 +685,16 @@ def mask_stats(m, eh, ew):
 def prepare_train_host(samples, params, spec):
     """The rule in numpy. samples: dicts with img (h, w, 3) uint8 BGR, gt_masks (n, h, w) uint8 / bool, gt_labels (n,), optionally
     gt_semantic_seg (h, w) uint8, the caption fields and filename / ori_filename (passed through) -- or raw panoptic samples with
-    pan_seg and segments in place of gt_masks / gt_semantic_seg (rule 5; all of a batch or none); params: one TrainParams each.
+    pan_seg and segments in place of gt_masks / gt_semantic_seg (rule 5; all of a batch or none), or raw polygon samples with
+    gt_polygons in place of gt_masks (rule 6; likewise); params: one TrainParams each.
     -> (kwargs, kept): kwargs holds img (B, 3, H, W) float32, img_metas, gt_masks (list of (k_b, H, W) uint8), gt_bboxes (list of
     (k_b, 4) float32), gt_labels, gt_semantic_seg (B, 1, H, W) uint8 when the pipeline loads one, and the caption fields as lists --
     numpy arrays, named as `forward_train` names them (`to_device` uploads them); kept = [k_b], the surviving instances per sample."""
     _check_batch(samples, params)
     if _batch_is_panoptic(samples):                          # by definition: the rule on the bitmap samples rule 5 makes
         return prepare_train_host([panoptic_to_bitmap_sample(s) for s in samples], params, spec)
+    if _batch_is_polygons(samples):                          # likewise: the rule on the bitmap samples rule 6 makes
+        return prepare_train_host([polygons_to_bitmap_sample(s, spec) for s in samples], params, spec)
     H, W = spec.size
     mean, rstd, pad = norm_constants(_norm_spec(spec))
     B = len(samples)
@@ -521,7 +764,10 @@ class TrainPrep:
     planes; mask and semantic planes with the per-instance area / box reduction), then ONE small D2H copy of the (N, 5) int32
     statistics. A batch of raw panoptic samples (pan_seg + segments) stages three tables, the images and the id maps -- no bitmap, no
     semantic map -- and runs `cgg_train_prep_panoptic_u8` instead (image planes; every thing mask, the semantic plane and the
-    statistics from one gather of the id map per pixel); the rest is the same. So, either way: ONE small D2H copy of the
+    statistics from one gather of the id map per pixel); the rest is the same. A batch of raw polygon samples (gt_polygons) stages
+    three tables, the images and the float64 coordinates -- no bitmap -- and runs `cgg_train_prep_polygons_u8`: three launches (image
+    planes; the instances' bit planes into a grow-only device workspace kept next to the staging slots; the plane kernel over those
+    bits). So, every way: ONE small D2H copy of the
     statistics. Waiting for that copy is the SINGLE synchronisation per batch: which instances survive decides the shapes of
     gt_masks / gt_bboxes / gt_labels, and the host has to know them. gt_masks[b] is a zero-copy slice of the masks tensor when every
     instance of image b survived, an index_select otherwise; gt_bboxes come from the statistics. A sample without a surviving
@@ -540,6 +786,7 @@ class TrainPrep:
         self.spec, self.device = spec, device
         self._slots = [None] * slots
         self._n = 0
+        self._workspace = self._workspace_used = None           # the polygon route's device workspace, grow-only
         self.last_staged_bytes = 0
 
     _slot = ImagePrep._slot                                  # the same rotation of pinned staging slots
@@ -604,6 +851,43 @@ class TrainPrep:
                   (seg_off, np.asarray(seg_rows, dtype=np.int32).reshape(S, TRAIN_PREP_SEG_COLS))]
         return n, tables, copies, 'train_prep_panoptic_u8'
 
+    def _layout_polygons(self, parsed, params, geoms, counts):
+        """the staged bytes of a polygon batch: the image, instance (image index, first part, parts) and part (byte offset, vertices)
+        tables, the images, then every part's coordinates as float64 from an 8-byte boundary on. No bitmap is staged."""
+        B, N = len(parsed), sum(counts)
+        P = sum(len(parts) for q in parsed for parts in q[1])
+        inst_off = 4 * TRAIN_PREP_IMG_COLS * B
+        part_off = inst_off + 4 * TRAIN_PREP_POLY_INST_COLS * N
+        n = part_off + 4 * TRAIN_PREP_POLY_PART_COLS * P
+        img_rows, inst_rows, part_rows, copies = [], [], [], []
+        first = 0
+        for b, ((img, _, _), p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
+            h, w = int(img.shape[0]), int(img.shape[1])
+            img_rows.append((n, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], -1))
+            copies.append((n, img))
+            n += h * w * 3
+            first += counts[b]
+        n = (n + 7) & ~7
+        pfirst = 0
+        for b, q in enumerate(parsed):
+            for parts in q[1]:
+                inst_rows.append((b, pfirst, len(parts)))
+                pfirst += len(parts)
+                for xy in parts:
+                    part_rows.append((n, xy.size // 2))
+                    copies.append((n, xy))
+                    n += xy.nbytes
+        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
+                  (inst_off, np.asarray(inst_rows, dtype=np.int32).reshape(N, TRAIN_PREP_POLY_INST_COLS)),
+                  (part_off, np.asarray(part_rows, dtype=np.int32).reshape(P, TRAIN_PREP_POLY_PART_COLS))]
+        return n, tables, copies, 'train_prep_polygons_u8'
+
+    def _workspace_for(self, nbytes):
+        """the grow-only device workspace of the polygon route (bit planes, toggle planes): the kernels clear what they read"""
+        if self._workspace is None or self._workspace.numel() * 4 < nbytes:
+            self._workspace = torch.empty((max(1 << 14, 1 << max(nbytes - 1, 1).bit_length()) // 4,), dtype=torch.int32, device=self.device)
+        return self._workspace
+
     def prep(self, samples, params):
         from . import ops
         spec = self.spec
@@ -615,6 +899,11 @@ class TrainPrep:
             labels_all = [q[4] for q in parsed]
             counts = [int(q[4].shape[0]) for q in parsed]
             layout = self._layout_panoptic
+        elif _batch_is_polygons(samples):
+            parsed = [_check_poly_sample(s, spec) for s in samples]
+            labels_all = [q[2] for q in parsed]
+            counts = [len(q[1]) for q in parsed]
+            layout = self._layout_polygons
         else:
             parsed = [_check_sample(s, spec) for s in samples]
             labels_all = [q[2] for q in parsed]
@@ -650,6 +939,15 @@ class TrainPrep:
             if op == 'train_prep_panoptic_u8':
                 ops.train_prep_panoptic_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
                                            pan_table_offset=offsets[1], seg_table_offset=offsets[2], **common)
+            elif op == 'train_prep_polygons_u8':
+                common.pop('seg_pad')
+                ws = self._workspace_for(ops.train_prep_polygons_workspace_bytes(host_tables[0], N))
+                if self._workspace_used is not None:
+                    stream.wait_event(self._workspace_used)   # device: the last batch's kernels have left the workspace (another stream)
+                ops.train_prep_polygons_u8(slot.dev, *host_tables, slot.pinned, img_out, masks_out, stats, ws, spec.mean, spec.std,
+                                           spec.pad_val[0], inst_table_offset=offsets[1], part_table_offset=offsets[2], **common)
+                self._workspace_used = torch.cuda.Event()
+                self._workspace_used.record(stream)
             else:
                 ops.train_prep_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
                                   inst_table_offset=offsets[1], **common)

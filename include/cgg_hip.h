@@ -855,6 +855,52 @@ int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_bytes, int6
                                const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img, uint8_t* masks,
                                uint8_t* seg, int32_t* stats, int H, int W, cgg_stream_t stream);
 
+/* The same pipeline for INSTANCE samples whose masks arrive as COCO polygons (`ann_info['masks']`: per instance a list of parts, per
+ * part a flat x0, y0, x1, y1, ... sequence), rasterised on the device (csrc/train_prep.hip): the image kernel of cgg_train_prep_u8,
+ * one kernel that turns every instance's parts into a COLUMN-MAJOR BIT PLANE at source resolution (pixel p = x * h + y is bit p & 31
+ * of word p >> 5), and the plane kernel of cgg_train_prep_u8 reading those bits instead of staged bytes -- rule 3 and the statistics
+ * are the same code. The raster rule is rule 6 of train_prep.py (`polygon_mask_host`), a restatement of the published maskApi.c
+ * (rleFrPoly, then merge with intersect = 0): vertices (int)(5 v + 0.5); the edge walk in steps of 1 / 5 pixel with
+ * (int)(ys + s * t + 0.5), product and sums rounded on their own; a crossing wherever consecutive points change their column, at
+ * the column-major index a = xd * h + yd; pixel p is set iff the number of crossings <= p is odd (one prefix parity over the whole
+ * plane, carried across columns); an instance is the OR of its parts. It claims equality with no particular pycocotools build.
+ * The fill kernel runs one workgroup per instance and takes the parts in turn: every point of every edge is closed-form in (edge, d),
+ * so lanes stride over d and each crossing toggles one bit (atomic XOR) of a toggle plane -- in LDS when h * w <=
+ * CGG_POLY_LDS_BITS, else in the workspace; then a prefix XOR over the plane in blocks of CGG_POLY_SCAN_BITS bits (shift-XOR inside
+ * a word, the parity of the preceding words' population counts through a wave ballot and across the four waves as the carry).
+ *   staged          DEVICE bytes (8-byte aligned base): the three tables at bytes img / inst / part_table_offset (multiples of 4), the
+ *                   images and the coordinates as float64; no bitmap. staged_bytes = how many are valid
+ *   img_table_host  HOST copy of the B image rows of cgg_train_prep_u8; the semantic-map offset is -1
+ *   inst_table_host HOST copy of the N instance rows of 3 int32: image index, first part, parts (>= 0; the instances own consecutive
+ *                   ranges of the P parts, in order). An instance without parts has an empty mask
+ *   part_table_host HOST copy of the P part rows of 2 int32: byte offset of the part's 2 k float64 (a multiple of 8), vertex count k
+ *   staged_host     HOST copy of the staged bytes; only the coordinates the part rows name are read, for validation
+ *   workspace       DEVICE, 4-byte aligned, >= cgg_train_prep_polygons_workspace_bytes(...) bytes: the N bit planes first, each
+ *                   max over the images of ceil(h * w / 32) words apart, then (workspace route) as many toggle planes. The kernels
+ *                   write every word they read: the caller clears nothing
+ *   force_workspace non-zero: toggle planes in the workspace whatever their size (for tests)
+ *   img, masks, stats, mean, std, pad_val, crop   as for cgg_train_prep_u8 (there is no semantic plane)
+ * cgg_polygon_fill_bits runs the fill kernel alone (same tables; of an image row only h, w, first instance, instances are used).
+ * cgg_train_prep_polygons_workspace_bytes answers the bytes of workspace either needs, or a negative status.
+ * Nothing synchronises. Checked on the host before the first launch: everything cgg_train_prep_u8 checks for the image rows, and
+ * CGG_EINVAL for null pointers, a table or a part extending past staged_bytes, a part offset that is no multiple of 8, a vertex
+ * count < 1, instance or part ranges that do not tile, a non-finite coordinate; CGG_EUNSUPPORTED for |coordinate| >
+ * CGG_IMAGE_PREP_MAX_DIM (it bounds the edge walk), h * w > 2^31 - 32, a workspace that is too small; CGG_EALIGN as for
+ * cgg_train_prep_u8, and for staged / workspace. */
+#define CGG_POLY_LDS_BITS 393216
+#define CGG_POLY_SCAN_BITS 8192
+int64_t cgg_train_prep_polygons_workspace_bytes(const int32_t* img_table_host, int B, int N, int force_workspace);
+int cgg_polygon_fill_bits(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                          int64_t part_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host,
+                          const int32_t* part_table_host, const uint8_t* staged_host, int B, int N, int P, uint32_t* workspace,
+                          int64_t workspace_bytes, int force_workspace, cgg_stream_t stream);
+int cgg_train_prep_polygons_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
+                               int64_t part_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host,
+                               const int32_t* part_table_host, const uint8_t* staged_host, int B, int N, int P, const float* mean,
+                               const float* std, const float* pad_val, int to_rgb, int crop_h, int crop_w, float* img,
+                               uint8_t* masks, int32_t* stats, int H, int W, uint32_t* workspace, int64_t workspace_bytes,
+                               int force_workspace, cgg_stream_t stream);
+
 /* One step of the caption beam search for a whole batch of images, decision and bookkeeping on the device (csrc/beam_step.hip):
  * the loop body of the reference's beam_search, open_set/utils/eval/inference.py:113-149 -- mean over the decoder blocks' generator
  * outputs, log-softmax, (log p + parent weight) / length^alpha, the top `beam` of an image's live rows, the walk over them that

@@ -9,7 +9,9 @@ default, from the synthetic COCO-shaped stream used by bench.py. Samples whose `
 labels, captions as the dataset loads them -- and go through `cfg.data.train.pipeline` on the device (cgg_amd.train_prep:
 flip, large-scale jitter, crop, annotation filter, pad, normalize); `--synthetic-u8 HxW` generates such samples. Raw PANOPTIC samples
 carry the panoptic id map (`pan_seg`) and its segment records (`segments`) instead of bitmaps: the thing masks and the semantic map
-are made on the device too (train_prep.py, rule 5); `--synthetic-panoptic HxW` generates such samples.
+are made on the device too (train_prep.py, rule 5); `--synthetic-panoptic HxW` generates such samples. Raw POLYGON samples carry
+`gt_polygons` (`ann_info['masks']`: per instance a list of flat x0, y0, x1, y1, ... polygons) instead of bitmaps and are rasterised on
+the device (train_prep.py, rule 6); `--synthetic-polygons HxW` generates such samples.
 
     python tools/train.py configs/instance/coco_b48n17.py --work-dir work --max-iters 100 --synthetic 512
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py CONFIG --launcher pytorch
@@ -58,7 +60,8 @@ def parse_args(argv=None):
                    help='pkg.module:function(cfg, rank, world) -> iterable of sample dicts: float `img` = already augmented, padded '
                         'and formatted; uint8 `img` (h, w, 3) BGR with gt_masks (n, h, w) bitmaps and gt_labels = raw, prepared on '
                         'the device by the config\'s data.train.pipeline; with pan_seg (the panoptic id map) and segments (its '
-                        'records) in place of gt_masks = raw panoptic, loaded and prepared on the device')
+                        'records) in place of gt_masks = raw panoptic, loaded and prepared on the device; with gt_polygons (per instance a list '
+                        'of flat x0, y0, x1, y1, ... polygons) in place of gt_masks = raw polygons, rasterised on the device')
     p.add_argument('--synthetic-u8', default=None, metavar='HxW',
                    help='synthetic RAW uint8 samples of this size (e.g. 480x640) with blob masks of mixed sizes instead of '
                         '--synthetic\'s prepared float samples: exercises the device-side training pipeline without a dataset')
@@ -66,10 +69,16 @@ def parse_args(argv=None):
                    help='synthetic RAW panoptic samples of this size: a uint8 image, a block-structured panoptic id map (int32 and RGB '
                         'forms in turn) and its segment records -- things, stuff, a crowd thing, ids that no record lists; exercises '
                         'the device-side panoptic loader + training pipeline (the config needs a Load*PanopticAnnotations pipeline)')
+    p.add_argument('--synthetic-polygons', default=None, metavar='HxW',
+                   help='synthetic RAW polygon samples of this size: a uint8 image and COCO polygons -- multi-part instances, one '
+                        'partly outside the image, a degenerate two-vertex part, one that no crop keeps; exercises the device-side '
+                        'polygon raster + training pipeline. Not together with --synthetic-u8 / --synthetic-panoptic')
     p.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'])
     p.add_argument('--log-interval', type=int, default=10)
     p.add_argument('--save-interval', type=int, default=0, help='iterations between checkpoints (0: only at the end)')
     args = p.parse_args(argv)
+    if args.synthetic_polygons and (args.synthetic_u8 or args.synthetic_panoptic):
+        p.error('--synthetic-polygons cannot be combined with --synthetic-u8 / --synthetic-panoptic')
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
 
@@ -229,13 +238,16 @@ def main(argv=None):
     head = cfg.model['panoptic_head']
     num_classes = head['num_things_classes'] + head['num_stuff_classes']
     stream_name = (f'--data {args.data}' if args.data else f'--synthetic-u8 {args.synthetic_u8}' if args.synthetic_u8 else
-                   f'--synthetic-panoptic {args.synthetic_panoptic}' if args.synthetic_panoptic else '--synthetic')
+                   f'--synthetic-panoptic {args.synthetic_panoptic}' if args.synthetic_panoptic else
+                   f'--synthetic-polygons {args.synthetic_polygons}' if args.synthetic_polygons else '--synthetic')
     vocab = ((head.get('caption_generator') or {}).get('nb_tokens')) or 30522          # token ids must index the table
     if args.data:
         mod, fn = args.data.split(':')
         samples = getattr(importlib.import_module(mod), fn)(cfg, rank, world)
-    elif args.synthetic_u8 or args.synthetic_panoptic:
-        flag, val = ('--synthetic-u8', args.synthetic_u8) if args.synthetic_u8 else ('--synthetic-panoptic', args.synthetic_panoptic)
+    elif args.synthetic_u8 or args.synthetic_panoptic or args.synthetic_polygons:
+        flag, val = (('--synthetic-u8', args.synthetic_u8) if args.synthetic_u8 else
+                     ('--synthetic-panoptic', args.synthetic_panoptic) if args.synthetic_panoptic else
+                     ('--synthetic-polygons', args.synthetic_polygons))
         try:
             hw = tuple(int(v) for v in val.lower().split('x'))
             assert len(hw) == 2 and min(hw) >= 1
@@ -243,9 +255,11 @@ def main(argv=None):
             raise SystemExit(f'{flag} {val!r}: expected HxW, e.g. 480x640')
         if args.synthetic_u8:
             samples = synthetic_u8_samples(hw, num_classes, seed=1000 * rank + seed, vocab=vocab)
-        else:
+        elif args.synthetic_panoptic:
             samples = synthetic.panoptic_samples(hw, head['num_things_classes'], head['num_stuff_classes'], seed=1000 * rank + seed,
                                                  vocab=vocab)
+        else:
+            samples = synthetic.polygon_samples(hw, num_classes, seed=1000 * rank + seed, vocab=vocab)
     else:
         samples = synthetic_samples(args.synthetic, num_classes, seed=1000 * rank + seed, vocab=vocab)
     max_iters = args.max_iters or (cfg.get('runner') or {}).get('max_iters')
