@@ -3251,3 +3251,106 @@ def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt
               opt(dt_match, 'dt_match', torch.int32, D), opt(dt_ignore, 'dt_ignore', torch.uint8, D),
               opt(gt_ignore, 'gt_ignore', torch.uint8, G), dev_ptr(counts, 'coco_match: counts', torch.int32), stream_ptr(dev))
     return dt_match, dt_ignore, gt_ignore, counts
+
+
+# ------------------------------------------------------------------------------------------------
+# Panoptic-quality evaluation on the device (csrc/pq_eval.hip; pq_eval.py states the rules in numpy)
+# ------------------------------------------------------------------------------------------------
+PQ_EVAL_MAX_SEGMENTS = 4096
+
+
+def pq_hash_size(n):
+    """entries of the kernel's id -> slot table for n ids: the power of two >= max(16, 2 n); an id starts probing at id % size"""
+    s = 16
+    while s < 2 * int(n):
+        s *= 2
+    return s
+
+
+def pq_eval_lds_bytes(G, P):
+    """LDS a workgroup of `pq_confusion` holds: the (G + 2) x (P + 1) int32 table and both id -> slot tables (-1 outside 0 .. 4096)"""
+    return int(_lib_().cgg_pq_eval_lds_bytes(int(G), int(P)))
+
+
+def pq_eval_ok(G, P, H, W, class0_is_thing=True):
+    """The gate of `pq_confusion` / `pq_match`, host arithmetic only: the confusion table plus both id tables fit the dynamic-LDS
+    limit, H * W < 2^31 (the counts are int32), and class 0 is a thing: were it stuff, its value 0 would collide with VOID after the
+    relabelling of `pan_result_segments_host`, which the host rule follows literally and the device route does not try.
+    Images outside it take the host rule (`pq_eval.pq_image_host`)."""
+    G, P, H, W = int(G), int(P), int(H), int(W)
+    if not (0 <= G <= PQ_EVAL_MAX_SEGMENTS and 0 <= P <= PQ_EVAL_MAX_SEGMENTS and H > 0 and W > 0 and H * W < (1 << 31)):
+        return False
+    return bool(class0_is_thing) and pq_eval_lds_bytes(G, P) <= int(_lib_().cgg_dynamic_lds_limit())
+
+
+def _pq_table(table, n_kept, who):
+    if table.dim() != 2 or table.shape[1] != 4 or n_kept.numel() != 1 or n_kept.device != table.device:
+        raise CggError(f'{who}: table must be (P, 4) int32 and n_kept one int32 on its device (got {tuple(table.shape)}, {n_kept.numel()} '
+                       f'on {n_kept.device})')
+    P = int(table.shape[0])
+    return P, (dev_ptr(table, f'{who}: table', torch.int32) if P else None), dev_ptr(n_kept, f'{who}: n_kept', torch.int32)
+
+
+def pq_confusion(pan_pred, table, n_kept, pan_gt, gt_ids, num_classes, ws=None):
+    """Confusion counts of one image on the device: pan_pred (H, W) int32; table (P, 4) int32 segment rows [value, category, area,
+    query] with the device int32 n_kept of them valid (as `panoptic_fuse_batched` leaves them: n_kept is read on the device); pan_gt
+    (H, W) int32 ids or (H, W, 3) uint8 RGB; gt_ids (G,) int32 -> int32 workspace whose first (G + 2) x (P + 1) cells are the table
+    (row 0 VOID, rows 1 .. G the listed ids, row G + 1 any other id; column 0 void, column 1 + k table row k) followed by two status
+    words. Two launches on the current stream, no host read. `pq_match` reads the workspace."""
+    who = 'pq_confusion'
+    dev = pan_pred.device
+    if pan_pred.dim() != 2 or tuple(pan_gt.shape[:2]) != tuple(pan_pred.shape) or pan_gt.device != dev:
+        raise CggError(f'{who}: pan_pred {tuple(pan_pred.shape)} on {dev} and pan_gt {tuple(pan_gt.shape)} on {pan_gt.device} must share '
+                       'H, W and the device')
+    H, W = int(pan_pred.shape[0]), int(pan_pred.shape[1])
+    rgb = pan_gt.dim() == 3
+    if (rgb and (pan_gt.shape[2] != 3 or pan_gt.dtype != torch.uint8)) or (not rgb and pan_gt.dtype != torch.int32):
+        raise CggError(f'{who}: pan_gt must be (H, W) int32 or (H, W, 3) uint8 (got {pan_gt.dtype}, shape {tuple(pan_gt.shape)})')
+    G = int(gt_ids.numel())
+    P, ptable, pkept = _pq_table(table, n_kept, who)
+    if not pq_eval_ok(G, P, H, W):
+        raise CggError(f'{who}: outside the kernel gate (G={G}, P={P}: {pq_eval_lds_bytes(G, P)} bytes of LDS, H * W = {H * W})')
+    need = int(_lib_().cgg_pq_confusion_workspace_bytes(G, P))
+    if ws is None:
+        ws = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    if ws.numel() * 4 < need or ws.device != dev:
+        raise CggError(f'{who}: workspace of {ws.numel() * 4} bytes on {ws.device}, {need} on {dev} needed')
+    with _timed('pq_confusion', bytes=float(H * W * (4 + (3 if rgb else 4))), shape=(G, P, H, W)):
+        _call('cgg_pq_confusion_i32', dev_ptr(pan_pred, f'{who}: pan_pred', torch.int32), dev_ptr(pan_gt, f'{who}: pan_gt'), int(rgb), H, W,
+              dev_ptr(gt_ids, f'{who}: gt_ids', torch.int32) if G else None, G, ptable, pkept, P, int(num_classes),
+              dev_ptr(ws, f'{who}: ws', torch.int32), stream_ptr(dev))
+    return ws
+
+
+def pq_match(ws, gt_cats, gt_crowd, gt_area, table, n_kept):
+    """The matching of `pq_eval.pq_image_host` for one image on the device, from the workspace of `pq_confusion`: gt_cats int32 (G,)
+    (category codes, compared with the table's category column as opaque integers), gt_crowd uint8 (G,), gt_area int32 (G,) ->
+    (record, offs): ONE uint8 device buffer, so that one copy carries it, and name -> (byte offset, bytes) of status int32 (2,),
+    gt_iou float64 (G,), gt_match int32 (G,), pred_area, pred_value, pred_cat int32 (P,), pred_flags uint8 (P,) (1 segment, 2 matched,
+    4 ignored). One launch on the current stream, no host read."""
+    who = 'pq_match'
+    dev = ws.device
+    G = int(gt_cats.numel())
+    P, ptable, pkept = _pq_table(table, n_kept, who)
+    if gt_crowd.numel() != G or gt_area.numel() != G or table.device != dev or gt_cats.device != dev:
+        raise CggError(f'{who}: gt_cats, gt_crowd, gt_area must have {G} elements each, everything on {dev}')
+    if pq_eval_lds_bytes(G, P) < 0 or ws.numel() * 4 < int(_lib_().cgg_pq_confusion_workspace_bytes(G, P)):
+        raise CggError(f'{who}: workspace of {ws.numel() * 4} bytes does not hold the table of G={G}, P={P}')
+    offs, total = {}, 0
+    for name, nbytes in (('status', 8), ('gt_iou', 8 * G), ('gt_match', 4 * G), ('pred_area', 4 * P), ('pred_value', 4 * P),
+                         ('pred_cat', 4 * P), ('pred_flags', P)):
+        offs[name] = (total, nbytes)
+        total += (nbytes + 7) & ~7
+    rec = torch.empty(total, dtype=torch.uint8, device=dev)
+
+    def part(name, dtype, n):
+        o, nb = offs[name]
+        return dev_ptr(rec[o:o + nb].view(dtype), f'{who}: {name}') if n else None
+
+    with _timed('pq_match', shape=(G, P)):
+        _call('cgg_pq_match', dev_ptr(ws, f'{who}: ws', torch.int32), dev_ptr(gt_cats, f'{who}: gt_cats', torch.int32) if G else None,
+              dev_ptr(gt_crowd, f'{who}: gt_crowd', torch.uint8) if G else None,
+              dev_ptr(gt_area, f'{who}: gt_area', torch.int32) if G else None, G, ptable, pkept, P, part('status', torch.int32, 2),
+              part('gt_iou', torch.float64, G), part('gt_match', torch.int32, G), part('pred_area', torch.int32, P),
+              part('pred_value', torch.int32, P), part('pred_cat', torch.int32, P), part('pred_flags', torch.uint8, P), stream_ptr(dev))
+    return rec, offs

@@ -309,3 +309,17 @@ def polygon_samples(hw, num_classes, seed=0, vocab=30522, extra=4, vertices=(6, 
     while True:
         yield polygon_sample(hw, num_classes, seed=seed + i, vocab=vocab, extra=extra, vertices=vertices)
         i += 1
+
+
+def pq_ground_truth(hw, num_things, num_stuff, all_cat_ids=None, seed=0, rgb=None, blocks=(4, 5)):
+    """Panoptic ground truth of one image as `pq_eval.PQEvaluator.add` (and `tools/test.py --eval PQ`, as the metas' `gt_pan_seg` /
+    `gt_segments`) takes it, from `panoptic_sample`: (id map -- (h, w) int32 or (h, w, 3) uint8 RGB --, records id, category_id,
+    iscrowd, area). all_cat_ids: label -> category id (default label + 1); the sample's crowd thing becomes iscrowd = 1, areas are
+    pixel counts, two blocks keep ids that no record lists."""
+    s = panoptic_sample(hw, num_things, num_stuff, seed=seed, rgb=rgb, blocks=blocks)
+    pan = s['pan_seg']
+    ids = pan if pan.ndim == 2 else pan[:, :, 0].astype(np.int32) + 256 * pan[:, :, 1].astype(np.int32) + 65536 * pan[:, :, 2].astype(np.int32)
+    cats = list(range(1, num_things + num_stuff + 1)) if all_cat_ids is None else list(all_cat_ids)
+    segments = [dict(id=r['id'], category_id=int(cats[r['category']]), iscrowd=int(r['category'] < num_things and not r['is_thing']),
+                     area=int((ids == r['id']).sum())) for r in s['segments']]
+    return pan, segments

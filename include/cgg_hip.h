@@ -1335,6 +1335,44 @@ int cgg_coco_match(const int32_t* inter, const int32_t* area_d, const int32_t* a
                    int max_det, int class_agnostic, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, int32_t* counts,
                    cgg_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Panoptic-quality evaluation on the device (csrc/pq_eval.hip). `pq_eval.py` states the rule in numpy (pq_image_host, a
+ * restatement of the loop body of the reference's pq_compute_single_core) and the kernels equal it exactly: integer counts, and
+ * one IEEE double quotient of two integers per pair. All pointers DEVICE; everything runs on `stream`; no host read, no
+ * allocation, no memset node: legal under stream capture.
+ *
+ * cgg_pq_confusion_i32: ws[g][p] = pixels of an H x W image whose ground-truth id has slot g and whose pred value has slot p, an
+ *   int32 table of (G + 2) x (P + 1) cells followed by two status words; ws: cgg_pq_confusion_workspace_bytes(G, P) bytes, which
+ *   a first launch zeroes. pred: int32[H * W]. gt: int32[H * W] (gt_rgb = 0) or uint8[H * W * 3] RGB with id = R + 256 G +
+ *   65536 B (gt_rgb = 1). Rows: 0 = id 0 (VOID), 1 + i = gt_ids[i] (ids >= 0; an id listed twice counts into its first slot),
+ *   G + 1 = any other id. Columns: 0 = void, 1 + k = row k of `table`, int32[P][4] rows [value, category, area, query] as
+ *   cgg_panoptic_fuse_batched writes them, of which the first *n_kept (read on the device, clamped to 0 .. P) are valid; rows
+ *   with value < 0 or area <= 0 are dropped and equal values count into the first of their rows. A pred pixel is void iff
+ *   value % 1000 == num_classes, or it is 0 and not in the table; any other value that is not in the table sets bit 1 of status
+ *   word 0 and leaves the smallest such value in status word 1 (INT_MAX when there is none).
+ *   Loads are 16 bytes wide where pred / gt are 16-byte aligned (RGB: 4-byte aligned), narrower otherwise.
+ *   CGG_EINVAL: null or misaligned pointer, H, W < 1, G, P, num_classes < 0. CGG_EUNSUPPORTED: H * W >= 2^31, G or P > 4096, or
+ *   cgg_pq_eval_lds_bytes(G, P) (the table and both id -> slot tables, held in LDS by every workgroup) above
+ *   cgg_dynamic_lds_limit(); cgg_pq_eval_lds_bytes answers -1 for sizes outside 0 .. 4096.
+ *
+ * cgg_pq_match: from `ws` as written above, for one image: gt_cats int32[G] and the table's category column are compared as
+ *   opaque integers; gt_crowd uint8[G]; gt_area int32[G] (the records' areas). Pred areas are the column sums. For a
+ *   non-crowd ground truth g and a segment row k of equal category with inter = ws[1 + g][1 + k] > 0: iou = (double)inter /
+ *   (double)(area_k + gt_area[g] - inter - ws[0][1 + k]), matched iff iou > 0.5. gt_match[g] = the matched row or -1, gt_iou[g]
+ *   its iou (0 without a match). pred_flags[k]: 1 = row k is a segment (valid, first of its value), 2 = matched, 4 = unmatched
+ *   and ignored: (ws[0][1 + k] + ws[1 + c][1 + k]) / area_k > 0.5 in double, c the LAST crowd of the row's category in gt order.
+ *   pred_area[k], pred_value[k] (-1 for a row that is no segment), pred_cat[k]. status[0] = the confusion's status word, with
+ *   bit 2 for a segment row without pixels and bit 4 for a ground truth with more than one match (gt_match keeps the first
+ *   row); status[1] as above. gt_iou 8-byte aligned. Error codes as above.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t cgg_pq_eval_lds_bytes(int G, int P);
+int64_t cgg_pq_confusion_workspace_bytes(int G, int P);
+int cgg_pq_confusion_i32(const int32_t* pred, const void* gt, int gt_rgb, int H, int W, const int32_t* gt_ids, int G,
+                         const int32_t* table, const int32_t* n_kept, int P, int num_classes, int32_t* ws, cgg_stream_t stream);
+int cgg_pq_match(const int32_t* ws, const int32_t* gt_cats, const uint8_t* gt_crowd, const int32_t* gt_area, int G,
+                 const int32_t* table, const int32_t* n_kept, int P, int32_t* status, double* gt_iou, int32_t* gt_match,
+                 int32_t* pred_area, int32_t* pred_value, int32_t* pred_cat, uint8_t* pred_flags, cgg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,10 @@
 """Minimal inference driver with the command line of the reference's tools/test.py: config + checkpoint -> detector from
 the registry -> `simple_test` over a stream of images -> results pickle (`--out`), one process per GPU under
 `--launcher pytorch` (images are sharded by rank, results gathered on rank 0). `--eval segm` computes COCO mask AP (and base /
-novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`); the other
-metrics need the dataset classes, which are out of this build's scope: they are accepted and reported as unavailable.
+novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`), `--eval PQ`
+panoptic quality over All / Known Things / Unknown Things / Stuff from the device maps and segment tables
+(`cgg_amd.pq_eval.PQEvaluator`); the other metrics need the dataset classes, which are out of this build's scope: they are accepted
+and reported as unavailable.
 
 Both precision modes serve through `pipeline.StagePipeline` (hipGraph per stage, encode of batch k+1 overlapped with decode of
 batch k): `--precision fp32` (default) is parity mode -- the reference's f32 semantics on the f32-class x3 kernels --,
@@ -46,6 +48,10 @@ def parse_args(argv=None):
                         'original size (gt_crowd, gt_area optional), and sets --mask-bits. The config may hold segm_eval = dict(all_results='
                         '[category id per label], base_results=[...], novel_results=[...], unknown_cat_ids=[...], all_cat_ids=[...], '
                         'class_agnostic=False, max_dets=(100, 300, 1000)); a type without a list takes label + 1 as the category id. '
+                        'PQ (or pq): panoptic quality of panoptic_all_results, evaluated on the device from the id maps and segment tables '
+                        '(sets with_segments); needs metas with gt_pan_seg ((h, w) int32 ids or (h, w, 3) uint8 RGB) and gt_segments '
+                        '(records id, category_id, iscrowd, area) at the original size. The config may hold pq_eval = dict(all_cat_ids=[...], '
+                        'isthing=[...], unknown_cat_ids=[...]); by default label + 1 and the first num_things_classes labels are things. '
                         'Other metrics need the dataset classes: unavailable here')
     p.add_argument('--cfg-options', nargs='+', default=None, help='key=value overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none')
@@ -119,6 +125,9 @@ def to_numpy(result):
     (n, H, W / 8) uint8 with --mask-bits)."""
     out = {}
     for key, val in result.items():
+        if isinstance(val, dict):          # panoptic_segments: the segment table block {n_kept, table, scores}
+            out[key] = {k: v.detach().cpu().numpy() if torch.is_tensor(v) else v for k, v in val.items()}
+            continue
         out[key] = tuple(v.detach().cpu().numpy() if torch.is_tensor(v) else v for v in val) \
             if isinstance(val, (tuple, list)) else (val.detach().cpu().numpy() if torch.is_tensor(val) else val)
     return out
@@ -166,6 +175,39 @@ def segm_summary(cfg, model, evaluators, eval_records, device, work_dir):
     return summary
 
 
+def pq_evaluator(cfg, model, device=None):
+    """the PQEvaluator of a run: categories from the config entry pq_eval, by default ids 1..n with the first num_things_classes things"""
+    from cgg_amd.pq_eval import PQEvaluator
+    fh = model.panoptic_fusion_head
+    opts = dict(cfg.get('pq_eval') or {})
+    n = int(fh.num_classes)
+    return PQEvaluator(opts.get('all_cat_ids') or list(range(1, n + 1)),
+                       opts.get('isthing') or [int(k < int(fh.num_things_classes)) for k in range(n)],
+                       opts.get('unknown_cat_ids'), num_classes=n, device=device)
+
+
+def pq_summary(cfg, model, records, work_dir):
+    """--eval PQ on rank 0: accumulate the image records (of all ranks, in image order), print the table and the twelve numbers and
+    write them to WORK_DIR/pq_eval.json. Without ground truth in the stream nothing was recorded: a message."""
+    from cgg_amd.pq_eval import format_pq_summary
+    if not records:
+        print('--eval PQ: the stream carries no ground truth (metas with gt_pan_seg and gt_segments come from a --data stream); dataset '
+              'classes / COCO evaluation are outside this build', flush=True)
+        return None
+    res = pq_evaluator(cfg, model).summarize(extra_records=records)
+    print(format_pq_summary(res['pq_results']), flush=True)
+    print('PQ_copypaste: ' + res['results']['PQ_copypaste'], flush=True)
+    summary = dict(images=res['images'], results=res['results'],
+                   splits={k: v for k, v in res['pq_results'].items() if k != 'classwise'},
+                   classwise={str(k): v for k, v in res['pq_results']['classwise'].items()},
+                   stats={str(k): dict(tp=v['tp'], fp=v['fp'], fn=v['fn'], iou=float(v['iou'])) for k, v in sorted(res['stats'].items())})
+    if work_dir:
+        os.makedirs(work_dir, exist_ok=True)
+        with open(os.path.join(work_dir, 'pq_eval.json'), 'w') as f:
+            json.dump(summary, f, indent=1)
+    return summary
+
+
 def _test_stages():
     """CGG_TEST_STAGES (pipeline stage split of the serving loop): validated up front, 2..5 as `pipeline.detector_pipeline` names them
     (4 and 5 add a separate post-processing stage to the 2- / 3-stage split)."""
@@ -199,10 +241,14 @@ def main(argv=None):
         model.CLASSES = meta['CLASSES']
     model = model.to(device).eval()
     eval_segm = bool(args.eval) and 'segm' in args.eval
-    if args.eval and [m for m in args.eval if m != 'segm']:
+    eval_pq = bool(args.eval) and any(m in ('PQ', 'pq') for m in args.eval)        # ('pq' is regarded as 'PQ', as in the reference)
+    if args.eval and [m for m in args.eval if m not in ('segm', 'PQ', 'pq')]:
         print('--eval: dataset classes / COCO evaluation are outside this build; results are written with --out', flush=True)
     if eval_segm:
         args.mask_bits = True
+    decode_kwargs = dict(with_segments=True) if eval_pq else {}        # --eval PQ reads the device segment table
+    pq = [None]                        # --eval PQ: the PQEvaluator, made when the first ground truth arrives
+    pq_slots = []                      # per image of this rank, in order: the index of its record in the evaluator, or None
     evaluators = {}                    # --eval segm: result type -> SegmEvaluator, made when the first ground truth arrives
     eval_metas = []                    # per submitted batch, in submission order: the metas of its images
     evaluated = [None]                 # event after the newest batch's evaluator launches
@@ -248,11 +294,22 @@ def main(argv=None):
             n_shown += 1
 
     def evaluate(device_results):
-        """--eval segm: every image's result of each type the head returns goes to that type's evaluator (masks stay on the device)"""
+        """--eval segm: every image's result of each type the head returns goes to that type's evaluator (masks stay on the device);
+        --eval PQ: its panoptic map and segment table go to the PQEvaluator"""
         from cgg_amd.mask_eval import SegmEvaluator
         opts = dict(cfg.get('segm_eval') or {})
         for m, res in zip(eval_metas.pop(0), device_results):
-            if m.get('gt_masks') is None or m.get('gt_labels') is None:
+            if eval_pq:
+                # --eval PQ: the image's panoptic map and segment table go to the PQEvaluator (both stay on the device)
+                pan = res.get('panoptic_all_results', res.get('pan_results'))
+                if m.get('gt_pan_seg') is None or m.get('gt_segments') is None or pan is None or res.get('panoptic_segments') is None:
+                    pq_slots.append(None)
+                else:
+                    if pq[0] is None:
+                        pq[0] = pq_evaluator(cfg, model, device)
+                    pq_slots.append(len(pq[0].records))
+                    pq[0].add(pan, res['panoptic_segments'], m['gt_pan_seg'], m['gt_segments'])
+            if not eval_segm or m.get('gt_masks') is None or m.get('gt_labels') is None:
                 continue
             for key, val in res.items():
                 if not (key.endswith('_results') and isinstance(val, (tuple, list)) and len(val) == 3):
@@ -267,7 +324,7 @@ def main(argv=None):
 
     def emit(device_results):
         """device results of one batch -> `results` (numpy now, or a future of the RLE collector)"""
-        if eval_segm:
+        if eval_segm or eval_pq:
             evaluate(device_results)
             # the evaluator's kernels read the result buffers on THIS stream: the pipeline's last stage waits for them before it
             # writes a slot again (a wait on the GPU; without the RLE collector the copies below end in a host wait anyway)
@@ -334,7 +391,7 @@ def main(argv=None):
                     imgs[k].copy_(g[0], non_blocking=True)
                 metas = [dict(g[1], batch_input_shape=tuple(imgs.shape[-2:])) for g in group]
                 shape = tuple(imgs.shape)
-            if eval_segm:
+            if eval_segm or eval_pq:
                 eval_metas.append(metas)
             use_pipe = (not args.no_pipeline and len(group) == B
                         and all(m['img_shape'] == metas[0]['img_shape'] and m['ori_shape'] == metas[0]['ori_shape'] for m in metas))
@@ -347,7 +404,7 @@ def main(argv=None):
                         from cgg_amd.pipeline import detector_pipeline
                         if imgs is None:
                             imgs = image_prep()(raw)[0]        # the example batch the graphs are captured on
-                        pipe = detector_pipeline(model, imgs, metas, stages=_test_stages(), defer_tail=False, rescale=True, device_results=True, mask_bits=args.mask_bits)
+                        pipe = detector_pipeline(model, imgs, metas, stages=_test_stages(), defer_tail=False, rescale=True, device_results=True, mask_bits=args.mask_bits, **decode_kwargs)
                         pipe.meta_key = key
                         pipes[key] = pipe
                         torch.cuda.synchronize()
@@ -388,7 +445,7 @@ def main(argv=None):
                     t0 = time.perf_counter()
                 if imgs is None:
                     imgs = image_prep()(raw)[0]
-                emit(model.simple_test(imgs, metas, rescale=True, device_results=True, mask_bits=args.mask_bits))
+                emit(model.simple_test(imgs, metas, rescale=True, device_results=True, mask_bits=args.mask_bits, **decode_kwargs))
                 if collector is not None:
                     copies_done()
             n_img += len(group)
@@ -434,6 +491,10 @@ def main(argv=None):
             collector.close()
     dt = time.perf_counter() - (t0 or time.perf_counter())
     eval_records = {key: ev.image_records() for key, ev in evaluators.items()}     # per image a few KB of match records, no masks
+    pq_records = []                    # --eval PQ: per image of this rank its record (a few hundred bytes) or None
+    if eval_pq:
+        recs = pq[0].image_records() if pq[0] is not None else []
+        pq_records = [None if k is None else recs[k] for k in pq_slots]
     if distributed:
         import torch.distributed as dist
         gathered = [None] * world if rank == 0 else None
@@ -447,9 +508,16 @@ def main(argv=None):
                 for part in parts[1:]:
                     for key, recs in part.items():
                         eval_records.setdefault(key, []).extend(recs)
+        if eval_pq:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(pq_records, parts, dst=0)
+            if rank == 0:
+                pq_records = interleave_rank_results(parts)        # image order: the float sums do not depend on the number of ranks
         dist.destroy_process_group()
     if eval_segm and rank == 0:
         segm_summary(cfg, model, evaluators, eval_records, device, args.work_dir)
+    if eval_pq and rank == 0:
+        pq_summary(cfg, model, [r for r in pq_records if r is not None], args.work_dir)
     if rank == 0:
         print(json.dumps(dict(images=len(results), images_per_sec_this_rank=round(n_img / max(dt, 1e-9), 1),
                               precision=args.precision, pipeline=pipe is not None,
