@@ -254,7 +254,8 @@ int cgg_attn_mask_from_logits(const float* logits, uint32_t* bits, int N, int H,
  *   kv    [B, S, 2*H*D] f32 or bf16: row = [K(H*D) | V(H*D)]  (projected keys / values)
  *   bits  [B, Q, ceil(S/32)] u32, nullable; bit set = key blocked; shared by heads. A row with all
  *         S bits set must have been cleared by cgg_attn_mask_fix_full_rows (else output is NaN,
- *         exactly like the reference).
+ *         exactly like the reference). The unused bits of the last word (S % 32 != 0) are ignored by every consumer
+ *         (forwards, backwards, the in-kernel full-row test) and written as 0 by every producer of `bits`.
  *   out   [B, Q, H*D]  f32   softmax(q k^T * scale + mask) v, heads concatenated
  *   ws    workspace, cgg_masked_xattn_workspace_bytes(...) bytes (split-K partials)
  * Requires D == 32, H*D <= 256, Q <= 128.
