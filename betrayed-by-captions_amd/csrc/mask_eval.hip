@@ -14,6 +14,9 @@
 //   cgg_coco_match   the IoU quotient in double and the greedy matching of COCOeval.evaluateImg, one thread per (category, area
 //     range, threshold): the scan is sequential by nature and the work is tiny. A workgroup serves one category and prepares its
 //     detections, ground truths and IoU block in LDS first (a thread that walked all D x G pairs in global memory took 540 us).
+//   cgg_coco_match_boxes   the same scan -- one kernel template, instantiated on its IoU source -- on box IoUs (`--eval bbox`):
+//     the `bbIou` rule on xywh boxes in double, every operation rounded on its own (mask_eval.box_iou_host).
+//   cgg_box_iou_f64   that rule alone: the (D, G) IoU matrix and the detections' areas.
 #include "cgg_common.h"
 
 namespace {
@@ -248,29 +251,90 @@ inline int mi_load_mode(const uint8_t* p, int64_t stride, int row_bytes) {
 // ---- matching -------------------------------------------------------------------------------------------------------------------
 // One workgroup per category, one thread per (area range, threshold). The first wave compacts, by ballots, the category's
 // detections (score order, cut to max_det) and ground truths, and per area range the scan order of the ground truths (those that
-// count first); all threads then fill the category's IoU block in LDS (when it fits: CM_IOU_LDS entries; computed from global
-// memory in the scan otherwise) and each runs its sequential scan on LDS alone.
+// count first); all threads then fill the category's IoU block in LDS (CM_IOU_LDS entries: in chunks of detections when the block
+// is larger) and each runs its sequential scan on LDS alone.
 constexpr int CM_MAX_T = 64, CM_MAX_A = 8, CM_MAX_K = 1024;
 constexpr int CM_IOU_LDS = 2048;
 
-__device__ __forceinline__ double cm_iou(const int32_t* __restrict__ inter, const int32_t* __restrict__ area_d, int32_t ag, int G, int d,
-                                         int g, bool crowd) {
-  const int64_t i = inter[(int64_t)d * G + g];
-  const int64_t u = crowd ? (int64_t)area_d[d] : (int64_t)area_d[d] + ag - i;
-  return u == 0 ? 0.0 : (double)i / (double)u;
+// The IoU source of the matching scan: what a (detection, ground truth) pair's IoU and a detection's own area are made from.
+//   gt_key(g)                 what ground truth g contributes besides its index; the kernel stages it in LDS with the category
+//   iou(d, g, key, crowd)     the pair's IoU in double
+//   det_area(d)               the detection's area, for the area ranges
+// Masks: the integer intersections and areas of cgg_mask_intersections_bits.
+struct CmMaskIou {
+  const int32_t* __restrict__ inter;
+  const int32_t* __restrict__ area_d;
+  const int32_t* __restrict__ area_g;
+  int G;
+  __device__ __forceinline__ int32_t gt_key(int g) const { return area_g[g]; }
+  __device__ __forceinline__ double iou(int d, int g, int32_t ag, bool crowd) const {
+    const int64_t i = inter[(int64_t)d * G + g];
+    const int64_t u = crowd ? (int64_t)area_d[d] : (int64_t)area_d[d] + ag - i;
+    return u == 0 ? 0.0 : (double)i / (double)u;
+  }
+  __device__ __forceinline__ double det_area(int d) const { return (double)area_d[d]; }
+};
+
+// Boxes (mask_eval.box_iou_host, the `bbIou` rule). A detection is a row (x0, y0, x1, y1, score) of float32 as the results hold
+// it: every coordinate is widened to double, then w = x1 - x0 and h = y1 - y0 in double (mask_eval.det_boxes_xywh_host). A ground
+// truth is (x, y, w, h) in double. Every operation below is an IEEE double operation of its own: contraction is off, since a
+// product fused into the following add rounds once where the rule rounds twice.
+struct CmBox {
+  double x, y, w, h;
+};
+
+__device__ __forceinline__ CmBox cm_det_box(const float* __restrict__ det5, int d) {
+#pragma clang fp contract(off)
+  const float* b = det5 + (int64_t)d * 5;
+  const double x0 = (double)b[0], y0 = (double)b[1], x1 = (double)b[2], y1 = (double)b[3];
+  return CmBox{x0, y0, x1 - x0, y1 - y0};
 }
 
+__device__ __forceinline__ CmBox cm_gt_box(const double* __restrict__ gt4, int g) {
+  const double* b = gt4 + (int64_t)g * 4;
+  return CmBox{b[0], b[1], b[2], b[3]};
+}
+
+__device__ __forceinline__ double cm_box_area(const CmBox& b) {
+#pragma clang fp contract(off)
+  return b.w * b.h;
+}
+
+__device__ __forceinline__ double cm_box_iou(const CmBox& D, const CmBox& G, bool crowd) {
+#pragma clang fp contract(off)
+  const double da = D.w * D.h, ga = G.w * G.h;
+  const double w = fmin(D.w + D.x, G.w + G.x) - fmax(D.x, G.x);
+  if (w <= 0) return 0.0;
+  const double h = fmin(D.h + D.y, G.h + G.y) - fmax(D.y, G.y);
+  if (h <= 0) return 0.0;
+  const double i = w * h;
+  const double u = crowd ? da : (da + ga) - i;
+  return i / u;
+}
+
+struct CmBoxIou {
+  const float* __restrict__ det5;
+  const double* __restrict__ gt4;
+  // nothing is staged per ground truth: its 32 bytes are read where the IoU block is filled (1024 of them do not fit the static LDS
+  // besides that block and the scan orders; the scan itself reads no box)
+  __device__ __forceinline__ int32_t gt_key(int) const { return 0; }
+  __device__ __forceinline__ double iou(int d, int g, int32_t, bool crowd) const {
+    return cm_box_iou(cm_det_box(det5, d), cm_gt_box(gt4, g), crowd);
+  }
+  __device__ __forceinline__ double det_area(int d) const { return cm_box_area(cm_det_box(det5, d)); }
+};
+
+template <class Iou>
 __global__ __launch_bounds__(CM_MAX_T* CM_MAX_A) void cgg_coco_match_kernel(
-    const int32_t* __restrict__ inter, const int32_t* __restrict__ area_d, const int32_t* __restrict__ area_g,
-    const int32_t* __restrict__ det_order, const int32_t* __restrict__ det_cats, const int32_t* __restrict__ gt_cats,
+    const Iou src, const int32_t* __restrict__ det_order, const int32_t* __restrict__ det_cats, const int32_t* __restrict__ gt_cats,
     const uint8_t* __restrict__ gt_crowd, const double* __restrict__ gt_area, const int32_t* __restrict__ cat_ids, int K,
     const double* __restrict__ area_rngs, int A, const double* __restrict__ iou_thrs, int T, int D, int G, int max_det,
     int class_agnostic, int32_t* __restrict__ dt_match, uint8_t* __restrict__ dt_ignore, uint8_t* __restrict__ gt_ignore,
     int32_t* __restrict__ counts) {
   __shared__ uint16_t dsel[MI_MAX_PLANES];             // the category's detections, in score order
   __shared__ uint16_t gsel[MI_MAX_PLANES];             // its ground truths, in their order
-  __shared__ uint16_t ord[CM_MAX_A][MI_MAX_PLANES];    // per area range: positions in gsel in scan order
-  __shared__ int32_t g_area[MI_MAX_PLANES];            // area_g of gsel[p]
+  __shared__ uint16_t ord[CM_MAX_A][MI_MAX_PLANES];    // per area range: positions in gsel in scan order, bit 15 = crowd
+  __shared__ int32_t g_key[MI_MAX_PLANES];             // src.gt_key of gsel[p] (masks: area_g)
   __shared__ uint8_t g_crowd[MI_MAX_PLANES];
   __shared__ double g_own_area[MI_MAX_PLANES];         // gt_area of gsel[p]
   __shared__ double iou_lds[CM_IOU_LDS];
@@ -303,7 +367,7 @@ __global__ __launch_bounds__(CM_MAX_T* CM_MAX_A) void cgg_coco_match_kernel(
       const int pos = cnt + __popcll(b & below);
       if (f) {
         gsel[pos] = (uint16_t)g;
-        g_area[pos] = area_g[g];
+        g_key[pos] = src.gt_key(g);
         g_crowd[pos] = gt_crowd[g] != 0;
         g_own_area[pos] = gt_area[g];
       }
@@ -320,14 +384,15 @@ __global__ __launch_bounds__(CM_MAX_T* CM_MAX_A) void cgg_coco_match_kernel(
       for (int pass = 0; pass < 2; ++pass) {
         for (int base = 0; base < Gk; base += 64) {
           const int p = base + lane;
-          bool f = false;
+          bool f = false, crowd = false;
           if (p < Gk) {
             const double ga = g_own_area[p];           // (written by this wave, above)
-            const bool ignored = g_crowd[p] != 0 || ga < lo || ga > hi;
+            crowd = g_crowd[p] != 0;
+            const bool ignored = crowd || ga < lo || ga > hi;
             f = ignored == (pass == 1);
           }
           const uint64_t b = __ballot(f);
-          if (f) ord[a][c + __popcll(b & below)] = (uint16_t)p;
+          if (f) ord[a][c + __popcll(b & below)] = (uint16_t)(p | (crowd ? 0x8000 : 0));
           c += __popcll(b);
         }
         if (pass == 0 && lane == 0) nreg[a] = c;
@@ -336,12 +401,6 @@ __global__ __launch_bounds__(CM_MAX_T* CM_MAX_A) void cgg_coco_match_kernel(
   }
   __syncthreads();
   const int Dk = n_sel[0], Gk = n_sel[1];
-  const bool iou_staged = (int64_t)Dk * Gk <= CM_IOU_LDS;
-  if (iou_staged)
-    for (int e = tid; e < Dk * Gk; e += blockDim.x) {
-      const int di = e / Gk, p = e - di * Gk;
-      iou_lds[e] = cm_iou(inter, area_d, g_area[p], G, dsel[di], gsel[p], g_crowd[p] != 0);
-    }
   // what lies past D_k / G_k is written too, as zeros; the ignore flags of the ground truths in scan order; the counts
   int32_t* dtm_k = dt_match + (int64_t)k * A * T * D;
   uint8_t* dti_k = dt_ignore + (int64_t)k * A * T * D;
@@ -359,43 +418,76 @@ __global__ __launch_bounds__(CM_MAX_T* CM_MAX_A) void cgg_coco_match_kernel(
     counts[2 * k] = Dk;
     counts[2 * k + 1] = Gk;
   }
-  __syncthreads();
-  if (tid >= A * T) return;
-  const int a = tid / T, t = tid - a * T;
+  // The scan, over chunks of detections whose IoU rows fit the LDS block (one chunk when D_k * G_k <= CM_IOU_LDS; G_k <= 1024, so
+  // a chunk holds at least two detections): all threads fill the chunk's block, the scanning threads walk it. Every thread of the
+  // workgroup stays for the barriers; Dk, Gk and the chunk are uniform.
+  const bool scans = tid < A * T;
+  const int a = scans ? tid / T : 0, t = scans ? tid - a * T : 0;
   const double lo = area_rngs[2 * a], hi = area_rngs[2 * a + 1];
   const double thr = iou_thrs[t];
   const int n_count = nreg[a];
-  uint32_t matched[MI_MAX_PLANES / 32];                 // per position in gsel: matched at this threshold
+  uint32_t matched[MI_MAX_PLANES / 32];                 // per position in the scan order: matched at this threshold
   for (int w = 0; w < (Gk + 31) / 32; ++w) matched[w] = 0;
   int32_t* dtm = dtm_k + (int64_t)tid * D;
   uint8_t* dti = dti_k + (int64_t)tid * D;
-  for (int di = 0; di < Dk; ++di) {
-    const int d = dsel[di];
-    double best = thr < 1 - 1e-10 ? thr : 1 - 1e-10;
-    int m = -1;
-    bool m_ignored = false;
-    for (int gi = 0; gi < Gk; ++gi) {
-      const bool ignored = gi >= n_count;
-      if (ignored && m > -1 && !m_ignored) break;        // matched one that counts: the ignored ones are not scanned
-      const int p = ord[a][gi];
-      const bool crowd = g_crowd[p] != 0;
-      if (((matched[p >> 5] >> (p & 31)) & 1u) && !crowd) continue;
-      const double v = iou_staged ? iou_lds[di * Gk + p] : cm_iou(inter, area_d, g_area[p], G, d, gsel[p], crowd);
-      if (v < best) continue;
-      best = v;
-      m = p;
-      m_ignored = ignored;
+  const int chunk = Gk > 0 && (int64_t)Dk * Gk > CM_IOU_LDS ? CM_IOU_LDS / Gk : Dk;
+  for (int c0 = 0; c0 < Dk; c0 += chunk) {
+    const int cn = Dk - c0 < chunk ? Dk - c0 : chunk;
+    __syncthreads();                                    // the previous chunk has been scanned (first: dsel .. nreg are written)
+    for (int e = tid; e < cn * Gk; e += blockDim.x) {
+      const int ci = e / Gk, p = e - ci * Gk;
+      iou_lds[e] = src.iou(dsel[c0 + ci], gsel[p], g_key[p], g_crowd[p] != 0);
     }
-    if (m > -1) {
-      matched[m >> 5] |= 1u << (m & 31);
-      dtm[di] = (int32_t)gsel[m] + 1;
-      dti[di] = m_ignored ? 1 : 0;
-    } else {
-      const double da = (double)area_d[d];
-      dtm[di] = 0;
-      dti[di] = (da < lo || da > hi) ? 1 : 0;
+    __syncthreads();
+    if (!scans) continue;
+    for (int di = c0; di < c0 + cn; ++di) {
+      double best = thr < 1 - 1e-10 ? thr : 1 - 1e-10;
+      int m = -1, m_gi = 0;
+      bool m_ignored = false;
+      const double* row = iou_lds + (di - c0) * Gk;
+      // the scan's chain of dependent LDS reads is its cost: the order entry (which carries the crowd flag) is read one step ahead,
+      // and the matched bits go by scan position, which all lanes share
+      uint32_t o_next = Gk > 0 ? ord[a][0] : 0;
+      for (int gi = 0; gi < Gk; ++gi) {
+        const uint32_t o = o_next;
+        o_next = ord[a][gi + 1 < Gk ? gi + 1 : gi];
+        const bool ignored = gi >= n_count;
+        if (ignored && m > -1 && !m_ignored) break;      // matched one that counts: the ignored ones are not scanned
+        if (((matched[gi >> 5] >> (gi & 31)) & 1u) && !(o & 0x8000u)) continue;      // (matched and not crowd)
+        const int p = (int)(o & 0x7fffu);
+        const double v = row[p];
+        if (v < best) continue;
+        best = v;
+        m = p;
+        m_gi = gi;
+        m_ignored = ignored;
+      }
+      if (m > -1) {
+        matched[m_gi >> 5] |= 1u << (m_gi & 31);
+        dtm[di] = (int32_t)gsel[m] + 1;
+        dti[di] = m_ignored ? 1 : 0;
+      } else {
+        const double da = src.det_area(dsel[di]);
+        dtm[di] = 0;
+        dti[di] = (da < lo || da > hi) ? 1 : 0;
+      }
     }
   }
+}
+
+// iou[d][g] and area_d[d] of cgg_box_iou_f64: one thread per pair (per detection when G = 0), the arithmetic of the matcher
+constexpr int BI_THREADS = 256;
+
+__global__ __launch_bounds__(BI_THREADS) void cgg_box_iou_kernel(const float* __restrict__ det5, int D, const double* __restrict__ gt4,
+                                                                 const uint8_t* __restrict__ gt_crowd, int G, double* __restrict__ iou,
+                                                                 double* __restrict__ area_d) {
+  const int e = blockIdx.x * BI_THREADS + threadIdx.x;
+  const int gn = G > 0 ? G : 1;
+  if (e >= D * gn) return;
+  const int d = e / gn, g = e - d * gn;
+  const CmBoxIou src{det5, gt4};
+  if (g == 0) area_d[d] = src.det_area(d);
+  if (G > 0) iou[(int64_t)d * G + g] = src.iou(d, g, 0, gt_crowd[g] != 0);
 }
 
 }  // namespace
@@ -457,9 +549,49 @@ extern "C" int cgg_coco_match(const int32_t* inter, const int32_t* area_d, const
   CGG_REQUIRE((((uintptr_t)gt_area | (uintptr_t)area_rngs | (uintptr_t)iou_thrs) & 7u) == 0, CGG_EINVAL,
               "cgg_coco_match: gt_area / area_rngs / iou_thrs must be 8-byte aligned");
   const int threads = ((A * T + 63) / 64) * 64;         // one thread per (area range, threshold), whole waves
-  hipLaunchKernelGGL(cgg_coco_match_kernel, dim3((unsigned)K), dim3(threads), 0, (hipStream_t)stream, inter, area_d, area_g, det_order,
-                     det_cats, gt_cats, gt_crowd, gt_area, cat_ids, K, area_rngs, A, iou_thrs, T, D, G, max_det, class_agnostic,
-                     dt_match, dt_ignore, gt_ignore, counts);
+  hipLaunchKernelGGL(cgg_coco_match_kernel<CmMaskIou>, dim3((unsigned)K), dim3(threads), 0, (hipStream_t)stream,
+                     CmMaskIou{inter, area_d, area_g, G}, det_order, det_cats, gt_cats, gt_crowd, gt_area, cat_ids, K, area_rngs, A,
+                     iou_thrs, T, D, G, max_det, class_agnostic, dt_match, dt_ignore, gt_ignore, counts);
   CGG_CHECK_LAUNCH("cgg_coco_match");
+  return CGG_OK;
+}
+
+extern "C" int cgg_box_iou_f64(const float* det_boxes5, int D, const double* gt_boxes_xywh, const uint8_t* gt_crowd, int G, double* iou,
+                               double* area_d, cgg_stream_t stream) {
+  CGG_REQUIRE(D >= 0 && G >= 0, CGG_EINVAL, "cgg_box_iou_f64: bad sizes (D=%d G=%d)", D, G);
+  CGG_REQUIRE(D <= MI_MAX_PLANES && G <= MI_MAX_PLANES, CGG_EUNSUPPORTED, "cgg_box_iou_f64: D=%d / G=%d above %d", D, G, MI_MAX_PLANES);
+  CGG_REQUIRE((D == 0 || (det_boxes5 && area_d)) && (G == 0 || (gt_boxes_xywh && gt_crowd)) && (D == 0 || G == 0 || iou), CGG_EINVAL,
+              "cgg_box_iou_f64: null pointer");
+  CGG_REQUIRE((((uintptr_t)det_boxes5) & 3u) == 0 && (((uintptr_t)gt_boxes_xywh | (uintptr_t)iou | (uintptr_t)area_d) & 7u) == 0,
+              CGG_EINVAL, "cgg_box_iou_f64: det_boxes5 must be 4-byte, gt_boxes_xywh / iou / area_d 8-byte aligned");
+  if (D == 0) return CGG_OK;
+  const int n = D * (G > 0 ? G : 1);                    // (<= 2^20)
+  hipLaunchKernelGGL(cgg_box_iou_kernel, dim3((unsigned)((n + BI_THREADS - 1) / BI_THREADS)), dim3(BI_THREADS), 0, (hipStream_t)stream,
+                     det_boxes5, D, gt_boxes_xywh, gt_crowd, G, iou, area_d);
+  CGG_CHECK_LAUNCH("cgg_box_iou_f64");
+  return CGG_OK;
+}
+
+extern "C" int cgg_coco_match_boxes(const float* det_boxes5, const double* gt_boxes_xywh, const int32_t* det_order,
+                                    const int32_t* det_cats, const int32_t* gt_cats, const uint8_t* gt_crowd, const double* gt_area,
+                                    const int32_t* cat_ids, int K, const double* area_rngs, int A, const double* iou_thrs, int T, int D,
+                                    int G, int max_det, int class_agnostic, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore,
+                                    int32_t* counts, cgg_stream_t stream) {
+  CGG_REQUIRE(D >= 0 && G >= 0 && K >= 1 && A >= 1 && T >= 1 && max_det >= 0, CGG_EINVAL,
+              "cgg_coco_match_boxes: bad sizes (D=%d G=%d K=%d A=%d T=%d max_det=%d)", D, G, K, A, T, max_det);
+  CGG_REQUIRE(T <= CM_MAX_T && A <= CM_MAX_A && K <= CM_MAX_K && D <= MI_MAX_PLANES && G <= MI_MAX_PLANES, CGG_EUNSUPPORTED,
+              "cgg_coco_match_boxes: T=%d A=%d K=%d D=%d G=%d above %d / %d / %d / %d / %d", T, A, K, D, G, CM_MAX_T, CM_MAX_A, CM_MAX_K,
+              MI_MAX_PLANES, MI_MAX_PLANES);
+  CGG_REQUIRE(cat_ids && area_rngs && iou_thrs && counts && (D == 0 || (det_boxes5 && det_order && det_cats && dt_match && dt_ignore)) &&
+                  (G == 0 || (gt_boxes_xywh && gt_cats && gt_crowd && gt_area && gt_ignore)),
+              CGG_EINVAL, "cgg_coco_match_boxes: null pointer");
+  CGG_REQUIRE((((uintptr_t)det_boxes5) & 3u) == 0 &&
+                  (((uintptr_t)gt_boxes_xywh | (uintptr_t)gt_area | (uintptr_t)area_rngs | (uintptr_t)iou_thrs) & 7u) == 0,
+              CGG_EINVAL, "cgg_coco_match_boxes: det_boxes5 must be 4-byte, gt_boxes_xywh / gt_area / area_rngs / iou_thrs 8-byte aligned");
+  const int threads = ((A * T + 63) / 64) * 64;
+  hipLaunchKernelGGL(cgg_coco_match_kernel<CmBoxIou>, dim3((unsigned)K), dim3(threads), 0, (hipStream_t)stream,
+                     CmBoxIou{det_boxes5, gt_boxes_xywh}, det_order, det_cats, gt_cats, gt_crowd, gt_area, cat_ids, K, area_rngs, A,
+                     iou_thrs, T, D, G, max_det, class_agnostic, dt_match, dt_ignore, gt_ignore, counts);
+  CGG_CHECK_LAUNCH("cgg_coco_match_boxes");
   return CGG_OK;
 }

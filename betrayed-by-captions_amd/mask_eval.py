@@ -1,19 +1,22 @@
-"""COCO instance-mask evaluation (`--eval segm`) on bit-packed masks: the rules in numpy, and `SegmEvaluator`, which runs them on the
-host or hands the two costly steps to the device (csrc/mask_eval.hip through `ops.mask_intersections` / `ops.coco_match`).
+"""COCO instance-mask evaluation (`--eval segm`) on bit-packed masks and COCO box evaluation (`--eval bbox`): the rules in numpy, and
+`SegmEvaluator` / `BboxEvaluator`, which run them on the host or hand the costly steps to the device (csrc/mask_eval.hip through
+`ops.mask_intersections` / `ops.coco_match`, and `ops.coco_match_boxes`).
 
 The rules restate the reference's own evaluator, [3P] open_set/utils/eval/cocoeval.py (pycocotools' COCOeval with a `class_agnostic`
 extension), and the base / novel / all average of open_set/datasets/coco_open.py:583-637:
 
   mask_intersections_host   |d & g| for every detection d and ground truth g of an image, and the areas
   mask_iou_host             pycocotools `rleIou`: inter / union, inter / area_d for a crowd, 0 where the denominator is 0
+  det_boxes_xywh_host       coco_open.py:359-377 `xyxy2xywh` and the JSON round trip of the result file
+  box_iou_host              the published maskApi.c `bbIou` on xywh boxes, every double operation rounded on its own
   evaluate_img_host         COCOeval.evaluateImg (cocoeval.py:244-325) for all (category, area range, threshold) of one image
   accumulate_host           COCOeval.accumulate (cocoeval.py:327-432)
   summarize_host            COCOeval._summarize, the twelve values of the standard COCO summary
   open_set_ap_host          coco_open.py:583-637
 
 Masks are bit planes as `cgg_rle_transitions` reads them: (n, H, row_bytes) uint8, pixel x of a row = bit (x & 7) of byte (x >> 3);
-only the first `width` pixels of a row count, pad bits may hold anything. The kernels equal the first three rules exactly (integers
-and IEEE double operations in a fixed order); accumulation stays on the host, its input is small.
+only the first `width` pixels of a row count, pad bits may hold anything. The kernels equal the first five rules exactly (integers
+and IEEE double operations in a fixed order, none fused); accumulation stays on the host, its input is small.
 """
 import numpy as np
 
@@ -88,6 +91,41 @@ def mask_iou_host(inter, area_d, area_g, gt_crowd):
     den = np.where(crowd, area_d + 0 * area_g, area_d + area_g - inter)
     out = np.zeros(inter.shape, np.float64)
     np.divide(inter.astype(np.float64), den.astype(np.float64), out=out, where=den != 0)
+    return out
+
+
+def det_boxes_xywh_host(det_boxes5):
+    """(D, 5) float32 (x0, y0, x1, y1, score), as the results hold them -> (D, 4) float64 (x, y, w, h): what the reference's
+    `xyxy2xywh` (coco_open.py:359-377) writes into the result file and `loadRes` reads back. `tolist()` widens every float32
+    coordinate to a Python float (float64), then x1 - x0 and y1 - y0 are float64 subtractions; JSON round-trips a float64."""
+    b = np.asarray(det_boxes5).reshape(-1, 5)[:, :4].astype(np.float32).astype(np.float64)
+    return np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], axis=1)
+
+
+def box_iou_host(det_xywh, gt_xywh, gt_crowd):
+    """float64 (D, G): the rule of `bbIou` in the published maskApi.c on (x, y, w, h) boxes. Per pair of detection D and ground
+    truth G:
+
+        da = D.w * D.h;  ga = G.w * G.h
+        w = min(D.w + D.x, G.w + G.x) - max(D.x, G.x);  if w <= 0 the value is 0
+        h = min(D.h + D.y, G.h + G.y) - max(D.y, G.y);  if h <= 0 the value is 0
+        i = w * h;  u = da for a crowd ground truth, else (da + ga) - i;  the value is i / u
+
+    Every operation is an IEEE float64 operation of its own: no product is fused into the following add (numpy does not fuse; the
+    kernel is built with contraction off for this function). THE RULE IS WHAT IS PINNED, here and in the kernel, bit for bit; no
+    equality with a particular pycocotools build is claimed (a C compiler is free to contract `da + ga - i` there)."""
+    d = np.asarray(det_xywh, np.float64).reshape(-1, 1, 4)
+    g = np.asarray(gt_xywh, np.float64).reshape(1, -1, 4)
+    crowd = np.asarray(gt_crowd).astype(bool).reshape(1, -1)
+    da = d[..., 2] * d[..., 3]
+    ga = g[..., 2] * g[..., 3]
+    w = np.minimum(d[..., 2] + d[..., 0], g[..., 2] + g[..., 0]) - np.maximum(d[..., 0], g[..., 0])
+    h = np.minimum(d[..., 3] + d[..., 1], g[..., 3] + g[..., 1]) - np.maximum(d[..., 1], g[..., 1])
+    i = w * h
+    u = np.where(crowd, da, (da + ga) - i)
+    out = np.zeros(i.shape, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        np.divide(i, u, out=out, where=~((w <= 0) | (h <= 0)))
     return out
 
 
@@ -284,21 +322,10 @@ def pack_bool_rows_host(masks):
     return np.packbits(masks, axis=2, bitorder='little')
 
 
-class SegmEvaluator:
-    """COCO mask AP of a stream of images, from the device results of `simple_test(device_results=True, mask_bits=True)`.
-
-    cat_ids: label -> category id of the detections' labels (the reference's `pred_cats`); ground-truth labels ARE category ids,
-    and a ground truth of a category outside cat_ids takes no part (the reference loads ground truth by `catIds`).
-    unknown_cat_ids / all_cat_ids: the novel categories and the categories present in the dataset, for base / novel / all AP50
-    (`open_set_ap_host`); both default to "no novel category, every category present".
-
-    device=None: the host rule on numpy arrays -- the comparison side and the CPU path. With a device, `add` launches
-    `ops.mask_intersections` and `ops.coco_match` on the current stream and queues one pinned device-to-host copy of the match
-    records; no mask leaves the device and nothing synchronises before `summarize()` (an `add` beyond `max_in_flight` queued
-    copies waits for the oldest one). Shapes outside `ops.mask_eval_ok` take the host rule.
-
-    skip_images_without_gt: leave out an image that has no ground truth of cat_ids, as the reference's `_get_valid_imgs` does
-    for its per-split runs (coco_open.py:567)."""
+class _CocoEvaluator:
+    """What `SegmEvaluator` and `BboxEvaluator` share: everything after an image's IoU matrix. The constructor, the record format
+    (per image the [K][A] list of `evaluate_img_host`, or a pending device record), the one-buffer pinned copy of the device match
+    records, `image_records` and `summarize`. A subclass adds `add`."""
 
     def __init__(self, cat_ids, unknown_cat_ids=None, all_cat_ids=None, max_dets=(100, 300, 1000), iou_thrs=None,
                  class_agnostic=False, device=None, skip_images_without_gt=False, max_in_flight=8):
@@ -324,80 +351,14 @@ class SegmEvaluator:
                 area_rngs=torch.tensor(self.area_rngs, dtype=torch.float64, device=self.device),
                 iou_thrs=torch.tensor(self.iou_thrs, dtype=torch.float64, device=self.device))
 
-    # -- one image ---------------------------------------------------------------------------------
-    def add(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd=None, gt_area=None):
-        """det_labels (D,) labels into cat_ids, det_boxes5 (D, 5) with the score last, det_masks (D, H, row_bytes) uint8 bit planes (or
-        (D, H, W) bool bitmaps, which are packed first);
-        gt_masks (G, H, W) bool / uint8 bitmaps (host or device; W is the image's width), gt_labels (G,) category ids, gt_crowd
-        (G,) or None (no crowd), gt_area (G,) the annotations' own `area` or None (the pixel count)."""
-        W = int(gt_masks.shape[2])
-        H = int(gt_masks.shape[1])
-        if len(det_masks.shape) != 3:
-            raise ValueError('SegmEvaluator.add: det_masks must be (D, H, row_bytes) bit planes (mask_bits=True)')
-        if str(det_masks.dtype).endswith('bool'):
-            # `mask_bits=True` is a request: geometries outside `ops.instance_masks_bitpack_ok` come back as (D, H, W) bool bitmaps
-            if self.device is not None and hasattr(det_masks, 'is_cuda') and det_masks.is_cuda:
-                from . import ops
-                det_masks = ops.pack_bool_masks(det_masks)
-            else:
-                det_masks = pack_bool_rows_host(_to_numpy(det_masks))
-        if int(det_masks.shape[1]) != H or int(det_masks.shape[2]) * 8 < W:
-            raise ValueError(f'SegmEvaluator.add: det_masks {tuple(det_masks.shape)} do not cover ground truth of {H} x {W}')
-        if self.skip_images_without_gt:
-            gl = _to_numpy(gt_labels)
-            if not np.isin(gl, self.cat_ids).any():
-                return
-        use_device = False
-        if self.device is not None:
-            from . import ops
-            use_device = ops.mask_eval_ok(int(det_masks.shape[0]), int(gt_masks.shape[0]), H, W)
-        if use_device:
-            self._add_device(det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, H, W)
-        else:
-            self._add_host(det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, W)
-
-    def _add_host(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, W):
-        det_bits = _to_numpy(det_masks)
-        if det_bits.dtype != np.uint8:
-            raise ValueError('SegmEvaluator.add: det_masks must be uint8 bit planes (mask_bits=True)')
-        gt_bits = pack_bool_rows_host(_to_numpy(gt_masks))
-        G = gt_bits.shape[0]
-        scores = _to_numpy(det_boxes5).reshape(-1, 5)[:, 4].astype(np.float64)
-        det_cats = np.asarray(self.cat_ids, np.int64)[_to_numpy(det_labels).astype(np.int64)] if len(scores) else np.zeros(0, np.int64)
-        crowd = np.zeros(G, bool) if gt_crowd is None else _to_numpy(gt_crowd).astype(bool)
-        inter, area_d, area_g = mask_intersections_host(det_bits, gt_bits, W)
-        area = area_g.astype(np.float64) if gt_area is None else _to_numpy(gt_area).astype(np.float64)
-        iou = mask_iou_host(inter, area_d, area_g, crowd)
-        self.records.append(evaluate_img_host(iou, scores, det_cats, _to_numpy(gt_labels), crowd, area, area_d, self.cat_ids,
-                                              self.area_rngs, self.iou_thrs, self.max_dets[-1], self.class_agnostic))
-
-    def _add_device(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, H, W):
+    def _queue_match(self, match, D, G, order, det_cats, scores):
+        """The device half of one `add` after its inputs are on the device: `match(out)` launches the matcher into the four output
+        tensors; they, the score order, the categories and the scores share one byte buffer, so that one pinned copy carries all
+        the host needs; an event follows the copy. Nothing waits (an `add` beyond `max_in_flight` queued copies waits for the
+        oldest one)."""
         import torch
-        from . import ops
         dev = self.device
-        D, G = int(det_masks.shape[0]), int(gt_masks.shape[0])
         K, A, T = len(self.cat_ids), len(self.area_rngs), len(self.iou_thrs)
-
-        def on_device(x, dtype):
-            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-            return t.to(device=dev, dtype=dtype, non_blocking=True)
-
-        gm = gt_masks if torch.is_tensor(gt_masks) else torch.from_numpy(np.ascontiguousarray(gt_masks))
-        if gm.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f'SegmEvaluator.add: gt_masks must be bool or uint8 bitmaps (got {gm.dtype})')
-        gm = gm.to(dev, non_blocking=True)                                      # host arrays: one H2D, packed on the device
-        gt_bits = ops.pack_bool_masks(gm.view(torch.bool) if gm.dtype == torch.uint8 else gm)      # (the kernel reads non-zero = set)
-        scores = on_device(det_boxes5, torch.float32).reshape(-1, 5)[:, 4].contiguous()
-        det_cats = self._dev['cat_ids'][on_device(det_labels, torch.int64)] if D else torch.zeros(0, dtype=torch.int32, device=dev)
-        order = torch.sort(scores, descending=True, stable=True).indices.to(torch.int32)
-        gt_cats = on_device(gt_labels, torch.int32)
-        crowd = torch.zeros(G, dtype=torch.uint8, device=dev) if gt_crowd is None else on_device(gt_crowd, torch.uint8)
-        det_masks = det_masks if torch.is_tensor(det_masks) else torch.from_numpy(np.ascontiguousarray(det_masks))
-        if det_masks.dtype != torch.uint8:
-            raise ValueError(f'SegmEvaluator.add: det_masks must be uint8 bit planes or bool bitmaps (got {det_masks.dtype})')
-        inter, area_d, area_g = ops.mask_intersections(det_masks.to(dev, non_blocking=True), gt_bits, W)
-        area = area_g.to(torch.float64) if gt_area is None else on_device(gt_area, torch.float64)
-        # one byte buffer holds everything the host needs, so that one copy carries it
         sizes = [('dt_match', 4 * K * A * T * D), ('counts', 4 * K * 2), ('order', 4 * D), ('det_cats', 4 * D), ('scores', 4 * D),
                  ('dt_ignore', K * A * T * D), ('gt_ignore', K * A * G)]
         offs, total = {}, 0
@@ -412,9 +373,7 @@ class SegmEvaluator:
 
         dt_match, counts = part('dt_match', torch.int32, (K, A, T, D)), part('counts', torch.int32, (K, 2))
         dt_ignore, gt_ignore = part('dt_ignore', torch.uint8, (K, A, T, D)), part('gt_ignore', torch.uint8, (K, A, G))
-        ops.coco_match(inter, area_d, area_g, order, det_cats, gt_cats, crowd, area, self._dev['cat_ids'], self._dev['area_rngs'],
-                       self._dev['iou_thrs'], self.max_dets[-1], self.class_agnostic,
-                       out=(dt_match, dt_ignore, gt_ignore, counts))
+        match((dt_match, dt_ignore, gt_ignore, counts))
         part('order', torch.int32, (D,)).copy_(order)
         part('det_cats', torch.int32, (D,)).copy_(det_cats)
         part('scores', torch.float32, (D,)).copy_(scores)
@@ -470,6 +429,167 @@ class SegmEvaluator:
                     base_ap50=base, novel_ap50=novel, all_ap50=both, images=len(records))
 
 
+class SegmEvaluator(_CocoEvaluator):
+    """COCO mask AP of a stream of images, from the device results of `simple_test(device_results=True, mask_bits=True)`.
+
+    cat_ids: label -> category id of the detections' labels (the reference's `pred_cats`); ground-truth labels ARE category ids,
+    and a ground truth of a category outside cat_ids takes no part (the reference loads ground truth by `catIds`).
+    unknown_cat_ids / all_cat_ids: the novel categories and the categories present in the dataset, for base / novel / all AP50
+    (`open_set_ap_host`); both default to "no novel category, every category present".
+
+    device=None: the host rule on numpy arrays -- the comparison side and the CPU path. With a device, `add` launches
+    `ops.mask_intersections` and `ops.coco_match` on the current stream and queues one pinned device-to-host copy of the match
+    records; no mask leaves the device and nothing synchronises before `summarize()` (an `add` beyond `max_in_flight` queued
+    copies waits for the oldest one). Shapes outside `ops.mask_eval_ok` take the host rule.
+
+    skip_images_without_gt: leave out an image that has no ground truth of cat_ids, as the reference's `_get_valid_imgs` does
+    for its per-split runs (coco_open.py:567)."""
+
+    # -- one image ---------------------------------------------------------------------------------
+    def add(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd=None, gt_area=None):
+        """det_labels (D,) labels into cat_ids, det_boxes5 (D, 5) with the score last, det_masks (D, H, row_bytes) uint8 bit planes (or
+        (D, H, W) bool bitmaps, which are packed first);
+        gt_masks (G, H, W) bool / uint8 bitmaps (host or device; W is the image's width), gt_labels (G,) category ids, gt_crowd
+        (G,) or None (no crowd), gt_area (G,) the annotations' own `area` or None (the pixel count)."""
+        W = int(gt_masks.shape[2])
+        H = int(gt_masks.shape[1])
+        if len(det_masks.shape) != 3:
+            raise ValueError('SegmEvaluator.add: det_masks must be (D, H, row_bytes) bit planes (mask_bits=True)')
+        if str(det_masks.dtype).endswith('bool'):
+            # `mask_bits=True` is a request: geometries outside `ops.instance_masks_bitpack_ok` come back as (D, H, W) bool bitmaps
+            if self.device is not None and hasattr(det_masks, 'is_cuda') and det_masks.is_cuda:
+                from . import ops
+                det_masks = ops.pack_bool_masks(det_masks)
+            else:
+                det_masks = pack_bool_rows_host(_to_numpy(det_masks))
+        if int(det_masks.shape[1]) != H or int(det_masks.shape[2]) * 8 < W:
+            raise ValueError(f'SegmEvaluator.add: det_masks {tuple(det_masks.shape)} do not cover ground truth of {H} x {W}')
+        if self.skip_images_without_gt:
+            gl = _to_numpy(gt_labels)
+            if not np.isin(gl, self.cat_ids).any():
+                return
+        use_device = False
+        if self.device is not None:
+            from . import ops
+            use_device = ops.mask_eval_ok(int(det_masks.shape[0]), int(gt_masks.shape[0]), H, W)
+        if use_device:
+            self._add_device(det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, H, W)
+        else:
+            self._add_host(det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, W)
+
+    def _add_host(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, W):
+        det_bits = _to_numpy(det_masks)
+        if det_bits.dtype != np.uint8:
+            raise ValueError('SegmEvaluator.add: det_masks must be uint8 bit planes (mask_bits=True)')
+        gt_bits = pack_bool_rows_host(_to_numpy(gt_masks))
+        G = gt_bits.shape[0]
+        scores = _to_numpy(det_boxes5).reshape(-1, 5)[:, 4].astype(np.float64)
+        det_cats = np.asarray(self.cat_ids, np.int64)[_to_numpy(det_labels).astype(np.int64)] if len(scores) else np.zeros(0, np.int64)
+        crowd = np.zeros(G, bool) if gt_crowd is None else _to_numpy(gt_crowd).astype(bool)
+        inter, area_d, area_g = mask_intersections_host(det_bits, gt_bits, W)
+        area = area_g.astype(np.float64) if gt_area is None else _to_numpy(gt_area).astype(np.float64)
+        iou = mask_iou_host(inter, area_d, area_g, crowd)
+        self.records.append(evaluate_img_host(iou, scores, det_cats, _to_numpy(gt_labels), crowd, area, area_d, self.cat_ids,
+                                              self.area_rngs, self.iou_thrs, self.max_dets[-1], self.class_agnostic))
+
+    def _add_device(self, det_labels, det_boxes5, det_masks, gt_masks, gt_labels, gt_crowd, gt_area, H, W):
+        import torch
+        from . import ops
+        dev = self.device
+        D, G = int(det_masks.shape[0]), int(gt_masks.shape[0])
+
+        def on_device(x, dtype):
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            return t.to(device=dev, dtype=dtype, non_blocking=True)
+
+        gm = gt_masks if torch.is_tensor(gt_masks) else torch.from_numpy(np.ascontiguousarray(gt_masks))
+        if gm.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'SegmEvaluator.add: gt_masks must be bool or uint8 bitmaps (got {gm.dtype})')
+        gm = gm.to(dev, non_blocking=True)                                      # host arrays: one H2D, packed on the device
+        gt_bits = ops.pack_bool_masks(gm.view(torch.bool) if gm.dtype == torch.uint8 else gm)      # (the kernel reads non-zero = set)
+        scores = on_device(det_boxes5, torch.float32).reshape(-1, 5)[:, 4].contiguous()
+        det_cats = self._dev['cat_ids'][on_device(det_labels, torch.int64)] if D else torch.zeros(0, dtype=torch.int32, device=dev)
+        order = torch.sort(scores, descending=True, stable=True).indices.to(torch.int32)
+        gt_cats = on_device(gt_labels, torch.int32)
+        crowd = torch.zeros(G, dtype=torch.uint8, device=dev) if gt_crowd is None else on_device(gt_crowd, torch.uint8)
+        det_masks = det_masks if torch.is_tensor(det_masks) else torch.from_numpy(np.ascontiguousarray(det_masks))
+        if det_masks.dtype != torch.uint8:
+            raise ValueError(f'SegmEvaluator.add: det_masks must be uint8 bit planes or bool bitmaps (got {det_masks.dtype})')
+        inter, area_d, area_g = ops.mask_intersections(det_masks.to(dev, non_blocking=True), gt_bits, W)
+        area = area_g.to(torch.float64) if gt_area is None else on_device(gt_area, torch.float64)
+        self._queue_match(lambda out: ops.coco_match(inter, area_d, area_g, order, det_cats, gt_cats, crowd, area, self._dev['cat_ids'],
+                                                     self._dev['area_rngs'], self._dev['iou_thrs'], self.max_dets[-1],
+                                                     self.class_agnostic, out=out), D, G, order, det_cats, scores)
+
+
+class BboxEvaluator(_CocoEvaluator):
+    """COCO box AP of a stream of images (`--eval bbox`), from the `(labels, bboxes (n, 5), masks)` tuples of the results: the
+    constructor, records and `summarize` of `SegmEvaluator`, with `box_iou_host` in place of the mask IoU. A detection is the box
+    `det_boxes_xywh_host` makes of its row, and its area -- for the area ranges -- is that box's w * h, which is what `loadRes`
+    stores for box results. The reference's `evaluate_det_segm` runs `proposal` as this very evaluation under another name.
+
+    device=None: the host rule. With a device, `add` uploads the small ground-truth arrays, launches `ops.coco_match_boxes` once on
+    the current stream and queues one pinned copy of the match records; nothing synchronises before `summarize()`. Shapes outside
+    `ops.box_eval_ok` take the host rule."""
+
+    def add(self, det_labels, det_boxes5, gt_boxes_xywh, gt_labels, gt_crowd=None, gt_area=None):
+        """det_labels (D,) labels into cat_ids, det_boxes5 (D, 5) float32 (x0, y0, x1, y1, score); gt_boxes_xywh (G, 4) float64, the
+        annotations' own `bbox`, gt_labels (G,) category ids, gt_crowd (G,) or None (no crowd), gt_area (G,) the annotations' own
+        `area` or None (the ground-truth box's w * h)."""
+        if len(det_boxes5.shape) != 2 or int(det_boxes5.shape[1]) != 5:
+            raise ValueError(f'BboxEvaluator.add: det_boxes5 must be (D, 5) (got {tuple(det_boxes5.shape)})')
+        gt_boxes = _to_numpy(gt_boxes_xywh).astype(np.float64).reshape(-1, 4)
+        gl = _to_numpy(gt_labels).reshape(-1)
+        D, G = int(det_boxes5.shape[0]), gt_boxes.shape[0]
+        if len(gl) != G or int(det_labels.shape[0]) != D:
+            raise ValueError(f'BboxEvaluator.add: {D} boxes with {int(det_labels.shape[0])} labels, {G} ground-truth boxes with {len(gl)}')
+        if self.skip_images_without_gt and not np.isin(gl, self.cat_ids).any():
+            return
+        crowd = np.zeros(G, bool) if gt_crowd is None else _to_numpy(gt_crowd).astype(bool).reshape(-1)
+        area = gt_boxes[:, 2] * gt_boxes[:, 3] if gt_area is None else _to_numpy(gt_area).astype(np.float64).reshape(-1)
+        use_device = False
+        if self.device is not None:
+            from . import ops
+            use_device = ops.box_eval_ok(D, G)
+        if use_device:
+            self._add_device(det_labels, det_boxes5, gt_boxes, gl, crowd, area, D, G)
+        else:
+            self._add_host(det_labels, det_boxes5, gt_boxes, gl, crowd, area)
+
+    def _add_host(self, det_labels, det_boxes5, gt_boxes, gt_labels, crowd, area):
+        boxes5 = _to_numpy(det_boxes5).astype(np.float32).reshape(-1, 5)
+        scores = boxes5[:, 4].astype(np.float64)
+        det_cats = np.asarray(self.cat_ids, np.int64)[_to_numpy(det_labels).astype(np.int64)] if len(scores) else np.zeros(0, np.int64)
+        det = det_boxes_xywh_host(boxes5)
+        iou = box_iou_host(det, gt_boxes, crowd)
+        self.records.append(evaluate_img_host(iou, scores, det_cats, gt_labels, crowd, area, det[:, 2] * det[:, 3], self.cat_ids,
+                                              self.area_rngs, self.iou_thrs, self.max_dets[-1], self.class_agnostic))
+
+    def _add_device(self, det_labels, det_boxes5, gt_boxes, gt_labels, crowd, area, D, G):
+        import torch
+        from . import ops
+        dev = self.device
+
+        def on_device(x, dtype):
+            t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            return t.to(device=dev, dtype=dtype, non_blocking=True)
+
+        # the ground truth of one image in ONE host-to-device copy: G rows of (x, y, w, h, area, category, crowd) in float64
+        # (category ids and flags are small integers: exact)
+        gt = np.empty((G, 7), np.float64)
+        gt[:, :4], gt[:, 4], gt[:, 5], gt[:, 6] = gt_boxes, area, gt_labels, crowd
+        gt = on_device(gt, torch.float64)
+        gt_xywh, gt_area = gt[:, :4].contiguous(), gt[:, 4].contiguous()
+        gt_cats, gt_crowd = gt[:, 5].to(torch.int32), gt[:, 6].to(torch.uint8)
+        boxes5 = on_device(det_boxes5, torch.float32).contiguous()
+        scores = boxes5[:, 4].contiguous()
+        det_cats = self._dev['cat_ids'][on_device(det_labels, torch.int64)] if D else torch.zeros(0, dtype=torch.int32, device=dev)
+        order = torch.sort(scores, descending=True, stable=True).indices.to(torch.int32)
+        self._queue_match(lambda out: ops.coco_match_boxes(boxes5, gt_xywh, order, det_cats, gt_cats, gt_crowd, gt_area,
+                                                           self._dev['cat_ids'], self._dev['area_rngs'], self._dev['iou_thrs'],
+                                                           self.max_dets[-1], self.class_agnostic, out=out), D, G, order, det_cats, scores)
+
+
 def records_from_match(dt_match, dt_ignore, gt_ignore, counts, order, det_cats, scores, cat_ids, class_agnostic):
     """The arrays `ops.coco_match` wrote for one image ((K, A, T, D), (K, A, T, D), (K, A, G), (K, 2)) with the image's score order,
     categories and scores (D,) -> the [K][A] list `evaluate_img_host` returns (copies: the staging buffer may be dropped)."""
@@ -489,9 +609,9 @@ def records_from_match(dt_match, dt_ignore, gt_ignore, counts, order, det_cats, 
     return out
 
 
-def format_summary(name, res):
-    """the printed form of one evaluator's `summarize()` result"""
-    lines = [f'segm {name}: {res["images"]} images']
+def format_summary(name, res, metric='segm'):
+    """the printed form of one evaluator's `summarize()` result; `metric` names the evaluation in the first line"""
+    lines = [f'{metric} {name}: {res["images"]} images']
     lines += [f'  {k:<12} = {v:0.3f}' for k, v in res['stats'].items()]
     lines.append(f'  AP50: base {res["base_ap50"]:0.1f}, novel {res["novel_ap50"]:0.1f}, all {res["all_ap50"]:0.1f}')
     return '\n'.join(lines)

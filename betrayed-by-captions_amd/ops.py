@@ -3208,6 +3208,28 @@ def mask_intersections(det_bits, gt_bits, width, ws=None):
     return inter, area_d, area_g
 
 
+def _match_args(who, dev, D, G, cat_ids, area_rngs, iou_thrs, per_box, out):
+    """What `coco_match` and `coco_match_boxes` check alike: the caps, the (D,) / (G,) operands `per_box` = ((tensor, name, n), ...)
+    and the four outputs (allocated when `out` is None) -> (K, A, T, out)"""
+    K, A, T = int(cat_ids.numel()), int(area_rngs.shape[0]), int(iou_thrs.numel())
+    if tuple(area_rngs.shape) != (A, 2):
+        raise CggError(f'{who}: area_rngs {tuple(area_rngs.shape)} must be (A, 2)')
+    if D > MASK_EVAL_MAX_MASKS or G > MASK_EVAL_MAX_MASKS or T > MASK_EVAL_MAX_THRS or A > MASK_EVAL_MAX_AREAS or K > MASK_EVAL_MAX_CATS \
+            or min(K, A, T) < 1:
+        raise CggError(f'{who}: outside the kernel gate (D={D}, G={G} <= {MASK_EVAL_MAX_MASKS}, 1 <= T={T} <= {MASK_EVAL_MAX_THRS}, '
+                       f'1 <= A={A} <= {MASK_EVAL_MAX_AREAS}, 1 <= K={K} <= {MASK_EVAL_MAX_CATS})')
+    for t, name, n in per_box:
+        if t.numel() != n or t.device != dev:
+            raise CggError(f'{who}: {name} must have {n} elements on {dev} (got {t.numel()} on {t.device})')
+    if out is None:
+        out = (torch.empty((K, A, T, D), dtype=torch.int32, device=dev), torch.empty((K, A, T, D), dtype=torch.uint8, device=dev),
+               torch.empty((K, A, G), dtype=torch.uint8, device=dev), torch.empty((K, 2), dtype=torch.int32, device=dev))
+    for t, name, shape in zip(out, ('dt_match', 'dt_ignore', 'gt_ignore', 'counts'), ((K, A, T, D), (K, A, T, D), (K, A, G), (K, 2))):
+        if tuple(t.shape) != shape or t.device != dev:
+            raise CggError(f'{who}: {name} must be {shape} on {dev} (got {tuple(t.shape)} on {t.device})')
+    return K, A, T, out
+
+
 def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt_area, cat_ids, area_rngs, iou_thrs, max_det,
                class_agnostic, out=None):
     """The matching of `mask_eval.evaluate_img_host` for one image on the device, from the outputs of `mask_intersections`:
@@ -3217,26 +3239,13 @@ def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt
     (K, 2) = (D_k, G_k)); row (k, a, t) holds the category's D_k detections in score order, 0 past them. One launch on the current
     stream, no host read. `out`: the four tensors, preallocated."""
     D, G = int(area_d.numel()), int(area_g.numel())
-    K, A, T = int(cat_ids.numel()), int(area_rngs.shape[0]), int(iou_thrs.numel())
     dev = area_d.device
-    if tuple(inter.shape) != (D, G) or tuple(area_rngs.shape) != (A, 2):
-        raise CggError(f'coco_match: inter {tuple(inter.shape)} / area_rngs {tuple(area_rngs.shape)} do not match D={D}, G={G}')
-    if D > MASK_EVAL_MAX_MASKS or G > MASK_EVAL_MAX_MASKS or T > MASK_EVAL_MAX_THRS or A > MASK_EVAL_MAX_AREAS or K > MASK_EVAL_MAX_CATS \
-            or min(K, A, T) < 1:
-        raise CggError(f'coco_match: outside the kernel gate (D={D}, G={G} <= {MASK_EVAL_MAX_MASKS}, 1 <= T={T} <= {MASK_EVAL_MAX_THRS}, '
-                       f'1 <= A={A} <= {MASK_EVAL_MAX_AREAS}, 1 <= K={K} <= {MASK_EVAL_MAX_CATS})')
-    for t, name, n in ((det_order, 'det_order', D), (det_cats, 'det_cats', D), (gt_cats, 'gt_cats', G), (gt_crowd, 'gt_crowd', G),
-                       (gt_area, 'gt_area', G)):
-        if t.numel() != n or t.device != dev:
-            raise CggError(f'coco_match: {name} must have {n} elements on {dev} (got {t.numel()} on {t.device})')
-    if out is None:
-        out = (torch.empty((K, A, T, D), dtype=torch.int32, device=dev), torch.empty((K, A, T, D), dtype=torch.uint8, device=dev),
-               torch.empty((K, A, G), dtype=torch.uint8, device=dev), torch.empty((K, 2), dtype=torch.int32, device=dev))
+    if tuple(inter.shape) != (D, G):
+        raise CggError(f'coco_match: inter {tuple(inter.shape)} does not match D={D}, G={G}')
+    K, A, T, out = _match_args('coco_match', dev, D, G, cat_ids, area_rngs, iou_thrs,
+                               ((det_order, 'det_order', D), (det_cats, 'det_cats', D), (gt_cats, 'gt_cats', G),
+                                (gt_crowd, 'gt_crowd', G), (gt_area, 'gt_area', G)), out)
     dt_match, dt_ignore, gt_ignore, counts = out
-    for t, name, shape in ((dt_match, 'dt_match', (K, A, T, D)), (dt_ignore, 'dt_ignore', (K, A, T, D)),
-                           (gt_ignore, 'gt_ignore', (K, A, G)), (counts, 'counts', (K, 2))):
-        if tuple(t.shape) != shape or t.device != dev:
-            raise CggError(f'coco_match: {name} must be {shape} on {dev} (got {tuple(t.shape)} on {t.device})')
 
     def opt(t, name, dtype, n):
         return dev_ptr(t, f'coco_match: {name}', dtype) if n else None
@@ -3250,6 +3259,68 @@ def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt
               dev_ptr(iou_thrs, 'coco_match: iou_thrs', torch.float64), T, D, G, int(max_det), int(bool(class_agnostic)),
               opt(dt_match, 'dt_match', torch.int32, D), opt(dt_ignore, 'dt_ignore', torch.uint8, D),
               opt(gt_ignore, 'gt_ignore', torch.uint8, G), dev_ptr(counts, 'coco_match: counts', torch.int32), stream_ptr(dev))
+    return dt_match, dt_ignore, gt_ignore, counts
+
+
+def box_eval_ok(D, G):
+    """The gate of `box_iou` / `coco_match_boxes`: at most 1024 boxes on each side, the matcher's caps. Shapes outside it take the
+    host rule (`mask_eval.box_iou_host`, `mask_eval.evaluate_img_host`)."""
+    return 0 <= int(D) <= MASK_EVAL_MAX_MASKS and 0 <= int(G) <= MASK_EVAL_MAX_MASKS
+
+
+def _boxes(det_boxes5, gt_xywh, gt_crowd, who):
+    """(D, G, device) of det_boxes5 (D, 5) float32, gt_xywh (G, 4) float64 and gt_crowd (G,) uint8 on one device"""
+    if not torch.is_tensor(det_boxes5) or det_boxes5.dim() != 2 or det_boxes5.shape[1] != 5:
+        raise CggError(f'{who}: det_boxes5 must be a (D, 5) float32 device tensor (x0, y0, x1, y1, score)')
+    if not torch.is_tensor(gt_xywh) or gt_xywh.dim() != 2 or gt_xywh.shape[1] != 4:
+        raise CggError(f'{who}: gt_xywh must be a (G, 4) float64 device tensor (x, y, w, h)')
+    D, G, dev = int(det_boxes5.shape[0]), int(gt_xywh.shape[0]), det_boxes5.device
+    if gt_xywh.device != dev or not torch.is_tensor(gt_crowd) or gt_crowd.numel() != G or gt_crowd.device != dev:
+        raise CggError(f'{who}: gt_xywh ({G}, 4) and gt_crowd ({G},) must live on {dev}')
+    if not box_eval_ok(D, G):
+        raise CggError(f'{who}: outside the kernel gate (D={D}, G={G} <= {MASK_EVAL_MAX_MASKS})')
+    return D, G, dev
+
+
+def box_iou(det_boxes5, gt_xywh, gt_crowd):
+    """det_boxes5 (D, 5) float32 (x0, y0, x1, y1, score) as the results hold them, gt_xywh (G, 4) float64, gt_crowd (G,) uint8, all
+    on one device -> (iou float64 (D, G), area_d float64 (D,)), equal to `mask_eval.box_iou_host` on
+    `mask_eval.det_boxes_xywh_host(det_boxes5)` bit for bit, and that box's w * h. One launch on the current stream, no host read."""
+    D, G, dev = _boxes(det_boxes5, gt_xywh, gt_crowd, 'box_iou')
+    iou = torch.empty((D, G), dtype=torch.float64, device=dev)
+    area_d = torch.empty(D, dtype=torch.float64, device=dev)
+    with _timed('box_iou', bytes=float(20 * D + 33 * G + 8 * D * G + 8 * D), shape=(D, G)):
+        _call('cgg_box_iou_f64', dev_ptr(det_boxes5, 'box_iou: det_boxes5', torch.float32) if D else None, D,
+              dev_ptr(gt_xywh, 'box_iou: gt_xywh', torch.float64) if G else None,
+              dev_ptr(gt_crowd, 'box_iou: gt_crowd', torch.uint8) if G else None, G, dev_ptr(iou, 'iou') if D * G else None,
+              dev_ptr(area_d, 'area_d') if D else None, stream_ptr(dev))
+    return iou, area_d
+
+
+def coco_match_boxes(det_boxes5, gt_xywh, det_order, det_cats, gt_cats, gt_crowd, gt_area, cat_ids, area_rngs, iou_thrs, max_det,
+                     class_agnostic, out=None):
+    """`coco_match` on the box IoUs of `box_iou`, formed inside the matcher: det_boxes5 (D, 5) float32, gt_xywh (G, 4) float64 in
+    place of inter / area_d / area_g (the detection's own area is its box's w * h); every other argument, the four outputs and
+    `out=` as there. Equal to `mask_eval.evaluate_img_host` on `mask_eval.box_iou_host`. One launch on the current stream, no host
+    read, no workspace."""
+    D, G, dev = _boxes(det_boxes5, gt_xywh, gt_crowd, 'coco_match_boxes')
+    K, A, T, out = _match_args('coco_match_boxes', dev, D, G, cat_ids, area_rngs, iou_thrs,
+                               ((det_order, 'det_order', D), (det_cats, 'det_cats', D), (gt_cats, 'gt_cats', G),
+                                (gt_area, 'gt_area', G)), out)
+    dt_match, dt_ignore, gt_ignore, counts = out
+
+    def opt(t, name, dtype, n):
+        return dev_ptr(t, f'coco_match_boxes: {name}', dtype) if n else None
+
+    with _timed('coco_match_boxes', shape=(D, G, K, A, T)):
+        _call('cgg_coco_match_boxes', opt(det_boxes5, 'det_boxes5', torch.float32, D), opt(gt_xywh, 'gt_xywh', torch.float64, G),
+              opt(det_order, 'det_order', torch.int32, D), opt(det_cats, 'det_cats', torch.int32, D),
+              opt(gt_cats, 'gt_cats', torch.int32, G), opt(gt_crowd, 'gt_crowd', torch.uint8, G),
+              opt(gt_area, 'gt_area', torch.float64, G), dev_ptr(cat_ids, 'coco_match_boxes: cat_ids', torch.int32), K,
+              dev_ptr(area_rngs, 'coco_match_boxes: area_rngs', torch.float64), A,
+              dev_ptr(iou_thrs, 'coco_match_boxes: iou_thrs', torch.float64), T, D, G, int(max_det), int(bool(class_agnostic)),
+              opt(dt_match, 'dt_match', torch.int32, D), opt(dt_ignore, 'dt_ignore', torch.uint8, D),
+              opt(gt_ignore, 'gt_ignore', torch.uint8, G), dev_ptr(counts, 'coco_match_boxes: counts', torch.int32), stream_ptr(dev))
     return dt_match, dt_ignore, gt_ignore, counts
 
 

@@ -1325,7 +1325,27 @@ int cgg_rowwise_softmax_argmax(const float* x, float* prob, float* maxv, int64_t
  *   G_k are written as 0.
  *   CGG_EINVAL: null pointer, K, A, T < 1, D, G, max_det < 0, misaligned doubles. CGG_EUNSUPPORTED: T > 64, A > 8, K > 1024,
  *   D > 1024, G > 1024.
+ *
+ * cgg_box_iou_f64: the box side of COCOeval.computeIoU (`--eval bbox`), equal to mask_eval.box_iou_host bit for bit.
+ *   det_boxes5 float[D][5] = (x0, y0, x1, y1, score) as the results hold them: every coordinate is widened to double, then the
+ *   detection is (x0, y0, x1 - x0, y1 - y0) in double. gt_boxes_xywh double[G][4] = (x, y, w, h); gt_crowd uint8[G].
+ *   Per pair, with D the detection and G the ground truth: da = D.w * D.h, ga = G.w * G.h;
+ *   w = fmin(D.w + D.x, G.w + G.x) - fmax(D.x, G.x), 0 if w <= 0; h likewise on y, 0 if h <= 0; i = w * h;
+ *   u = da for a crowd, else (da + ga) - i; iou = i / u. Every operation is an IEEE double operation of its own (no product is
+ *   fused into an add). iou double[D][G]; area_d double[D] = da. D = 0 or G = 0 is legal (G = 0: the areas alone).
+ *   CGG_EINVAL: null pointer, D, G < 0, misaligned pointers. CGG_EUNSUPPORTED: D > 1024, G > 1024.
+ *
+ * cgg_coco_match_boxes: cgg_coco_match with the IoU of cgg_box_iou_f64 in place of inter / area_d / area_g (the same kernel
+ *   template: one scan, two IoU sources); the detection's own area, for the area ranges, is da. Every other argument, the
+ *   outputs, their layouts and the error codes are those of cgg_coco_match. One launch, no workspace.
  * ---------------------------------------------------------------------------------------------- */
+int cgg_box_iou_f64(const float* det_boxes5, int D, const double* gt_boxes_xywh, const uint8_t* gt_crowd, int G, double* iou,
+                    double* area_d, cgg_stream_t stream);
+int cgg_coco_match_boxes(const float* det_boxes5, const double* gt_boxes_xywh, const int32_t* det_order, const int32_t* det_cats,
+                         const int32_t* gt_cats, const uint8_t* gt_crowd, const double* gt_area, const int32_t* cat_ids, int K,
+                         const double* area_rngs, int A, const double* iou_thrs, int T, int D, int G, int max_det,
+                         int class_agnostic, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, int32_t* counts,
+                         cgg_stream_t stream);
 int64_t cgg_mask_intersections_workspace_bytes(int D, int G, int H, int W);
 int cgg_mask_intersections_bits(const uint8_t* det_bits, int D, int64_t det_stride_bytes, const uint8_t* gt_bits, int G,
                                 int64_t gt_stride_bytes, int H, int W, int row_bytes, void* ws, int32_t* inter, int32_t* area_d,

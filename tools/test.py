@@ -2,7 +2,8 @@
 """Minimal inference driver with the command line of the reference's tools/test.py: config + checkpoint -> detector from
 the registry -> `simple_test` over a stream of images -> results pickle (`--out`), one process per GPU under
 `--launcher pytorch` (images are sharded by rank, results gathered on rank 0). `--eval segm` computes COCO mask AP (and base /
-novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`), `--eval PQ`
+novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`), `--eval bbox`
+(or `proposal`, which the reference runs as the same evaluation) COCO box AP from the results' boxes (`BboxEvaluator`), `--eval PQ`
 panoptic quality over All / Known Things / Unknown Things / Stuff from the device maps and segment tables
 (`cgg_amd.pq_eval.PQEvaluator`); the other metrics need the dataset classes, which are out of this build's scope: they are accepted
 and reported as unavailable.
@@ -48,6 +49,11 @@ def parse_args(argv=None):
                         'original size (gt_crowd, gt_area optional), and sets --mask-bits. The config may hold segm_eval = dict(all_results='
                         '[category id per label], base_results=[...], novel_results=[...], unknown_cat_ids=[...], all_cat_ids=[...], '
                         'class_agnostic=False, max_dets=(100, 300, 1000)); a type without a list takes label + 1 as the category id. '
+                        'bbox: COCO box AP of every result type, evaluated on the device from the results\' (n, 5) boxes; needs metas with '
+                        'gt_boxes_xywh (n, 4) float64, the annotations\' own bbox at the original size, and gt_labels (gt_crowd, gt_area '
+                        'optional); categories from segm_eval, as for segm; runs alone (no --mask-bits) or next to segm. proposal: the same '
+                        'run under that name, as the reference\'s evaluate_det_segm maps it to bbox with unchanged parameters. '
+                        'proposal_fast is refused: the reference\'s result files never hold it. '
                         'PQ (or pq): panoptic quality of panoptic_all_results, evaluated on the device from the id maps and segment tables '
                         '(sets with_segments); needs metas with gt_pan_seg ((h, w) int32 ids or (h, w, 3) uint8 RGB) and gt_segments '
                         '(records id, category_id, iscrowd, area) at the original size. The config may hold pq_eval = dict(all_cat_ids=[...], '
@@ -147,30 +153,39 @@ def interleave_rank_results(parts):
     return out[:total]
 
 
-def segm_summary(cfg, model, evaluators, eval_records, device, work_dir):
-    """--eval segm on rank 0: accumulate every type's image records (this rank's and the gathered ones), print the summary and write
-    it to WORK_DIR/segm_eval.json. Without ground truth in the stream nothing was recorded: today's message."""
-    from cgg_amd.mask_eval import SegmEvaluator, format_summary
-    if not eval_records:
-        print('--eval segm: the stream carries no ground truth (metas with gt_masks and gt_labels come from a --data stream); dataset '
-              'classes / COCO evaluation are outside this build', flush=True)
-        return None
+def coco_evaluator(cls, cfg, model, key, device=None):
+    """the SegmEvaluator / BboxEvaluator (`cls`) of result type `key`: categories and options from the config entry segm_eval"""
     opts = dict(cfg.get('segm_eval') or {})
+    n_cls = getattr(model.panoptic_fusion_head, key.replace('_results', '_classes'), None) or model.num_classes
+    agnostic = bool(opts.get('class_agnostic', False))
+    return cls(opts.get(key) or list(range(1, int(n_cls) + 1)), opts.get('unknown_cat_ids'), opts.get('all_cat_ids'),
+               max_dets=tuple(opts.get('max_dets', (100, 300, 1000))), class_agnostic=agnostic, device=device,
+               skip_images_without_gt=device is not None and not agnostic)
+
+
+def segm_summary(cfg, model, evaluators, eval_records, device, work_dir, metric='segm'):
+    """--eval segm / bbox on rank 0: accumulate every type's image records (this rank's and the gathered ones), print the summary and
+    write it to WORK_DIR/segm_eval.json / bbox_eval.json. Without ground truth in the stream nothing was recorded: today's message.
+    `metric` is the name the run was asked for (segm, bbox or proposal; proposal writes bbox_eval.json)."""
+    from cgg_amd.mask_eval import BboxEvaluator, SegmEvaluator, format_summary
+    boxes = metric != 'segm'
+    if not eval_records:
+        print(f'--eval {metric}: the stream carries no ground truth (metas with {"gt_boxes_xywh" if boxes else "gt_masks"} and gt_labels '
+              'come from a --data stream); dataset classes / COCO evaluation are outside this build', flush=True)
+        return None
     summary = {}
     for key in sorted(eval_records):
         ev = evaluators.get(key)
         if ev is None:                  # a type only other ranks saw: the same evaluator, without records of its own
-            n_cls = getattr(model.panoptic_fusion_head, key.replace('_results', '_classes'), None) or model.num_classes
-            ev = SegmEvaluator(opts.get(key) or list(range(1, int(n_cls) + 1)), opts.get('unknown_cat_ids'), opts.get('all_cat_ids'),
-                               max_dets=tuple(opts.get('max_dets', (100, 300, 1000))), class_agnostic=bool(opts.get('class_agnostic', False)))
+            ev = coco_evaluator(BboxEvaluator if boxes else SegmEvaluator, cfg, model, key)
         ev.records = list(eval_records[key])
         res = ev.summarize()
-        print(format_summary(key, res), flush=True)
+        print(format_summary(key, res, metric), flush=True)
         summary[key] = dict(images=res['images'], stats=res['stats'], base_ap50=res['base_ap50'], novel_ap50=res['novel_ap50'],
                             all_ap50=res['all_ap50'])
     if work_dir:
         os.makedirs(work_dir, exist_ok=True)
-        with open(os.path.join(work_dir, 'segm_eval.json'), 'w') as f:
+        with open(os.path.join(work_dir, 'bbox_eval.json' if boxes else 'segm_eval.json'), 'w') as f:
             json.dump(summary, f, indent=1)
     return summary
 
@@ -219,6 +234,10 @@ def _test_stages():
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.eval and 'proposal_fast' in args.eval:
+        # the reference's allow-list admits the name, and its evaluate_det_segm then raises KeyError('proposal_fast is not in results')
+        raise SystemExit('--eval proposal_fast: the reference\'s result files hold bbox, proposal and segm, never proposal_fast (its '
+                         'evaluate_det_segm raises KeyError for it); use bbox or proposal')
     cfg = Config.fromfile(args.config)
     if args.cfg_options:
         cfg.merge_from_dict({k: parse_option_value(v) for k, v in (kv.split('=', 1) for kv in args.cfg_options)})
@@ -242,14 +261,18 @@ def main(argv=None):
     model = model.to(device).eval()
     eval_segm = bool(args.eval) and 'segm' in args.eval
     eval_pq = bool(args.eval) and any(m in ('PQ', 'pq') for m in args.eval)        # ('pq' is regarded as 'PQ', as in the reference)
-    if args.eval and [m for m in args.eval if m not in ('segm', 'PQ', 'pq')]:
+    # --eval bbox / proposal: one box evaluation per name asked for (the reference runs proposal as bbox with unchanged parameters)
+    box_metrics = [m for m in ('bbox', 'proposal') if args.eval and m in args.eval]
+    if args.eval and [m for m in args.eval if m not in ('segm', 'bbox', 'proposal', 'PQ', 'pq')]:
         print('--eval: dataset classes / COCO evaluation are outside this build; results are written with --out', flush=True)
     if eval_segm:
         args.mask_bits = True
+    eval_any = eval_segm or eval_pq or bool(box_metrics)
     decode_kwargs = dict(with_segments=True) if eval_pq else {}        # --eval PQ reads the device segment table
     pq = [None]                        # --eval PQ: the PQEvaluator, made when the first ground truth arrives
     pq_slots = []                      # per image of this rank, in order: the index of its record in the evaluator, or None
     evaluators = {}                    # --eval segm: result type -> SegmEvaluator, made when the first ground truth arrives
+    box_evaluators = {}                # --eval bbox / proposal: result type -> BboxEvaluator, likewise
     eval_metas = []                    # per submitted batch, in submission order: the metas of its images
     evaluated = [None]                 # event after the newest batch's evaluator launches
 
@@ -296,8 +319,7 @@ def main(argv=None):
     def evaluate(device_results):
         """--eval segm: every image's result of each type the head returns goes to that type's evaluator (masks stay on the device);
         --eval PQ: its panoptic map and segment table go to the PQEvaluator"""
-        from cgg_amd.mask_eval import SegmEvaluator
-        opts = dict(cfg.get('segm_eval') or {})
+        from cgg_amd.mask_eval import BboxEvaluator, SegmEvaluator
         for m, res in zip(eval_metas.pop(0), device_results):
             if eval_pq:
                 # --eval PQ: the image's panoptic map and segment table go to the PQEvaluator (both stay on the device)
@@ -309,22 +331,26 @@ def main(argv=None):
                         pq[0] = pq_evaluator(cfg, model, device)
                     pq_slots.append(len(pq[0].records))
                     pq[0].add(pan, res['panoptic_segments'], m['gt_pan_seg'], m['gt_segments'])
-            if not eval_segm or m.get('gt_masks') is None or m.get('gt_labels') is None:
+            with_masks = eval_segm and m.get('gt_masks') is not None and m.get('gt_labels') is not None
+            with_boxes = bool(box_metrics) and m.get('gt_boxes_xywh') is not None and m.get('gt_labels') is not None
+            if not (with_masks or with_boxes):
                 continue
             for key, val in res.items():
                 if not (key.endswith('_results') and isinstance(val, (tuple, list)) and len(val) == 3):
                     continue
-                if key not in evaluators:
-                    n_cls = getattr(model.panoptic_fusion_head, key.replace('_results', '_classes'), None) or model.num_classes
-                    agnostic = bool(opts.get('class_agnostic', False))
-                    evaluators[key] = SegmEvaluator(opts.get(key) or list(range(1, int(n_cls) + 1)), opts.get('unknown_cat_ids'),
-                                                    opts.get('all_cat_ids'), max_dets=tuple(opts.get('max_dets', (100, 300, 1000))),
-                                                    class_agnostic=agnostic, device=device, skip_images_without_gt=not agnostic)
-                evaluators[key].add(val[0], val[1], val[2], m['gt_masks'], m['gt_labels'], m.get('gt_crowd'), m.get('gt_area'))
+                if with_masks:
+                    if key not in evaluators:
+                        evaluators[key] = coco_evaluator(SegmEvaluator, cfg, model, key, device)
+                    evaluators[key].add(val[0], val[1], val[2], m['gt_masks'], m['gt_labels'], m.get('gt_crowd'), m.get('gt_area'))
+                if with_boxes:
+                    # (gt_area is the annotation's own area: the masks' for a dataset that has them, the box's w * h when None)
+                    if key not in box_evaluators:
+                        box_evaluators[key] = coco_evaluator(BboxEvaluator, cfg, model, key, device)
+                    box_evaluators[key].add(val[0], val[1], m['gt_boxes_xywh'], m['gt_labels'], m.get('gt_crowd'), m.get('gt_area'))
 
     def emit(device_results):
         """device results of one batch -> `results` (numpy now, or a future of the RLE collector)"""
-        if eval_segm or eval_pq:
+        if eval_any:
             evaluate(device_results)
             # the evaluator's kernels read the result buffers on THIS stream: the pipeline's last stage waits for them before it
             # writes a slot again (a wait on the GPU; without the RLE collector the copies below end in a host wait anyway)
@@ -391,7 +417,7 @@ def main(argv=None):
                     imgs[k].copy_(g[0], non_blocking=True)
                 metas = [dict(g[1], batch_input_shape=tuple(imgs.shape[-2:])) for g in group]
                 shape = tuple(imgs.shape)
-            if eval_segm or eval_pq:
+            if eval_any:
                 eval_metas.append(metas)
             use_pipe = (not args.no_pipeline and len(group) == B
                         and all(m['img_shape'] == metas[0]['img_shape'] and m['ori_shape'] == metas[0]['ori_shape'] for m in metas))
@@ -491,6 +517,7 @@ def main(argv=None):
             collector.close()
     dt = time.perf_counter() - (t0 or time.perf_counter())
     eval_records = {key: ev.image_records() for key, ev in evaluators.items()}     # per image a few KB of match records, no masks
+    box_records = {key: ev.image_records() for key, ev in box_evaluators.items()}
     pq_records = []                    # --eval PQ: per image of this rank its record (a few hundred bytes) or None
     if eval_pq:
         recs = pq[0].image_records() if pq[0] is not None else []
@@ -508,6 +535,13 @@ def main(argv=None):
                 for part in parts[1:]:
                     for key, recs in part.items():
                         eval_records.setdefault(key, []).extend(recs)
+        if box_metrics:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(box_records, parts, dst=0)
+            if rank == 0:
+                for part in parts[1:]:
+                    for key, recs in part.items():
+                        box_records.setdefault(key, []).extend(recs)
         if eval_pq:
             parts = [None] * world if rank == 0 else None
             dist.gather_object(pq_records, parts, dst=0)
@@ -516,6 +550,9 @@ def main(argv=None):
         dist.destroy_process_group()
     if eval_segm and rank == 0:
         segm_summary(cfg, model, evaluators, eval_records, device, args.work_dir)
+    if rank == 0:
+        for metric in box_metrics:
+            segm_summary(cfg, model, box_evaluators, box_records, device, args.work_dir, metric=metric)
     if eval_pq and rank == 0:
         pq_summary(cfg, model, [r for r in pq_records if r is not None], args.work_dir)
     if rank == 0:
