@@ -8,9 +8,16 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable"
 OBJS=""
 pids=""
+# an object is stale when its source, ANY header here or the ABI header is newer: no per-header list to forget a new header in
+newer_header() {
+  for h in "$HERE"/*.h "$HERE/../../include/cgg_hip.h"; do
+    [ "$h" -nt "$1" ] && return 0
+  done
+  return 1
+}
 for f in "$HERE"/*.hip; do
   o="$OUT/$(basename "${f%.hip}").o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/cgg_common.h" -nt "$o" ] || [ "$HERE/x3.h" -nt "$o" ] || [ "$HERE/msda_common.h" -nt "$o" ] || [ "$HERE/resize_taps.h" -nt "$o" ] || [ "$HERE/../../include/cgg_hip.h" -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || newer_header "$o"; then
     # a source may ask for extra compiler flags on a "// build-flags: ..." line (e.g. the MFMA VGPR form)
     extra="$(grep -m1 '^// build-flags:' "$f" | sed 's|^// build-flags:||')"
     $HIPCC $FLAGS $extra -c "$f" -o "$o" &

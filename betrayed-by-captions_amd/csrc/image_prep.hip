@@ -11,47 +11,30 @@
 //
 // Geometry: a workgroup of 4 wavefronts owns an IP_TH x IP_TW = 16 x 256 tile of one image's output planes; a lane owns 4 consecutive
 // columns, a wavefront one 256-column row segment at a time (1 KiB per plane per store instruction), 4 rows each. The source bytes the
-// tile needs -- rows i(y0) .. i(y1) + 1, bytes 3 i(x0) .. 3 (i(x1) + 2) of each -- are staged into LDS with aligned dword loads (a 3-byte
-// pixel, a pitch that is no multiple of 4 and an arbitrary image offset make every row start at its own byte phase; the phase is kept
-// in LDS and added back when a tap is read), so each source byte crosses the memory pipeline once per tile instead of once per tap.
-// A dword that is not wholly inside the image's bytes is assembled from guarded byte loads: nothing outside offset .. offset + h * pitch
-// is read. A tile whose span does not fit IP_LDS_BYTES (downsampling by more than ~1.5 x) reads its taps from global memory instead.
+// tile needs -- rows i(y0) .. i(y1) + 1, bytes 3 i(x0) .. 3 (i(x1) + 2) of each -- are staged into LDS (u8_resize.h), so each source
+// byte crosses the memory pipeline once per tile instead of once per tap. A tile whose span does not fit U8_LDS_BYTES (downsampling
+// by more than ~1.5 x) reads its taps from global memory instead.
 // Every element of `out` is written exactly once, with non-temporal float4 stores when Wb % 4 == 0 (scalar stores otherwise).
 //
 // build-flags: -ffp-contract=off
 #include "cgg_common.h"
 
+// the tap rule, the tile's LDS image and the address of a tap in it, the three-plane store, PrepConst
+#include "u8_resize.h"
+
 #pragma clang fp contract(off)
 
 #define IP_TW 256
 #define IP_TH 16
-#define IP_LDS_BYTES 32768
 #define IP_COLS 8 /* descriptor row: byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w */
-
-struct IpConst {
-  float mean[3], rstd[3], pad[3];
-  int to_rgb;
-};
 
 // rule 2 for one target index k of an axis with source length s: taps i0 / i1 and their 11-bit weights
 __device__ __forceinline__ void ip_coef(int k, int s, double scale, int& i0, int& i1, int& a0, int& a1) {
-  const double t = ((double)k + 0.5) * scale;
-  float fx = (float)(t - 0.5);
-  const float fl = floorf(fx);
-  int i = (int)fl;
-  fx -= fl;
-  if (i < 0) {
-    i = 0;
-    fx = 0.f;
-  }
-  if (i >= s - 1) {
-    i = s - 1;
-    fx = 0.f;
-  }
-  a0 = (int)rintf((1.f - fx) * 2048.f);
-  a1 = (int)rintf(fx * 2048.f);
-  i0 = i;
-  i1 = min(i + 1, s - 1);
+  const U8Tap t = u8_tap(k, s, scale);
+  a0 = (int)rintf((1.f - t.fx) * 2048.f);
+  a1 = (int)rintf(t.fx * 2048.f);
+  i0 = t.i0;
+  i1 = t.i1;
 }
 
 __device__ __forceinline__ int ip_pixel(int p00, int p01, int p10, int p11, int a0, int a1, int b0, int b1) {
@@ -60,8 +43,8 @@ __device__ __forceinline__ int ip_pixel(int p00, int p01, int p10, int p11, int 
 }
 
 __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
-                                                                 IpConst cst, float* __restrict__ out, int Hb, int Wb) {
-  __shared__ uint32_t lds[IP_LDS_BYTES / 4];
+                                                                 PrepConst cst, float* __restrict__ out, int Hb, int Wb) {
+  __shared__ uint32_t lds[U8_LDS_BYTES / 4];
   const int b = blockIdx.z;
   const int32_t* d = table + IP_COLS * b;
   const int off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], ph = d[6], pw = d[7];
@@ -71,42 +54,9 @@ __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* _
 
   // ---- the tile's source span (workgroup-uniform) and its LDS image -----------------------------------------------------------
   const bool resized = x0 < nw && y0 < nh;
-  int r0 = 0, cb0 = 0, ls = 0;
-  bool use_lds = false;
-  if (resized) {
-    int i0, i1, a0, a1, r1, cb1;
-    ip_coef(y0, h, sy, r0, i1, a0, a1);
-    ip_coef(min(y0 + IP_TH, nh) - 1, h, sy, i0, r1, a0, a1);
-    ip_coef(x0, w, sx, i0, i1, a0, a1);
-    cb0 = 3 * i0;
-    ip_coef(min(x0 + IP_TW, nw) - 1, w, sx, i0, i1, a0, a1);
-    cb1 = 3 * (i1 + 1);
-    const int nrows = r1 - r0 + 1, nbytes = cb1 - cb0;
-    ls = (nbytes + 6) & ~3;                       // row stride in LDS: the bytes, up to 3 of phase, rounded up to dwords
-    use_lds = (long long)nrows * ls <= IP_LDS_BYTES;
-    if (use_lds) {
-      const int lo = off, hi = off + h * pitch;  // the image's bytes
-      for (int rr = wv; rr < nrows; rr += 4) {
-        const int a = off + (r0 + rr) * pitch + cb0, phase = a & 3, a4 = a - phase;
-        const int ndw = (phase + nbytes + 3) >> 2;   // <= ls / 4
-        for (int j = lane; j < ndw; j += 64) {
-          const int g = a4 + 4 * j;
-          uint32_t v;
-          if (g >= lo && g <= hi - 4) {
-            v = *reinterpret_cast<const uint32_t*>(src + g);
-          } else {
-            v = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              if (g + q >= lo && g + q < hi) v |= (uint32_t)src[g + q] << (8 * q);
-          }
-          lds[(rr * ls >> 2) + j] = v;
-        }
-      }
-    }
-  }
-  if (use_lds) __syncthreads();                    // uniform: every wavefront of the workgroup takes the same side
-  const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
+  const U8Tile tile =
+      u8_tile_stage(lds, src, resized, off, h, w, pitch, y0, min(y0 + IP_TH, nh) - 1, x0, min(x0 + IP_TW, nw) - 1, sy, sx, false);
+  if (tile.use_lds) __syncthreads();               // uniform: every wavefront of the workgroup takes the same side
 
   // ---- this lane's 4 columns ----------------------------------------------------------------------------------------------------
   const int xl = x0 + 4 * lane;
@@ -120,7 +70,6 @@ __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* _
       xi1[c] *= 3;
     }
   }
-  const bool vec = (Wb & 3) == 0;
   const size_t plane = (size_t)Hb * Wb;
 
 #pragma unroll 1
@@ -131,15 +80,7 @@ __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* _
     const bool yin = y < nh;
     int j0 = 0, j1 = 0, b0 = 0, b1 = 0;
     if (resized && yin) ip_coef(y, h, sy, j0, j1, b0, b1);
-    // byte address of column-byte 0 of the two source rows, in LDS (phase included, relative to cb0) or in global memory
-    int base0, base1;
-    if (use_lds) {
-      base0 = (j0 - r0) * ls + ((off + j0 * pitch + cb0) & 3) - cb0;
-      base1 = (j1 - r0) * ls + ((off + j1 * pitch + cb0) & 3) - cb0;
-    } else {
-      base0 = off + j0 * pitch;
-      base1 = off + j1 * pitch;
-    }
+    const int base0 = u8_tile_row(tile, off, pitch, j0), base1 = u8_tile_row(tile, off, pitch, j1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int x = xl + c;
@@ -147,14 +88,8 @@ __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* _
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const int ch = cst.to_rgb ? 2 - q : q;
-          int p00, p01, p10, p11;
-          if (use_lds) {
-            p00 = lb[base0 + xi0[c] + ch], p01 = lb[base0 + xi1[c] + ch];
-            p10 = lb[base1 + xi0[c] + ch], p11 = lb[base1 + xi1[c] + ch];
-          } else {
-            p00 = src[base0 + xi0[c] + ch], p01 = src[base0 + xi1[c] + ch];
-            p10 = src[base1 + xi0[c] + ch], p11 = src[base1 + xi1[c] + ch];
-          }
+          const int p00 = tile.mem[base0 + xi0[c] + ch], p01 = tile.mem[base0 + xi1[c] + ch];
+          const int p10 = tile.mem[base1 + xi0[c] + ch], p11 = tile.mem[base1 + xi1[c] + ch];
           const int o = ip_pixel(p00, p01, p10, p11, xa0[c], xa1[c], b0, b1);
           v[q][c] = ((float)o - cst.mean[q]) * cst.rstd[q];
         }
@@ -164,20 +99,7 @@ __global__ __launch_bounds__(256) void cgg_image_prep_u8_kernel(const uint8_t* _
         for (int q = 0; q < 3; ++q) v[q][c] = padded ? cst.pad[q] : 0.f;
       }
     }
-    float* o = out + (size_t)b * 3 * plane + (size_t)y * Wb + xl;
-    if (vec) {                                       // Wb % 4 == 0 and xl % 4 == 0: xl < Wb implies xl + 3 < Wb
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        f32x4 t = {v[q][0], v[q][1], v[q][2], v[q][3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(o + q * plane));
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (xl + c < Wb) o[q * plane + c] = v[q][c];
-    }
+    u8_store_planes(out + (size_t)b * 3 * plane + (size_t)y * Wb + xl, plane, v, xl, Wb);
   }
 }
 
@@ -215,14 +137,7 @@ extern "C" int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
                 "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
                 (long long)(off + h * pitch), (long long)staged_bytes);
   }
-  IpConst cst;
-  for (int q = 0; q < 3; ++q) {
-    cst.mean[q] = mean[q];
-    cst.rstd[q] = (float)(1.0 / (double)std_[q]);
-    const float p = pad_val[(pad_before_norm && to_rgb) ? 2 - q : q];   // a per-channel value is in source order ahead of Normalize
-    cst.pad[q] = pad_before_norm ? (p - cst.mean[q]) * cst.rstd[q] : p;
-  }
-  cst.to_rgb = to_rgb ? 1 : 0;
+  const PrepConst cst = u8_prep_const(mean, std_, pad_val, to_rgb, pad_before_norm);
   const dim3 grid((unsigned)((Wb + IP_TW - 1) / IP_TW), (unsigned)((Hb + IP_TH - 1) / IP_TH), (unsigned)B);
   hipLaunchKernelGGL(cgg_image_prep_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, staged,
                      reinterpret_cast<const int32_t*>(staged + table_offset), cst, out, Hb, Wb);

@@ -14,6 +14,9 @@
 // an f32 GEMM (rounds 1-2 used a 3 x bf16 split, 8-10 x less accurate, and an exact-f32 MFMA kernel at 172 us).
 #include "x3.h"
 
+// the grid_sample rule of cgg_point_sample_nhwc_x3_kernel
+#include "grid_taps.h"
+
 // -------------------------------------------------------------------------------------------------
 // pack: [B, C, H, W] f32  ->  [B, T, C/8, 32, 8] bf16 (hi [+ lo residual]),  T = ceil(npix/32)
 // thread = (pixel p, channel octet kc): 8 coalesced dword loads (lanes run along p), one 16-B store.
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(256) void cgg_pack_nhwc_f32_x3_kernel(const float* 
 // mask_embed . sample(mask_feature) at the P random points of every decoder layer, open_set/models/mask2former_head.py:899-921 with
 // sample(E F) = E sample(F)): round 5 wrote the samples as (B, n P, C) f32 rows (2 GB at configs[2]) and ran one f32 library bmm
 // per layer over them (10 x 234 us at 44 TF/s). Here a workgroup samples one 32-point tile -- the arithmetic of
-// cgg_point_sample_nhwc_kernel (ATen's grid_sampler_2d order), a point's taps read as 1-KiB channel rows by 32 lanes -- splits the
+// cgg_point_sample_nhwc_kernel (grid_taps.h), a point's taps read as 1-KiB channel rows by 32 lanes -- splits the
 // values into their f16 pieces and writes the tile octet-major through LDS like the pack kernel above: the result IS the packed B
 // operand of cgg_mask_logits' split mode, one image per (layer, batch image) in layer-major order, so the per-layer einsum runs
 // on the f32-class MFMA kernel with no pack pass and no f32 sample tensor.
@@ -192,20 +195,10 @@ __global__ __launch_bounds__(256) void cgg_point_sample_nhwc_x3_kernel(const flo
   for (int idx = threadIdx.x; idx < n; idx += 256) {
     const int pl = idx / KC, kc = idx - pl * KC;
     const long long bp = (long long)b * P_total + (long long)t_all * 32 + pl;
-    const float px = pts[bp * 2], py = pts[bp * 2 + 1];
-    const float gx = __fsub_rn(__fmul_rn(px, 2.0f), 1.0f), gy = __fsub_rn(__fmul_rn(py, 2.0f), 1.0f);
-    const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)W), 1.f), 2.f);
-    const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)H), 1.f), 2.f);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float tx = __fsub_rn(ix, fx), ty = __fsub_rn(iy, fy);
-    const float ux = __fsub_rn(__fadd_rn(fx, 1.f), ix), uy = __fsub_rn(__fadd_rn(fy, 1.f), iy);
-    const float wnw = __fmul_rn(ux, uy), wne = __fmul_rn(tx, uy), wsw = __fmul_rn(ux, ty), wse = __fmul_rn(tx, ty);
+    const GridTaps g = cgg_grid_taps(pts[bp * 2], pts[bp * 2 + 1], H, W);
     const float* fb = feat + (size_t)b * H * W * C + kc * 8;
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-    const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
-    auto tap = [&](int yy, int xx, float w) {
+    cgg_grid_taps_visit(g, 0, H, W, [&](int yy, int xx, float w) {
       const float* s0 = fb + ((size_t)yy * W + xx) * C;
       const f32x4 v0 = *reinterpret_cast<const f32x4*>(s0), v1 = *reinterpret_cast<const f32x4*>(s0 + 4);
 #pragma unroll
@@ -213,11 +206,7 @@ __global__ __launch_bounds__(256) void cgg_point_sample_nhwc_x3_kernel(const flo
         a0[c] = fmaf(v0[c], w, a0[c]);
         a1[c] = fmaf(v1[c], w, a1[c]);
       }
-    };
-    if (xin0 && yin0) tap(y0, x0, wnw);
-    if (xin1 && yin0) tap(y0, x0 + 1, wne);
-    if (xin0 && yin1) tap(y0 + 1, x0, wsw);
-    if (xin1 && yin1) tap(y0 + 1, x0 + 1, wse);
+    });
     u32x4 ph, plo;
     cgg_x3_split8(a0, a1, ph, plo);
     tile[kc * 32 + pl] = ph;

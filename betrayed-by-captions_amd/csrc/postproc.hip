@@ -7,6 +7,9 @@
 // bilinear taps, the two-stage resized logit, ResizeGeom / make_geom, cgg_sigmoid
 #include "resize_taps.h"
 
+// the grid_sample rule of the point samplers
+#include "grid_taps.h"
+
 // -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cgg_upsample_kernel(const float* __restrict__ x,
                                                            float* __restrict__ y, int H, int W, int h,
@@ -17,6 +20,46 @@ __global__ __launch_bounds__(256) void cgg_upsample_kernel(const float* __restri
   const int oy = (int)(p / w), ox = (int)(p - (long long)oy * w);
   const BiTap ty = cgg_bitap(oy, sy, H), tx = cgg_bitap(ox, sx, W);
   y[(size_t)n * h * w + p] = cgg_bilerp(x + (size_t)n * H * W, W, ty, tx);
+}
+
+// The tail of both instance-mask kernels below: a block's sum of sigmoids, pixel count and box -> ONE set of atomics on row i of ws.
+// Butterfly over the wave (xor 32 .. 1), then waves 1 .. 3 added serially by thread 0 through LDS. Holds a barrier: every thread of
+// the block calls it.
+__device__ __forceinline__ void cgg_instance_reduce(float sig, int cnt, int xmin, int ymin, int xmax, int ymax,
+                                                    int32_t* __restrict__ ws, int i) {
+  for (int o = 32; o > 0; o >>= 1) {
+    sig += __shfl_xor(sig, o);
+    cnt += __shfl_xor(cnt, o);
+    xmin = min(xmin, __shfl_xor(xmin, o));
+    ymin = min(ymin, __shfl_xor(ymin, o));
+    xmax = max(xmax, __shfl_xor(xmax, o));
+    ymax = max(ymax, __shfl_xor(ymax, o));
+  }
+  __shared__ float s_sig[4];
+  __shared__ int s_i[4][5];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    s_sig[wave] = sig;
+    s_i[wave][0] = cnt; s_i[wave][1] = xmin; s_i[wave][2] = ymin; s_i[wave][3] = xmax; s_i[wave][4] = ymax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      sig += s_sig[w];
+      cnt += s_i[w][0];
+      xmin = min(xmin, s_i[w][1]); ymin = min(ymin, s_i[w][2]);
+      xmax = max(xmax, s_i[w][3]); ymax = max(ymax, s_i[w][4]);
+    }
+    if (cnt > 0) {
+      int32_t* w = ws + (size_t)i * 8;
+      atomicAdd(reinterpret_cast<float*>(w), sig);
+      atomicAdd(w + 1, cnt);
+      atomicMin(w + 2, xmin);
+      atomicMin(w + 3, ymin);
+      atomicMax(w + 4, xmax);
+      atomicMax(w + 5, ymax);
+    }
+  }
 }
 
 // instance masks: thread = 16 consecutive output pixels (one 16-B mask store) of detection blockIdx.y;
@@ -73,39 +116,7 @@ __global__ __launch_bounds__(256) void cgg_instance_masks_kernel(const float* __
       }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    sig += __shfl_xor(sig, o);
-    cnt += __shfl_xor(cnt, o);
-    xmin = min(xmin, __shfl_xor(xmin, o));
-    ymin = min(ymin, __shfl_xor(ymin, o));
-    xmax = max(xmax, __shfl_xor(xmax, o));
-    ymax = max(ymax, __shfl_xor(ymax, o));
-  }
-  __shared__ float s_sig[4];
-  __shared__ int s_i[4][5];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_sig[wave] = sig;
-    s_i[wave][0] = cnt; s_i[wave][1] = xmin; s_i[wave][2] = ymin; s_i[wave][3] = xmax; s_i[wave][4] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      sig += s_sig[w];
-      cnt += s_i[w][0];
-      xmin = min(xmin, s_i[w][1]); ymin = min(ymin, s_i[w][2]);
-      xmax = max(xmax, s_i[w][3]); ymax = max(ymax, s_i[w][4]);
-    }
-    if (cnt > 0) {
-      int32_t* w = ws + (size_t)i * 8;
-      atomicAdd(reinterpret_cast<float*>(w), sig);
-      atomicAdd(w + 1, cnt);
-      atomicMin(w + 2, xmin);
-      atomicMin(w + 3, ymin);
-      atomicMax(w + 4, xmax);
-      atomicMax(w + 5, ymax);
-    }
-  }
+  cgg_instance_reduce(sig, cnt, xmin, ymin, xmax, ymax, ws, i);
 }
 
 // Fast path: one-stage resize by an INTEGER factor S (up == S * low-res, out == crop, out_w % 16 == 0).
@@ -199,39 +210,7 @@ __global__ __launch_bounds__(256) void cgg_instance_masks_int_kernel(const float
       }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    sig += __shfl_xor(sig, o);
-    cnt += __shfl_xor(cnt, o);
-    xmin = min(xmin, __shfl_xor(xmin, o));
-    ymin = min(ymin, __shfl_xor(ymin, o));
-    xmax = max(xmax, __shfl_xor(xmax, o));
-    ymax = max(ymax, __shfl_xor(ymax, o));
-  }
-  __shared__ float s_sig[4];
-  __shared__ int s_i[4][5];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    s_sig[wave] = sig;
-    s_i[wave][0] = cnt; s_i[wave][1] = xmin; s_i[wave][2] = ymin; s_i[wave][3] = xmax; s_i[wave][4] = ymax;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      sig += s_sig[w];
-      cnt += s_i[w][0];
-      xmin = min(xmin, s_i[w][1]); ymin = min(ymin, s_i[w][2]);
-      xmax = max(xmax, s_i[w][3]); ymax = max(ymax, s_i[w][4]);
-    }
-    if (cnt > 0) {
-      int32_t* w = ws + (size_t)i * 8;
-      atomicAdd(reinterpret_cast<float*>(w), sig);
-      atomicAdd(w + 1, cnt);
-      atomicMin(w + 2, xmin);
-      atomicMin(w + 3, ymin);
-      atomicMax(w + 4, xmax);
-      atomicMax(w + 5, ymax);
-    }
-  }
+  cgg_instance_reduce(sig, cnt, xmin, ymin, xmax, ymax, ws, i);
 }
 
 __global__ void cgg_instance_init_kernel(int32_t* __restrict__ ws, int n) {
@@ -360,27 +339,14 @@ extern "C" int cgg_upsample_bilinear(const float* x, float* y, int N, int H, int
   return CGG_OK;
 }
 
-static int instance_masks_launch(const float* logits, const int32_t* sel, const int32_t* dest_off,
-                                 const int32_t* dest_slot, uint8_t* masks, float* mask_score, float* bbox, void* ws,
-                                 int Q, int H, int W, int up_h, int up_w, int crop_h, int crop_w, int out_h, int out_w,
-                                 int n, cgg_stream_t stream);
-
-extern "C" int cgg_instance_masks(const float* logits, const int32_t* sel, uint8_t* masks,
-                                  float* mask_score, float* bbox, void* ws, int Q, int H, int W,
-                                  int up_h, int up_w, int crop_h, int crop_w, int out_h, int out_w,
-                                  int n, cgg_stream_t stream) {
-  CGG_REQUIRE(sel != nullptr, CGG_EINVAL, "cgg_instance_masks: null pointer");
-  return instance_masks_launch(logits, sel, nullptr, nullptr, masks, mask_score, bbox, ws, Q, H, W, up_h, up_w, crop_h,
-                               crop_w, out_h, out_w, n, stream);
-}
-
-extern "C" int cgg_instance_masks_multi(const float* logits, const int32_t* dest_off, const int32_t* dest_slot,
-                                        uint8_t* masks, float* mask_score, float* bbox, void* ws, int Q, int H, int W,
-                                        int up_h, int up_w, int crop_h, int crop_w, int out_h, int out_w,
-                                        cgg_stream_t stream) {
-  CGG_REQUIRE(dest_off && dest_slot, CGG_EINVAL, "cgg_instance_masks_multi: null pointer");
-  return instance_masks_launch(logits, nullptr, dest_off, dest_slot, masks, mask_score, bbox, ws, Q, H, W, up_h, up_w,
-                               crop_h, crop_w, out_h, out_w, Q, stream);
+// one integer-scale mask kernel, byte or bit-packed output
+template <int S>
+static void instance_masks_int_launch(bool bits, dim3 tgrid, hipStream_t s, const float* logits, const int32_t* sel, uint8_t* masks,
+                                      int32_t* ws, const ResizeGeom& g, const int32_t* dest_off, const int32_t* dest_slot) {
+  if (bits)
+    hipLaunchKernelGGL((cgg_instance_masks_int_kernel<S, true>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
+  else
+    hipLaunchKernelGGL((cgg_instance_masks_int_kernel<S, false>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
 }
 
 // the mask pass itself (between the workspace init and the per-instance finalisation)
@@ -398,24 +364,13 @@ static bool instance_masks_dispatch(const float* logits, const int32_t* sel, con
     const long long ntile = (long long)((out_h + S - 1) / S) * (out_w / IM_PPT);   // one thread per 16 x S block
     tgrid.x = (unsigned)((ntile + 255) / 256);
   }
-  if (bits) {
-    if (!(int_path && (S == 2 || S == 4 || S == 8))) return false;     // bit-packed output: integer-scale path only
-    if (S == 4)
-      hipLaunchKernelGGL((cgg_instance_masks_int_kernel<4, true>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-    else if (S == 2)
-      hipLaunchKernelGGL((cgg_instance_masks_int_kernel<2, true>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-    else
-      hipLaunchKernelGGL((cgg_instance_masks_int_kernel<8, true>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-    return true;
+  switch (int_path ? S : 0) {
+    case 2: instance_masks_int_launch<2>(bits, tgrid, s, logits, sel, masks, ws, g, dest_off, dest_slot); return true;
+    case 4: instance_masks_int_launch<4>(bits, tgrid, s, logits, sel, masks, ws, g, dest_off, dest_slot); return true;
+    case 8: instance_masks_int_launch<8>(bits, tgrid, s, logits, sel, masks, ws, g, dest_off, dest_slot); return true;
   }
-  if (int_path && S == 4)
-    hipLaunchKernelGGL((cgg_instance_masks_int_kernel<4, false>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-  else if (int_path && S == 2)
-    hipLaunchKernelGGL((cgg_instance_masks_int_kernel<2, false>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-  else if (int_path && S == 8)
-    hipLaunchKernelGGL((cgg_instance_masks_int_kernel<8, false>), tgrid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
-  else
-    hipLaunchKernelGGL(cgg_instance_masks_kernel, grid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
+  if (bits) return false;                                   // bit-packed output: integer-scale path only
+  hipLaunchKernelGGL(cgg_instance_masks_kernel, grid, dim3(256), 0, s, logits, sel, masks, ws, g, dest_off, dest_slot);
   return true;
 }
 
@@ -437,6 +392,24 @@ static int instance_masks_launch(const float* logits, const int32_t* sel, const 
                      (const int32_t*)ws, mask_score, bbox, n);
   CGG_CHECK_LAUNCH("cgg_instance_masks");
   return CGG_OK;
+}
+
+extern "C" int cgg_instance_masks(const float* logits, const int32_t* sel, uint8_t* masks,
+                                  float* mask_score, float* bbox, void* ws, int Q, int H, int W,
+                                  int up_h, int up_w, int crop_h, int crop_w, int out_h, int out_w,
+                                  int n, cgg_stream_t stream) {
+  CGG_REQUIRE(sel != nullptr, CGG_EINVAL, "cgg_instance_masks: null pointer");
+  return instance_masks_launch(logits, sel, nullptr, nullptr, masks, mask_score, bbox, ws, Q, H, W, up_h, up_w, crop_h,
+                               crop_w, out_h, out_w, n, stream);
+}
+
+extern "C" int cgg_instance_masks_multi(const float* logits, const int32_t* dest_off, const int32_t* dest_slot,
+                                        uint8_t* masks, float* mask_score, float* bbox, void* ws, int Q, int H, int W,
+                                        int up_h, int up_w, int crop_h, int crop_w, int out_h, int out_w,
+                                        cgg_stream_t stream) {
+  CGG_REQUIRE(dest_off && dest_slot, CGG_EINVAL, "cgg_instance_masks_multi: null pointer");
+  return instance_masks_launch(logits, nullptr, dest_off, dest_slot, masks, mask_score, bbox, ws, Q, H, W, up_h, up_w,
+                               crop_h, crop_w, out_h, out_w, Q, stream);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -776,8 +749,7 @@ extern "C" int cgg_rowwise_softmax_argmax(const float* x, float* prob, float* ma
 // sample(E F) = E sample(F), mask2former_head.py:357-366 / [3P] mmcv.ops.point_sample = F.grid_sample(points * 2 - 1,
 // bilinear, zeros, align_corners=False)). ATen's grid_sampler_2d walks the C = 256 channel planes of an NCHW tensor per
 // point (4 scattered 4-byte loads per channel); here a point's 4 taps are 4 contiguous C * 4-byte rows and C / 4 lanes
-// share the geometry. Same coordinate arithmetic and accumulation order as the ATen kernel (unnormalise ((g + 1) * size - 1)
-// / 2 on g = 2 p - 1; nw, ne, sw, se).
+// share the geometry.
 __global__ __launch_bounds__(256) void cgg_point_sample_nhwc_kernel(const float* __restrict__ feat, const float* __restrict__ pts,
                                                                    float* __restrict__ out, int H, int W, int C4, int P,
                                                                    long long total) {
@@ -786,35 +758,20 @@ __global__ __launch_bounds__(256) void cgg_point_sample_nhwc_kernel(const float*
   const int c4 = (int)(i % C4);
   const long long bp = i / C4;
   const int b = (int)(bp / P);
-  const float px = pts[bp * 2], py = pts[bp * 2 + 1];
-  const float gx = __fsub_rn(__fmul_rn(px, 2.0f), 1.0f), gy = __fsub_rn(__fmul_rn(py, 2.0f), 1.0f);
-  const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)W), 1.f), 2.f);
-  const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)H), 1.f), 2.f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float tx = __fsub_rn(ix, fx), ty = __fsub_rn(iy, fy);             // ix - ix_nw, iy - iy_nw
-  const float ux = __fsub_rn(__fadd_rn(fx, 1.f), ix), uy = __fsub_rn(__fadd_rn(fy, 1.f), iy);   // ix_se - ix, iy_se - iy
-  const float wnw = __fmul_rn(ux, uy), wne = __fmul_rn(tx, uy), wsw = __fmul_rn(ux, ty), wse = __fmul_rn(tx, ty);
+  const GridTaps t = cgg_grid_taps(pts[bp * 2], pts[bp * 2 + 1], H, W);
   const f32x4* fb = reinterpret_cast<const f32x4*>(feat) + (size_t)b * H * W * C4 + c4;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
-  const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
-  f32x4 v;
-  if (xin0 && yin0) { v = fb[((size_t)y0 * W + x0) * C4];
-    acc[0] = fmaf(v[0], wnw, acc[0]); acc[1] = fmaf(v[1], wnw, acc[1]); acc[2] = fmaf(v[2], wnw, acc[2]); acc[3] = fmaf(v[3], wnw, acc[3]); }
-  if (xin1 && yin0) { v = fb[((size_t)y0 * W + x0 + 1) * C4];
-    acc[0] = fmaf(v[0], wne, acc[0]); acc[1] = fmaf(v[1], wne, acc[1]); acc[2] = fmaf(v[2], wne, acc[2]); acc[3] = fmaf(v[3], wne, acc[3]); }
-  if (xin0 && yin1) { v = fb[((size_t)(y0 + 1) * W + x0) * C4];
-    acc[0] = fmaf(v[0], wsw, acc[0]); acc[1] = fmaf(v[1], wsw, acc[1]); acc[2] = fmaf(v[2], wsw, acc[2]); acc[3] = fmaf(v[3], wsw, acc[3]); }
-  if (xin1 && yin1) { v = fb[((size_t)(y0 + 1) * W + x0 + 1) * C4];
-    acc[0] = fmaf(v[0], wse, acc[0]); acc[1] = fmaf(v[1], wse, acc[1]); acc[2] = fmaf(v[2], wse, acc[2]); acc[3] = fmaf(v[3], wse, acc[3]); }
+  cgg_grid_taps_visit(t, 0, H, W, [&](int y, int x, float w) {
+    const f32x4 v = fb[((size_t)y * W + x) * C4];
+    acc[0] = fmaf(v[0], w, acc[0]); acc[1] = fmaf(v[1], w, acc[1]); acc[2] = fmaf(v[2], w, acc[2]); acc[3] = fmaf(v[3], w, acc[3]);
+  });
   reinterpret_cast<f32x4*>(out)[i] = acc;
 }
 
 // Single-channel variant with a plane index per row: out[j][p] = bilinear sample of planes[index[j]] (H x W, f32) at
 // pts[j][p]. Training losses sample the ASSIGNED ground-truth mask of every matched query at its own 12 544 points
 // (mask2former_head.py:609-612): one launch per decoder layer for all images instead of one F.grid_sample per image
-// over ALL of the image's masks (G x the work, 160 launches per step). Same arithmetic as the kernel above.
+// over ALL of the image's masks (G x the work, 160 launches per step).
 __global__ __launch_bounds__(256) void cgg_point_sample_planes_kernel(const float* __restrict__ planes,
                                                                      const int32_t* __restrict__ index,
                                                                      const float* __restrict__ pts, float* __restrict__ out,
@@ -822,23 +779,10 @@ __global__ __launch_bounds__(256) void cgg_point_sample_planes_kernel(const floa
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (row j, point p)
   if (i >= total) return;
   const long long j = i / P;
-  const float px = pts[i * 2], py = pts[i * 2 + 1];
-  const float gx = __fsub_rn(__fmul_rn(px, 2.0f), 1.0f), gy = __fsub_rn(__fmul_rn(py, 2.0f), 1.0f);
-  const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)W), 1.f), 2.f);
-  const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)H), 1.f), 2.f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float tx = __fsub_rn(ix, fx), ty = __fsub_rn(iy, fy);
-  const float ux = __fsub_rn(__fadd_rn(fx, 1.f), ix), uy = __fsub_rn(__fadd_rn(fy, 1.f), iy);
-  const float wnw = __fmul_rn(ux, uy), wne = __fmul_rn(tx, uy), wsw = __fmul_rn(ux, ty), wse = __fmul_rn(tx, ty);
+  const GridTaps t = cgg_grid_taps(pts[i * 2], pts[i * 2 + 1], H, W);
   const float* pl = planes + (size_t)index[j] * H * W;
-  const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
-  const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
   float acc = 0.f;
-  if (xin0 && yin0) acc = fmaf(pl[(size_t)y0 * W + x0], wnw, acc);
-  if (xin1 && yin0) acc = fmaf(pl[(size_t)y0 * W + x0 + 1], wne, acc);
-  if (xin0 && yin1) acc = fmaf(pl[(size_t)(y0 + 1) * W + x0], wsw, acc);
-  if (xin1 && yin1) acc = fmaf(pl[(size_t)(y0 + 1) * W + x0 + 1], wse, acc);
+  cgg_grid_taps_visit(t, 0, H, W, [&](int y, int x, float w) { acc = fmaf(pl[(size_t)y * W + x], w, acc); });
   out[i] = acc;
 }
 
@@ -863,22 +807,10 @@ __global__ __launch_bounds__(256) void cgg_point_sample_planes_bwd_kernel(const 
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (row j, point p)
   if (i >= total) return;
   const long long j = i / P;
-  const float px = pts[i * 2], py = pts[i * 2 + 1];
-  const float gx = __fsub_rn(__fmul_rn(px, 2.0f), 1.0f), gy = __fsub_rn(__fmul_rn(py, 2.0f), 1.0f);
-  const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)W), 1.f), 2.f);
-  const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)H), 1.f), 2.f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float tx = __fsub_rn(ix, fx), ty = __fsub_rn(iy, fy);
-  const float ux = __fsub_rn(__fadd_rn(fx, 1.f), ix), uy = __fsub_rn(__fadd_rn(fy, 1.f), iy);
+  const GridTaps t = cgg_grid_taps(pts[i * 2], pts[i * 2 + 1], H, W);
   const float g = gout[i];
   float* pl = gplanes + (size_t)(index ? index[j] : (int)j) * H * W;
-  const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
-  const bool yin0 = y0 >= 0 && y0 < H, yin1 = y0 + 1 >= 0 && y0 + 1 < H;
-  if (xin0 && yin0) atomicAdd(pl + (size_t)y0 * W + x0, __fmul_rn(__fmul_rn(ux, uy), g));
-  if (xin1 && yin0) atomicAdd(pl + (size_t)y0 * W + x0 + 1, __fmul_rn(__fmul_rn(tx, uy), g));
-  if (xin0 && yin1) atomicAdd(pl + (size_t)(y0 + 1) * W + x0, __fmul_rn(__fmul_rn(ux, ty), g));
-  if (xin1 && yin1) atomicAdd(pl + (size_t)(y0 + 1) * W + x0 + 1, __fmul_rn(__fmul_rn(tx, ty), g));
+  cgg_grid_taps_visit(t, 0, H, W, [&](int y, int x, float w) { atomicAdd(pl + (size_t)y * W + x, __fmul_rn(w, g)); });
 }
 
 extern "C" int cgg_point_sample_planes_backward(const float* grad_out, const int32_t* index, const float* pts, float* grad_planes,
@@ -909,22 +841,10 @@ __global__ __launch_bounds__(256) void cgg_point_sample_planes_bwd_tiled_kernel(
   const float* gj = gout + (size_t)j * P;
   for (int p = threadIdx.x; p < P; p += 256) {
     const float2 xy = *reinterpret_cast<const float2*>(pj + 2 * p);
-    const float gx = __fsub_rn(__fmul_rn(xy.x, 2.0f), 1.0f), gy = __fsub_rn(__fmul_rn(xy.y, 2.0f), 1.0f);
-    const float ix = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), (float)W), 1.f), 2.f);
-    const float iy = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), (float)H), 1.f), 2.f);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    if (y0 + 1 < r0 || y0 >= r1) continue;            // neither tap row in this band
-    const float tx = __fsub_rn(ix, fx), ty = __fsub_rn(iy, fy);
-    const float ux = __fsub_rn(__fadd_rn(fx, 1.f), ix), uy = __fsub_rn(__fadd_rn(fy, 1.f), iy);
+    const GridTaps t = cgg_grid_taps(xy.x, xy.y, H, W);
+    if (t.y0 + 1 < r0 || t.y0 >= r1) continue;        // neither tap row in this band
     const float g = gj[p];
-    const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool yin0 = y0 >= r0 && y0 < r1, yin1 = y0 + 1 >= r0 && y0 + 1 < r1;
-    float* t0 = tile + (y0 - r0) * W + x0;
-    if (xin0 && yin0) atomicAdd(t0, __fmul_rn(__fmul_rn(ux, uy), g));
-    if (xin1 && yin0) atomicAdd(t0 + 1, __fmul_rn(__fmul_rn(tx, uy), g));
-    if (xin0 && yin1) atomicAdd(t0 + W, __fmul_rn(__fmul_rn(ux, ty), g));
-    if (xin1 && yin1) atomicAdd(t0 + W + 1, __fmul_rn(__fmul_rn(tx, ty), g));
+    cgg_grid_taps_visit(t, r0, r1, W, [&](int y, int x, float w) { atomicAdd(tile + (y - r0) * W + x, __fmul_rn(w, g)); });
   }
   __syncthreads();
   float* o = gplanes + ((size_t)j * H + r0) * W;

@@ -20,10 +20,9 @@
 //
 // Image kernel: the tile geometry of image_prep.hip -- a workgroup of 4 wavefronts owns a 16 x 256 tile of one image's output planes,
 // a lane 4 consecutive columns, non-temporal float4 stores when W % 4 == 0. Only the window is computed. The source bytes a tile needs
-// are staged into LDS with aligned dword loads when they fit TP_LDS_BYTES (always when upsampling, where up to 4 output pixels share a
-// source pixel at ratio 2); a tile that downsamples by more than ~1.5 x reads its taps from global memory. A dword that is not wholly
-// inside the image's bytes is assembled from guarded byte loads: nothing outside offset .. offset + h * pitch is read. The workgroup of
-// an image's first tile also initialises the statistics rows of the image's instances, so the caller clears nothing.
+// are staged into LDS (u8_resize.h) when they fit U8_LDS_BYTES (always when upsampling, where up to 4 output pixels share a source
+// pixel at ratio 2); a tile that downsamples by more than ~1.5 x reads its taps from global memory. The workgroup of an image's
+// first tile also initialises the statistics rows of the image's instances, so the caller clears nothing.
 //
 // Plane kernel: one 16 x 256 tile of one instance mask or one semantic map per workgroup, one byte gathered per pixel, 4 pixels packed
 // into one dword store when W % 4 == 0. A mask tile reduces its area, and the smallest / largest set column and row, inside the
@@ -41,38 +40,23 @@
 // build-flags: -ffp-contract=off
 #include "cgg_common.h"
 
+// the tap rule, the tile's LDS image and the address of a tap in it, the three-plane store, PrepConst
+#include "u8_resize.h"
+
 #pragma clang fp contract(off)
 
 #define TP_TW 256
 #define TP_TH 16
-#define TP_LDS_BYTES 32768
 #define TP_IMG_COLS 12 /* byte offset, h, w, pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset or -1 */
 #define TP_INST_COLS 3 /* image index, byte offset, pitch */
 
-struct TpConst {
-  float mean[3], rstd[3], pad[3];
-  int to_rgb;
-};
-
 // rule 2 for one resized index k of an axis with source length s: taps i0 / i1 and their float32 weights
 __device__ __forceinline__ void tp_coef(int k, int s, double scale, int& i0, int& i1, float& a0, float& a1) {
-  const double t = ((double)k + 0.5) * scale;
-  float fx = (float)(t - 0.5);
-  const float fl = floorf(fx);
-  int i = (int)fl;
-  fx -= fl;
-  if (i < 0) {
-    i = 0;
-    fx = 0.f;
-  }
-  if (i >= s - 1) {
-    i = s - 1;
-    fx = 0.f;
-  }
-  a0 = 1.f - fx;
-  a1 = fx;
-  i0 = i;
-  i1 = min(i + 1, s - 1);
+  const U8Tap t = u8_tap(k, s, scale);
+  a0 = 1.f - t.fx;
+  a1 = t.fx;
+  i0 = t.i0;
+  i1 = t.i1;
 }
 
 // rule 3: the source index of resized index k
@@ -84,9 +68,9 @@ __device__ __forceinline__ float tp_pixel(int p00, int p01, int p10, int p11, fl
 }
 
 __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t* __restrict__ src, const int32_t* __restrict__ table,
-                                                                    TpConst cst, float* __restrict__ out, int32_t* __restrict__ stats,
+                                                                    PrepConst cst, float* __restrict__ out, int32_t* __restrict__ stats,
                                                                     int H, int W, int ch, int cw) {
-  __shared__ uint32_t lds[TP_LDS_BYTES / 4];
+  __shared__ uint32_t lds[U8_LDS_BYTES / 4];
   const int b = blockIdx.z;
   const int32_t* d = table + TP_IMG_COLS * b;
   const int off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8];
@@ -105,48 +89,9 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
 
   // ---- the tile's source span (workgroup-uniform) and its LDS image -----------------------------------------------------------
   const bool inside = x0 < ew && y0 < eh;
-  int r0 = 0, cb0 = 0, ls = 0;
-  bool use_lds = false;
-  if (inside) {
-    int i0, i1, r1, cb1, lo_c, hi_c;
-    float a0, a1;
-    tp_coef(y0 + oy, h, sy, r0, i1, a0, a1);
-    tp_coef(min(y0 + TP_TH, eh) - 1 + oy, h, sy, i0, r1, a0, a1);
-    tp_coef(x0 + ox, w, sx, lo_c, i1, a0, a1);
-    tp_coef(min(x0 + TP_TW, ew) - 1 + ox, w, sx, i0, hi_c, a0, a1);
-    if (flip) {                                               // columns lo_c .. hi_c of the mirrored image
-      const int t = w - 1 - hi_c;
-      hi_c = w - 1 - lo_c;
-      lo_c = t;
-    }
-    cb0 = 3 * lo_c;
-    cb1 = 3 * (hi_c + 1);
-    const int nrows = r1 - r0 + 1, nbytes = cb1 - cb0;
-    ls = (nbytes + 6) & ~3;                       // row stride in LDS: the bytes, up to 3 of phase, rounded up to dwords
-    use_lds = (long long)nrows * ls <= TP_LDS_BYTES;
-    if (use_lds) {
-      const int lo = off, hi = off + h * pitch;  // the image's bytes
-      for (int rr = wv; rr < nrows; rr += 4) {
-        const int a = off + (r0 + rr) * pitch + cb0, phase = a & 3, a4 = a - phase;
-        const int ndw = (phase + nbytes + 3) >> 2;   // <= ls / 4
-        for (int j = lane; j < ndw; j += 64) {
-          const int g = a4 + 4 * j;
-          uint32_t v;
-          if (g >= lo && g <= hi - 4) {
-            v = *reinterpret_cast<const uint32_t*>(src + g);
-          } else {
-            v = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              if (g + q >= lo && g + q < hi) v |= (uint32_t)src[g + q] << (8 * q);
-          }
-          lds[(rr * ls >> 2) + j] = v;
-        }
-      }
-    }
-  }
-  if (use_lds) __syncthreads();                    // uniform: every wavefront of the workgroup takes the same side
-  const uint8_t* lb = reinterpret_cast<const uint8_t*>(lds);
+  const U8Tile tile = u8_tile_stage(lds, src, inside, off, h, w, pitch, y0 + oy, min(y0 + TP_TH, eh) - 1 + oy, x0 + ox,
+                                     min(x0 + TP_TW, ew) - 1 + ox, sy, sx, flip != 0);
+  if (tile.use_lds) __syncthreads();               // uniform: every wavefront of the workgroup takes the same side
 
   // ---- this lane's 4 columns ----------------------------------------------------------------------------------------------------
   const int xl = x0 + 4 * lane;
@@ -162,7 +107,6 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
       xi1[c] = 3 * (flip ? w - 1 - xi1[c] : xi1[c]);
     }
   }
-  const bool vec = (W & 3) == 0;
   const size_t plane = (size_t)H * W;
 
 #pragma unroll 1
@@ -174,15 +118,7 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
     int j0 = 0, j1 = 0;
     float b0 = 0.f, b1 = 0.f;
     if (inside && yin) tp_coef(y + oy, h, sy, j0, j1, b0, b1);
-    // byte address of column-byte 0 of the two source rows, in LDS (phase included, relative to cb0) or in global memory
-    int base0, base1;
-    if (use_lds) {
-      base0 = (j0 - r0) * ls + ((off + j0 * pitch + cb0) & 3) - cb0;
-      base1 = (j1 - r0) * ls + ((off + j1 * pitch + cb0) & 3) - cb0;
-    } else {
-      base0 = off + j0 * pitch;
-      base1 = off + j1 * pitch;
-    }
+    const int base0 = u8_tile_row(tile, off, pitch, j0), base1 = u8_tile_row(tile, off, pitch, j1);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int x = xl + c;
@@ -190,14 +126,8 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
           const int chn = cst.to_rgb ? 2 - q : q;
-          int p00, p01, p10, p11;
-          if (use_lds) {
-            p00 = lb[base0 + xi0[c] + chn], p01 = lb[base0 + xi1[c] + chn];
-            p10 = lb[base1 + xi0[c] + chn], p11 = lb[base1 + xi1[c] + chn];
-          } else {
-            p00 = src[base0 + xi0[c] + chn], p01 = src[base0 + xi1[c] + chn];
-            p10 = src[base1 + xi0[c] + chn], p11 = src[base1 + xi1[c] + chn];
-          }
+          const int p00 = tile.mem[base0 + xi0[c] + chn], p01 = tile.mem[base0 + xi1[c] + chn];
+          const int p10 = tile.mem[base1 + xi0[c] + chn], p11 = tile.mem[base1 + xi1[c] + chn];
           const float o = tp_pixel(p00, p01, p10, p11, xa0[c], xa1[c], b0, b1);
           v[q][c] = (o - cst.mean[q]) * cst.rstd[q];
         }
@@ -206,20 +136,7 @@ __global__ __launch_bounds__(256) void cgg_train_prep_image_kernel(const uint8_t
         for (int q = 0; q < 3; ++q) v[q][c] = cst.pad[q];
       }
     }
-    float* o = out + (size_t)b * 3 * plane + (size_t)y * W + xl;
-    if (vec) {                                       // W % 4 == 0 and xl % 4 == 0: xl < W implies xl + 3 < W
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        f32x4 t = {v[q][0], v[q][1], v[q][2], v[q][3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(o + q * plane));
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (xl + c < W) o[q * plane + c] = v[q][c];
-    }
+    u8_store_planes(out + (size_t)b * 3 * plane + (size_t)y * W + xl, plane, v, xl, W);
   }
 }
 
@@ -656,14 +573,7 @@ static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int
 static int tp_launch_image(const char* me, const uint8_t* staged, const int32_t* table, int B, const float* mean, const float* std_,
                            const float* pad_val, int to_rgb, int crop_h, int crop_w, float* img, int32_t* stats, int H, int W,
                            cgg_stream_t stream) {
-  TpConst cst;
-  for (int q = 0; q < 3; ++q) {
-    cst.mean[q] = mean[q];
-    cst.rstd[q] = (float)(1.0 / (double)std_[q]);
-    const float p = pad_val[to_rgb ? 2 - q : q];                 // Pad runs ahead of Normalize: pad_val is in source channel order
-    cst.pad[q] = (p - cst.mean[q]) * cst.rstd[q];
-  }
-  cst.to_rgb = to_rgb ? 1 : 0;
+  const PrepConst cst = u8_prep_const(mean, std_, pad_val, to_rgb, 1);   // Pad runs ahead of Normalize
   const unsigned gx = (unsigned)((W + TP_TW - 1) / TP_TW), gy = (unsigned)((H + TP_TH - 1) / TP_TH);
   hipLaunchKernelGGL(cgg_train_prep_image_kernel, dim3(gx, gy, (unsigned)B), dim3(256), 0, (hipStream_t)stream, staged, table, cst, img,
                      stats, H, W, crop_h, crop_w);
