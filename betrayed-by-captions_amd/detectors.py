@@ -161,6 +161,11 @@ class MaskFormerOpen(nn.Module):
         results = self.panoptic_fusion_head.simple_test(assigned_labels, mask_cls_emb_results,
                                                         mask_pred_results, img_metas, **kwargs)
         if not host:
+            if kwargs.get('keep_captions', False) and caption_results is not None:
+                # this build's extension (tools/test.py --eval caption): the captions next to the device results
+                per_image = isinstance(caption_results, list) and (len(results) > 1 or kwargs.get('caption_batched', False))
+                for i in range(len(results)):
+                    results[i]['cap_results'] = caption_results[i] if per_image else caption_results
             return results
         fh = self.panoptic_fusion_head
         for i in range(len(results)):

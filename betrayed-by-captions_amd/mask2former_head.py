@@ -1588,8 +1588,9 @@ class Mask2FormerHeadOpen(nn.Module):
             from .caption_search import beam_search, beam_search_batched
             if mask_cls_emb_results.shape[0] > 1 or kwargs.get('caption_batched', False):
                 # a batch of images (or `caption_batched=True`): one search for all of them, a LIST of captions, one per image
+                # (`caption_tokenizer`, this build's extension: the tokenizer that renders the ids, instead of the cached one)
                 caption_generation_results = beam_search_batched(self, mask_cls_emb_results, BOS_TOKEN, EOS_TOKEN,
-                                                                 max_len=35, beam_width=7)
+                                                                 max_len=35, beam_width=7, tokenizer=kwargs.get('caption_tokenizer'))
             else:
                 caption_generation_results = beam_search(self, mask_cls_emb_results, BOS_TOKEN, EOS_TOKEN,
                                                          max_len=35, beam_width=7,

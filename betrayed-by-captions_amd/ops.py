@@ -3425,3 +3425,91 @@ def pq_match(ws, gt_cats, gt_crowd, gt_area, table, n_kept):
               part('gt_iou', torch.float64, G), part('gt_match', torch.int32, G), part('pred_area', torch.int32, P),
               part('pred_value', torch.int32, P), part('pred_cat', torch.int32, P), part('pred_flags', torch.uint8, P), stream_ptr(dev))
     return rec, offs
+
+
+# ------------------------------------------------------------------------------------------------
+# Caption metrics on the device (csrc/caption_eval.hip; caption_eval.py states the rules in plain Python)
+# ------------------------------------------------------------------------------------------------
+CAPTION_MAX_LEN = CONSTANTS['CGG_CAPTION_MAX_LEN']       # tokens of a sentence, in either token stream
+CAPTION_MAX_REFS = CONSTANTS['CGG_CAPTION_MAX_REFS']     # references of an image
+CAPTION_MAX_VOCAB = 65535                                # an n-gram key packs four 16-bit token ids, 0 is no token
+
+
+def caption_eval_ok(V, max_len, max_refs):
+    """The gate of the caption kernels, host arithmetic only: at most 65535 distinct tokens (the n-gram keys pack 16-bit ids), a
+    longest sentence of at most CAPTION_MAX_LEN tokens in either stream and at most CAPTION_MAX_REFS references per image (both from
+    the kernels' static LDS layout, see the header). A corpus outside it takes the rules of `caption_eval`, as a whole."""
+    return 0 <= int(V) <= CAPTION_MAX_VOCAB and 0 <= int(max_len) <= CAPTION_MAX_LEN and 0 <= int(max_refs) <= CAPTION_MAX_REFS
+
+
+def _caption_offsets(sent_off, img_off, who):
+    N, S = int(img_off.numel()) - 1, int(sent_off.numel()) - 1
+    if N < 0 or S < N:
+        raise CggError(f'{who}: img_off must hold N + 1 and sent_off S + 1 >= N + 1 offsets (got {img_off.numel()} and {sent_off.numel()})')
+    return N, S
+
+
+def _caption_out(t, name, dtype, shape, dev, who):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise CggError(f'{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev} (got {t.dtype}, {tuple(t.shape)} on {t.device})')
+    return t
+
+
+def caption_bleu_lcs(words, sent_off, words_sp, sent_off_sp, img_off, bleu=None, lcs=None):
+    """The integer parts of BLEU and ROUGE-L of an interned corpus (`caption_eval.intern_corpus_host`, its arrays on the device) ->
+    (bleu int32 (N, 10): testlen, closest reference length, guess[4], correct[4] from the split() stream; lcs int32 (P,): the LCS
+    length of every (hypothesis, reference) pair from the split(" ") stream). An image outside the kernel's caps is marked -1. One
+    launch on the current stream, no host read."""
+    who = 'caption_bleu_lcs'
+    dev = img_off.device
+    N, S = _caption_offsets(sent_off, img_off, who)
+    if sent_off_sp.numel() != S + 1:
+        raise CggError(f'{who}: sent_off_sp must hold the same {S + 1} offsets as sent_off (got {sent_off_sp.numel()})')
+    W, Wsp = int(words.numel()), int(words_sp.numel())
+    bleu = _caption_out(bleu, 'bleu', torch.int32, (N, 10), dev, who)
+    lcs = _caption_out(lcs, 'lcs', torch.int32, (S - N,), dev, who)
+    with _timed('caption_bleu_lcs', shape=(N, S, W, Wsp)):
+        _call('cgg_caption_bleu_lcs_i32', dev_ptr(words, f'{who}: words', torch.int32) if W else None,
+              dev_ptr(sent_off, f'{who}: sent_off', torch.int32), W, dev_ptr(words_sp, f'{who}: words_sp', torch.int32) if Wsp else None,
+              dev_ptr(sent_off_sp, f'{who}: sent_off_sp', torch.int32), Wsp, dev_ptr(img_off, f'{who}: img_off', torch.int32), N, S,
+              dev_ptr(bleu, f'{who}: bleu') if N else None, dev_ptr(lcs, f'{who}: lcs') if S > N else None, stream_ptr(dev))
+    return bleu, lcs
+
+
+def caption_ngram_keys(words, sent_off, img_off, keys=None, flags=None):
+    """-> (keys int64 (W, 4): per word and order k the ids of words i .. i + k of its sentence packed 16 bits each, 0 where the
+    sentence ends first; flags uint8 (W, 4): 1 iff the position is in a reference and no earlier position of its image's references
+    has the same key -- so that the sum of the flags of a key is its document frequency). One launch, no host read."""
+    who = 'caption_ngram_keys'
+    dev = img_off.device
+    N, S = _caption_offsets(sent_off, img_off, who)
+    W = int(words.numel())
+    keys = _caption_out(keys, 'keys', torch.int64, (W, 4), dev, who)
+    flags = _caption_out(flags, 'flags', torch.uint8, (W, 4), dev, who)
+    with _timed('caption_ngram_keys', shape=(N, S, W)):
+        _call('cgg_caption_ngram_keys_i64', dev_ptr(words, f'{who}: words', torch.int32) if W else None,
+              dev_ptr(sent_off, f'{who}: sent_off', torch.int32), W, dev_ptr(img_off, f'{who}: img_off', torch.int32), N, S,
+              dev_ptr(keys, f'{who}: keys') if W else None, dev_ptr(flags, f'{who}: flags') if W else None, stream_ptr(dev))
+    return keys, flags
+
+
+def cider_sums(gids, df, idf_by_df, sent_off, img_off, norm2=None, num=None):
+    """The ordered double sums of CIDEr (`caption_eval.cider_sums_host`): gids int32 (W, 4) an n-gram id per position and order, df
+    int32 (U,) the document frequency of every id, idf_by_df float64 (N + 1,) the host-made table (`caption_eval.idf_table_host`) ->
+    (norm2 float64 (S, 4), num float64 (P, 4)); an image outside the kernel's caps is marked -1.0. One launch, no host read."""
+    who = 'cider_sums'
+    dev = img_off.device
+    N, S = _caption_offsets(sent_off, img_off, who)
+    W, U = int(gids.shape[0]), int(df.numel())
+    if gids.dim() != 2 or gids.shape[1] != 4 or idf_by_df.numel() != N + 1:
+        raise CggError(f'{who}: gids must be (W, 4) and idf_by_df hold N + 1 = {N + 1} entries (got {tuple(gids.shape)}, {idf_by_df.numel()})')
+    norm2 = _caption_out(norm2, 'norm2', torch.float64, (S, 4), dev, who)
+    num = _caption_out(num, 'num', torch.float64, (S - N, 4), dev, who)
+    with _timed('cider_sums', shape=(N, S, W, U)):
+        _call('cgg_cider_sums_f64', dev_ptr(gids, f'{who}: gids', torch.int32) if W else None, dev_ptr(df, f'{who}: df', torch.int32) if U else None,
+              U, dev_ptr(idf_by_df, f'{who}: idf_by_df', torch.float64), dev_ptr(sent_off, f'{who}: sent_off', torch.int32), W,
+              dev_ptr(img_off, f'{who}: img_off', torch.int32), N, S, dev_ptr(norm2, f'{who}: norm2') if S else None,
+              dev_ptr(num, f'{who}: num') if S > N else None, stream_ptr(dev))
+    return norm2, num

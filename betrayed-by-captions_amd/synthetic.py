@@ -323,3 +323,20 @@ def pq_ground_truth(hw, num_things, num_stuff, all_cat_ids=None, seed=0, rgb=Non
     segments = [dict(id=r['id'], category_id=int(cats[r['category']]), iscrowd=int(r['category'] < num_things and not r['is_thing']),
                      area=int((ids == r['id']).sum())) for r in s['segments']]
     return pan, segments
+
+
+CAPTION_WORDS = ('a', 'the', 'man', 'woman', 'dog', 'cat', 'horse', 'bus', 'street', 'beach', 'table', 'plate', 'red', 'white', 'two',
+                 'on', 'in', 'near', 'with', 'rides', 'sits', 'stands', 'holds', 'and', 'of', 'food', 'kite', 'hill', 'field', 'snow')
+
+
+def caption_ground_truth(seed, n, words=CAPTION_WORDS):
+    """Caption ground truth of n images as `caption_eval.CaptionEvaluator.add` (and `tools/test.py --eval caption`, as the metas'
+    `gt_captions`) takes it: per image a list of 1 .. 5 reference strings of 4 .. 10 words from a small word list, seeded. Every
+    image's first reference starts with "a", so that one unigram has idf 0."""
+    rs = np.random.RandomState(seed)
+    out = []
+    for _ in range(n):
+        refs = [' '.join(words[int(k)] for k in rs.randint(0, len(words), int(rs.randint(4, 11)))) for _ in range(int(rs.randint(1, 6)))]
+        refs[0] = 'a ' + refs[0]
+        out.append(refs)
+    return out

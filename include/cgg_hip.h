@@ -1394,6 +1394,47 @@ int cgg_pq_match(const int32_t* ws, const int32_t* gt_cats, const uint8_t* gt_cr
                  const int32_t* table, const int32_t* n_kept, int P, int32_t* status, double* gt_iou, int32_t* gt_match,
                  int32_t* pred_area, int32_t* pred_value, int32_t* pred_cat, uint8_t* pred_flags, cgg_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Caption metrics on the device (csrc/caption_eval.hip): the integer parts of BLEU-1..4 and ROUGE-L and the ordered double sums
+ * of CIDEr. `caption_eval.py` states the rules in plain Python (bleu_components_host, lcs_host, ngram_df_host, cider_sums_host)
+ * and the kernels equal them exactly: integers, and double sums whose every product and add is rounded on its own, in the
+ * rule's order. All pointers DEVICE; everything runs on `stream`; no host read, no allocation.
+ *
+ * The corpus: N images, S sentences, the first sentence of an image its hypothesis, the others its references (P = S - N
+ * pairs, pair p = sentence index - image index - 1). img_off int32[N + 1]: first sentence of every image, img_off[N] = S.
+ * sent_off int32[S + 1]: first word of every sentence in `words` int32[W], token ids 1 .. 65535. One workgroup of one wave per
+ * image, the image's words staged in LDS. The caps come from that layout and are not measured: a sentence holds at most
+ * CGG_CAPTION_MAX_LEN tokens and an image at most CGG_CAPTION_MAX_REFS references, so that (32 + 1) * 128 staged words (16.5
+ * KiB) and the other tables of a kernel -- the 129 x 64 uint16 LCS rows (16.1 KiB), or the term counts of one order (16.3 KiB)
+ * -- stay under the 64 KiB of static LDS. An image beyond a cap, or whose offsets are not ascending within 0 .. W, is NOT
+ * evaluated and touches nothing out of bounds: its int32 outputs are -1, its keys 0, its flags 0, its sums -1.0.
+ *
+ * cgg_caption_bleu_lcs_i32: bleu int32[N][10] = testlen, the closest reference length (min of (|l - testlen|, l): a tie takes
+ *   the shorter; 0 without references), guess[k] = max(0, testlen - k), correct[k] = sum over the distinct hypothesis
+ *   (k + 1)-grams of min(count, max over the references of their count), k = 0 .. 3, from `words` / `sent_off`; lcs int32[P] =
+ *   the length of the longest common subsequence of hypothesis and reference in the second token stream `words_sp` /
+ *   `sent_off_sp` (W_sp words), which cuts the same sentences differently.
+ * cgg_caption_ngram_keys_i64: keys int64[W][4]: for the word at position i of its sentence and order k, the ids of words
+ *   i .. i + k packed 16 bits each, the first lowest; 0 where the sentence ends before i + k. flags uint8[W][4]: 1 iff the
+ *   position lies in a reference and no earlier position of the references of its image has the same key.
+ * cgg_cider_sums_f64: gids int32[W][4] = an id in 0 .. U - 1 per key (ignored where the n-gram does not exist), df int32[U] the
+ *   document frequency of every id, idf_by_df double[N + 1] the host-made table idf(df). With tf = the count of an n-gram in its
+ *   sentence and v = (double)tf * idf: norm2 double[S][4] = sum of v * v over the sentence's distinct n-grams of that order in
+ *   order of first occurrence; num double[P][4] = sum over the hypothesis' distinct n-grams, in that order, of
+ *   min(v_hyp, v_ref) * v_ref, v_ref = 0.0 for an n-gram the reference lacks. No contraction. An id outside 0 .. U - 1 or a
+ *   df outside 0 .. N reads entry 0.
+ * CGG_EINVAL: a null pointer with work to do, a negative size, S < N, keys / sums not 8-byte aligned. CGG_EUNSUPPORTED: more than
+ * 2^28 words or sentences (the [W][4] indices stay in int32). N = 0 is legal and launches nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define CGG_CAPTION_MAX_LEN 128
+#define CGG_CAPTION_MAX_REFS 32
+int cgg_caption_bleu_lcs_i32(const int32_t* words, const int32_t* sent_off, int W, const int32_t* words_sp, const int32_t* sent_off_sp,
+                             int W_sp, const int32_t* img_off, int N, int S, int32_t* bleu, int32_t* lcs, cgg_stream_t stream);
+int cgg_caption_ngram_keys_i64(const int32_t* words, const int32_t* sent_off, int W, const int32_t* img_off, int N, int S,
+                               int64_t* keys, uint8_t* flags, cgg_stream_t stream);
+int cgg_cider_sums_f64(const int32_t* gids, const int32_t* df, int U, const double* idf_by_df, const int32_t* sent_off, int W,
+                       const int32_t* img_off, int N, int S, double* norm2, double* num, cgg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,9 @@ the registry -> `simple_test` over a stream of images -> results pickle (`--out`
 novel / all AP50) on the device when the `--data` stream's metas carry ground truth (`cgg_amd.mask_eval.SegmEvaluator`), `--eval bbox`
 (or `proposal`, which the reference runs as the same evaluation) COCO box AP from the results' boxes (`BboxEvaluator`), `--eval PQ`
 panoptic quality over All / Known Things / Unknown Things / Stuff from the device maps and segment tables
-(`cgg_amd.pq_eval.PQEvaluator`); the other metrics need the dataset classes, which are out of this build's scope: they are accepted
-and reported as unavailable.
+(`cgg_amd.pq_eval.PQEvaluator`), `--eval caption` BLEU-1..4, CIDEr and ROUGE-L of the generated captions against the metas'
+`gt_captions` (`cgg_amd.caption_eval.CaptionEvaluator`, the n-gram work on the device); the other metrics need the dataset classes,
+which are out of this build's scope: they are accepted and reported as unavailable.
 
 Both precision modes serve through `pipeline.StagePipeline` (hipGraph per stage, encode of batch k+1 overlapped with decode of
 batch k): `--precision fp32` (default) is parity mode -- the reference's f32 semantics on the f32-class x3 kernels --,
@@ -58,7 +59,11 @@ def parse_args(argv=None):
                         '(sets with_segments); needs metas with gt_pan_seg ((h, w) int32 ids or (h, w, 3) uint8 RGB) and gt_segments '
                         '(records id, category_id, iscrowd, area) at the original size. The config may hold pq_eval = dict(all_cat_ids=[...], '
                         'isthing=[...], unknown_cat_ids=[...]); by default label + 1 and the first num_things_classes labels are things. '
-                        'Other metrics need the dataset classes: unavailable here')
+                        'caption: BLEU-1..4, CIDEr and ROUGE-L (the reference\'s eval_cap_results) of every image\'s caption against the '
+                        'reference strings in its meta\'s gt_captions (list of str), on raw whitespace tokens. Captions come from the '
+                        'batched beam search, which reads a count on the host and cannot be captured into the staged pipeline: --eval '
+                        'caption implies --no-pipeline (the eager route). Token ids are rendered by transformers.BertTokenizer, from '
+                        '--caption-vocab or the local cache. Other metrics need the dataset classes: unavailable here')
     p.add_argument('--cfg-options', nargs='+', default=None, help='key=value overrides merged into the config')
     p.add_argument('--launcher', choices=['none', 'pytorch'], default='none')
     p.add_argument('--local_rank', type=int, default=0)
@@ -93,6 +98,12 @@ def parse_args(argv=None):
                    help='directory where every image of the run is written with its result painted over it (model.show_result on the '
                         'device results the run already holds): DIR/<base name of ori_filename, or index>.png (a base name met before gets _<index> appended). Needs raw uint8 images')
     p.add_argument('--show-score-thr', type=float, default=0.3, help='score threshold of --show-dir (default 0.3)')
+    p.add_argument('--caption-vocab', default=None, metavar='VOCAB.TXT',
+                   help='--eval caption: the BERT vocabulary file (one token per line) that renders the generated ids; without it the '
+                        'locally cached bert-base-uncased tokenizer is used (nothing is downloaded), and the run ends if there is none')
+    p.add_argument('--synthetic-captions', action='store_true',
+                   help='attach seeded reference captions (synthetic.caption_ground_truth) as gt_captions to the metas of the '
+                        'synthetic streams (--synthetic / --synthetic-u8): exercises --eval caption without a dataset')
     args = p.parse_args(argv)
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
     return args
@@ -223,6 +234,40 @@ def pq_summary(cfg, model, records, work_dir):
     return summary
 
 
+def caption_tokenizer(vocab=None):
+    """--eval caption: the transformers.BertTokenizer that renders token ids, from a vocabulary file or else from the local cache"""
+    try:
+        import transformers
+    except ImportError:
+        raise SystemExit('--eval caption: the generated ids are rendered by transformers.BertTokenizer, and transformers is not importable')
+    if vocab:
+        if not os.path.isfile(vocab):
+            raise SystemExit(f'--caption-vocab {vocab}: no such file')
+        return transformers.BertTokenizer(vocab)
+    try:
+        return transformers.BertTokenizer.from_pretrained('bert-base-uncased', local_files_only=True)
+    except Exception:
+        raise SystemExit('--eval caption: no bert-base-uncased vocabulary in the local cache; give --caption-vocab VOCAB.TXT')
+
+
+def caption_summary(records, device, work_dir):
+    """--eval caption on rank 0: score the (hypothesis, references) records of all ranks, in image order, print the reference's lines
+    and write the six numbers to WORK_DIR/caption_eval.json. Without gt_captions in the stream nothing was recorded: a message."""
+    from cgg_amd.caption_eval import SCORE_NAMES, CaptionEvaluator, format_caption_summary
+    if not records:
+        print('--eval caption: the stream carries no ground truth (metas with gt_captions come from a --data stream, or from '
+              '--synthetic-captions); dataset classes / COCO evaluation are outside this build', flush=True)
+        return None
+    res = CaptionEvaluator(device=device).summarize(extra_records=records)
+    print(format_caption_summary(res), flush=True)
+    summary = dict(images=res['images'], route=res['route'], **{k: res[k] for k in SCORE_NAMES})
+    if work_dir:
+        os.makedirs(work_dir, exist_ok=True)
+        with open(os.path.join(work_dir, 'caption_eval.json'), 'w') as f:
+            json.dump(summary, f, indent=1)
+    return summary
+
+
 def _test_stages():
     """CGG_TEST_STAGES (pipeline stage split of the serving loop): validated up front, 2..5 as `pipeline.detector_pipeline` names them
     (4 and 5 add a separate post-processing stage to the 2- / 3-stage split)."""
@@ -263,18 +308,34 @@ def main(argv=None):
     eval_pq = bool(args.eval) and any(m in ('PQ', 'pq') for m in args.eval)        # ('pq' is regarded as 'PQ', as in the reference)
     # --eval bbox / proposal: one box evaluation per name asked for (the reference runs proposal as bbox with unchanged parameters)
     box_metrics = [m for m in ('bbox', 'proposal') if args.eval and m in args.eval]
-    if args.eval and [m for m in args.eval if m not in ('segm', 'bbox', 'proposal', 'PQ', 'pq')]:
+    eval_caption = bool(args.eval) and 'caption' in args.eval
+    if args.eval and [m for m in args.eval if m not in ('segm', 'bbox', 'proposal', 'PQ', 'pq', 'caption')]:
         print('--eval: dataset classes / COCO evaluation are outside this build; results are written with --out', flush=True)
     if eval_segm:
         args.mask_bits = True
-    eval_any = eval_segm or eval_pq or bool(box_metrics)
+    eval_any = eval_segm or eval_pq or bool(box_metrics) or eval_caption
     decode_kwargs = dict(with_segments=True) if eval_pq else {}        # --eval PQ reads the device segment table
+    cap_records = []                   # --eval caption: per image of this rank, in order: (hypothesis, references) or None
+    if eval_caption:
+        if not getattr(model.panoptic_head, 'use_caption_generation', False):
+            raise SystemExit('--eval caption: the config\'s head has no caption generator (use_caption_generation)')
+        # the batched beam search reads the count of finished images on the host: it cannot be captured, so this is the eager route
+        args.no_pipeline = True
+        decode_kwargs.update(with_caption=True, caption_batched=True, keep_captions=True,
+                             caption_tokenizer=caption_tokenizer(args.caption_vocab))
     pq = [None]                        # --eval PQ: the PQEvaluator, made when the first ground truth arrives
     pq_slots = []                      # per image of this rank, in order: the index of its record in the evaluator, or None
     evaluators = {}                    # --eval segm: result type -> SegmEvaluator, made when the first ground truth arrives
     box_evaluators = {}                # --eval bbox / proposal: result type -> BboxEvaluator, likewise
     eval_metas = []                    # per submitted batch, in submission order: the metas of its images
     evaluated = [None]                 # event after the newest batch's evaluator launches
+
+    def with_captions(samples):
+        """--synthetic-captions: seeded reference captions as the metas' gt_captions, by image index"""
+        if not args.synthetic_captions:
+            return samples
+        caps = synthetic.caption_ground_truth(11, args.num_images)
+        return ((img, dict(meta, gt_captions=caps[i])) for i, (img, meta) in enumerate(samples))
 
     if args.data:
         mod, fn = args.data.split(':')
@@ -285,9 +346,9 @@ def main(argv=None):
             assert len(hw) == 2 and min(hw) >= 1
         except (ValueError, AssertionError):
             raise SystemExit(f'--synthetic-u8 {args.synthetic_u8!r}: expected HxW, e.g. 480x640')
-        stream = (s for i, s in enumerate(synthetic_u8_images(args.num_images, hw, seed=11)) if i % world == rank)
+        stream = (s for i, s in enumerate(with_captions(synthetic_u8_images(args.num_images, hw, seed=11))) if i % world == rank)
     else:
-        stream = (s for i, s in enumerate(synthetic_images(args.num_images, args.synthetic, seed=11)) if i % world == rank)
+        stream = (s for i, s in enumerate(with_captions(synthetic_images(args.num_images, args.synthetic, seed=11))) if i % world == rank)
 
     B = args.samples_per_gpu
     collector, in_copy = None, []
@@ -321,6 +382,11 @@ def main(argv=None):
         --eval PQ: its panoptic map and segment table go to the PQEvaluator"""
         from cgg_amd.mask_eval import BboxEvaluator, SegmEvaluator
         for m, res in zip(eval_metas.pop(0), device_results):
+            if eval_caption:
+                # --eval caption: the image's rendered caption and its reference strings; scored at the end (CIDEr's document
+                # frequencies span the corpus)
+                refs, cap = m.get('gt_captions'), res.get('cap_results')
+                cap_records.append((cap, [str(r) for r in refs]) if refs and isinstance(cap, str) else None)
             if eval_pq:
                 # --eval PQ: the image's panoptic map and segment table go to the PQEvaluator (both stay on the device)
                 pan = res.get('panoptic_all_results', res.get('pan_results'))
@@ -547,6 +613,11 @@ def main(argv=None):
             dist.gather_object(pq_records, parts, dst=0)
             if rank == 0:
                 pq_records = interleave_rank_results(parts)        # image order: the float sums do not depend on the number of ranks
+        if eval_caption:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(cap_records, parts, dst=0)
+            if rank == 0:
+                cap_records = interleave_rank_results(parts)       # image order, as for PQ
         dist.destroy_process_group()
     if eval_segm and rank == 0:
         segm_summary(cfg, model, evaluators, eval_records, device, args.work_dir)
@@ -555,6 +626,8 @@ def main(argv=None):
             segm_summary(cfg, model, box_evaluators, box_records, device, args.work_dir, metric=metric)
     if eval_pq and rank == 0:
         pq_summary(cfg, model, [r for r in pq_records if r is not None], args.work_dir)
+    if eval_caption and rank == 0:
+        caption_summary([r for r in cap_records if r is not None], device, args.work_dir)
     if rank == 0:
         print(json.dumps(dict(images=len(results), images_per_sec_this_rank=round(n_img / max(dt, 1e-9), 1),
                               precision=args.precision, pipeline=pipe is not None,
