@@ -30,17 +30,12 @@
 #define BN_TS 72                // LDS row stride of t1 / t2 in bf16 elements (144 B)
 #define BN_PF 4                 // global prefetch distance (k-steps)
 
-__device__ __forceinline__ uint32_t bn_pk(float a, float b) {
-  const f32x2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
-}
-
 // lanes j, j ^ 1 hold neighbouring columns: they swap one value per register pair; afterwards the even lane owns row(2 rp), the odd
 // lane row(2 rp + 1), each with the bf16 pair of columns (j & ~1, (j & ~1) + 1)
 __device__ __forceinline__ uint32_t bn_pair(float v0, float v1, int odd, uint32_t rot) {
   const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
   const float recv = cgg_lane_xor1(sent);
-  const uint32_t w = bn_pk(kept, recv);
+  const uint32_t w = cgg_pk_bf16(kept, recv);
   return __builtin_amdgcn_alignbit(w, w, rot);
 }
 
@@ -213,8 +208,8 @@ __global__ __launch_bounds__(256) void cgg_bottleneck64_kernel(const uint16_t* _
           const float v1 = cgg_lane_xor1(s1);
           // even lane: (k0, v0) = columns (ch, ch + 1); odd lane: (v0, k0)
           const float e0 = odd ? v0 : k0, e1 = odd ? k0 : v0, e2 = odd ? v1 : k1, e3 = odd ? k1 : v1;
-          const uint32_t o0 = bn_pk(fmaxf(e0 + r00, 0.f), fmaxf(e1 + r01, 0.f));
-          const uint32_t o1 = bn_pk(fmaxf(e2 + r10, 0.f), fmaxf(e3 + r11, 0.f));
+          const uint32_t o0 = cgg_pk_bf16(fmaxf(e0 + r00, 0.f), fmaxf(e1 + r01, 0.f));
+          const uint32_t o1 = cgg_pk_bf16(fmaxf(e2 + r10, 0.f), fmaxf(e3 + r11, 0.f));
           *reinterpret_cast<uint2*>(y + (size_t)b * H * W * 256 + off) = make_uint2(o0, o1);
         }
       }

@@ -118,6 +118,12 @@ __device__ __forceinline__ void cgg_split_bf(float f, uint16_t& hi, uint16_t& lo
 __device__ __forceinline__ uint32_t cgg_pack2(uint16_t a, uint16_t b) {
   return (uint32_t)a | ((uint32_t)b << 16);
 }
+// (bf16(a), bf16(b)) as one word, a in the low half: one v_cvt_pk_bf16_f32; the 4-wide form packs v[0..3] in order
+__device__ __forceinline__ uint32_t cgg_pk_bf16(float a, float b) {
+  const f32x2 pr = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
+}
+__device__ __forceinline__ uint2 cgg_pk_bf16(f32x4 v) { return make_uint2(cgg_pk_bf16(v[0], v[1]), cgg_pk_bf16(v[2], v[3])); }
 
 // XCD-aware block remap: hardware places block b on XCD b % 8; give every XCD one contiguous chunk
 // of the logical index space so neighbouring work shares that XCD's private L2 (bijective form,

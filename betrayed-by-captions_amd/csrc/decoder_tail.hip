@@ -10,6 +10,7 @@
 // X3 = true (parity mode): every linear of the chain is the f32-class f16 x 3 contraction of x3.h -- weights are x3 images,
 // each fragment image has a hi and a lo half, outputs are un-scaled by the weight's column scale. Same launches, same
 // structure; the f32-MFMA launch chain it replaces ran 123 x 17 us per forward.
+#include "row_norm.h"
 #include "x3.h"
 
 #define DT_C 256
@@ -110,8 +111,7 @@ __device__ __forceinline__ void dt_store4(const DtImg<X3>& frag, int o, const f3
     *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(frag.hi) + o) = h;
     *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(frag.lo) + o) = l;
   } else {
-    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(frag.hi) + o) =
-        make_uint2(cgg_pack2(cgg_f2bf(v[0]), cgg_f2bf(v[1])), cgg_pack2(cgg_f2bf(v[2]), cgg_f2bf(v[3])));
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(frag.hi) + o) = cgg_pk_bf16(v);
   }
 }
 
@@ -176,7 +176,6 @@ __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
   {
     const f32x4 g_a = *reinterpret_cast<const f32x4*>(ga + 4 * lane), b_a = *reinterpret_cast<const f32x4*>(ba + 4 * lane);
     const f32x4 g_b = *reinterpret_cast<const f32x4*>(gb + 4 * lane), b_b = *reinterpret_cast<const f32x4*>(bb + 4 * lane);
-    constexpr float inv_n = 1.f / (float)DT_C;
     // A-fragment slot of (row, columns 4l .. 4l+3): k-step l/4, half (l/2)&1, elements 4(l&1) .. +3 -> one 8-byte store
     const int fslot = ((lane >> 2) * 64 + ((lane >> 1) & 1) * 32) * 8 + 4 * (lane & 1);
 #pragma unroll
@@ -185,14 +184,8 @@ __global__ __launch_bounds__(512) void cgg_decoder_tail_kernel(
       f32x4 v = acc4[rr];
 #pragma unroll
       for (int stage = 0; stage < 2; ++stage) {
-        float sm = (v[0] + v[1]) + (v[2] + v[3]);
-        for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
-        const float mean = sm * inv_n;
-        const f32x4 d = v - mean;
-        float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-        const float rstd = rsqrtf(q * inv_n + (stage == 0 ? eps_a : eps_b));
-        v = (v - mean) * rstd * (stage == 0 ? g_a : g_b) + (stage == 0 ? b_a : b_b);
+        const float rstd = cgg_wave_norm(v, stage == 0 ? eps_a : eps_b);
+        v = v * rstd * (stage == 0 ? g_a : g_b) + (stage == 0 ? b_a : b_b);
         if (stage == 0) {
           f32x4 xp = v;
           if (m < M) {
@@ -368,19 +361,12 @@ __global__ __launch_bounds__(512) void cgg_decoder_mid_kernel(
   f32x4 keep[4];
   {
     const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * lane), be = *reinterpret_cast<const f32x4*>(beta + 4 * lane);
-    constexpr float inv_n = 1.f / (float)DT_C;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int row = 4 * wave + rr, m = m0 + row;
       f32x4 v = *reinterpret_cast<const f32x4*>(&tile[row * DM_TS + 4 * lane]);
-      float sm = (v[0] + v[1]) + (v[2] + v[3]);
-      for (int o = 32; o > 0; o >>= 1) sm += __shfl_xor(sm, o);
-      const float mean = sm * inv_n;
-      const f32x4 d = v - mean;
-      float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-      for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-      const float rstd = rsqrtf(q * inv_n + eps);
-      v = d * rstd * g + be;
+      const float rstd = cgg_wave_norm(v, eps);
+      v = v * rstd * g + be;
       keep[rr] = v;
       if (m < M) *reinterpret_cast<f32x4*>(x1 + (size_t)m * DT_C + 4 * lane) = v;
       if (wqkv.hi) {

@@ -21,7 +21,7 @@
 // build-flags: -mllvm -amdgpu-mfma-vgpr-form=1
 // (both accumulator blocks live in VGPRs; the default AGPR form copied the 64 persistent GEMM-2 accumulators in and out of
 //  a[0:63] around every GEMM-1 block: 384 v_accvgpr moves per chunk and wave, a third of the MFMA time.)
-#include "cgg_common.h"
+#include "row_norm.h"
 
 #define EF_C 256
 #define EF_STEPS 16
@@ -31,11 +31,6 @@
 #define EF_PF 4                // B-fragment prefetch distance (k-steps); must divide EF_STEPS (the queue rotates across blocks)
 #define EF_PA 1                // A-fragment (LDS) prefetch distance (k-steps); 2 measured no better (78 vs 76 us)
 static_assert(EF_STEPS % EF_PF == 0, "the B queue index s % EF_PF must line up across blocks");
-
-__device__ __forceinline__ uint32_t ef_pk(float a, float b) {            // v_cvt_pk_bf16_f32
-  const f32x2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
-}
 
 // One 64 x 64 block of C += A B^T over 16 k-steps. A-fragment images of the two 32-row m-tiles in LDS (a0 / a1 = lane
 // pointers for even k-steps, a0o / a1o for odd ones -- the hidden image is bank-swizzled by k-step parity); B fragments of the
@@ -90,9 +85,8 @@ __device__ __forceinline__ void ef_block(f32x16 (&acc)[2][2], const u32x4* __res
 
 // KV = false: y16 = bf16(y), yp16 = bf16(y + pos[m % pos_rows]) at row m.
 // KV = true (last encoder layer, see cgg_add_layernorm_kv): pos_rows = S rows per image, y16 = bf16(y + shift[s]) and
-// yp16 = bf16(y + shift[s] + pos[s]) written LEVEL-MAJOR (row B * start_l + b * hw_l + (s - start_l)); y32 stays row m.
-struct EfLevels { int n; int start[9]; };
-
+// yp16 = bf16(y + shift[s] + pos[s]) written LEVEL-MAJOR (row B * start_l + b * hw_l + (s - start_l): cgg_level_row); y32 stays row m.
+//
 // PRO = true: the block starts one step earlier, at the attention output projection and its residual LayerNorm
 // ('self_attn' tail + first 'norm' of the layer): x1 = LN0(x + a Wo^T + bo) is computed in the workgroup from the attention
 // rows a16 (GEMM K = N = 256 on the same row image / weight-stream machinery, f32 tile, row LayerNorm with the layer-input rows
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
     const uint16_t* __restrict__ x16, const u32x4* __restrict__ w1, const float* __restrict__ b1,
     const u32x4* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, const float* __restrict__ pos, int pos_rows, uint16_t* __restrict__ y16,
-    uint16_t* __restrict__ yp16, float* __restrict__ y32, int M, int F, const float* __restrict__ shift, EfLevels lv, EfPro pro) {
+    uint16_t* __restrict__ yp16, float* __restrict__ y32, int M, int F, const float* __restrict__ shift, CggLevelRows lv, EfPro pro) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ef_smem[];
   u32x4* xfrag = reinterpret_cast<u32x4*>(ef_smem);                     // row image      [2 m-tiles][16][64]   32 KiB
   u32x4* hfrag = xfrag + (EF_RB / 32) * EF_STEPS * 64;                     // hidden chunk   [2 m-tiles][16][64]   32 KiB
@@ -190,7 +184,6 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
     for (int it = 0; it < 4; ++it) {
       const int row = 16 * wave + 4 * it + rsub;
       f32x4 v[4];
-      float sm = 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         v[k] = *reinterpret_cast<const f32x4*>(&tile[row * EF_TS + 4 * sub + 64 * k]);
@@ -199,24 +192,14 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
         v[k][1] += __uint_as_float(xr.x & 0xffff0000u);
         v[k][2] += __uint_as_float(xr.y << 16);
         v[k][3] += __uint_as_float(xr.y & 0xffff0000u);
-        sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
       }
-      sm = cgg_row16_sum(sm);
-      const float mean = sm * (1.f / (float)EF_C);
-      float q = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        v[k] = v[k] - mean;
-        q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
-      }
-      q = cgg_row16_sum(q);
-      const float rstd = rsqrtf(q * (1.f / (float)EF_C) + pro.eps0);
+      const float rstd = cgg_row16_norm(v, pro.eps0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const f32x4 g = *reinterpret_cast<const f32x4*>(pro.gamma0 + 4 * sub + 64 * k);
         const f32x4 be = *reinterpret_cast<const f32x4*>(pro.beta0 + 4 * sub + 64 * k);
         const f32x4 y = v[k] * rstd * g + be;
-        xs[it][k] = make_uint2(ef_pk(y[0], y[1]), ef_pk(y[2], y[3]));
+        xs[it][k] = cgg_pk_bf16(y);
       }
     }
     __syncthreads();
@@ -307,7 +290,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
           const float v0 = fmaxf(acc[mt][nt][2 * rp] + bias1, 0.f), v1 = fmaxf(acc[mt][nt][2 * rp + 1] + bias1, 0.f);
           const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
           const float recv = cgg_lane_xor1(sent);  // lane ^ 1
-          const uint32_t pk = ef_pk(kept, recv);
+          const uint32_t pk = cgg_pk_bf16(kept, recv);
           h32[hb[rp & 1][(rp >> 1) & 1] + (((mt * EF_STEPS + 2 * nt) * 64 + 16 * (rp >> 2)) << 2)] =
               __builtin_amdgcn_alignbit(pk, pk, rot);              // odd lanes: (recv, kept)
         }
@@ -349,7 +332,6 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
     g4[k] = *reinterpret_cast<const f32x4*>(gamma + 4 * sub + 64 * k);
     be4[k] = *reinterpret_cast<const f32x4*>(beta + 4 * sub + 64 * k);
   }
-  constexpr float inv_n = 1.f / (float)EF_C;
 #pragma unroll 2
   for (int it = 0; it < 4; ++it) {
     // no implicit mul + add contraction in the row statistics: which products the compiler fuses depends on the code around them,
@@ -375,38 +357,22 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
       for (int k = 0; k < 4; ++k) tp[k] = *reinterpret_cast<const f32x4*>(prow0 + 4 * sub + 64 * k);
     }
     f32x4 v[4];
-    float sm = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] = *reinterpret_cast<const f32x4*>(&tile[row * EF_TS + 4 * sub + 64 * k]);
-      sm += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-    }
-    sm = cgg_row16_sum(sm);
-    const float mean = sm * inv_n;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[k] = v[k] - mean;
-      q += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
-    }
-    q = cgg_row16_sum(q);
-    const float rstd = rsqrtf(q * inv_n + eps);
+    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const f32x4*>(&tile[row * EF_TS + 4 * sub + 64 * k]);
+    const float rstd = cgg_row16_norm_strict(v, eps);
     if (!live) continue;
     if constexpr (KV) {
-      const int S = pos_rows, nimg = M / S;
-      const int bi = m / S, si = m - bi * S;
-      int l = 0;
-      while (l + 1 < lv.n && si >= lv.start[l + 1]) ++l;
-      const size_t orow = (size_t)nimg * lv.start[l] + (size_t)bi * (lv.start[l + 1] - lv.start[l]) + (si - lv.start[l]);
+      const int S = pos_rows, bi = m / S;
+      const size_t orow = cgg_level_row(lv, M / S, bi, m - bi * S);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const f32x4 y = __builtin_elementwise_fma(v[k] * rstd, g4[k], be4[k]);   // explicit: both variants must round alike
         const int cofs = 4 * sub + 64 * k;
         if (y32) *reinterpret_cast<f32x4*>(y32 + (size_t)m * EF_C + cofs) = y;
         const f32x4 mm = y + ts[k];
-        *reinterpret_cast<uint2*>(y16 + orow * EF_C + cofs) = make_uint2(ef_pk(mm[0], mm[1]), ef_pk(mm[2], mm[3]));
+        *reinterpret_cast<uint2*>(y16 + orow * EF_C + cofs) = cgg_pk_bf16(mm);
         const f32x4 z = mm + tp[k];
-        *reinterpret_cast<uint2*>(yp16 + orow * EF_C + cofs) = make_uint2(ef_pk(z[0], z[1]), ef_pk(z[2], z[3]));
+        *reinterpret_cast<uint2*>(yp16 + orow * EF_C + cofs) = cgg_pk_bf16(z);
       }
     } else {
 #pragma unroll
@@ -414,10 +380,10 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
         const f32x4 y = __builtin_elementwise_fma(v[k] * rstd, g4[k], be4[k]);   // explicit: both variants must round alike
         const size_t o = (size_t)m * EF_C + 4 * sub + 64 * k;
         if (y32) *reinterpret_cast<f32x4*>(y32 + o) = y;
-        if (y16) *reinterpret_cast<uint2*>(y16 + o) = make_uint2(ef_pk(y[0], y[1]), ef_pk(y[2], y[3]));
+        if (y16) *reinterpret_cast<uint2*>(y16 + o) = cgg_pk_bf16(y);
         if (yp16) {
           const f32x4 yp = y + tp[k];
-          *reinterpret_cast<uint2*>(yp16 + o) = make_uint2(ef_pk(yp[0], yp[1]), ef_pk(yp[2], yp[3]));
+          *reinterpret_cast<uint2*>(yp16 + o) = cgg_pk_bf16(yp);
         }
       }
     }
@@ -426,7 +392,7 @@ __global__ __launch_bounds__(EF_NT) void cgg_encoder_ffn_ln_kernel(
 
 static int ef_launch(bool kv, const EfPro* prop, const void* x16, const void* w1_packed, const float* b1, const void* w2_packed,
                      const float* b2, const float* gamma, const float* beta, float eps, const float* pos, int pos_rows, void* y16,
-                     void* yp16, float* y32, int M, int C, int F, const float* shift, const EfLevels& lv, cgg_stream_t stream,
+                     void* yp16, float* y32, int M, int C, int F, const float* shift, const CggLevelRows& lv, cgg_stream_t stream,
                      const char* who) {
   CGG_REQUIRE(x16 && w1_packed && b1 && w2_packed && b2 && gamma && beta && (y16 || y32), CGG_EINVAL, "%s: null pointer", who);
   CGG_REQUIRE(C == EF_C, CGG_EUNSUPPORTED, "%s: C=%d (only 256 is built)", who, C);
@@ -460,25 +426,11 @@ static int ef_launch(bool kv, const EfPro* prop, const void* x16, const void* w1
   return CGG_OK;
 }
 
-static int ef_levels(EfLevels& lv, const int* level_start_host, int n_levels, int M, int S, const char* who) {
-  CGG_REQUIRE(level_start_host, CGG_EINVAL, "%s: null pointer", who);
-  CGG_REQUIRE(M > 0 && S > 0 && M % S == 0, CGG_EINVAL, "%s: M=%d not a multiple of S=%d", who, M, S);
-  CGG_REQUIRE(n_levels >= 1 && n_levels <= 8, CGG_EUNSUPPORTED, "%s: n_levels=%d (1..8)", who, n_levels);
-  lv.n = n_levels;
-  for (int l = 0; l < n_levels; ++l) {
-    lv.start[l] = level_start_host[l];
-    CGG_REQUIRE(lv.start[l] >= 0 && lv.start[l] < S && (l == 0 ? lv.start[l] == 0 : lv.start[l] > lv.start[l - 1]), CGG_EINVAL,
-                "%s: level_start must start at 0 and increase (level %d: %d)", who, l, lv.start[l]);
-  }
-  lv.start[n_levels] = S;
-  return CGG_OK;
-}
-
 extern "C" int cgg_encoder_ffn_ln_bf16(const void* x16, const void* w1_packed, const float* b1, const void* w2_packed,
                                        const float* b2, const float* gamma, const float* beta, float eps, const float* pos,
                                        int pos_rows, void* y16, void* yp16, float* y32, int M, int C, int F,
                                        cgg_stream_t stream) {
-  EfLevels lv;
+  CggLevelRows lv;
   lv.n = 0;
   int rc = ef_launch(false, nullptr, x16, w1_packed, b1, w2_packed, b2, gamma, beta, eps, pos, pos_rows, y16, yp16, y32, M, C, F,
                      nullptr, lv, stream, "cgg_encoder_ffn_ln_bf16");
@@ -493,8 +445,8 @@ extern "C" int cgg_encoder_ffn_ln_kv_bf16(const void* x16, const void* w1_packed
                                           int n_levels, float* y32, void* m16, void* mp16, int M, int C, int F,
                                           cgg_stream_t stream) {
   CGG_REQUIRE(shift && pos && m16 && mp16, CGG_EINVAL, "cgg_encoder_ffn_ln_kv_bf16: null pointer");
-  EfLevels lv;
-  int rc = ef_levels(lv, level_start_host, n_levels, M, S, "cgg_encoder_ffn_ln_kv_bf16");
+  CggLevelRows lv;
+  int rc = cgg_level_rows(lv, level_start_host, n_levels, M, S, "cgg_encoder_ffn_ln_kv_bf16");
   if (rc != CGG_OK) return rc;
   rc = ef_launch(true, nullptr, x16, w1_packed, b1, w2_packed, b2, gamma, beta, eps, pos, S, m16, mp16, y32, M, C, F, shift, lv,
                  stream, "cgg_encoder_ffn_ln_kv_bf16");
@@ -509,11 +461,11 @@ extern "C" int cgg_encoder_layer_tail_bf16(const void* a16, const void* x16, con
                                            const float* beta1, float eps1, const float* pos, int pos_rows, const float* shift,
                                            const int* level_start_host, int n_levels, void* y16, void* yp16, float* y32, int M,
                                            int C, int F, cgg_stream_t stream) {
-  EfLevels lv;
+  CggLevelRows lv;
   lv.n = 0;
   if (shift) {
     CGG_REQUIRE(pos && y16 && yp16, CGG_EINVAL, "cgg_encoder_layer_tail_bf16: null pointer (K / V mode)");
-    int rc = ef_levels(lv, level_start_host, n_levels, M, pos_rows, "cgg_encoder_layer_tail_bf16");
+    int rc = cgg_level_rows(lv, level_start_host, n_levels, M, pos_rows, "cgg_encoder_layer_tail_bf16");
     if (rc != CGG_OK) return rc;
   }
   const EfPro pro = {(const uint16_t*)a16, (const u32x4*)wo_packed, bo, gamma0, beta0, eps0};

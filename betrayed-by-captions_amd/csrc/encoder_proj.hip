@@ -26,11 +26,6 @@
 #define EP_RB 64
 #define EP_PF 4
 
-__device__ __forceinline__ uint32_t ep_pk(float a, float b) {            // v_cvt_pk_bf16_f32
-  const f32x2 pr = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(pr, bf16x2));
-}
-
 // acc[2][NT] += A (two 32-row m-tiles, fragment images in LDS at a0 / a1) x B (NT consecutive n-tiles of the packed weight,
 // b = lane pointer to k-step 0 of the first; n-tiles are EP_STEPS * 64 fragments apart)
 // TR = true: the operand roles are swapped (weight fragment as A, row image as B): acc[mt][t] is the TRANSPOSED block, rows =
@@ -99,7 +94,7 @@ __device__ __forceinline__ void ep_store(const f32x16 (&acc)[2][NT], const float
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
         const float recv = cgg_lane_xor1(sent);  // lane ^ 1
         // even lane: row(2 rp), columns (even, odd) = (kept, recv); odd lane: row(2 rp + 1), (recv, kept)
-        const uint32_t w = ep_pk(kept, recv);
+        const uint32_t w = cgg_pk_bf16(kept, recv);
         pk[t] = __builtin_amdgcn_alignbit(w, w, rot);
       }
       const int row = 32 * mt + 2 * (rp & 1) + 8 * (rp >> 1) + 4 * hi5 + odd;
@@ -133,7 +128,7 @@ __device__ __forceinline__ void ep_store_value_hm(const f32x16 (&acc)[2][2], con
         const float v0 = acc[mt][t][2 * rp] + bs[t], v1 = acc[mt][t][2 * rp + 1] + bs[t];
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
         const float recv = cgg_lane_xor1(sent);  // lane ^ 1
-        const uint32_t w = ep_pk(kept, recv);
+        const uint32_t w = cgg_pk_bf16(kept, recv);
         pk[t] = __builtin_amdgcn_alignbit(w, w, rot);
       }
       const int m = m0 + 32 * mt + 2 * (rp & 1) + 8 * (rp >> 1) + 4 * hi5 + odd;
@@ -164,7 +159,7 @@ __global__ __launch_bounds__(256) void cgg_encoder_proj_pack_kernel(const float*
   const int NT = ep_wave_nt(ntiles, wave), tile0 = ep_wave_tile0(ntiles, wave);
   const int n = 32 * tile0 + ep_col(NT, tile - tile0, lane & 31);
   const float* s = w + (size_t)n * EP_C + ks * 16 + 8 * (lane >> 5);
-  out[i] = u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
+  out[i] = u32x4{cgg_pk_bf16(s[0], s[1]), cgg_pk_bf16(s[2], s[3]), cgg_pk_bf16(s[4], s[5]), cgg_pk_bf16(s[6], s[7])};
 }
 
 __global__ __launch_bounds__(256) void cgg_encoder_proj_kernel(
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(256) void cgg_encoder_proj_kernel(
           const u32x4 b = *reinterpret_cast<const u32x4*>(pos16 + (size_t)((m0 + row) % pos_rows) * EP_C + 8 * k8);
 #pragma unroll
           for (int d = 0; d < 4; ++d)
-            v[i][d] = ep_pk(__uint_as_float(a[d] << 16) + __uint_as_float(b[d] << 16),
+            v[i][d] = cgg_pk_bf16(__uint_as_float(a[d] << 16) + __uint_as_float(b[d] << 16),
                             __uint_as_float(a[d] & 0xffff0000u) + __uint_as_float(b[d] & 0xffff0000u));
         } else {
           v[i] = *reinterpret_cast<const u32x4*>((which ? xp16 : x16) + (size_t)(m0 + row) * EP_C + 8 * k8);
@@ -302,7 +297,7 @@ __device__ __forceinline__ void ep_store_tr(const f32x16 (&acc)[2][NT], uint16_t
         const float v0 = acc[mt][t][2 * rp], v1 = acc[mt][t][2 * rp + 1];
         const float kept = odd ? v1 : v0, sent = odd ? v0 : v1;
         const float recv = cgg_lane_xor1(sent);  // lane ^ 1
-        const uint32_t w = ep_pk(kept, recv);          // even lane: channel row(2 rp), pixels (j, j + 1) of m-tile mt; odd: row + 1
+        const uint32_t w = cgg_pk_bf16(kept, recv);          // even lane: channel row(2 rp), pixels (j, j + 1) of m-tile mt; odd: row + 1
         pk[mt] = __builtin_amdgcn_alignbit(w, w, rot);
       }
       const int ch = 32 * (tile0 + t) + 2 * (rp & 1) + 8 * (rp >> 1) + 4 * hi5 + odd;
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(256) void cgg_decoder_kv_pack_k_kernel(const float*
   const int ks = t_all % EP_STEPS, tile = t_all / EP_STEPS;
   const int n = 64 * (tile >> 1) + ep_col(2, tile & 1, lane & 31);
   const float* s = w + (size_t)n * EP_C + ks * 16 + 8 * (lane >> 5);
-  out[i] = u32x4{ep_pk(s[0], s[1]), ep_pk(s[2], s[3]), ep_pk(s[4], s[5]), ep_pk(s[6], s[7])};
+  out[i] = u32x4{cgg_pk_bf16(s[0], s[1]), cgg_pk_bf16(s[2], s[3]), cgg_pk_bf16(s[4], s[5]), cgg_pk_bf16(s[6], s[7])};
 }
 
 extern "C" int cgg_decoder_kv_pack_k(const float* w, void* packed, int N, int K, cgg_stream_t stream) {

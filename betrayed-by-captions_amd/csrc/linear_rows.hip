@@ -7,7 +7,7 @@
 // 128-row m-block) per workgroup, one 32-row m-tile per wave; W tile lives in LDS as bf16 MFMA B fragments
 // (converted on the fly, K chunked by 512), x fragments go global -> registers -> bf16.
 // SPLIT = f32-class accuracy via 3 bf16 MFMAs on (hi, lo) operands; otherwise plain bf16.
-#include "cgg_common.h"
+#include "row_norm.h"
 
 #define LR_KC 256  // K chunk staged per pass (16 MFMA k-steps)
 
@@ -191,12 +191,6 @@ extern "C" int cgg_linear_rows(const float* x, int ldx, const float* w, const fl
 //   y32 (f32 residual stream), y16 = bf16(y) (next GEMM's input), yp16 = bf16(y + pos[row % pos_rows])
 //   (the "query + query_pos" input of the next layer's sampling-offset GEMM). One wave per row, N == 256:
 //   each lane owns 4 consecutive channels (16-B loads / stores).
-__device__ __forceinline__ f32x4 cgg_ln_load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 cgg_ln_load4(const uint16_t* p) {
-  const uint2 u = *reinterpret_cast<const uint2*>(p);
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-               __uint_as_float(u.y & 0xffff0000u)};
-}
 
 template <typename AT, typename BT>
 __global__ __launch_bounds__(256) void cgg_add_layernorm256_kernel(
@@ -207,28 +201,20 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm256_kernel(
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const size_t off = (size_t)row * 256 + lane * 4;
-  f32x4 v = cgg_ln_load4(a + off);
-  if (b != nullptr) v += cgg_ln_load4(b + off);
-  float s = (v[0] + v[1]) + (v[2] + v[3]);
-  s = cgg_wave_sum(s);
-  const float mean = s * (1.f / 256.f);
-  f32x4 d = v - mean;
-  float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-  q = cgg_wave_sum(q);
-  const float rstd = rsqrtf(q * (1.f / 256.f) + eps);
+  f32x4 v = cgg_row_load4(a + off);
+  if (b != nullptr) v += cgg_row_load4(b + off);
+  const float rstd = cgg_wave_norm(v, eps);
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + lane * 4);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + lane * 4);
-  f32x4 y = d * rstd * g + be;
+  f32x4 y = v * rstd * g + be;
   if (y32) *reinterpret_cast<f32x4*>(y32 + off) = y;
   if (y16) {
-    *reinterpret_cast<uint2*>(y16 + off) =
-        make_uint2(cgg_pack2(cgg_f2bf(y[0]), cgg_f2bf(y[1])), cgg_pack2(cgg_f2bf(y[2]), cgg_f2bf(y[3])));
+    *reinterpret_cast<uint2*>(y16 + off) = cgg_pk_bf16(y);
   }
   if (yp16) {
     const f32x4 p = *reinterpret_cast<const f32x4*>(pos + (size_t)(row % pos_rows) * 256 + lane * 4);
     const f32x4 z = y + p;
-    *reinterpret_cast<uint2*>(yp16 + off) =
-        make_uint2(cgg_pack2(cgg_f2bf(z[0]), cgg_f2bf(z[1])), cgg_pack2(cgg_f2bf(z[2]), cgg_f2bf(z[3])));
+    *reinterpret_cast<uint2*>(yp16 + off) = cgg_pk_bf16(z);
   }
 }
 
@@ -266,6 +252,8 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm256_bf16x8_kernel(
     y[k] = v[k] * rstd * g0[k] + b0[k];
     y[4 + k] = v[4 + k] * rstd * g1[k] + b1[k];
   }
+  // (the element-wise cgg_pack2(cgg_f2bf, cgg_f2bf) spelling stays in this kernel: with cgg_pk_bf16 here the compiler no longer
+  //  fuses the first two products of q above into one fma -- other bits of q)
   if (y16)
     y16[off] = make_uint4(cgg_pack2(cgg_f2bf(y[0]), cgg_f2bf(y[1])), cgg_pack2(cgg_f2bf(y[2]), cgg_f2bf(y[3])),
                           cgg_pack2(cgg_f2bf(y[4]), cgg_f2bf(y[5])), cgg_pack2(cgg_f2bf(y[6]), cgg_f2bf(y[7])));
@@ -320,63 +308,41 @@ extern "C" int cgg_add_layernorm_ex(const void* a, int a_dtype, const void* b, i
 // (V) and `memory_l + level_embed_l + decoder_pos_l` (K) per level (mask2former_head.py:795-812). Both bf16 operands
 // are produced here, by the LayerNorm that finishes the memory, written LEVEL-MAJOR ([level][batch][hw_l][256]) so each
 // level is one contiguous (B * hw_l, 256) GEMM operand:  m16 = bf16(y + shift[s]),  mp16 = bf16((y + shift[s]) + pos[s]).
-struct LnKvLevels { int n; int start[9]; };
-
 template <typename AT, typename BT>
 __global__ __launch_bounds__(256) void cgg_add_layernorm256_kv_kernel(
     const AT* __restrict__ a, const BT* __restrict__ b, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ shift, const float* __restrict__ pos, int S, int B,
-    LnKvLevels lv, float* __restrict__ y32, uint16_t* __restrict__ m16, uint16_t* __restrict__ mp16, int rows, float eps) {
+    CggLevelRows lv, float* __restrict__ y32, uint16_t* __restrict__ m16, uint16_t* __restrict__ mp16, int rows, float eps) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const size_t off = (size_t)row * 256 + lane * 4;
-  f32x4 v = cgg_ln_load4(a + off);
-  if (b != nullptr) v += cgg_ln_load4(b + off);
-  float s = (v[0] + v[1]) + (v[2] + v[3]);
-  s = cgg_wave_sum(s);
-  const float mean = s * (1.f / 256.f);
-  f32x4 d = v - mean;
-  float q = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-  q = cgg_wave_sum(q);
-  const float rstd = rsqrtf(q * (1.f / 256.f) + eps);
+  f32x4 v = cgg_row_load4(a + off);
+  if (b != nullptr) v += cgg_row_load4(b + off);
+  const float rstd = cgg_wave_norm(v, eps);
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + lane * 4);
   const f32x4 be = *reinterpret_cast<const f32x4*>(beta + lane * 4);
-  f32x4 y = d * rstd * g + be;
+  f32x4 y = v * rstd * g + be;
   if (y32) *reinterpret_cast<f32x4*>(y32 + off) = y;
   const int bi = row / S, si = row - bi * S;
-  int l = 0;
-  while (l + 1 < lv.n && si >= lv.start[l + 1]) ++l;
-  const int hw = lv.start[l + 1] - lv.start[l];
-  const size_t orow = (size_t)B * lv.start[l] + (size_t)bi * hw + (si - lv.start[l]);
-  const size_t ooff = orow * 256 + lane * 4;
+  const size_t ooff = cgg_level_row(lv, B, bi, si) * 256 + lane * 4;
   const f32x4 m = y + *reinterpret_cast<const f32x4*>(shift + (size_t)si * 256 + lane * 4);
-  *reinterpret_cast<uint2*>(m16 + ooff) =
-      make_uint2(cgg_pack2(cgg_f2bf(m[0]), cgg_f2bf(m[1])), cgg_pack2(cgg_f2bf(m[2]), cgg_f2bf(m[3])));
+  *reinterpret_cast<uint2*>(m16 + ooff) = cgg_pk_bf16(m);
   const f32x4 z = m + *reinterpret_cast<const f32x4*>(pos + (size_t)si * 256 + lane * 4);
-  *reinterpret_cast<uint2*>(mp16 + ooff) =
-      make_uint2(cgg_pack2(cgg_f2bf(z[0]), cgg_f2bf(z[1])), cgg_pack2(cgg_f2bf(z[2]), cgg_f2bf(z[3])));
+  *reinterpret_cast<uint2*>(mp16 + ooff) = cgg_pk_bf16(z);
 }
 
 extern "C" int cgg_add_layernorm_kv(const void* a, int a_dtype, const void* b, int b_dtype, const float* gamma, const float* beta,
                                     const float* shift, const float* pos, int S, const int* level_start_host,
                                     int n_levels, float* y32, void* m16, void* mp16, int rows, int N, float eps,
                                     cgg_stream_t stream) {
-  CGG_REQUIRE(a && gamma && beta && shift && pos && m16 && mp16 && level_start_host, CGG_EINVAL,
-              "cgg_add_layernorm_kv: null pointer");
-  CGG_REQUIRE(rows > 0 && S > 0 && rows % S == 0, CGG_EINVAL, "cgg_add_layernorm_kv: rows=%d not a multiple of S=%d", rows, S);
+  CGG_REQUIRE(a && gamma && beta && shift && pos && m16 && mp16, CGG_EINVAL, "cgg_add_layernorm_kv: null pointer");
   CGG_REQUIRE(N == 256, CGG_EUNSUPPORTED, "cgg_add_layernorm_kv: N=%d (only 256 is built)", N);
-  CGG_REQUIRE(n_levels >= 1 && n_levels <= 8, CGG_EUNSUPPORTED, "cgg_add_layernorm_kv: n_levels=%d (1..8)", n_levels);
   CGG_REQUIRE(b_dtype == CGG_F32 || b_dtype == CGG_BF16, CGG_EUNSUPPORTED, "cgg_add_layernorm_kv: b dtype %d", b_dtype);
-  LnKvLevels lv;
-  lv.n = n_levels;
-  for (int l = 0; l < n_levels; ++l) {
-    lv.start[l] = level_start_host[l];
-    CGG_REQUIRE(lv.start[l] >= 0 && lv.start[l] < S && (l == 0 ? lv.start[l] == 0 : lv.start[l] > lv.start[l - 1]),
-                CGG_EINVAL, "cgg_add_layernorm_kv: level_start must start at 0 and increase (level %d: %d)", l, lv.start[l]);
-  }
-  lv.start[n_levels] = S;
   CGG_REQUIRE(a_dtype == CGG_F32 || a_dtype == CGG_BF16, CGG_EUNSUPPORTED, "cgg_add_layernorm_kv: a dtype %d", a_dtype);
+  CggLevelRows lv;
+  const int rc = cgg_level_rows(lv, level_start_host, n_levels, rows, S, "cgg_add_layernorm_kv");
+  if (rc != CGG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((rows + 3) / 4);
 #define CGG_LNKV_LAUNCH(AT, BT)                                                                                          \

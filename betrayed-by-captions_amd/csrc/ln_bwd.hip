@@ -10,16 +10,9 @@
 //
 // 16 lanes share a row (lane sub = lane & 15 holds columns 4 sub + 64 k .. + 3, k = 0..3): the four row reductions are DPP adds
 // inside a 16-lane row, a wavefront works on 4 rows at a time, the column sums stay in 32 registers per lane until the end.
-#include "cgg_common.h"
+#include "row_norm.h"
 
 #define LNB_ROWS 256          // rows per workgroup (4 wavefronts x 4 rows x 16 iterations)
-
-__device__ __forceinline__ f32x4 lnb_load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 lnb_load4(const uint16_t* p) {
-  const uint2 u = *reinterpret_cast<const uint2*>(p);
-  return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-               __uint_as_float(u.y & 0xffff0000u)};
-}
 
 template <typename BT>
 __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float* __restrict__ dy, const uint16_t* __restrict__ dy16a,
@@ -49,11 +42,11 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float*
     float sm = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      s[k] = lnb_load4(a + off + 64 * k);
-      if (b != nullptr) s[k] += lnb_load4(b + off + 64 * k);
-      y[k] = dy != nullptr ? lnb_load4(dy + off + 64 * k) : f32x4{0.f, 0.f, 0.f, 0.f};
-      if (dy16a != nullptr) y[k] += lnb_load4(dy16a + off + 64 * k);
-      if (dy16b != nullptr) y[k] += lnb_load4(dy16b + off + 64 * k);
+      s[k] = cgg_row_load4(a + off + 64 * k);
+      if (b != nullptr) s[k] += cgg_row_load4(b + off + 64 * k);
+      y[k] = dy != nullptr ? cgg_row_load4(dy + off + 64 * k) : f32x4{0.f, 0.f, 0.f, 0.f};
+      if (dy16a != nullptr) y[k] += cgg_row_load4(dy16a + off + 64 * k);
+      if (dy16b != nullptr) y[k] += cgg_row_load4(dy16b + off + 64 * k);
       sm += (s[k][0] + s[k][1]) + (s[k][2] + s[k][3]);
     }
     const float mean = cgg_row16_sum(sm) * inv_n;
@@ -81,9 +74,7 @@ __global__ __launch_bounds__(256) void cgg_add_layernorm_bwd_kernel(const float*
         const f32x4 d = (y[k] * g4[k] - c1 - s[k] * c2) * rstd;
         *reinterpret_cast<f32x4*>(dx + off + 64 * k) = d;
         lmax = fmaxf(fmaxf(lmax, fmaxf(fabsf(d[0]), fabsf(d[1]))), fmaxf(fabsf(d[2]), fabsf(d[3])));
-        if (dx16)
-          *reinterpret_cast<uint2*>(dx16 + off + 64 * k) =
-              make_uint2(cgg_pack2(cgg_f2bf(d[0]), cgg_f2bf(d[1])), cgg_pack2(cgg_f2bf(d[2]), cgg_f2bf(d[3])));
+        if (dx16) *reinterpret_cast<uint2*>(dx16 + off + 64 * k) = cgg_pk_bf16(d);
         dg[k] += y[k] * s[k];
         db[k] += y[k];
       }
