@@ -17,7 +17,7 @@
 #define DT_STEPS (DT_C / 16)
 
 #define DT_FRAG (DT_STEPS * 64)     // u32x4 slots of one 32 x 256 A-fragment image (16 KiB)
-#define DT_MAX_PLANES 8             // split-K planes cgg_decoder_tail_kernel holds in registers per row (2048 / 256)
+#define DT_MAX_PLANES CGG_DECODER_TAIL_MAX_PLANES
 
 // a 32 x 256 A-fragment image: one 16-KiB half (bf16) or a hi and a lo half (x3: f16 pieces)
 template <bool X3>

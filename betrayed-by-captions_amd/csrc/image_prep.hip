@@ -19,14 +19,14 @@
 // build-flags: -ffp-contract=off
 #include "cgg_common.h"
 
-// the tap rule, the tile's LDS image and the address of a tap in it, the three-plane store, PrepConst
+// the tap rule, the tile's LDS image and the address of a tap in it, the three-plane store, PrepConst; the host checks of the staged bytes
 #include "u8_resize.h"
 
 #pragma clang fp contract(off)
 
 #define IP_TW 256
 #define IP_TH 16
-#define IP_COLS 8 /* descriptor row: byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w */
+#define IP_COLS CGG_IMAGE_PREP_TABLE_COLS
 
 // rule 2 for one target index k of an axis with source length s: taps i0 / i1 and their 11-bit weights
 __device__ __forceinline__ void ip_coef(int k, int s, double scale, int& i0, int& i1, int& a0, int& a1) {
@@ -111,31 +111,19 @@ extern "C" int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, in
   CGG_REQUIRE(B >= 1 && Hb >= 1 && Wb >= 1, CGG_EINVAL, "%s: B, Hb, Wb must be >= 1 (got %d, %d, %d)", me, B, Hb, Wb);
   CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && Hb <= CGG_IMAGE_PREP_MAX_DIM && Wb <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
               "%s: B, Hb, Wb must be <= %d (got %d, %d, %d)", me, CGG_IMAGE_PREP_MAX_DIM, B, Hb, Wb);
-  // the kernel forms byte addresses up to 7 past an image's end in int arithmetic before it guards them
-  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
-              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
-  CGG_REQUIRE(table_offset >= 0 && (table_offset & 3) == 0 && table_offset + (int64_t)B * IP_COLS * 4 <= staged_bytes, CGG_EINVAL,
-              "%s: the descriptor table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
-              (long long)table_offset, (long long)staged_bytes);
+  U8_TRY(u8_check_staged_bytes(me, staged_bytes));
+  U8_TRY(u8_check_table(me, "descriptor", table_offset, B, IP_COLS, staged_bytes));
   CGG_REQUIRE((((uintptr_t)staged) & 3u) == 0, CGG_EALIGN, "%s: staged must be 4-byte aligned", me);
   CGG_REQUIRE((Wb & 3) != 0 || cgg_aligned16(out), CGG_EALIGN, "%s: out must be 16-byte aligned when Wb %% 4 == 0", me);
-  for (int c = 0; c < 3; ++c)
-    CGG_REQUIRE(std_[c] != 0.f && std_[c] == std_[c] && mean[c] == mean[c] && pad_val[c] == pad_val[c], CGG_EINVAL,
-                "%s: mean / std / pad_val must be numbers and std non-zero (channel %d)", me, c);
+  U8_TRY(u8_check_norm3(me, mean, std_, pad_val));
   for (int b = 0; b < B; ++b) {
     const int32_t* d = table_host + IP_COLS * b;
     const int64_t off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], ph = d[6], pw = d[7];
-    CGG_REQUIRE(h >= 1 && w >= 1 && nh >= 1 && nw >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld -> %lld x %lld)", me, b,
-                (long long)h, (long long)w, (long long)nh, (long long)nw);
-    CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
-                "%s: image %d is %lld x %lld, larger than %d on a side", me, b, (long long)h, (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+    U8_TRY(u8_check_sizes(me, b, h, w, nh, nw));
     CGG_REQUIRE(nh <= ph && ph <= Hb && nw <= pw && pw <= Wb, CGG_EINVAL,
                 "%s: image %d: need new <= pad <= batch, got rows %lld / %lld / %d, columns %lld / %lld / %d", me, b, (long long)nh,
                 (long long)ph, Hb, (long long)nw, (long long)pw, Wb);
-    CGG_REQUIRE(pitch >= 3 * w, CGG_EINVAL, "%s: image %d: row pitch %lld < 3 * w = %lld", me, b, (long long)pitch, (long long)(3 * w));
-    CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
-                "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
-                (long long)(off + h * pitch), (long long)staged_bytes);
+    U8_TRY(u8_check_bytes(me, b, off, h, w, pitch, staged_bytes));
   }
   const PrepConst cst = u8_prep_const(mean, std_, pad_val, to_rgb, pad_before_norm);
   const dim3 grid((unsigned)((Wb + IP_TW - 1) / IP_TW), (unsigned)((Hb + IP_TH - 1) / IP_TH), (unsigned)B);

@@ -26,7 +26,7 @@
 #include "cgg_common.h"
 
 #define LSAP_DESC 6          // int64 words per problem: cost offset, nr, nc, output offset, label-row offset, gt-label offset
-#define LSAP_MAX_SIDE 1024
+#define LSAP_MAX_SIDE CGG_LSAP_MAX_SIDE
 
 namespace {
 

@@ -25,7 +25,7 @@ constexpr int MI_THREADS = 256;
 constexpr int MI_BLOCK = 64;                         // planes of each side per workgroup
 constexpr int MI_SLAB_WORDS = 64;                    // 32-bit words of one plane in a slab (64 beat 128 and 32 at 1024^2 and 480 x 640)
 constexpr int MI_STRIDE_WORDS = MI_SLAB_WORDS + 4;   // LDS words between planes: 17 quads, odd
-constexpr int MI_MAX_PLANES = 1024;
+constexpr int MI_MAX_PLANES = CGG_MASK_EVAL_MAX_MASKS;
 constexpr int MI_TARGET_GROUPS = 1024;               // workgroups aimed at: slab groups = TARGET / pair blocks
 
 struct MiGeom {
@@ -253,7 +253,7 @@ inline int mi_load_mode(const uint8_t* p, int64_t stride, int row_bytes) {
 // detections (score order, cut to max_det) and ground truths, and per area range the scan order of the ground truths (those that
 // count first); all threads then fill the category's IoU block in LDS (CM_IOU_LDS entries: in chunks of detections when the block
 // is larger) and each runs its sequential scan on LDS alone.
-constexpr int CM_MAX_T = 64, CM_MAX_A = 8, CM_MAX_K = 1024;
+constexpr int CM_MAX_T = CGG_MASK_EVAL_MAX_THRS, CM_MAX_A = CGG_MASK_EVAL_MAX_AREAS, CM_MAX_K = CGG_MASK_EVAL_MAX_CATS;
 constexpr int CM_IOU_LDS = 2048;
 
 // The IoU source of the matching scan: what a (detection, ground truth) pair's IoU and a detection's own area are made from.

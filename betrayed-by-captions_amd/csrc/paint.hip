@@ -22,8 +22,8 @@
 namespace {
 
 constexpr int PI_THREADS = 256;          // 4 rows x 64 mask bytes
-constexpr int PI_MAX_N = 1024;
-constexpr int PP_MAX_IDS = 1024;
+constexpr int PI_MAX_N = CGG_PAINT_MAX_MASKS;
+constexpr int PP_MAX_IDS = CGG_PAINT_MAX_IDS;
 constexpr int CC_THREADS = 256;
 
 __device__ __forceinline__ uint8_t paint_blend(uint8_t v, double ca, double oma) {

@@ -16,7 +16,7 @@
 #define PF_PPT 2                 // pixels per thread: rows ly and ly + 8 of the tile
 #define PF_STAGE_FLOATS 8192     // LDS window for one chunk of queries (32 KB)
 #define PF_MIN_CHUNK 8           // a footprint that leaves room for fewer queries per chunk reads global memory instead
-#define PF_MAX_Q 1024
+#define PF_MAX_Q CGG_PANOPTIC_FUSE_MAX_Q
 #define PF_GEOM_COLS 5           // geometry row: crop_h, crop_w, out_h, out_w, pixel offset into the flat map
 static_assert(PF_TW * PF_TH == 256 * PF_PPT, "one block covers its tile");
 static_assert(sizeof(int32_t) * 3 * PF_MAX_Q + sizeof(float) * PF_STAGE_FLOATS <= 64 * 1024,

@@ -19,7 +19,7 @@
 namespace {
 
 constexpr int PQ_THREADS = 256;
-constexpr int PQ_MAX_SLOTS = 4096;        // G and P (the LDS limit binds first for all but very lopsided shapes)
+constexpr int PQ_MAX_SLOTS = CGG_PQ_EVAL_MAX_SEGMENTS;
 constexpr int PQ_MAX_GROUPS = 256;
 constexpr int PQ_INSTANCE_OFFSET = 1000;  // [3P] mmdet.core.evaluation.panoptic_utils.INSTANCE_OFFSET
 

@@ -47,8 +47,8 @@
 
 #define TP_TW 256
 #define TP_TH 16
-#define TP_IMG_COLS 12 /* byte offset, h, w, pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset or -1 */
-#define TP_INST_COLS 3 /* image index, byte offset, pitch */
+#define TP_IMG_COLS CGG_TRAIN_PREP_IMG_COLS
+#define TP_INST_COLS CGG_TRAIN_PREP_INST_COLS
 
 // rule 2 for one resized index k of an axis with source length s: taps i0 / i1 and their float32 weights
 __device__ __forceinline__ void tp_coef(int k, int s, double scale, int& i0, int& i1, float& a0, float& a1) {
@@ -289,8 +289,8 @@ __global__ __launch_bounds__(256) void cgg_train_prep_plane_bits_kernel(const in
 }
 
 // ---- panoptic samples: every plane from ONE gather of the id map -------------------------------------------------------------------
-#define TP_PAN_COLS 5 /* byte offset of the id map, row pitch in bytes, format (0: int32, 1: R, G, B bytes), first segment row, rows */
-#define TP_SEG_COLS 2 /* id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t */
+#define TP_PAN_COLS CGG_TRAIN_PREP_PAN_COLS
+#define TP_SEG_COLS CGG_TRAIN_PREP_SEG_COLS
 #define TP_MAX_SEG CGG_TRAIN_PREP_MAX_SEGMENTS
 
 // the packed (slot, category) of `id` among the n rows sorted by id (lower bound, then equality); an id no row lists: no slot, 255
@@ -491,6 +491,17 @@ __global__ __launch_bounds__(256) void cgg_train_prep_panoptic_kernel(const uint
   }
 }
 
+// The images own consecutive ranges of the N instances, in order: image b's part of that rule. `next` carries the walk from row to
+// row (0 before the first); after the last row the ranges must have tiled 0 .. N.
+static int tp_instance_range(const char* me, int b, int B, int64_t first, int64_t n, int64_t* next, int N) {
+  CGG_REQUIRE(n >= 0 && first == *next && first + n <= N, CGG_EINVAL,
+              "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
+              (long long)first, (long long)(first + n), (long long)*next, N);
+  *next = first + n;
+  CGG_REQUIRE(b < B - 1 || *next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)*next, N);
+  return CGG_OK;
+}
+
 // Everything both entry points check about the scalar arguments, the outputs and the image rows, before any launch. `panoptic`: there
 // is no instance table (the things are found in the id map) and no staged semantic map (column 11 must be -1).
 static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset,
@@ -507,43 +518,26 @@ static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int
   CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && H <= CGG_IMAGE_PREP_MAX_DIM && W <= CGG_IMAGE_PREP_MAX_DIM &&
                   (int64_t)N + B <= CGG_IMAGE_PREP_MAX_DIM,
               CGG_EUNSUPPORTED, "%s: B + N, H, W must be <= %d (got %d + %d, %d, %d)", me, CGG_IMAGE_PREP_MAX_DIM, B, N, H, W);
-  // the kernels form byte addresses up to 7 past an image's end in int arithmetic before they guard them
-  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
-              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
-  CGG_REQUIRE(img_table_offset >= 0 && (img_table_offset & 3) == 0 && img_table_offset + (int64_t)B * TP_IMG_COLS * 4 <= staged_bytes,
-              CGG_EINVAL, "%s: the image table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
-              (long long)img_table_offset, (long long)staged_bytes);
-  CGG_REQUIRE(panoptic ||
-                  (inst_table_offset >= 0 && (inst_table_offset & 3) == 0 && inst_table_offset + (int64_t)N * TP_INST_COLS * 4 <= staged_bytes),
-              CGG_EINVAL, "%s: the instance table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, N,
-              (long long)inst_table_offset, (long long)staged_bytes);
+  U8_TRY(u8_check_staged_bytes(me, staged_bytes));
+  U8_TRY(u8_check_table(me, "image", img_table_offset, B, TP_IMG_COLS, staged_bytes));
+  if (!panoptic) U8_TRY(u8_check_table(me, "instance", inst_table_offset, N, TP_INST_COLS, staged_bytes));
   CGG_REQUIRE((((uintptr_t)staged) & 3u) == 0 && (((uintptr_t)stats) & 3u) == 0, CGG_EALIGN, "%s: staged and stats must be 4-byte aligned",
               me);
   CGG_REQUIRE((W & 3) != 0 || (cgg_aligned16(img) && (((uintptr_t)masks) & 3u) == 0 && (((uintptr_t)seg) & 3u) == 0), CGG_EALIGN,
               "%s: when W %% 4 == 0, img must be 16-byte and masks / seg 4-byte aligned", me);
-  for (int c = 0; c < 3; ++c)
-    CGG_REQUIRE(std_[c] != 0.f && std_[c] == std_[c] && mean[c] == mean[c] && pad_val[c] == pad_val[c], CGG_EINVAL,
-                "%s: mean / std / pad_val must be numbers and std non-zero (channel %d)", me, c);
+  U8_TRY(u8_check_norm3(me, mean, std_, pad_val));
   int64_t next = 0;
   for (int b = 0; b < B; ++b) {
     const int32_t* d = img_table_host + TP_IMG_COLS * b;
     const int64_t off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4], nw = d[5], oy = d[6], ox = d[7], flip = d[8], first = d[9],
                   n = d[10], soff = d[11];
-    CGG_REQUIRE(h >= 1 && w >= 1 && nh >= 1 && nw >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld -> %lld x %lld)", me, b,
-                (long long)h, (long long)w, (long long)nh, (long long)nw);
-    CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
-                "%s: image %d is %lld x %lld, larger than %d on a side", me, b, (long long)h, (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+    U8_TRY(u8_check_sizes(me, b, h, w, nh, nw));
     CGG_REQUIRE(oy >= 0 && ox >= 0 && oy <= (nh > crop_h ? nh - crop_h : 0) && ox <= (nw > crop_w ? nw - crop_w : 0), CGG_EINVAL,
                 "%s: image %d: the window at (%lld, %lld) lies outside the %lld x %lld resized image (crop %d x %d)", me, b,
                 (long long)oy, (long long)ox, (long long)nh, (long long)nw, crop_h, crop_w);
     CGG_REQUIRE(flip == 0 || flip == 1, CGG_EINVAL, "%s: image %d: flip must be 0 or 1 (got %lld)", me, b, (long long)flip);
-    CGG_REQUIRE(pitch >= 3 * w, CGG_EINVAL, "%s: image %d: row pitch %lld < 3 * w = %lld", me, b, (long long)pitch, (long long)(3 * w));
-    CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
-                "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
-                (long long)(off + h * pitch), (long long)staged_bytes);
-    CGG_REQUIRE(n >= 0 && first == next && first + n <= N, CGG_EINVAL,
-                "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
-                (long long)first, (long long)(first + n), (long long)next, N);
+    U8_TRY(u8_check_bytes(me, b, off, h, w, pitch, staged_bytes));
+    U8_TRY(tp_instance_range(me, b, B, first, n, &next, N));
     CGG_REQUIRE(!panoptic || soff == -1, CGG_EINVAL,
                 "%s: image %d: the semantic-map offset must be -1 (got %lld): no semantic map is staged", me, b,
                 (long long)soff);
@@ -563,9 +557,7 @@ static int tp_validate(const char* me, bool panoptic, const uint8_t* staged, int
                   "%s: instance %lld (bytes %lld .. %lld) extends past the %lld staged bytes", me, (long long)i, (long long)ioff,
                   (long long)(ioff + h * ipitch), (long long)staged_bytes);
     }
-    next = first + n;
   }
-  CGG_REQUIRE(next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)next, N);
   return CGG_OK;
 }
 
@@ -614,12 +606,8 @@ extern "C" int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_
   int rc = tp_validate(me, true, staged, staged_bytes, img_table_offset, 0, img_table_host, nullptr, B, N, mean, std_, pad_val, seg_pad,
                        crop_h, crop_w, img, masks, seg, stats, H, W);
   if (rc != CGG_OK) return rc;
-  CGG_REQUIRE(pan_table_offset >= 0 && (pan_table_offset & 3) == 0 && pan_table_offset + (int64_t)B * TP_PAN_COLS * 4 <= staged_bytes,
-              CGG_EINVAL, "%s: the panoptic table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, B,
-              (long long)pan_table_offset, (long long)staged_bytes);
-  CGG_REQUIRE(seg_table_offset >= 0 && (seg_table_offset & 3) == 0 && seg_table_offset + (int64_t)S * TP_SEG_COLS * 4 <= staged_bytes,
-              CGG_EINVAL, "%s: the segment table (%d rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, S,
-              (long long)seg_table_offset, (long long)staged_bytes);
+  U8_TRY(u8_check_table(me, "panoptic", pan_table_offset, B, TP_PAN_COLS, staged_bytes));
+  U8_TRY(u8_check_table(me, "segment", seg_table_offset, S, TP_SEG_COLS, staged_bytes));
   int64_t next = 0;
   for (int b = 0; b < B; ++b) {
     const int32_t* d = img_table_host + TP_IMG_COLS * b;
@@ -675,8 +663,8 @@ extern "C" int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_
 }
 
 // ---- polygon samples: the masks rasterised on the device (rule 6 of train_prep.py) ------------------------------------------------
-#define TP_POLY_INST_COLS 3 /* image index, first part, parts */
-#define TP_POLY_PART_COLS 2 /* byte offset of the part's 2 k float64 (a multiple of 8), vertex count k */
+#define TP_POLY_INST_COLS CGG_TRAIN_PREP_POLY_INST_COLS
+#define TP_POLY_PART_COLS CGG_TRAIN_PREP_POLY_PART_COLS
 #define PF_LDS_WORDS (CGG_POLY_LDS_BITS / 32)
 #define PF_SCAN_WORDS (CGG_POLY_SCAN_BITS / 32)
 static_assert(PF_SCAN_WORDS == 256, "one word per thread of the fill kernel's workgroup");
@@ -838,7 +826,9 @@ __global__ __launch_bounds__(256) void cgg_poly_fill_kernel(const uint8_t* __res
 }
 
 // h, w, first instance, instances of the image rows, as the polygon entry points need them: sizes, and ranges that tile 0 .. N
-static int pf_validate_images(const char* me, const int32_t* img_table_host, int B, int N, int force_ws, int64_t* pw, int* any_ws) {
+// (ranges_checked: tp_validate has walked them already)
+static int pf_validate_images(const char* me, const int32_t* img_table_host, int B, int N, int force_ws, bool ranges_checked,
+                              int64_t* pw, int* any_ws) {
   CGG_REQUIRE(img_table_host, CGG_EINVAL, "%s: null pointer (img_table_host)", me);
   CGG_REQUIRE(B >= 1 && N >= 0, CGG_EINVAL, "%s: B must be >= 1 and N >= 0 (got %d, %d)", me, B, N);
   CGG_REQUIRE(B <= CGG_IMAGE_PREP_MAX_DIM && (int64_t)N + B <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
@@ -852,16 +842,12 @@ static int pf_validate_images(const char* me, const int32_t* img_table_host, int
     CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM && h * w <= (int64_t)INT32_MAX - 31, CGG_EUNSUPPORTED,
                 "%s: image %d is %lld x %lld: larger than %d on a side, or more than 2^31 - 32 pixels", me, b, (long long)h,
                 (long long)w, CGG_IMAGE_PREP_MAX_DIM);
-    CGG_REQUIRE(n >= 0 && first == next && first + n <= N, CGG_EINVAL,
-                "%s: image %d: instances %lld .. %lld must follow the previous image's (%lld) and stay below N = %d", me, b,
-                (long long)first, (long long)(first + n), (long long)next, N);
+    if (!ranges_checked) U8_TRY(tp_instance_range(me, b, B, first, n, &next, N));
     if (n > 0) {
       words = words > (h * w + 31) / 32 ? words : (h * w + 31) / 32;
       if (h * w > CGG_POLY_LDS_BITS) ws = 1;
     }
-    next = first + n;
   }
-  CGG_REQUIRE(next == N, CGG_EINVAL, "%s: the images own %lld instances, N = %d", me, (long long)next, N);
   *pw = words;
   *any_ws = (ws || force_ws) && N > 0;
   return CGG_OK;
@@ -870,7 +856,7 @@ static int pf_validate_images(const char* me, const int32_t* img_table_host, int
 extern "C" int64_t cgg_train_prep_polygons_workspace_bytes(const int32_t* img_table_host, int B, int N, int force_workspace) {
   int64_t pw = 0;
   int any_ws = 0;
-  const int rc = pf_validate_images("cgg_train_prep_polygons_workspace_bytes", img_table_host, B, N, force_workspace, &pw, &any_ws);
+  const int rc = pf_validate_images("cgg_train_prep_polygons_workspace_bytes", img_table_host, B, N, force_workspace, false, &pw, &any_ws);
   if (rc != CGG_OK) return rc;
   return (int64_t)N * pw * 4 * (any_ws ? 2 : 1);
 }
@@ -879,27 +865,18 @@ extern "C" int64_t cgg_train_prep_polygons_workspace_bytes(const int32_t* img_ta
 static int pf_validate(const char* me, const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
                        int64_t part_table_offset, const int32_t* img_table_host, const int32_t* inst_table_host,
                        const int32_t* part_table_host, const uint8_t* staged_host, int B, int N, int P, const uint32_t* workspace,
-                       int64_t workspace_bytes, int force_ws, int64_t* pw_out) {
+                       int64_t workspace_bytes, int force_ws, bool ranges_checked, int64_t* pw_out) {
   CGG_REQUIRE(staged && img_table_host && P >= 0 && (N <= 0 || (inst_table_host && workspace)) &&
                   (P == 0 || (part_table_host && staged_host)),
               CGG_EINVAL, "%s: null pointer (staged, img_table_host; inst_table_host, workspace with N = %d; part_table_host, "
               "staged_host with P = %d)", me, N, P);
-  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
-              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
+  U8_TRY(u8_check_staged_bytes(me, staged_bytes));
   int64_t pw = 0;
   int any_ws = 0;
-  const int rc = pf_validate_images(me, img_table_host, B, N, force_ws, &pw, &any_ws);
-  if (rc != CGG_OK) return rc;
-  const struct {
-    const char* name;
-    int64_t off, rows, cols;
-  } tabs[3] = {{"image", img_table_offset, B, TP_IMG_COLS},
-               {"instance", inst_table_offset, N, TP_POLY_INST_COLS},
-               {"part", part_table_offset, P, TP_POLY_PART_COLS}};
-  for (int t = 0; t < 3; ++t)
-    CGG_REQUIRE(tabs[t].off >= 0 && (tabs[t].off & 3) == 0 && tabs[t].off + tabs[t].rows * tabs[t].cols * 4 <= staged_bytes, CGG_EINVAL,
-                "%s: the %s table (%lld rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, tabs[t].name,
-                (long long)tabs[t].rows, (long long)tabs[t].off, (long long)staged_bytes);
+  U8_TRY(pf_validate_images(me, img_table_host, B, N, force_ws, ranges_checked, &pw, &any_ws));
+  U8_TRY(u8_check_table(me, "image", img_table_offset, B, TP_IMG_COLS, staged_bytes));
+  U8_TRY(u8_check_table(me, "instance", inst_table_offset, N, TP_POLY_INST_COLS, staged_bytes));
+  U8_TRY(u8_check_table(me, "part", part_table_offset, P, TP_POLY_PART_COLS, staged_bytes));
   CGG_REQUIRE((((uintptr_t)staged) & 7u) == 0 && (((uintptr_t)workspace) & 3u) == 0, CGG_EALIGN,
               "%s: staged must be 8-byte and workspace 4-byte aligned", me);
   int64_t next = 0;
@@ -959,7 +936,8 @@ extern "C" int cgg_polygon_fill_bits(const uint8_t* staged, int64_t staged_bytes
   const char* me = "cgg_polygon_fill_bits";
   int64_t pw = 0;
   const int rc = pf_validate(me, staged, staged_bytes, img_table_offset, inst_table_offset, part_table_offset, img_table_host,
-                             inst_table_host, part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, &pw);
+                             inst_table_host, part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, false,
+                             &pw);
   if (rc != CGG_OK) return rc;
   return pf_launch(me, staged, img_table_offset, inst_table_offset, part_table_offset, N, workspace, (int)pw, force_workspace, stream);
 }
@@ -976,7 +954,7 @@ extern "C" int cgg_train_prep_polygons_u8(const uint8_t* staged, int64_t staged_
   if (rc != CGG_OK) return rc;
   int64_t pw = 0;
   rc = pf_validate(me, staged, staged_bytes, img_table_offset, inst_table_offset, part_table_offset, img_table_host, inst_table_host,
-                   part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, &pw);
+                   part_table_host, staged_host, B, N, P, workspace, workspace_bytes, force_workspace, true, &pw);
   if (rc != CGG_OK) return rc;
   const int32_t* table = reinterpret_cast<const int32_t*>(staged + img_table_offset);
   rc = tp_launch_image(me, staged, table, B, mean, std_, pad_val, to_rgb, crop_h, crop_w, img, stats, H, W, stream);

@@ -1,6 +1,7 @@
 // What the two uint8 image resizers share (cgg_image_prep_u8_kernel in image_prep.hip, cgg_train_prep_image_kernel in
 // train_prep.hip): the tap rule, a tile's source bytes staged into LDS, the address of a tap, the three-plane store and the
-// mean / 1 / std / pad constant. Each kernel keeps its own weights (11-bit integers or floats) and its own pixel formula.
+// mean / 1 / std / pad constant. Each kernel keeps its own weights (11-bit integers or floats) and its own pixel formula. At the
+// end, for the host: the checks of the staged-batch contract that the entry points of both files run before any launch.
 //
 // The rounding of (k + 0.5) * scale - 0.5 decides which source pixel a tap lands on, and the compiler would fuse exactly that
 // pattern, so this header turns contraction off. The pragma is at file scope and therefore LEAKS into the rest of the including
@@ -133,4 +134,53 @@ __device__ __forceinline__ void u8_store_planes(float* __restrict__ o, size_t pl
       for (int c = 0; c < 4; ++c)
         if (xl + c < Wb) o[q * plane + c] = v[q][c];
   }
+}
+
+// ---- the staged-batch contract, host side ----------------------------------------------------------------------------------------
+// What every entry point of the two files checks, before any launch, about the staged bytes, the tables in them and the source
+// images their rows describe. Each check sets the error string under the entry point's name `me` and answers the status.
+#define U8_TRY(call)                     \
+  do {                                   \
+    const int rc__ = (call);             \
+    if (rc__ != CGG_OK) return rc__;     \
+  } while (0)
+
+// the kernels form byte addresses up to 7 past an image's end in int arithmetic before they guard them
+static inline int u8_check_staged_bytes(const char* me, int64_t staged_bytes) {
+  CGG_REQUIRE(staged_bytes >= 1 && staged_bytes <= (int64_t)INT32_MAX - 8, staged_bytes < 1 ? CGG_EINVAL : CGG_EUNSUPPORTED,
+              "%s: staged_bytes must be in 1 .. 2^31 - 9 (got %lld)", me, (long long)staged_bytes);
+  return CGG_OK;
+}
+
+// the `name` table: `rows` rows of `cols` int32 at byte `off`, a multiple of 4, inside the staged bytes
+static inline int u8_check_table(const char* me, const char* name, int64_t off, int64_t rows, int64_t cols, int64_t staged_bytes) {
+  CGG_REQUIRE(off >= 0 && (off & 3) == 0 && off + rows * cols * 4 <= staged_bytes, CGG_EINVAL,
+              "%s: the %s table (%lld rows at byte %lld, a multiple of 4) must lie inside the %lld staged bytes", me, name,
+              (long long)rows, (long long)off, (long long)staged_bytes);
+  return CGG_OK;
+}
+
+static inline int u8_check_norm3(const char* me, const float* mean, const float* std_, const float* pad_val) {
+  for (int c = 0; c < 3; ++c)
+    CGG_REQUIRE(std_[c] != 0.f && std_[c] == std_[c] && mean[c] == mean[c] && pad_val[c] == pad_val[c], CGG_EINVAL,
+                "%s: mean / std / pad_val must be numbers and std non-zero (channel %d)", me, c);
+  return CGG_OK;
+}
+
+// the sizes of image b's row: h x w resized to nh x nw, neither empty, the source within the index arithmetic of the kernels
+static inline int u8_check_sizes(const char* me, int b, int64_t h, int64_t w, int64_t nh, int64_t nw) {
+  CGG_REQUIRE(h >= 1 && w >= 1 && nh >= 1 && nw >= 1, CGG_EINVAL, "%s: image %d is zero-sized (%lld x %lld -> %lld x %lld)", me, b,
+              (long long)h, (long long)w, (long long)nh, (long long)nw);
+  CGG_REQUIRE(h <= CGG_IMAGE_PREP_MAX_DIM && w <= CGG_IMAGE_PREP_MAX_DIM, CGG_EUNSUPPORTED,
+              "%s: image %d is %lld x %lld, larger than %d on a side", me, b, (long long)h, (long long)w, CGG_IMAGE_PREP_MAX_DIM);
+  return CGG_OK;
+}
+
+// the bytes of image b's row: h rows of 3 w bytes, `pitch` apart from byte `off`, inside the staged bytes
+static inline int u8_check_bytes(const char* me, int b, int64_t off, int64_t h, int64_t w, int64_t pitch, int64_t staged_bytes) {
+  CGG_REQUIRE(pitch >= 3 * w, CGG_EINVAL, "%s: image %d: row pitch %lld < 3 * w = %lld", me, b, (long long)pitch, (long long)(3 * w));
+  CGG_REQUIRE(off >= 0 && off + h * pitch <= staged_bytes, CGG_EINVAL,
+              "%s: image %d (bytes %lld .. %lld) extends past the %lld staged bytes", me, b, (long long)off,
+              (long long)(off + h * pitch), (long long)staged_bytes);
+  return CGG_OK;
 }

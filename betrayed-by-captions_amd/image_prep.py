@@ -273,6 +273,44 @@ class _Slot:
         self.consumed = None        # event behind the slot's last kernel: the device bytes may be overwritten after it
 
 
+class _StagingRing:
+    """`slots` staging slots used in rotation, and the events that let a slot be used again without a synchronisation. Per batch:
+    `acquire` a slot, fill its pinned bytes, `upload` them, launch what reads the device bytes, `release`."""
+
+    def __init__(self, device, slots, who):
+        if slots < 1:
+            raise CggError(f'{who}: slots must be >= 1')
+        self.device = device
+        self.slots = [None] * slots
+        self.n = 0                  # batches so far: batch i takes slot i % len(slots)
+
+    def acquire(self, nbytes):
+        """the next slot, of at least `nbytes`, its pinned bytes free to be overwritten"""
+        k = self.n % len(self.slots)
+        self.n += 1
+        slot = self.slots[k]
+        if slot is not None and slot.copied is not None:
+            slot.copied.synchronize()                        # host: the pinned bytes have left
+        if slot is None or slot.pinned.numel() < nbytes:
+            if slot is not None and slot.consumed is not None:
+                torch.cuda.current_stream(self.device).wait_event(slot.consumed)
+            slot = self.slots[k] = _Slot(max(1 << 16, 1 << (nbytes - 1).bit_length()), self.device)
+        return slot
+
+    def upload(self, slot, n, stream):
+        """the ONE H2D copy of the batch: the slot's first `n` pinned bytes to its device bytes, on `stream`"""
+        if slot.consumed is not None:
+            stream.wait_event(slot.consumed)                 # device: the kernels that read this slot last are done (another stream)
+        slot.dev[:n].copy_(slot.pinned[:n], non_blocking=True)
+        slot.copied = torch.cuda.Event()
+        slot.copied.record(stream)
+
+    def release(self, slot, stream):
+        """after the last launch that reads the slot's device bytes"""
+        slot.consumed = torch.cuda.Event()
+        slot.consumed.record(stream)
+
+
 class ImagePrep:
     """Device-side test pipeline: `prep(imgs) -> (batch (B, 3, Hb, Wb) float32 on `device`, img_metas)`, equal to `prepare_host`.
 
@@ -288,23 +326,8 @@ class ImagePrep:
             raise CggError(f'ImagePrep needs a ROCm device (got {device}); prepare_host is the host-side form of the same rule')
         if not isinstance(spec, PrepSpec):
             spec = parse_test_pipeline(spec)
-        if slots < 1:
-            raise CggError('ImagePrep: slots must be >= 1')
         self.spec, self.device = spec, device
-        self._slots = [None] * slots
-        self._n = 0
-
-    def _slot(self, nbytes):
-        k = self._n % len(self._slots)
-        self._n += 1
-        slot = self._slots[k]
-        if slot is not None and slot.copied is not None:
-            slot.copied.synchronize()                        # host: the pinned bytes have left
-        if slot is None or slot.pinned.numel() < nbytes:
-            if slot is not None and slot.consumed is not None:
-                torch.cuda.current_stream(self.device).wait_event(slot.consumed)
-            slot = self._slots[k] = _Slot(max(1 << 16, 1 << (nbytes - 1).bit_length()), self.device)
-        return slot
+        self._ring = _StagingRing(device, slots, 'ImagePrep')
 
     def describe(self, imgs):
         """((B, 3, Hb, Wb), img_metas) of the batch `self(imgs)` would return; no device work."""
@@ -334,7 +357,7 @@ class ImagePrep:
         elif tuple(out.shape) != (B, 3, Hb, Wb):
             raise CggError(f'ImagePrep: out must be {(B, 3, Hb, Wb)} for this batch (got {tuple(out.shape)})')
         with torch.cuda.device(self.device):
-            slot = self._slot(n)
+            slot = self._ring.acquire(n)
             stream = torch.cuda.current_stream(self.device)
             table = slot.host[:table_bytes].view(np.int32).reshape(B, TABLE_COLS)
             on_device = []
@@ -345,16 +368,11 @@ class ImagePrep:
                     on_device.append((s, off, h, w))
                 else:
                     np.copyto(slot.host[off:off + h * w * 3].reshape(h, w, 3), s)
-            if slot.consumed is not None:
-                stream.wait_event(slot.consumed)             # device: the kernel that read this slot last is done (another stream)
-            slot.dev[:n].copy_(slot.pinned[:n], non_blocking=True)
-            slot.copied = torch.cuda.Event()
-            slot.copied.record(stream)
+            self._ring.upload(slot, n, stream)
             for s, off, h, w in on_device:
                 slot.dev[off:off + h * w * 3].view(h, w, 3).copy_(s, non_blocking=True)
             ops.image_prep_u8(slot.dev, slot.pinned[:table_bytes].view(torch.int32).view(B, TABLE_COLS), out, spec.mean, spec.std,
                               spec.pad_val, to_rgb=spec.to_rgb, pad_before_norm=spec.pad_before_norm, table_offset=0, staged_bytes=n)
-            slot.consumed = torch.cuda.Event()
-            slot.consumed.record(stream)
+            self._ring.release(slot, stream)
         metas = [image_meta(s.shape[:2], spec, g) for s, g in zip(srcs, geoms)]
         return out, metas

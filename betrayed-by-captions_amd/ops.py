@@ -868,7 +868,7 @@ def panoptic_paint(ids, win_half, lut_val, lut_half, void_label):
     return seg
 
 
-PANOPTIC_FUSE_MAX_Q = 1024
+PANOPTIC_FUSE_MAX_Q = CONSTANTS['CGG_PANOPTIC_FUSE_MAX_Q']
 
 
 def panoptic_fuse_geometry(out_sizes, crop_sizes, device):
@@ -2070,7 +2070,7 @@ def self_attn_rows_bf16(q, kv, B, num_heads, scale=None):
     return out
 
 
-DECODER_TAIL_MAX_PLANES = 8          # csrc/decoder_tail.hip DT_MAX_PLANES: more planes are refused (CGG_EUNSUPPORTED), not dropped
+DECODER_TAIL_MAX_PLANES = CONSTANTS['CGG_DECODER_TAIL_MAX_PLANES']   # more planes are refused (CGG_EUNSUPPORTED), not dropped
 
 
 def decoder_tail(planes, norm_a, pos, norm_b, mlp, qproj=None, want_pos=False):
@@ -2350,7 +2350,7 @@ def linear_sum_assignment_batch(costs):
     return out
 
 
-LSAP_MAX_SIDE = 1024                # cgg_lsap_device_f32: sides of a problem
+LSAP_MAX_SIDE = CONSTANTS['CGG_LSAP_MAX_SIDE']     # cgg_lsap_device_f32: sides of a problem
 LSAP_OK, LSAP_INVALID, LSAP_INFEASIBLE, LSAP_BAD_DESCRIPTOR = 0, 1, 2, 3
 
 
@@ -2535,7 +2535,21 @@ def subsample_nhwc(x, stride):
 # ------------------------------------------------------------------------------------------------
 # input side: the reference's test pipeline on raw uint8 images (image_prep.py states the rule)
 # ------------------------------------------------------------------------------------------------
-IMAGE_PREP_TABLE_COLS = 8     # byte offset, h, w, row pitch, new_h, new_w, pad_h, pad_w
+# The staged-batch contract of the four entry families below, stated once. `staged` is a 1-D DEVICE uint8 buffer that carries the
+# descriptor tables (int32 rows, by default back to back from byte `*_table_offset`) and the raw planes, moved with one H2D copy;
+# every table is also handed over as a contiguous HOST int32 copy, which the library validates before any launch. A call is refused
+# on types and shapes first, then on `staged_bytes`, then on where the tensors live. The widths are include/cgg_hip.h's.
+IMAGE_PREP_TABLE_COLS = CONSTANTS['CGG_IMAGE_PREP_TABLE_COLS']
+TRAIN_PREP_IMG_COLS = CONSTANTS['CGG_TRAIN_PREP_IMG_COLS']
+TRAIN_PREP_INST_COLS = CONSTANTS['CGG_TRAIN_PREP_INST_COLS']
+TRAIN_PREP_PAN_COLS = CONSTANTS['CGG_TRAIN_PREP_PAN_COLS']
+TRAIN_PREP_SEG_COLS = CONSTANTS['CGG_TRAIN_PREP_SEG_COLS']
+TRAIN_PREP_MAX_SEGMENTS = CONSTANTS['CGG_TRAIN_PREP_MAX_SEGMENTS']
+TRAIN_PREP_POLY_INST_COLS = CONSTANTS['CGG_TRAIN_PREP_POLY_INST_COLS']
+TRAIN_PREP_POLY_PART_COLS = CONSTANTS['CGG_TRAIN_PREP_POLY_PART_COLS']
+TRAIN_PREP_MAX_COORD = CONSTANTS['CGG_IMAGE_PREP_MAX_DIM']      # |coordinate| of a polygon vertex: it bounds the edge walk
+POLY_LDS_BITS = CONSTANTS['CGG_POLY_LDS_BITS']                  # a plane of more pixels keeps its toggle plane in the workspace
+POLY_SCAN_BITS = CONSTANTS['CGG_POLY_SCAN_BITS']                # pixels of one scan block of the fill kernel
 
 
 def three_floats(v, name):
@@ -2546,100 +2560,123 @@ def three_floats(v, name):
     return vals
 
 
+def _norm3(me, mean, std, pad_val):
+    """the three per-channel float arrays of a prep call"""
+    return ((ctypes.c_float * 3)(*three_floats(mean, f'{me}: mean')), (ctypes.c_float * 3)(*three_floats(std, f'{me}: std')),
+            (ctypes.c_float * 3)(*three_floats(pad_val, f'{me}: pad_val')))
+
+
+def _shaped(me, name, t, shape, dtype, like=None):
+    """`t` is a tensor of `dtype` and `shape` (None: any extent), on the device of the img tensor `like` where one is given"""
+    if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != len(shape) or \
+            any(want is not None and want != got for want, got in zip(shape, t.shape)):
+        want = ', '.join('?' if n is None else str(n) for n in shape)
+        raise CggError(f'{me}: {name} must be a ({want}{"," if len(shape) == 1 else ""}) {dtype} tensor '
+                       f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
+    if like is not None and t.device != like.device:
+        raise CggError(f'{me}: {name} ({t.device}) and img ({like.device}) live on different devices')
+
+
+def _host_tables(me, *tables):
+    """every (name, tensor, cols) is a contiguous HOST int32 (rows, cols) tensor, and the first, with one row per image, is not
+    empty -> the row counts"""
+    for name, t, cols in tables:
+        _shaped(me, name, t, (None, cols), torch.int32)
+        if t.is_cuda or not t.is_contiguous():
+            raise CggError(f'{me}: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
+    if tables[0][1].shape[0] < 1:
+        raise CggError(f'{me}: an empty batch')
+    return [int(t.shape[0]) for _, t, _ in tables]
+
+
+def _staged_u8(me, staged, staged_bytes, staged_host=None, with_host=False):
+    """`staged` is 1-D uint8 (with_host: and `staged_host` its 1-D uint8 HOST copy) and holds `staged_bytes` -> that byte count
+    (all of `staged` by default)"""
+    _shaped(me, 'staged', staged, (None,), torch.uint8)
+    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
+    if with_host:
+        _shaped(me, 'staged_host', staged_host, (None,), torch.uint8)
+        if staged_host.is_cuda:
+            raise CggError(f'{me}: staged_host must be a HOST tensor, the copy of the staged bytes')
+        if nbytes > staged_host.numel():
+            raise CggError(f'{me}: staged_bytes {nbytes} exceeds the {staged_host.numel()} bytes of staged_host')
+    if nbytes > staged.numel():
+        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
+    return nbytes
+
+
+def _staged_and_img(me, staged, img, name='img'):
+    """device addresses of `staged` and of the image batch, which live on one device"""
+    sp, ip = dev_ptr(staged, f'{me}: staged'), dev_ptr(img, f'{me}: {name}')
+    if staged.device != img.device:
+        raise CggError(f'{me}: staged ({staged.device}) and {name} ({img.device}) live on different devices')
+    return sp, ip
+
+
+def _back_to_back(first, *following):
+    """byte offsets of the tables: `first`, then per (offset or None, cols, rows of the table before) the offset given, or by
+    default the byte after the table before"""
+    offsets = [int(first)]
+    for off, cols, rows in following:
+        offsets.append(offsets[-1] + 4 * cols * rows if off is None else int(off))
+    return offsets
+
+
 def image_prep_u8(staged, table, out, mean, std, pad_val=0.0, to_rgb=True, pad_before_norm=True, table_offset=0, staged_bytes=None):
     """Resize (8-bit bilinear) + Pad + Normalize(to_rgb) + collate of a whole batch in one launch (`cgg_image_prep_u8`, no
     synchronisation). staged: DEVICE uint8 (n,) -- the raw HWC images back to back and the descriptor table at byte `table_offset`;
-    table: HOST int32 (B, 8) copy of those rows (byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w), read for validation during
-    the call; out: DEVICE float32 (B, 3, Hb, Wb) contiguous, every element of which is written. Returns `out`."""
-    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
-        raise CggError(f'image_prep_u8: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))}, '
-                       f'{getattr(staged, "dim", lambda: "?")()} dims)')
-    if not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != IMAGE_PREP_TABLE_COLS:
-        raise CggError(f'image_prep_u8: table must be a (B, {IMAGE_PREP_TABLE_COLS}) torch.int32 tensor '
-                       f'(got {getattr(table, "dtype", type(table))}, shape {tuple(getattr(table, "shape", ()))})')
-    if table.is_cuda or not table.is_contiguous():
-        raise CggError('image_prep_u8: table must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
-    if not torch.is_tensor(out) or out.dtype != torch.float32:
-        raise CggError(f'image_prep_u8: out must be torch.float32 (got {getattr(out, "dtype", type(out))})')
-    B = int(table.shape[0])
-    if out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3:
-        raise CggError(f'image_prep_u8: out must be ({B}, 3, Hb, Wb) (got {tuple(out.shape)})')
-    if B < 1:
-        raise CggError('image_prep_u8: an empty batch')
-    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
-    if nbytes > staged.numel():
-        raise CggError(f'image_prep_u8: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
-    sp, op = dev_ptr(staged, 'image_prep_u8: staged'), dev_ptr(out, 'image_prep_u8: out')
-    if staged.device != out.device:
-        raise CggError(f'image_prep_u8: staged ({staged.device}) and out ({out.device}) live on different devices')
-    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'image_prep_u8: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    table: HOST int32 (B, IMAGE_PREP_TABLE_COLS) copy of those rows (byte offset, h, w, pitch, new_h, new_w, pad_h, pad_w), read for
+    validation during the call; out: DEVICE float32 (B, 3, Hb, Wb) contiguous, every element of which is written. Returns `out`."""
+    me = 'image_prep_u8'
+    B, = _host_tables(me, ('table', table, IMAGE_PREP_TABLE_COLS))
+    _shaped(me, 'out', out, (B, 3, None, None), torch.float32)
+    nbytes = _staged_u8(me, staged, staged_bytes)
+    sp, op = _staged_and_img(me, staged, out, 'out')
+    m, s, p = _norm3(me, mean, std, pad_val)
     Hb, Wb = int(out.shape[2]), int(out.shape[3])
-    with _timed('image_prep_u8', bytes=float(nbytes + out.numel() * 4), shape=(B, Hb, Wb)):
+    with _timed(me, bytes=float(nbytes + out.numel() * 4), shape=(B, Hb, Wb)):
         _call('cgg_image_prep_u8', sp, nbytes, int(table_offset), host_ptr(table, 'table', torch.int32), B, m, s, p, int(bool(to_rgb)),
               int(bool(pad_before_norm)), op, Hb, Wb, stream_ptr(out.device))
     return out
 
 
-TRAIN_PREP_IMG_COLS = 12      # byte offset, h, w, row pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset / -1
-TRAIN_PREP_INST_COLS = 3      # image index, byte offset, row pitch
+def _train_outputs(me, img, B, N, masks, seg, stats):
+    """img (B, 3, H, W) f32, masks (N, H, W) u8 (N None: as many as it has), seg (B, 1, H, W) u8 or None, stats (N, 5) i32, all on
+    img's device -> N, H, W"""
+    _shaped(me, 'img', img, (B, 3, None, None), torch.float32)
+    H, W = int(img.shape[2]), int(img.shape[3])
+    _shaped(me, 'masks', masks, (N, H, W), torch.uint8, img)
+    N = int(masks.shape[0])
+    if seg is not None:
+        _shaped(me, 'seg', seg, (B, 1, H, W), torch.uint8, img)
+    _shaped(me, 'stats', stats, (N, 5), torch.int32, img)
+    return N, H, W
 
 
 def train_prep_u8(staged, img_table, inst_table, img, masks, seg, stats, mean, std, pad_val=0.0, to_rgb=True, crop_size=None, seg_pad=255,
                   img_table_offset=0, inst_table_offset=None, staged_bytes=None):
     """Flip + jittered Resize + RandomCrop + Pad + Normalize(to_rgb) of a whole batch of raw samples -- images, instance bitmaps,
     semantic maps -- in two launches (`cgg_train_prep_u8`, no synchronisation; train_prep.py states the rule). staged: DEVICE uint8
-    (n,) -- the two tables at bytes `img_table_offset` / `inst_table_offset` and the planes; img_table (B, 12) / inst_table (N, 3):
-    HOST int32 copies of those rows, read for validation during the call; img (B, 3, H, W) f32, masks (N, H, W) u8, seg (B, 1, H, W)
-    u8 or None, stats (N, 5) i32: DEVICE, contiguous, every element written (the caller clears nothing). crop_size (h, w) defaults
-    to the plane. Returns (img, masks, seg, stats)."""
-    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
-        raise CggError(f'train_prep_u8: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
-    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_INST_COLS)):
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
-            raise CggError(f'train_prep_u8: {name} must be a (rows, {cols}) torch.int32 tensor '
-                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
-        if t.is_cuda or not t.is_contiguous():
-            raise CggError(f'train_prep_u8: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
-    B, N = int(img_table.shape[0]), int(inst_table.shape[0])
-    if B < 1:
-        raise CggError('train_prep_u8: an empty batch')
-    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
-        raise CggError(f'train_prep_u8: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
-                       f'shape {tuple(getattr(img, "shape", ()))})')
-    H, W = int(img.shape[2]), int(img.shape[3])
-    for name, t, shape, dt in (('masks', masks, (N, H, W), torch.uint8), ('seg', seg, (B, 1, H, W), torch.uint8),
-                               ('stats', stats, (N, 5), torch.int32)):
-        if t is None and name == 'seg':
-            continue
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
-            raise CggError(f'train_prep_u8: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
-                           f'shape {tuple(getattr(t, "shape", ()))})')
-        if t.device != img.device:
-            raise CggError(f'train_prep_u8: {name} ({t.device}) and img ({img.device}) live on different devices')
-    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
-    if nbytes > staged.numel():
-        raise CggError(f'train_prep_u8: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
-    sp, ip = dev_ptr(staged, 'train_prep_u8: staged'), dev_ptr(img, 'train_prep_u8: img')
-    if staged.device != img.device:
-        raise CggError(f'train_prep_u8: staged ({staged.device}) and img ({img.device}) live on different devices')
-    mp = dev_ptr(masks, 'train_prep_u8: masks') if N else None
-    tp = dev_ptr(stats, 'train_prep_u8: stats') if N else None
-    gp = dev_ptr(seg, 'train_prep_u8: seg')
-    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'train_prep_u8: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    (n,) -- the two tables at bytes `img_table_offset` / `inst_table_offset` and the planes; img_table (B, TRAIN_PREP_IMG_COLS) /
+    inst_table (N, TRAIN_PREP_INST_COLS): HOST int32 copies of those rows, read for validation during the call; img (B, 3, H, W) f32,
+    masks (N, H, W) u8, seg (B, 1, H, W) u8 or None, stats (N, 5) i32: DEVICE, contiguous, every element written (the caller clears
+    nothing). crop_size (h, w) defaults to the plane. Returns (img, masks, seg, stats)."""
+    me = 'train_prep_u8'
+    B, N = _host_tables(me, ('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_INST_COLS))
+    N, H, W = _train_outputs(me, img, B, N, masks, seg, stats)
+    nbytes = _staged_u8(me, staged, staged_bytes)
+    sp, ip = _staged_and_img(me, staged, img)
+    mp = dev_ptr(masks, f'{me}: masks') if N else None
+    tp = dev_ptr(stats, f'{me}: stats') if N else None
+    gp = dev_ptr(seg, f'{me}: seg')
+    m, s, p = _norm3(me, mean, std, pad_val)
     ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
-    if inst_table_offset is None:
-        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
-    with _timed('train_prep_u8', bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)),
-                shape=(B, N, H, W)):
-        _call('cgg_train_prep_u8', sp, nbytes, int(img_table_offset), int(inst_table_offset),
-              host_ptr(img_table, 'img_table', torch.int32), host_ptr(inst_table, 'inst_table', torch.int32) if N else None, B, N, m, s,
-              p, int(bool(to_rgb)), int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
+    img_off, inst_off = _back_to_back(img_table_offset, (inst_table_offset, TRAIN_PREP_IMG_COLS, B))
+    with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)), shape=(B, N, H, W)):
+        _call('cgg_train_prep_u8', sp, nbytes, img_off, inst_off, host_ptr(img_table, 'img_table', torch.int32),
+              host_ptr(inst_table, 'inst_table', torch.int32) if N else None, B, N, m, s, p, int(bool(to_rgb)), int(seg_pad), ch, cw,
+              ip, mp, gp, tp, H, W, stream_ptr(img.device))
     return img, masks, seg, stats
-
-
-TRAIN_PREP_PAN_COLS = 5       # byte offset of the id map, row pitch, format (0: int32 ids, 1: R, G, B bytes), first segment row, segment rows
-TRAIN_PREP_SEG_COLS = 2       # id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t
-TRAIN_PREP_MAX_SEGMENTS = CONSTANTS['CGG_TRAIN_PREP_MAX_SEGMENTS']
 
 
 def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, seg, stats, mean, std, pad_val=0.0, to_rgb=True,
@@ -2648,99 +2685,45 @@ def train_prep_panoptic_u8(staged, img_table, pan_table, seg_table, img, masks, 
     """`train_prep_u8` for panoptic samples: the thing masks, the semantic plane and the statistics come from ONE gather of the staged
     id map per output pixel (`cgg_train_prep_panoptic_u8`, two launches, no synchronisation; train_prep.py states the rule). staged:
     DEVICE uint8 (n,) -- the three tables at bytes `img_table_offset` / `pan_table_offset` / `seg_table_offset` (by default back to
-    back), the images and the id maps; img_table (B, 12) with the thing counts and -1 for the semantic-map offset, pan_table (B, 5),
-    seg_table (S, 2) rows sorted by id within an image: HOST int32 copies, read for validation during the call; img (B, 3, H, W)
-    f32, masks (N, H, W) u8, seg (B, 1, H, W) u8 or None, stats (N, 5) i32: DEVICE, contiguous, every element written (the caller
-    clears nothing). Returns (img, masks, seg, stats)."""
+    back), the images and the id maps; img_table (B, TRAIN_PREP_IMG_COLS) with the thing counts and -1 for the semantic-map offset,
+    pan_table (B, TRAIN_PREP_PAN_COLS), seg_table (S, TRAIN_PREP_SEG_COLS) rows sorted by id within an image: HOST int32 copies, read
+    for validation during the call; img (B, 3, H, W) f32, masks (N, H, W) u8, seg (B, 1, H, W) u8 or None, stats (N, 5) i32: DEVICE,
+    contiguous, every element written (the caller clears nothing). Returns (img, masks, seg, stats)."""
     me = 'train_prep_panoptic_u8'
-    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
-        raise CggError(f'{me}: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
-    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('pan_table', pan_table, TRAIN_PREP_PAN_COLS),
-                          ('seg_table', seg_table, TRAIN_PREP_SEG_COLS)):
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
-            raise CggError(f'{me}: {name} must be a (rows, {cols}) torch.int32 tensor '
-                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
-        if t.is_cuda or not t.is_contiguous():
-            raise CggError(f'{me}: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
-    B, S = int(img_table.shape[0]), int(seg_table.shape[0])
-    if B < 1:
-        raise CggError(f'{me}: an empty batch')
-    if pan_table.shape[0] != B:
-        raise CggError(f'{me}: pan_table must have one row per image ({B}), got {int(pan_table.shape[0])}')
-    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
-        raise CggError(f'{me}: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
-                       f'shape {tuple(getattr(img, "shape", ()))})')
-    H, W = int(img.shape[2]), int(img.shape[3])
-    if not torch.is_tensor(masks) or masks.dtype != torch.uint8 or masks.dim() != 3 or tuple(masks.shape[1:]) != (H, W):
-        raise CggError(f'{me}: masks must be a (N, {H}, {W}) torch.uint8 tensor (got {getattr(masks, "dtype", type(masks))}, '
-                       f'shape {tuple(getattr(masks, "shape", ()))})')
-    N = int(masks.shape[0])
-    for name, t, shape, dt in (('seg', seg, (B, 1, H, W), torch.uint8), ('stats', stats, (N, 5), torch.int32)):
-        if t is None and name == 'seg':
-            continue
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
-            raise CggError(f'{me}: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
-                           f'shape {tuple(getattr(t, "shape", ()))})')
-    for name, t in (('masks', masks), ('seg', seg), ('stats', stats)):
-        if t is not None and t.device != img.device:
-            raise CggError(f'{me}: {name} ({t.device}) and img ({img.device}) live on different devices')
-    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
-    if nbytes > staged.numel():
-        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the {staged.numel()} bytes of staged')
-    sp, ip = dev_ptr(staged, f'{me}: staged'), dev_ptr(img, f'{me}: img')
-    if staged.device != img.device:
-        raise CggError(f'{me}: staged ({staged.device}) and img ({img.device}) live on different devices')
+    B, Bp, S = _host_tables(me, ('img_table', img_table, TRAIN_PREP_IMG_COLS), ('pan_table', pan_table, TRAIN_PREP_PAN_COLS),
+                            ('seg_table', seg_table, TRAIN_PREP_SEG_COLS))
+    if Bp != B:
+        raise CggError(f'{me}: pan_table must have one row per image ({B}), got {Bp}')
+    N, H, W = _train_outputs(me, img, B, None, masks, seg, stats)
+    nbytes = _staged_u8(me, staged, staged_bytes)
+    sp, ip = _staged_and_img(me, staged, img)
     mp = dev_ptr(masks, f'{me}: masks') if N else None
     tp = dev_ptr(stats, f'{me}: stats') if N else None
     gp = dev_ptr(seg, f'{me}: seg')
-    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'{me}: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    m, s, p = _norm3(me, mean, std, pad_val)
     ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
-    if pan_table_offset is None:
-        pan_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
-    if seg_table_offset is None:
-        seg_table_offset = int(pan_table_offset) + 4 * TRAIN_PREP_PAN_COLS * B
+    img_off, pan_off, seg_off = _back_to_back(img_table_offset, (pan_table_offset, TRAIN_PREP_IMG_COLS, B),
+                                              (seg_table_offset, TRAIN_PREP_PAN_COLS, B))
     with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W + (B * H * W if seg is not None else 0)), shape=(B, N, H, W)):
-        _call('cgg_train_prep_panoptic_u8', sp, nbytes, int(img_table_offset), int(pan_table_offset), int(seg_table_offset),
-              host_ptr(img_table, 'img_table', torch.int32), host_ptr(pan_table, 'pan_table', torch.int32),
-              host_ptr(seg_table, 'seg_table', torch.int32) if S else None, B, N, S, m, s, p, int(bool(to_rgb)), int(seg_pad), ch, cw,
-              ip, mp, gp, tp, H, W, stream_ptr(img.device))
+        _call('cgg_train_prep_panoptic_u8', sp, nbytes, img_off, pan_off, seg_off, host_ptr(img_table, 'img_table', torch.int32),
+              host_ptr(pan_table, 'pan_table', torch.int32), host_ptr(seg_table, 'seg_table', torch.int32) if S else None, B, N, S, m,
+              s, p, int(bool(to_rgb)), int(seg_pad), ch, cw, ip, mp, gp, tp, H, W, stream_ptr(img.device))
     return img, masks, seg, stats
 
 
-TRAIN_PREP_POLY_INST_COLS = 3  # image index, first part, parts
-TRAIN_PREP_POLY_PART_COLS = 2  # byte offset of the part's float64 coordinates (a multiple of 8), vertex count
-TRAIN_PREP_MAX_COORD = CONSTANTS['CGG_IMAGE_PREP_MAX_DIM']      # |coordinate| of a polygon vertex: it bounds the edge walk
-POLY_LDS_BITS = CONSTANTS['CGG_POLY_LDS_BITS']                  # a plane of more pixels keeps its toggle plane in the workspace
-POLY_SCAN_BITS = CONSTANTS['CGG_POLY_SCAN_BITS']                # pixels of one scan block of the fill kernel
-
-
-def _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace):
-    if not torch.is_tensor(staged) or staged.dtype != torch.uint8 or staged.dim() != 1:
-        raise CggError(f'{me}: staged must be a 1-D torch.uint8 tensor (got {getattr(staged, "dtype", type(staged))})')
-    for name, t, cols in (('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_POLY_INST_COLS),
-                          ('part_table', part_table, TRAIN_PREP_POLY_PART_COLS)):
-        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != cols:
-            raise CggError(f'{me}: {name} must be a (rows, {cols}) torch.int32 tensor '
-                           f'(got {getattr(t, "dtype", type(t))}, shape {tuple(getattr(t, "shape", ()))})')
-        if t.is_cuda or not t.is_contiguous():
-            raise CggError(f'{me}: {name} must be a contiguous HOST tensor (the copy of the rows that `staged` carries)')
-    if not torch.is_tensor(staged_host) or staged_host.dtype != torch.uint8 or staged_host.dim() != 1 or staged_host.is_cuda:
-        raise CggError(f'{me}: staged_host must be a 1-D torch.uint8 HOST tensor, the copy of the staged bytes')
-    if not torch.is_tensor(workspace) or workspace.dtype != torch.int32 or workspace.dim() != 1:
-        raise CggError(f'{me}: workspace must be a 1-D torch.int32 tensor (got {getattr(workspace, "dtype", type(workspace))})')
-    if workspace.device != staged.device:
-        raise CggError(f'{me}: workspace ({workspace.device}) and staged ({staged.device}) live on different devices')
-    if int(img_table.shape[0]) < 1:
-        raise CggError(f'{me}: an empty batch')
-    return int(img_table.shape[0]), int(inst_table.shape[0]), int(part_table.shape[0])
-
-
 def train_prep_polygons_workspace_bytes(img_table, N, force_workspace=False):
-    """bytes of workspace `train_prep_polygons_u8` / `polygon_fill_bits` need for these (B, 12) HOST image rows and N instances"""
-    if not torch.is_tensor(img_table) or img_table.dtype != torch.int32 or img_table.dim() != 2 or img_table.shape[1] != TRAIN_PREP_IMG_COLS:
-        raise CggError(f'train_prep_polygons_workspace_bytes: img_table must be a (B, {TRAIN_PREP_IMG_COLS}) torch.int32 HOST tensor')
+    """bytes of workspace `train_prep_polygons_u8` / `polygon_fill_bits` need for these (B, TRAIN_PREP_IMG_COLS) HOST image rows and
+    N instances"""
+    _shaped('train_prep_polygons_workspace_bytes', 'img_table', img_table, (None, TRAIN_PREP_IMG_COLS), torch.int32)
     return int(_call('cgg_train_prep_polygons_workspace_bytes', host_ptr(img_table, 'img_table', torch.int32), int(img_table.shape[0]),
                      int(N), int(bool(force_workspace)), total=True))
+
+
+def _poly_call(symbol, sp, nbytes, offsets, img_table, inst_table, part_table, staged_host, B, N, P, *rest):
+    """the argument head the two polygon entry points share: staged bytes, the three table offsets and HOST copies, the counts"""
+    _call(symbol, sp, nbytes, *offsets, host_ptr(img_table, 'img_table', torch.int32),
+          host_ptr(inst_table, 'inst_table', torch.int32) if N else None, host_ptr(part_table, 'part_table', torch.int32) if P else None,
+          host_ptr(staged_host, 'staged_host', torch.uint8), B, N, P, *rest)
 
 
 def polygon_fill_bits(staged, img_table, inst_table, part_table, staged_host, workspace, img_table_offset=0, inst_table_offset=None,
@@ -2750,21 +2733,18 @@ def polygon_fill_bits(staged, img_table, inst_table, part_table, staged_host, wo
     as for `train_prep_polygons_u8`; of an image row only h, w, first instance, instances are used. force_workspace (tests): toggle
     planes in the workspace whatever their size. Returns (workspace, plane_words); `polygon_bits_to_mask` unpacks a plane."""
     me = 'polygon_fill_bits'
-    B, N, P = _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace)
-    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
-    if nbytes > staged.numel() or nbytes > staged_host.numel():
-        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the bytes of staged ({staged.numel()}) or staged_host ({staged_host.numel()})')
-    if inst_table_offset is None:
-        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
-    if part_table_offset is None:
-        part_table_offset = int(inst_table_offset) + 4 * TRAIN_PREP_POLY_INST_COLS * N
+    B, N, P = _host_tables(me, ('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_POLY_INST_COLS),
+                           ('part_table', part_table, TRAIN_PREP_POLY_PART_COLS))
+    _shaped(me, 'workspace', workspace, (None,), torch.int32)
+    nbytes = _staged_u8(me, staged, staged_bytes, staged_host, with_host=True)
+    if workspace.device != staged.device:
+        raise CggError(f'{me}: workspace ({workspace.device}) and staged ({staged.device}) live on different devices')
+    offsets = _back_to_back(img_table_offset, (inst_table_offset, TRAIN_PREP_IMG_COLS, B),
+                            (part_table_offset, TRAIN_PREP_POLY_INST_COLS, N))
     with _timed(me, bytes=float(nbytes), shape=(B, N, P)):
-        _call('cgg_polygon_fill_bits', dev_ptr(staged, f'{me}: staged'), nbytes, int(img_table_offset), int(inst_table_offset),
-              int(part_table_offset), host_ptr(img_table, 'img_table', torch.int32),
-              host_ptr(inst_table, 'inst_table', torch.int32) if N else None,
-              host_ptr(part_table, 'part_table', torch.int32) if P else None, host_ptr(staged_host, 'staged_host', torch.uint8), B, N,
-              P, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(), int(bool(force_workspace)),
-              stream_ptr(staged.device))
+        _poly_call('cgg_polygon_fill_bits', dev_ptr(staged, f'{me}: staged'), nbytes, offsets, img_table, inst_table, part_table,
+                   staged_host, B, N, P, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(), int(bool(force_workspace)),
+                   stream_ptr(staged.device))
     hw = [int(r[1]) * int(r[2]) for r in img_table.tolist() if r[10] > 0]
     return workspace, (max(hw) + 31) // 32 if hw else 0
 
@@ -2782,43 +2762,29 @@ def train_prep_polygons_u8(staged, img_table, inst_table, part_table, staged_hos
     """`train_prep_u8` for instance samples whose masks are COCO polygons, rasterised on the device (`cgg_train_prep_polygons_u8`:
     image kernel, polygon fill kernel, plane kernel over the bit planes; no synchronisation; train_prep.py states the rule, rule 6
     for the raster). staged: DEVICE uint8 (n,) -- the three tables at bytes `img_table_offset` / `inst_table_offset` /
-    `part_table_offset` (by default back to back), the images and the float64 coordinates; img_table (B, 12) with -1 for the
-    semantic-map offset, inst_table (N, 3) = image index, first part, parts, part_table (P, 2) = byte offset (a multiple of 8),
-    vertices: HOST int32 copies; staged_host: HOST uint8 copy of the staged bytes (the coordinates are validated from it); img
-    (B, 3, H, W) f32, masks (N, H, W) u8, stats (N, 5) i32, workspace 1-D int32 of `train_prep_polygons_workspace_bytes` or more:
-    DEVICE, contiguous; the caller clears nothing. Returns (img, masks, stats)."""
+    `part_table_offset` (by default back to back), the images and the float64 coordinates; img_table (B, TRAIN_PREP_IMG_COLS) with -1
+    for the semantic-map offset, inst_table (N, TRAIN_PREP_POLY_INST_COLS) = image index, first part, parts, part_table
+    (P, TRAIN_PREP_POLY_PART_COLS) = byte offset (a multiple of 8), vertices: HOST int32 copies; staged_host: HOST uint8 copy of the
+    staged bytes (the coordinates are validated from it); img (B, 3, H, W) f32, masks (N, H, W) u8, stats (N, 5) i32, workspace 1-D
+    int32 of `train_prep_polygons_workspace_bytes` or more: DEVICE, contiguous; the caller clears nothing. Returns (img, masks,
+    stats)."""
     me = 'train_prep_polygons_u8'
-    B, N, P = _poly_tables(me, staged, img_table, inst_table, part_table, staged_host, workspace)
-    if not torch.is_tensor(img) or img.dtype != torch.float32 or img.dim() != 4 or img.shape[0] != B or img.shape[1] != 3:
-        raise CggError(f'{me}: img must be a ({B}, 3, H, W) torch.float32 tensor (got {getattr(img, "dtype", type(img))}, '
-                       f'shape {tuple(getattr(img, "shape", ()))})')
-    H, W = int(img.shape[2]), int(img.shape[3])
-    for name, t, shape, dt in (('masks', masks, (N, H, W), torch.uint8), ('stats', stats, (N, 5), torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
-            raise CggError(f'{me}: {name} must be a {shape} {dt} tensor (got {getattr(t, "dtype", type(t))}, '
-                           f'shape {tuple(getattr(t, "shape", ()))})')
-        if t.device != img.device:
-            raise CggError(f'{me}: {name} ({t.device}) and img ({img.device}) live on different devices')
-    nbytes = staged.numel() if staged_bytes is None else int(staged_bytes)
-    if nbytes > staged.numel() or nbytes > staged_host.numel():
-        raise CggError(f'{me}: staged_bytes {nbytes} exceeds the bytes of staged ({staged.numel()}) or staged_host ({staged_host.numel()})')
-    sp, ip = dev_ptr(staged, f'{me}: staged'), dev_ptr(img, f'{me}: img')
-    if staged.device != img.device:
-        raise CggError(f'{me}: staged ({staged.device}) and img ({img.device}) live on different devices')
+    B, N, P = _host_tables(me, ('img_table', img_table, TRAIN_PREP_IMG_COLS), ('inst_table', inst_table, TRAIN_PREP_POLY_INST_COLS),
+                           ('part_table', part_table, TRAIN_PREP_POLY_PART_COLS))
+    N, H, W = _train_outputs(me, img, B, N, masks, None, stats)
+    _shaped(me, 'workspace', workspace, (None,), torch.int32, img)
+    nbytes = _staged_u8(me, staged, staged_bytes, staged_host, with_host=True)
+    sp, ip = _staged_and_img(me, staged, img)
     mp = dev_ptr(masks, f'{me}: masks') if N else None
     tp = dev_ptr(stats, f'{me}: stats') if N else None
-    m, s, p = ((ctypes.c_float * 3)(*three_floats(v, f'{me}: {k}')) for k, v in (('mean', mean), ('std', std), ('pad_val', pad_val)))
+    m, s, p = _norm3(me, mean, std, pad_val)
     ch, cw = (H, W) if crop_size is None else (int(crop_size[0]), int(crop_size[1]))
-    if inst_table_offset is None:
-        inst_table_offset = int(img_table_offset) + 4 * TRAIN_PREP_IMG_COLS * B
-    if part_table_offset is None:
-        part_table_offset = int(inst_table_offset) + 4 * TRAIN_PREP_POLY_INST_COLS * N
+    offsets = _back_to_back(img_table_offset, (inst_table_offset, TRAIN_PREP_IMG_COLS, B),
+                            (part_table_offset, TRAIN_PREP_POLY_INST_COLS, N))
     with _timed(me, bytes=float(nbytes + img.numel() * 4 + N * H * W), shape=(B, N, H, W)):
-        _call('cgg_train_prep_polygons_u8', sp, nbytes, int(img_table_offset), int(inst_table_offset), int(part_table_offset),
-              host_ptr(img_table, 'img_table', torch.int32), host_ptr(inst_table, 'inst_table', torch.int32) if N else None,
-              host_ptr(part_table, 'part_table', torch.int32) if P else None, host_ptr(staged_host, 'staged_host', torch.uint8), B, N,
-              P, m, s, p, int(bool(to_rgb)), ch, cw, ip, mp, tp, H, W, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(),
-              int(bool(force_workspace)), stream_ptr(img.device))
+        _poly_call('cgg_train_prep_polygons_u8', sp, nbytes, offsets, img_table, inst_table, part_table, staged_host, B, N, P, m, s,
+                   p, int(bool(to_rgb)), ch, cw, ip, mp, tp, H, W, dev_ptr(workspace, f'{me}: workspace'), 4 * workspace.numel(),
+                   int(bool(force_workspace)), stream_ptr(img.device))
     return img, masks, stats
 
 
@@ -3033,8 +2999,8 @@ def rle_encode_colmajor(cols, H, width, threads=8):
 # ------------------------------------------------------------------------------------------------
 # drawing a result over its image on the device (csrc/paint.hip; paint.py states the rules in numpy)
 # ------------------------------------------------------------------------------------------------
-PAINT_MAX_MASKS = 1024
-PAINT_MAX_IDS = 1024
+PAINT_MAX_MASKS = CONSTANTS['CGG_PAINT_MAX_MASKS']
+PAINT_MAX_IDS = CONSTANTS['CGG_PAINT_MAX_IDS']
 PAINT_MAX_IMAGE_BYTES = 1 << 31
 
 
@@ -3059,7 +3025,7 @@ def pack_bool_masks(masks):
 
 def paint_instances_ok(img, bits):
     """The gate of `paint_instances`: a contiguous (H, W, 3) uint8 device image of at most 2^31 bytes, and bit-packed masks
-    (n <= 1024, H, row_bytes) on the same device with contiguous rows -- the layout `rle_transitions` reads."""
+    (n <= PAINT_MAX_MASKS, H, row_bytes) on the same device with contiguous rows -- the layout `rle_transitions` reads."""
     if not _u8_image_ok(img) or not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 3:
         return False
     n, H, rb = bits.shape
@@ -3129,7 +3095,7 @@ def paint_panoptic_ok(img, pan, nids):
 
 
 def paint_panoptic(img, pan, ids, colors, alpha=0.8, edges=True, out=None):
-    """img (H, W, 3) uint8, pan (H, W) int32, ids (k <= 1024) int32 strictly ascending, colors (k, 3) uint8, all on one device -> the
+    """img (H, W, 3) uint8, pan (H, W) int32, ids (k <= PAINT_MAX_IDS) int32 strictly ascending, colors (k, 3) uint8, all on one device -> the
     painted image, equal to `paint.paint_panoptic_host` bit for bit. One launch on the current stream, no host read."""
     k = int(ids.numel()) if torch.is_tensor(ids) else -1
     if k < 0 or not paint_panoptic_ok(img, pan, k):
@@ -3154,14 +3120,14 @@ def paint_panoptic(img, pan, ids, colors, alpha=0.8, edges=True, out=None):
 # ------------------------------------------------------------------------------------------------
 # COCO mask evaluation on the device (csrc/mask_eval.hip; mask_eval.py states the rules in numpy)
 # ------------------------------------------------------------------------------------------------
-MASK_EVAL_MAX_MASKS = 1024
-MASK_EVAL_MAX_THRS = 64
-MASK_EVAL_MAX_AREAS = 8
-MASK_EVAL_MAX_CATS = 1024
+MASK_EVAL_MAX_MASKS = CONSTANTS['CGG_MASK_EVAL_MAX_MASKS']
+MASK_EVAL_MAX_THRS = CONSTANTS['CGG_MASK_EVAL_MAX_THRS']
+MASK_EVAL_MAX_AREAS = CONSTANTS['CGG_MASK_EVAL_MAX_AREAS']
+MASK_EVAL_MAX_CATS = CONSTANTS['CGG_MASK_EVAL_MAX_CATS']
 
 
 def mask_eval_ok(D, G, H, W):
-    """The gate of `mask_intersections` / `coco_match`: at most 1024 masks on each side and H * W < 2^31 (the sums are int32).
+    """The gate of `mask_intersections` / `coco_match`: at most MASK_EVAL_MAX_MASKS masks on each side and H * W < 2^31 (the sums are int32).
     Shapes outside it take the host rule (`mask_eval.mask_intersections_host`, `mask_eval.evaluate_img_host`)."""
     return 0 <= int(D) <= MASK_EVAL_MAX_MASKS and 0 <= int(G) <= MASK_EVAL_MAX_MASKS and int(H) > 0 and int(W) > 0 \
         and int(H) * int(W) < (1 << 31)
@@ -3263,7 +3229,7 @@ def coco_match(inter, area_d, area_g, det_order, det_cats, gt_cats, gt_crowd, gt
 
 
 def box_eval_ok(D, G):
-    """The gate of `box_iou` / `coco_match_boxes`: at most 1024 boxes on each side, the matcher's caps. Shapes outside it take the
+    """The gate of `box_iou` / `coco_match_boxes`: at most MASK_EVAL_MAX_MASKS boxes on each side, the matcher's caps. Shapes outside it take the
     host rule (`mask_eval.box_iou_host`, `mask_eval.evaluate_img_host`)."""
     return 0 <= int(D) <= MASK_EVAL_MAX_MASKS and 0 <= int(G) <= MASK_EVAL_MAX_MASKS
 
@@ -3327,7 +3293,7 @@ def coco_match_boxes(det_boxes5, gt_xywh, det_order, det_cats, gt_cats, gt_crowd
 # ------------------------------------------------------------------------------------------------
 # Panoptic-quality evaluation on the device (csrc/pq_eval.hip; pq_eval.py states the rules in numpy)
 # ------------------------------------------------------------------------------------------------
-PQ_EVAL_MAX_SEGMENTS = 4096
+PQ_EVAL_MAX_SEGMENTS = CONSTANTS['CGG_PQ_EVAL_MAX_SEGMENTS']
 
 
 def pq_hash_size(n):

@@ -83,14 +83,16 @@ of the bitmap route gathers from those bits: rule 3 and rule 4 are the same code
 reference dataset sends those to bboxes_ignore), an odd coordinate count, an empty part, non-finite coordinates, |coordinate| >
 CGG_IMAGE_PREP_MAX_DIM (it bounds the edge walk), gt_masks next to gt_polygons, a pipeline with with_seg.
 """
+import functools
 from dataclasses import dataclass
 from typing import NamedTuple, Tuple
 
 import numpy as np
 import torch
 
+from . import ops
 from ._lib import CggError
-from .image_prep import ImagePrep, PrepSpec, _as_hwc_u8, norm_constants, rescale_size
+from .image_prep import PrepSpec, _StagingRing, _as_hwc_u8, norm_constants, rescale_size
 from .ops import (TRAIN_PREP_IMG_COLS, TRAIN_PREP_INST_COLS, TRAIN_PREP_MAX_SEGMENTS, TRAIN_PREP_PAN_COLS, TRAIN_PREP_POLY_INST_COLS,
                   TRAIN_PREP_POLY_PART_COLS, TRAIN_PREP_SEG_COLS, three_floats)
 
@@ -781,115 +783,120 @@ class TrainPrep:
             raise CggError(f'TrainPrep needs a ROCm device (got {device}); prepare_train_host is the host-side form of the same rule')
         if not isinstance(spec, TrainPrepSpec):
             spec = parse_train_pipeline(spec)
-        if slots < 1:
-            raise CggError('TrainPrep: slots must be >= 1')
         self.spec, self.device = spec, device
-        self._slots = [None] * slots
-        self._n = 0
+        self._ring = _StagingRing(device, slots, 'TrainPrep')
         self._workspace = self._workspace_used = None           # the polygon route's device workspace, grow-only
         self.last_staged_bytes = 0
 
-    _slot = ImagePrep._slot                                  # the same rotation of pinned staging slots
+    # A layout lays out the staged bytes of one batch -- the tables back to back from byte 0 (the default offsets of the ops), then the
+    # planes -- and answers (n bytes, [int32 rows of each table], [(byte offset, array)] to copy, launch). `launch(slot, tables, img,
+    # masks, seg, stats, n, stream)` runs the batch's kernels on the uploaded slot.
+    @staticmethod
+    def _image_rows(parsed, params, geoms, counts, n, copies, planes=None):
+        """The image table of every layout, the images staged from byte `n` on. `planes(b, q, h, w, n) -> (n, semantic-map offset)`
+        stages what else belongs to image b right behind it. Returns (n, rows)."""
+        rows, first = [], 0
+        for b, (q, p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
+            h, w = int(q[0].shape[0]), int(q[0].shape[1])
+            off, seg_off = n, -1
+            copies.append((off, q[0]))
+            n += h * w * 3
+            if planes is not None:
+                n, seg_off = planes(b, q, h, w, n)
+            rows.append((off, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], seg_off))
+            first += counts[b]
+        return n, rows
+
+    @staticmethod
+    def _table_bytes(shapes):
+        """bytes of the int32 tables of these (rows, cols), back to back: where the planes start"""
+        return 4 * sum(rows * cols for rows, cols in shapes)
+
+    @staticmethod
+    def _tables(shapes, *rows):
+        """the row lists of the tables as int32 arrays of their (rows, cols)"""
+        return [np.asarray(r, dtype=np.int32).reshape(shape) for r, shape in zip(rows, shapes)]
 
     def _layout_bitmaps(self, parsed, params, geoms, counts):
-        """the staged bytes of a bitmap batch: (n, [(byte offset, int32 rows)] image table first, [(byte offset, array)], op)"""
+        """image and instance (image index, byte offset, row pitch) tables, then per sample the image, its instance bitmaps and its
+        semantic map"""
         B, N = len(parsed), sum(counts)
-        img_rows, inst_rows, copies = [], [], []
-        inst_off = 4 * TRAIN_PREP_IMG_COLS * B
-        n = inst_off + 4 * TRAIN_PREP_INST_COLS * N
-        first = 0
-        for b, ((img, masks, _, seg), p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
-            h, w = int(img.shape[0]), int(img.shape[1])
-            off = n
-            copies.append((off, img))
-            n += h * w * 3
+        inst_rows, copies = [], []
+
+        def planes(b, q, h, w, n):
             for i in range(counts[b]):
                 inst_rows.append((b, n, w))
-                copies.append((n, masks[i]))
+                copies.append((n, q[1][i]))
                 n += h * w
-            seg_off = -1
-            if seg is not None:
-                seg_off = n
-                copies.append((n, seg))
-                n += h * w
-            img_rows.append((off, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], seg_off))
-            first += counts[b]
-        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
-                  (inst_off, np.asarray(inst_rows, dtype=np.int32).reshape(N, TRAIN_PREP_INST_COLS))]
-        return n, tables, copies, 'train_prep_u8'
+            if q[3] is None:
+                return n, -1
+            copies.append((n, q[3]))
+            return n + h * w, n
+        shapes = (B, TRAIN_PREP_IMG_COLS), (N, TRAIN_PREP_INST_COLS)
+        n, img_rows = self._image_rows(parsed, params, geoms, counts, self._table_bytes(shapes), copies, planes)
+        return n, self._tables(shapes, img_rows, inst_rows), copies, functools.partial(self._launch, ops.train_prep_u8)
 
     def _layout_panoptic(self, parsed, params, geoms, counts):
-        """the staged bytes of a panoptic batch: the image, panoptic and segment tables, then per sample the image and the id map (an
-        int32 map on a 4-byte boundary). No bitmap and no semantic map is staged."""
-        B = len(parsed)
-        S = sum(len(q[3]) for q in parsed)
-        pan_off = 4 * TRAIN_PREP_IMG_COLS * B
-        seg_off = pan_off + 4 * TRAIN_PREP_PAN_COLS * B
-        n = seg_off + 4 * TRAIN_PREP_SEG_COLS * S
-        img_rows, pan_rows, seg_rows, copies = [], [], [], []
-        first = sfirst = 0
-        for b, ((img, pan, fmt, recs, _), p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
-            h, w = int(img.shape[0]), int(img.shape[1])
-            img_rows.append((n, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], -1))
-            copies.append((n, img))
-            n += h * w * 3
+        """image, panoptic and segment tables, then per sample the image and the id map (an int32 map on a 4-byte boundary). No
+        bitmap and no semantic map is staged."""
+        B, S = len(parsed), sum(len(q[3]) for q in parsed)
+        pan_rows, seg_rows, copies = [], [], []
+
+        def planes(b, q, h, w, n):
+            _, pan, fmt, recs, _ = q
             if fmt == 0:
                 n = (n + 3) & ~3
             bpp = 3 if fmt else 4
-            pan_rows.append((n, bpp * w, fmt, sfirst, len(recs)))
+            pan_rows.append((n, bpp * w, fmt, len(seg_rows), len(recs)))
             copies.append((n, pan))
-            n += h * w * bpp
             slot, rows = 0, []
             for sid, cat, is_thing in recs:                  # slot t + 1 = the image's thing t, in record order; 0 = no thing
                 slot += int(is_thing)
                 rows.append((sid, ((slot if is_thing else 0) << 8) | cat))
-            seg_rows += sorted(rows)                         # the kernel searches them by id
-            first += counts[b]
-            sfirst += len(recs)
-        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
-                  (pan_off, np.asarray(pan_rows, dtype=np.int32).reshape(B, TRAIN_PREP_PAN_COLS)),
-                  (seg_off, np.asarray(seg_rows, dtype=np.int32).reshape(S, TRAIN_PREP_SEG_COLS))]
-        return n, tables, copies, 'train_prep_panoptic_u8'
+            seg_rows.extend(sorted(rows))                    # the kernel searches them by id
+            return n + h * w * bpp, -1
+        shapes = (B, TRAIN_PREP_IMG_COLS), (B, TRAIN_PREP_PAN_COLS), (S, TRAIN_PREP_SEG_COLS)
+        n, img_rows = self._image_rows(parsed, params, geoms, counts, self._table_bytes(shapes), copies, planes)
+        return n, self._tables(shapes, img_rows, pan_rows, seg_rows), copies, functools.partial(self._launch, ops.train_prep_panoptic_u8)
 
     def _layout_polygons(self, parsed, params, geoms, counts):
-        """the staged bytes of a polygon batch: the image, instance (image index, first part, parts) and part (byte offset, vertices)
-        tables, the images, then every part's coordinates as float64 from an 8-byte boundary on. No bitmap is staged."""
+        """image, instance (image index, first part, parts) and part (byte offset, vertices) tables, the images, then every part's
+        coordinates as float64 from an 8-byte boundary on. No bitmap is staged."""
         B, N = len(parsed), sum(counts)
         P = sum(len(parts) for q in parsed for parts in q[1])
-        inst_off = 4 * TRAIN_PREP_IMG_COLS * B
-        part_off = inst_off + 4 * TRAIN_PREP_POLY_INST_COLS * N
-        n = part_off + 4 * TRAIN_PREP_POLY_PART_COLS * P
-        img_rows, inst_rows, part_rows, copies = [], [], [], []
-        first = 0
-        for b, ((img, _, _), p, (nh, nw, oy, ox, _, _)) in enumerate(zip(parsed, params, geoms)):
-            h, w = int(img.shape[0]), int(img.shape[1])
-            img_rows.append((n, h, w, 3 * w, nh, nw, oy, ox, int(bool(p.flip)), first, counts[b], -1))
-            copies.append((n, img))
-            n += h * w * 3
-            first += counts[b]
+        inst_rows, part_rows, copies = [], [], []
+        shapes = (B, TRAIN_PREP_IMG_COLS), (N, TRAIN_PREP_POLY_INST_COLS), (P, TRAIN_PREP_POLY_PART_COLS)
+        n, img_rows = self._image_rows(parsed, params, geoms, counts, self._table_bytes(shapes), copies)
         n = (n + 7) & ~7
-        pfirst = 0
         for b, q in enumerate(parsed):
             for parts in q[1]:
-                inst_rows.append((b, pfirst, len(parts)))
-                pfirst += len(parts)
+                inst_rows.append((b, len(part_rows), len(parts)))
                 for xy in parts:
                     part_rows.append((n, xy.size // 2))
                     copies.append((n, xy))
                     n += xy.nbytes
-        tables = [(0, np.asarray(img_rows, dtype=np.int32).reshape(B, TRAIN_PREP_IMG_COLS)),
-                  (inst_off, np.asarray(inst_rows, dtype=np.int32).reshape(N, TRAIN_PREP_POLY_INST_COLS)),
-                  (part_off, np.asarray(part_rows, dtype=np.int32).reshape(P, TRAIN_PREP_POLY_PART_COLS))]
-        return n, tables, copies, 'train_prep_polygons_u8'
+        return n, self._tables(shapes, img_rows, inst_rows, part_rows), copies, self._launch_polygons
 
-    def _workspace_for(self, nbytes):
-        """the grow-only device workspace of the polygon route (bit planes, toggle planes): the kernels clear what they read"""
+    def _launch(self, op, slot, tables, img, masks, seg, stats, n, stream):
+        spec = self.spec
+        op(slot.dev, *tables, img, masks, seg, stats, spec.mean, spec.std, spec.pad_val[0], to_rgb=spec.to_rgb,
+           crop_size=spec.crop_size, seg_pad=spec.pad_val[2], staged_bytes=n)
+
+    def _launch_polygons(self, slot, tables, img, masks, seg, stats, n, stream):
+        """the polygon route keeps a grow-only device workspace (bit planes, toggle planes) next to the staging slots: the kernels
+        clear what they read, and an event says when the last batch's kernels have left it"""
+        spec = self.spec
+        nbytes = ops.train_prep_polygons_workspace_bytes(tables[0], masks.shape[0])
         if self._workspace is None or self._workspace.numel() * 4 < nbytes:
             self._workspace = torch.empty((max(1 << 14, 1 << max(nbytes - 1, 1).bit_length()) // 4,), dtype=torch.int32, device=self.device)
-        return self._workspace
+        if self._workspace_used is not None:
+            stream.wait_event(self._workspace_used)           # device: the last batch's kernels have left the workspace (another stream)
+        ops.train_prep_polygons_u8(slot.dev, *tables, slot.pinned, img, masks, stats, self._workspace, spec.mean, spec.std,
+                                   spec.pad_val[0], to_rgb=spec.to_rgb, crop_size=spec.crop_size, staged_bytes=n)
+        self._workspace_used = torch.cuda.Event()
+        self._workspace_used.record(stream)
 
     def prep(self, samples, params):
-        from . import ops
         spec = self.spec
         _check_batch(samples, params)
         H, W = spec.size
@@ -911,7 +918,7 @@ class TrainPrep:
             layout = self._layout_bitmaps
         geoms = [sample_geometry(q[0].shape[:2], p, spec) for q, p in zip(parsed, params)]
         N = sum(counts)
-        n, tables, copies, op = layout(parsed, params, geoms, counts)
+        n, tables, copies, launch = layout(parsed, params, geoms, counts)
         self.last_staged_bytes = n                            # tables + raw planes of this call (what the one H2D copy moves)
         img_out = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
         masks_out = torch.empty((N, H, W), dtype=torch.uint8, device=self.device)
@@ -919,40 +926,20 @@ class TrainPrep:
         stats = torch.empty((N, 5), dtype=torch.int32, device=self.device)
         stats_host = torch.empty((N, 5), dtype=torch.int32).pin_memory()
         with torch.cuda.device(self.device):
-            slot = self._slot(n)
+            slot = self._ring.acquire(n)
             stream = torch.cuda.current_stream(self.device)
-            host_tables = []
-            for off, rows in tables:                         # written into the slot; the views are the host copies the op validates
+            host_tables, off = [], 0
+            for rows in tables:                              # written into the slot; the views are the host copies the op validates
                 t = slot.pinned[off:off + 4 * rows.size].view(torch.int32).view(rows.shape)
                 if rows.size:
                     t.numpy()[:] = rows
                 host_tables.append(t)
+                off += 4 * rows.size
             for off, a in copies:
                 np.copyto(slot.host[off:off + a.nbytes].view(a.dtype).reshape(a.shape), a)
-            if slot.consumed is not None:
-                stream.wait_event(slot.consumed)             # device: the kernels that read this slot last are done (another stream)
-            slot.dev[:n].copy_(slot.pinned[:n], non_blocking=True)
-            slot.copied = torch.cuda.Event()
-            slot.copied.record(stream)
-            offsets = [off for off, _ in tables]
-            common = dict(to_rgb=spec.to_rgb, crop_size=spec.crop_size, seg_pad=spec.pad_val[2], img_table_offset=offsets[0], staged_bytes=n)
-            if op == 'train_prep_panoptic_u8':
-                ops.train_prep_panoptic_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
-                                           pan_table_offset=offsets[1], seg_table_offset=offsets[2], **common)
-            elif op == 'train_prep_polygons_u8':
-                common.pop('seg_pad')
-                ws = self._workspace_for(ops.train_prep_polygons_workspace_bytes(host_tables[0], N))
-                if self._workspace_used is not None:
-                    stream.wait_event(self._workspace_used)   # device: the last batch's kernels have left the workspace (another stream)
-                ops.train_prep_polygons_u8(slot.dev, *host_tables, slot.pinned, img_out, masks_out, stats, ws, spec.mean, spec.std,
-                                           spec.pad_val[0], inst_table_offset=offsets[1], part_table_offset=offsets[2], **common)
-                self._workspace_used = torch.cuda.Event()
-                self._workspace_used.record(stream)
-            else:
-                ops.train_prep_u8(slot.dev, *host_tables, img_out, masks_out, seg_out, stats, spec.mean, spec.std, spec.pad_val[0],
-                                  inst_table_offset=offsets[1], **common)
-            slot.consumed = torch.cuda.Event()
-            slot.consumed.record(stream)
+            self._ring.upload(slot, n, stream)
+            launch(slot, host_tables, img_out, masks_out, seg_out, stats, n, stream)
+            self._ring.release(slot, stream)
             stats_host.copy_(stats, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)

@@ -500,6 +500,7 @@ int64_t cgg_rle_encode_colmajor(const uint64_t* cols, int n, int H, int W, int t
  *   frame, is then blended with white at alpha 0.8. One launch. CGG_EINVAL: null pointer, H, W < 1, nids < 0, alpha pair outside
  *   [0, 1]. CGG_EUNSUPPORTED: nids > 1024, H * W * 3 > 2^31.
  * ---------------------------------------------------------------------------------------------- */
+#define CGG_PAINT_MAX_MASKS 1024 /* planes of one cgg_paint_instances_u8 call */
 int cgg_paint_instances_u8(const uint8_t* img, uint8_t* out, int H, int W, const uint8_t* bits, int n, int64_t mask_stride_bytes,
                            int row_bytes, const uint8_t* keep, const uint8_t* colors, const int32_t* boxes,
                            const uint8_t* box_colors, double alpha, double one_minus_alpha, int thickness, int edges,
@@ -510,6 +511,7 @@ int cgg_pack_bool_rows_u8(const uint8_t* masks, int64_t rows, int W, int row_byt
 int64_t cgg_label_components_workspace_bytes(int H, int W);
 int cgg_label_components_i32(const int32_t* pan, int H, int W, int void_id, void* ws, int64_t* records, int capacity,
                              int32_t* status, cgg_stream_t stream);
+#define CGG_PAINT_MAX_IDS 1024 /* ids of one cgg_paint_panoptic_u8 call */
 int cgg_paint_panoptic_u8(const uint8_t* img, uint8_t* out, const int32_t* pan, int H, int W, const int32_t* ids,
                           const uint8_t* colors, int nids, double alpha, double one_minus_alpha, int edges, cgg_stream_t stream);
 
@@ -571,6 +573,7 @@ int cgg_layernorm_chain(const float* a, int lda, const float* gamma_a, const flo
  * layer's cross-attention query projection (:829). w1 / w2 / w3 / wq: 256 x 256 weights packed by cgg_linear_rows_pack.
  * Same arithmetic per stage as cgg_layernorm_chain + 4 x cgg_linear_rows_bf16 (bf16 operands, f32 accumulate).
  * nsum <= 8 (F = 2048): more planes are CGG_EUNSUPPORTED -- cgg_layernorm_chain sums any number.                      */
+#define CGG_DECODER_TAIL_MAX_PLANES 8 /* split-K planes held in registers per row (2048 / 256): more are refused (CGG_EUNSUPPORTED), not dropped */
 int cgg_decoder_tail_bf16(const float* planes, int nsum, int64_t plane_stride, int ld, const float* gamma_a,
                           const float* beta_a, float eps_a, const float* pos, int pos_rows, const float* gamma_b,
                           const float* beta_b, float eps_b, const void* w1, const float* b1, const void* w2,
@@ -784,6 +787,7 @@ int cgg_mask_feature_head_x3_cfg(const float* z, const void* gn_ws, const float*
  * either axis, pitch < 3 w, an image or the table extending past staged_bytes, std == 0; CGG_EUNSUPPORTED beyond the index arithmetic
  * of the kernel: B, h, w, Hb, Wb <= CGG_IMAGE_PREP_MAX_DIM and staged_bytes <= 2^31 - 9. The kernel reads no byte outside the table rows
  * and offset .. offset + h * pitch of each image. */
+#define CGG_IMAGE_PREP_TABLE_COLS 8 /* descriptor row: byte offset, h, w, row pitch, new_h, new_w, pad_h, pad_w */
 #define CGG_IMAGE_PREP_MAX_DIM 65535
 int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table_offset, const int32_t* table_host, int B,
                       const float* mean, const float* std, const float* pad_val, int to_rgb, int pad_before_norm, float* out, int Hb,
@@ -819,6 +823,8 @@ int cgg_image_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t table
  * ranges that do not tile 0 .. N, std == 0; CGG_EUNSUPPORTED beyond the index arithmetic of the kernels: B + N, h, w, H, W <=
  * CGG_IMAGE_PREP_MAX_DIM and staged_bytes <= 2^31 - 9; CGG_EALIGN as above. The kernels read no byte outside the table rows and
  * offset .. offset + h * pitch of each image, bitmap and map. */
+#define CGG_TRAIN_PREP_IMG_COLS 12 /* byte offset, h, w, row pitch, new_h, new_w, oy, ox, flip, first instance, instances, semantic-map offset or -1 */
+#define CGG_TRAIN_PREP_INST_COLS 3 /* image index, byte offset, row pitch */
 int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t inst_table_offset,
                       const int32_t* img_table_host, const int32_t* inst_table_host, int B, int N, const float* mean, const float* std,
                       const float* pad_val, int to_rgb, int seg_pad, int crop_h, int crop_w, float* img, uint8_t* masks, uint8_t* seg,
@@ -849,6 +855,8 @@ int cgg_train_prep_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_t
  * category > 254, slots that are no permutation; CGG_EUNSUPPORTED for more than CGG_TRAIN_PREP_MAX_SEGMENTS rows of one image;
  * CGG_EALIGN as for cgg_train_prep_u8. The kernels read no byte outside the table rows and offset .. offset + h * pitch of each
  * image and map. */
+#define CGG_TRAIN_PREP_PAN_COLS 5 /* byte offset of the id map, row pitch in bytes, format (0: int32 ids, 1: R, G, B bytes), first segment row, segment rows */
+#define CGG_TRAIN_PREP_SEG_COLS 2 /* id, (slot << 8) | category: slot 0 = no thing, t + 1 = the image's thing t */
 #define CGG_TRAIN_PREP_MAX_SEGMENTS 256
 int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_bytes, int64_t img_table_offset, int64_t pan_table_offset,
                                int64_t seg_table_offset, const int32_t* img_table_host, const int32_t* pan_table_host,
@@ -888,6 +896,8 @@ int cgg_train_prep_panoptic_u8(const uint8_t* staged, int64_t staged_bytes, int6
  * count < 1, instance or part ranges that do not tile, a non-finite coordinate; CGG_EUNSUPPORTED for |coordinate| >
  * CGG_IMAGE_PREP_MAX_DIM (it bounds the edge walk), h * w > 2^31 - 32, a workspace that is too small; CGG_EALIGN as for
  * cgg_train_prep_u8, and for staged / workspace. */
+#define CGG_TRAIN_PREP_POLY_INST_COLS 3 /* image index, first part, parts */
+#define CGG_TRAIN_PREP_POLY_PART_COLS 2 /* byte offset of the part's 2 k float64 (a multiple of 8), vertex count k */
 #define CGG_POLY_LDS_BITS 393216
 #define CGG_POLY_SCAN_BITS 8192
 int64_t cgg_train_prep_polygons_workspace_bytes(const int32_t* img_table_host, int B, int N, int force_workspace);
@@ -1137,6 +1147,7 @@ int cgg_linear_sum_assignment_f32(const float* cost, int n_problems, const int* 
  * already non-zero is only replaced by a lower index): 1 = NaN / -inf entries, 2 = infeasible (both write the identity
  * pairing k -> (k, k), in range for every consumer), 3 = a descriptor that does not fit the buffers or lds_bytes (nothing
  * written). The other problems of the launch are unaffected; nothing here waits for the device.                          */
+#define CGG_LSAP_MAX_SIDE 1024 /* sides of a problem */
 int64_t cgg_lsap_device_lds_bytes(int nr, int nc);
 int cgg_lsap_device_f32(const float* cost, int64_t cost_numel, const int64_t* desc, int n_problems, int64_t lds_bytes,
                         int64_t* q_out, int64_t* g_out, int64_t out_numel, const int64_t* gt_labels, int64_t gt_numel,
@@ -1277,6 +1288,7 @@ int cgg_panoptic_paint(const int32_t* ids, const uint8_t* win_half, const int32_
  * defer_stuff = 1 is the `_emb` variant (stuff after the things, unfiltered area >= stuff_area_limit, painted without
  * the 0.5 filter); 0 paints stuff in query order. CGG_EINVAL: null pointer, bad sizes, workspace too small;
  * CGG_EUNSUPPORTED: Q > 1024 (the LDS histogram is sized by Q). */
+#define CGG_PANOPTIC_FUSE_MAX_Q 1024 /* queries of one image */
 int64_t cgg_panoptic_fuse_batched_workspace_bytes(int B, int Q, int64_t total_out_pixels);
 int cgg_panoptic_fuse_batched(const float* logits, const float* score, const int64_t* label, const int64_t* geom,
                               int32_t* seg, int32_t* n_kept, int32_t* segments, float* kept_score, void* ws,
@@ -1341,11 +1353,15 @@ int cgg_rowwise_softmax_argmax(const float* x, float* prob, float* maxv, int64_t
  * ---------------------------------------------------------------------------------------------- */
 int cgg_box_iou_f64(const float* det_boxes5, int D, const double* gt_boxes_xywh, const uint8_t* gt_crowd, int G, double* iou,
                     double* area_d, cgg_stream_t stream);
+#define CGG_MASK_EVAL_MAX_THRS 64    /* IoU thresholds, area ranges and categories of one cgg_coco_match / cgg_coco_match_boxes call */
+#define CGG_MASK_EVAL_MAX_AREAS 8
+#define CGG_MASK_EVAL_MAX_CATS 1024
 int cgg_coco_match_boxes(const float* det_boxes5, const double* gt_boxes_xywh, const int32_t* det_order, const int32_t* det_cats,
                          const int32_t* gt_cats, const uint8_t* gt_crowd, const double* gt_area, const int32_t* cat_ids, int K,
                          const double* area_rngs, int A, const double* iou_thrs, int T, int D, int G, int max_det,
                          int class_agnostic, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, int32_t* counts,
                          cgg_stream_t stream);
+#define CGG_MASK_EVAL_MAX_MASKS 1024 /* planes (or boxes) on each side of an intersection table */
 int64_t cgg_mask_intersections_workspace_bytes(int D, int G, int H, int W);
 int cgg_mask_intersections_bits(const uint8_t* det_bits, int D, int64_t det_stride_bytes, const uint8_t* gt_bits, int G,
                                 int64_t gt_stride_bytes, int H, int W, int row_bytes, void* ws, int32_t* inter, int32_t* area_d,
@@ -1386,6 +1402,7 @@ int cgg_coco_match(const int32_t* inter, const int32_t* area_d, const int32_t* a
  *   bit 2 for a segment row without pixels and bit 4 for a ground truth with more than one match (gt_match keeps the first
  *   row); status[1] as above. gt_iou 8-byte aligned. Error codes as above.
  * ---------------------------------------------------------------------------------------------- */
+#define CGG_PQ_EVAL_MAX_SEGMENTS 4096 /* G and P (the LDS limit binds first for all but very lopsided shapes) */
 int64_t cgg_pq_eval_lds_bytes(int G, int P);
 int64_t cgg_pq_confusion_workspace_bytes(int G, int P);
 int cgg_pq_confusion_i32(const int32_t* pred, const void* gt, int gt_rgb, int H, int W, const int32_t* gt_ids, int G,

@@ -70,7 +70,7 @@ def main():
         f'(min {min(walls):.2f}, max {max(walls):.2f}); kept {sum(kept)} of {B * N_INST} instances in the last batch')
 
     # the two launches alone, on the staged bytes of the last call
-    slot = prep._slots[(prep._n - 1) % len(prep._slots)]
+    slot = prep._ring.slots[(prep._ring.n - 1) % len(prep._ring.slots)]
     samples, params = batches[-1]
     N = B * N_INST
     img_table = slot.pinned[:4 * ops.TRAIN_PREP_IMG_COLS * B].view(torch.int32).view(B, -1).clone()
