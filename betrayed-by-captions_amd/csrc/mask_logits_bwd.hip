@@ -155,7 +155,8 @@ __global__ __launch_bounds__(512) void cgg_mask_logits_grad_embed_kernel(const f
   }
   const int plast = npix - 8;                              // last legal 8-pixel vector start (npix % 8 == 0)
   auto load_step = [&](int s, f32x4 (&fx)[2], f32x4 (&gx)[MT][2]) {
-    const int po = max(0, min(16 * s, plast - 8 * hi));   // frow / grows already carry + 8 hi: keep po + 8 hi <= plast
+    // frow / grows already carry + 8 hi: keep 0 <= po + 8 hi <= plast (npix == 8: the upper half reads [0, 8), not [8, 16))
+    const int po = max(-8 * hi, min(16 * s, plast - 8 * hi));
     fx[0] = *reinterpret_cast<const f32x4*>(frow + po);
     fx[1] = *reinterpret_cast<const f32x4*>(frow + po + 4);
 #pragma unroll
