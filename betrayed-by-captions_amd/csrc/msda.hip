@@ -145,28 +145,78 @@ __device__ __forceinline__ void msda_reduce8(float& v) {
   v += cgg_dpp<0x141>(v);      // row_half_mirror
 }
 
-template <int PSEL>
-__device__ __forceinline__ void msda_point_gather(f32x2 (&acc)[4], const uint16_t* __restrict__ vl, const int (&my_o)[4],
-                                                  const float (&my_w)[4]) {
+// The quad gather of the stream kernels, stated once: every lane of a quad takes lane PSEL's four corner offsets and weights (already
+// multiplied by the point's attention probability) by DPP, has the four corner pieces (its 8 channels of each tap) in flight together,
+// then accumulates them with packed FMAs. TAPS says how a piece is loaded from a broadcast offset and unpacked to channel pair c.
+struct MsdaTapsBf16 {                       // offsets in bf16 elements; a piece = 8 bf16 = one 16-byte load
+  const uint16_t* vl;
+  using Piece = uint4;
+  __device__ __forceinline__ Piece load(int o) const { return *reinterpret_cast<const uint4*>(vl + o); }
+  __device__ static __forceinline__ f32x2 pair(const Piece& u, int c) {
+    const uint32_t q[4] = {u.x, u.y, u.z, u.w};
+    return f32x2{__uint_as_float(q[c] << 16), __uint_as_float(q[c] & 0xffff0000u)};
+  }
+};
+struct MsdaTapsF32 {                        // offsets in f32 elements; a piece = channels 4 cq .. + 3 and 16 + 4 cq .. + 3: two 16-byte loads
+  const float* vl;
+  struct Piece { f32x4 v[2]; };
+  __device__ __forceinline__ Piece load(int o) const {
+    return Piece{{*reinterpret_cast<const f32x4*>(vl + o), *reinterpret_cast<const f32x4*>(vl + o + 16)}};
+  }
+  __device__ static __forceinline__ f32x2 pair(const Piece& u, int c) { return f32x2{u.v[c >> 1][2 * (c & 1)], u.v[c >> 1][2 * (c & 1) + 1]}; }
+};
+// ... with the level base in scalar registers and the taps as 32-bit BYTE offsets (T2D == 2: image and head are block-uniform): the
+// loads take the `saddr + voffset` form, no 64-bit pointer arithmetic per tap (28 + 17 of the ~200 VALU instructions per level)
+struct MsdaTapsF32Bytes {
+  const char* vlb;
+  uint32_t lane_b;                          // the lane's own channel offset: added AFTER the broadcast
+  using Piece = MsdaTapsF32::Piece;
+  __device__ __forceinline__ Piece load(int ob) const {
+    const uint32_t o = (uint32_t)ob + lane_b;
+    return Piece{{*reinterpret_cast<const f32x4*>(vlb + o), *reinterpret_cast<const f32x4*>(vlb + o + 64u)}};
+  }
+  __device__ static __forceinline__ f32x2 pair(const Piece& u, int c) { return MsdaTapsF32::pair(u, c); }
+};
+
+template <int PSEL, typename TAPS, typename OT>
+__device__ __forceinline__ void msda_point_gather(f32x2 (&acc)[4], const TAPS& taps, const OT (&my_o)[4], const float (&my_w)[4]) {
   constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);      // quad_perm: every lane reads lane PSEL of its quad
-  uint4 u[4];
+  typename TAPS::Piece u[4];
   float w[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int o = cgg_dpp<CTRL>(my_o[k]);
+    const int o = cgg_dpp<CTRL>((int)my_o[k]);
     w[k] = cgg_dpp<CTRL>(my_w[k]);
-    u[k] = *reinterpret_cast<const uint4*>(vl + o);
+    u[k] = taps.load(o);
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const uint32_t q[4] = {u[k].x, u[k].y, u[k].z, u[k].w};
     const f32x2 ww = {w[k], w[k]};
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x2 vv = {__uint_as_float(q[c] << 16), __uint_as_float(q[c] & 0xffff0000u)};
-      acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
-    }
+    for (int c = 0; c < 4; ++c) acc[c] = __builtin_elementwise_fma(TAPS::pair(u[k], c), ww, acc[c]);
   }
+}
+
+// Softmax of the 12 logits of a (query, head) = 3 levels x 4 points, held in registers: pw[l] = the attention probability of THIS
+// lane's point (cq of its quad) on level l. (The logits are copied, not exponentiated in place: with an in/out array the compiler
+// spelled the per-lane selects with other compares in all eight stream kernels.)
+__device__ __forceinline__ void msda_softmax12_point(const float (&logit)[12], int cq, float (&pw)[3]) {
+  float e[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) e[i] = logit[i];
+  float smax = e[0];
+#pragma unroll
+  for (int i = 1; i < 12; ++i) smax = fmaxf(smax, e[i]);
+  float ssum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    e[i] = __expf(e[i] - smax);
+    ssum += e[i];
+  }
+  const float sinv = 1.f / ssum;
+#pragma unroll
+  for (int l = 0; l < 3; ++l)
+    pw[l] = (cq == 0 ? e[4 * l] : (cq == 1 ? e[4 * l + 1] : (cq == 2 ? e[4 * l + 2] : e[4 * l + 3]))) * sinv;
 }
 
 // HM = true: `value` is HEAD-MAJOR, (B, H, Nv, 32): the two x-neighbours of a bilinear tap are then adjacent 64-byte pieces (one
@@ -216,21 +266,8 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_kernel(
       e[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
     }
   }
-  float smax = e[0];
-#pragma unroll
-  for (int i = 1; i < LP; ++i) smax = fmaxf(smax, e[i]);
-  float ssum = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP; ++i) {
-    e[i] = __expf(e[i] - smax);
-    ssum += e[i];
-  }
-  const float sinv = 1.f / ssum;
-  // attention probability of THIS lane's point on each level
   float pw[L];
-#pragma unroll
-  for (int l = 0; l < L; ++l)
-    pw[l] = (cq == 0 ? e[4 * l] : (cq == 1 ? e[4 * l + 1] : (cq == 2 ? e[4 * l + 2] : e[4 * l + 3]))) * sinv;
+  msda_softmax12_point(e, cq, pw);
 
   f32x2 acc[4];
 #pragma unroll
@@ -246,10 +283,11 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_kernel(
     const float wl = l == 0 ? pw[0] : (l == 1 ? pw[1] : pw[2]);
     const int my_o[4] = {t.o00 * rowstride, t.o01 * rowstride, t.o10 * rowstride, t.o11 * rowstride};
     const float my_w[4] = {t.w00 * wl, t.w01 * wl, t.w10 * wl, t.w11 * wl};
-    msda_point_gather<0>(acc, vl, my_o, my_w);
-    msda_point_gather<1>(acc, vl, my_o, my_w);
-    msda_point_gather<2>(acc, vl, my_o, my_w);
-    msda_point_gather<3>(acc, vl, my_o, my_w);
+    const MsdaTapsBf16 taps{vl};
+    msda_point_gather<0>(acc, taps, my_o, my_w);
+    msda_point_gather<1>(acc, taps, my_o, my_w);
+    msda_point_gather<2>(acc, taps, my_o, my_w);
+    msda_point_gather<3>(acc, taps, my_o, my_w);
   }
   uint16_t* op = out + (size_t)bq * (H * D) + (size_t)h * D + cq * CPL;
   *reinterpret_cast<uint4*>(op) =
@@ -262,56 +300,6 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_kernel(
 // f32 output. Same lane geometry (4 lanes per (query, head), each evaluates one point's taps and broadcasts them with DPP,
 // 8 channels per lane = two 16-byte loads per tap), same arithmetic order as the bf16 kernel with exact f32 operands; replaces
 // the generic cgg_msda_fwd_kernel<float> (one lane per 4 channels, software 64-bit divisions) in the x3 encoder stream.
-template <int PSEL>
-__device__ __forceinline__ void msda_point_gather_f32(f32x2 (&acc)[4], const float* __restrict__ vl, const int (&my_o)[4],
-                                                      const float (&my_w)[4]) {
-  constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);      // quad_perm: every lane reads lane PSEL of its quad
-  f32x4 u[4][2];
-  float w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int o = cgg_dpp<CTRL>(my_o[k]);
-    w[k] = cgg_dpp<CTRL>(my_w[k]);
-    u[k][0] = *reinterpret_cast<const f32x4*>(vl + o);
-    u[k][1] = *reinterpret_cast<const f32x4*>(vl + o + 16);
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 ww = {w[k], w[k]};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x2 vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
-      acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
-    }
-  }
-}
-
-// ... with the level base in scalar registers and the taps as 32-bit BYTE offsets (T2D == 2: image and head are block-uniform): the
-// loads take the `saddr + voffset` form, no 64-bit pointer arithmetic per tap (28 + 17 of the ~200 VALU instructions per level)
-template <int PSEL>
-__device__ __forceinline__ void msda_point_gather_f32_b(f32x2 (&acc)[4], const char* __restrict__ vlb, const uint32_t (&my_o)[4],
-                                                        const float (&my_w)[4], uint32_t lane_b) {
-  constexpr int CTRL = PSEL | (PSEL << 2) | (PSEL << 4) | (PSEL << 6);
-  f32x4 u[4][2];
-  float w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t o = (uint32_t)cgg_dpp<CTRL>((int)my_o[k]) + lane_b;      // (the lane's own channel offset: AFTER the broadcast)
-    w[k] = cgg_dpp<CTRL>(my_w[k]);
-    u[k][0] = *reinterpret_cast<const f32x4*>(vlb + o);
-    u[k][1] = *reinterpret_cast<const f32x4*>(vlb + o + 64u);
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const f32x2 ww = {w[k], w[k]};
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x2 vv = {u[k][c >> 1][2 * (c & 1)], u[k][c >> 1][2 * (c & 1) + 1]};
-      acc[c] = __builtin_elementwise_fma(vv, ww, acc[c]);
-    }
-  }
-}
-
 // T2D: 0 = a wave is 16 consecutive queries, the block's 4 waves are 4 heads; 1 = a wave is a 4 x 4 pixel tile of its level, the
 // block's 4 waves are 4 heads of it; 2 = a wave is a 4 x 4 tile, the block's 4 waves are the four tiles of an 8 x 8 pixel block
 // of ONE head (their taps share a (8 + 2 r)^2 window of lines), blockIdx enumerates (8 x 8 block, head)
@@ -376,20 +364,8 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_f32_kernel(
       e[8 + i] = d[i];
     }
   }
-  float smax = e[0];
-#pragma unroll
-  for (int i = 1; i < LP; ++i) smax = fmaxf(smax, e[i]);
-  float ssum = 0.f;
-#pragma unroll
-  for (int i = 0; i < LP; ++i) {
-    e[i] = __expf(e[i] - smax);
-    ssum += e[i];
-  }
-  const float sinv = 1.f / ssum;
-  float pw[L];                              // attention probability of THIS lane's point on each level
-#pragma unroll
-  for (int l = 0; l < L; ++l)
-    pw[l] = (cq == 0 ? e[4 * l] : (cq == 1 ? e[4 * l + 1] : (cq == 2 ? e[4 * l + 2] : e[4 * l + 3]))) * sinv;
+  float pw[L];
+  msda_softmax12_point(e, cq, pw);
 
   f32x2 acc[4];
 #pragma unroll
@@ -408,16 +384,18 @@ __global__ __launch_bounds__(256) void cgg_msda_fwd_stream2_f32_kernel(
       const char* vlb = reinterpret_cast<const char*>(vbu + (size_t)lv.start[l] * rowstride);
       const uint32_t rs4 = (uint32_t)rowstride * 4u;
       const uint32_t my_ob[4] = {(uint32_t)t.o00 * rs4, (uint32_t)t.o01 * rs4, (uint32_t)t.o10 * rs4, (uint32_t)t.o11 * rs4};
-      msda_point_gather_f32_b<0>(acc, vlb, my_ob, my_w, lane_b);
-      msda_point_gather_f32_b<1>(acc, vlb, my_ob, my_w, lane_b);
-      msda_point_gather_f32_b<2>(acc, vlb, my_ob, my_w, lane_b);
-      msda_point_gather_f32_b<3>(acc, vlb, my_ob, my_w, lane_b);
+      const MsdaTapsF32Bytes taps{vlb, lane_b};
+      msda_point_gather<0>(acc, taps, my_ob, my_w);
+      msda_point_gather<1>(acc, taps, my_ob, my_w);
+      msda_point_gather<2>(acc, taps, my_ob, my_w);
+      msda_point_gather<3>(acc, taps, my_ob, my_w);
     } else {
       const int my_o[4] = {t.o00 * rowstride, t.o01 * rowstride, t.o10 * rowstride, t.o11 * rowstride};
-      msda_point_gather_f32<0>(acc, vl, my_o, my_w);
-      msda_point_gather_f32<1>(acc, vl, my_o, my_w);
-      msda_point_gather_f32<2>(acc, vl, my_o, my_w);
-      msda_point_gather_f32<3>(acc, vl, my_o, my_w);
+      const MsdaTapsF32 taps{vl};
+      msda_point_gather<0>(acc, taps, my_o, my_w);
+      msda_point_gather<1>(acc, taps, my_o, my_w);
+      msda_point_gather<2>(acc, taps, my_o, my_w);
+      msda_point_gather<3>(acc, taps, my_o, my_w);
     }
   }
   float* op = out + (size_t)bq * (H * D) + (size_t)h * D + cq * 4;
@@ -706,20 +684,13 @@ static int msda_read_levels(const int64_t* spatial_shapes, const int64_t* level_
     cgg_set_error("%s: reading level table failed: %s", who, hipGetErrorString(e));
     return (int)e;
   }
-  long long tot = 0;
-  for (int l = 0; l < L; ++l) {
-    lv->h[l] = (int)hs[2 * l];
-    lv->w[l] = (int)hs[2 * l + 1];
-    lv->start[l] = (int)st[l];
-    if (lv->h[l] <= 0 || lv->w[l] <= 0 || st[l] < 0 || st[l] + hs[2 * l] * hs[2 * l + 1] > Nv) {
-      cgg_set_error("%s: level %d (%lldx%lld @%lld) does not fit Nv=%d", who, l, (long long)hs[2 * l],
-                    (long long)hs[2 * l + 1], (long long)st[l], Nv);
-      return CGG_EINVAL;
-    }
-    tot += hs[2 * l] * hs[2 * l + 1];
-  }
-  (void)tot;
-  return CGG_OK;
+  return msda_levels_from_host(who, hs, st, L, Nv, lv);
+}
+
+// the level table of an entry: mmcv's int64 DEVICE tensors (dev_hw != null) or host int32 arrays, through the one checked reader
+static int msda_entry_levels(const char* who, const int64_t* dev_hw, const int64_t* dev_start, const int32_t* level_hw,
+                             const int32_t* level_start, int L, int Nv, hipStream_t s, MsdaLevels* lv) {
+  return dev_hw ? msda_read_levels(dev_hw, dev_start, L, Nv, s, lv, who) : msda_levels_from_host(who, level_hw, level_start, L, Nv, lv);
 }
 
 // The ONE synchronising helper of the MSDeformAttn family: the mmcv-style device level table -> host int32 arrays for the
@@ -739,16 +710,9 @@ extern "C" int cgg_msda_read_levels(const int64_t* spatial_shapes, const int64_t
   return CGG_OK;
 }
 
-// Host-side level table variant: identical kernels, no D2H (used by the graph-captured forward).
-extern "C" int cgg_msda_forward_hostlevels(const void* value, const int32_t* level_hw,
-                                           const int32_t* level_start, const float* sampling_loc,
-                                           const float* attn_weight, const float* ref_points, int ld,
-                                           float* out, int B, int Nv, int H, int D, int L, int Nq,
-                                           int P, int value_dtype, int fused, cgg_stream_t stream);
-
 static int msda_fwd_launch(const void* value, const MsdaLevels& lv, const float* loc,
                            const float* attw, const float* ref, int ld, float* out, int B, int Nv,
-                           int H, int D, int L, int Nq, int P, int dtype, bool fused, hipStream_t s, int vld = 0) {
+                           int H, int D, int L, int Nq, int P, int dtype, bool fused, hipStream_t s, int vld) {
   if (vld == H * D) vld = 0;                                // 0 = the packed (B, Nv, H, D) layout
   const int cpl = dtype == CGG_F32 ? 4 : 8;
   const long long total = (long long)B * Nq * H * (D / cpl);
@@ -770,18 +734,9 @@ static int msda_fwd_launch(const void* value, const MsdaLevels& lv, const float*
     // (caps of 26 / 32 / 40 KB: 112 / 110 / 110 us; 44-53 KB = 3 blocks: 114 us; 64 KB = 2 blocks: 134 us). The block's taps then
     // share a (8 + 2 r)^2 window of 128-B lines that a 16-wave CU keeps in its L1; the kernel stays L2-request bound (every tap
     // of the first toucher is a 128-B request), <= 80 us is out of reach for f32 values.
-    bool t2d = Nq == Nv && Nq % 16 == 0;
-    // the 2-D mappings rebuild q as start[l] + tile arithmetic: the levels must tile [0, Nq) in ascending order without gaps
-    // (msda_read_levels only checks st + h w <= Nv; a gapped / reordered table would compute some queries twice and skip others)
-    long long expect = 0;
-    for (int l = 0; l < L && t2d; ++l) {
-      t2d = lv.start[l] == expect;
-      expect += (long long)lv.h[l] * lv.w[l];
-    }
-    t2d = t2d && expect == Nq;
-    for (int l = 0; l < L && t2d; ++l) t2d = lv.w[l] % 4 == 0 && lv.h[l] % 4 == 0 && lv.start[l] % 16 == 0;
-    bool t8 = t2d && Nq % 64 == 0;
-    for (int l = 0; l < L && t8; ++l) t8 = lv.w[l] % 8 == 0 && lv.h[l] % 8 == 0 && lv.start[l] % 64 == 0;
+    // (the 2-D mappings rebuild q as start[l] + tile arithmetic: msda_levels_tile; 8 x 8 blocks are made of 4 x 4 tiles, t8 implies t2d)
+    const bool t2d = Nq == Nv && Nq % 16 == 0 && msda_levels_tile(lv, L, Nq, 4, 4, 16);
+    const bool t8 = Nq == Nv && Nq % 64 == 0 && msda_levels_tile(lv, L, Nq, 8, 8, 64);
     const unsigned nb = 2 * (unsigned)(((long long)B * Nq + 15) / 16);
 #define CGG_S2(T, LDS)                                                                                                          \
   do {                                                                                                                          \
@@ -825,20 +780,30 @@ static int msda_check(const char* who, const void* value, const void* a, const v
   return CGG_OK;
 }
 
+// The one forward behind cgg_msda_forward, _fused, _hostlevels and _fused_vld, in the order every entry checks: operands and sizes
+// (fused: loc = [offsets | logits] rows of ld floats and ref is read, else loc and attw), the level table's pointers, the entry's own
+// row-stride rule (`strides` sets the error under the entry's text), the table (device tensors or host arrays), the launch.
+template <typename Strides>
+static int msda_forward_impl(const char* who, const void* value, const int64_t* dev_hw, const int64_t* dev_start, const int32_t* level_hw,
+                             const int32_t* level_start, const float* loc, const float* attw, const float* ref, int ld, float* out,
+                             int B, int Nv, int H, int D, int L, int Nq, int P, int dtype, bool fused, int vld, cgg_stream_t stream,
+                             Strides strides) {
+  int rc = msda_check(who, value, loc, fused ? (const void*)ref : (const void*)attw, out, B, Nv, H, D, L, Nq, P, dtype);
+  if (rc) return rc;
+  CGG_REQUIRE((dev_hw && dev_start) || (level_hw && level_start), CGG_EINVAL, "%s: null level table", who);
+  if ((rc = strides())) return rc;
+  MsdaLevels lv;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = msda_entry_levels(who, dev_hw, dev_start, level_hw, level_start, L, Nv, s, &lv))) return rc;
+  return msda_fwd_launch(value, lv, loc, attw, ref, ld, out, B, Nv, H, D, L, Nq, P, dtype, fused, s, vld);
+}
+
 extern "C" int cgg_msda_forward(const void* value, const int64_t* spatial_shapes,
                                 const int64_t* level_start, const float* sampling_loc,
                                 const float* attn_weight, float* out, int B, int Nv, int H, int D,
                                 int L, int Nq, int P, int value_dtype, cgg_stream_t stream) {
-  int rc = msda_check("cgg_msda_forward", value, sampling_loc, attn_weight, out, B, Nv, H, D, L, Nq, P,
-                      value_dtype);
-  if (rc) return rc;
-  CGG_REQUIRE(spatial_shapes && level_start, CGG_EINVAL, "cgg_msda_forward: null level table");
-  MsdaLevels lv;
-  hipStream_t s = (hipStream_t)stream;
-  rc = msda_read_levels(spatial_shapes, level_start, L, Nv, s, &lv, "cgg_msda_forward");
-  if (rc) return rc;
-  return msda_fwd_launch(value, lv, sampling_loc, attn_weight, nullptr, 0, out, B, Nv, H, D, L, Nq, P,
-                         value_dtype, false, s);
+  return msda_forward_impl("cgg_msda_forward", value, spatial_shapes, level_start, nullptr, nullptr, sampling_loc, attn_weight, nullptr,
+                           0, out, B, Nv, H, D, L, Nq, P, value_dtype, false, 0, stream, [] { return CGG_OK; });
 }
 
 extern "C" int cgg_msda_forward_fused(const void* value, const int64_t* spatial_shapes,
@@ -846,41 +811,24 @@ extern "C" int cgg_msda_forward_fused(const void* value, const int64_t* spatial_
                                       const float* ref_points, float* out, int B, int Nv, int H,
                                       int D, int L, int Nq, int P, int value_dtype,
                                       cgg_stream_t stream) {
-  int rc = msda_check("cgg_msda_forward_fused", value, offs_logits, ref_points, out, B, Nv, H, D, L, Nq,
-                      P, value_dtype);
-  if (rc) return rc;
-  CGG_REQUIRE(spatial_shapes && level_start, CGG_EINVAL, "cgg_msda_forward_fused: null level table");
-  CGG_REQUIRE(ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_fused: ld=%d < H*L*P*3", ld);
-  MsdaLevels lv;
-  hipStream_t s = (hipStream_t)stream;
-  rc = msda_read_levels(spatial_shapes, level_start, L, Nv, s, &lv, "cgg_msda_forward_fused");
-  if (rc) return rc;
-  return msda_fwd_launch(value, lv, offs_logits, nullptr, ref_points, ld, out, B, Nv, H, D, L, Nq, P,
-                         value_dtype, true, s);
+  return msda_forward_impl("cgg_msda_forward_fused", value, spatial_shapes, level_start, nullptr, nullptr, offs_logits, nullptr,
+                           ref_points, ld, out, B, Nv, H, D, L, Nq, P, value_dtype, true, 0, stream, [&] {
+                             CGG_REQUIRE(ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_fused: ld=%d < H*L*P*3", ld);
+                             return CGG_OK;
+                           });
 }
 
+// Host-side level table variant: identical kernels, no D2H (used by the graph-captured forward).
 extern "C" int cgg_msda_forward_hostlevels(const void* value, const int32_t* level_hw,
                                            const int32_t* level_start, const float* sampling_loc,
                                            const float* attn_weight, const float* ref_points, int ld,
                                            float* out, int B, int Nv, int H, int D, int L, int Nq,
                                            int P, int value_dtype, int fused, cgg_stream_t stream) {
-  int rc = msda_check("cgg_msda_forward_hostlevels", value, sampling_loc,
-                      fused ? (const void*)ref_points : (const void*)attn_weight, out, B, Nv, H, D, L,
-                      Nq, P, value_dtype);
-  if (rc) return rc;
-  CGG_REQUIRE(level_hw && level_start, CGG_EINVAL, "cgg_msda_forward_hostlevels: null level table");
-  if (fused) CGG_REQUIRE(ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_hostlevels: ld too small");
-  MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-    CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0 && lv.start[l] >= 0 &&
-                    (long long)lv.start[l] + (long long)lv.h[l] * lv.w[l] <= Nv,
-                CGG_EINVAL, "cgg_msda_forward_hostlevels: level %d does not fit Nv=%d", l, Nv);
-  }
-  return msda_fwd_launch(value, lv, sampling_loc, attn_weight, ref_points, ld, out, B, Nv, H, D, L, Nq,
-                         P, value_dtype, fused != 0, (hipStream_t)stream);
+  return msda_forward_impl("cgg_msda_forward_hostlevels", value, nullptr, nullptr, level_hw, level_start, sampling_loc, attn_weight,
+                           ref_points, ld, out, B, Nv, H, D, L, Nq, P, value_dtype, fused != 0, 0, stream, [&] {
+                             if (fused) CGG_REQUIRE(ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_hostlevels: ld too small");
+                             return CGG_OK;
+                           });
 }
 
 // Fused f32 form with the value operand as COLUMNS of wider rows: value[b, n, h, :] = value_rows[(b Nv + n) vld + h D ...] (vld % 32
@@ -888,45 +836,12 @@ extern "C" int cgg_msda_forward_hostlevels(const void* value, const int32_t* lev
 extern "C" int cgg_msda_forward_fused_vld(const float* value_rows, int vld, const int32_t* level_hw, const int32_t* level_start,
                                           const float* offs_logits, int ld, const float* ref_points, float* out, int B, int Nv, int H,
                                           int D, int L, int Nq, int P, cgg_stream_t stream) {
-  int rc = msda_check("cgg_msda_forward_fused_vld", value_rows, offs_logits, ref_points, out, B, Nv, H, D, L, Nq, P, CGG_F32);
-  if (rc) return rc;
-  CGG_REQUIRE(level_hw && level_start, CGG_EINVAL, "cgg_msda_forward_fused_vld: null level table");
-  CGG_REQUIRE(vld >= H * D && vld % 32 == 0 && ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_fused_vld: vld=%d ld=%d", vld, ld);
-  MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-    CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0 && lv.start[l] >= 0 && (long long)lv.start[l] + (long long)lv.h[l] * lv.w[l] <= Nv,
-                CGG_EINVAL, "cgg_msda_forward_fused_vld: level %d does not fit Nv=%d", l, Nv);
-  }
-  return msda_fwd_launch(value_rows, lv, offs_logits, nullptr, ref_points, ld, out, B, Nv, H, D, L, Nq, P, CGG_F32, true,
-                         (hipStream_t)stream, vld);
-}
-
-static int msda_bwd_launch(const float* value, const MsdaLevels& lv, const float* sampling_loc, const float* attn_weight,
-                           const float* grad_out, float* grad_value, float* grad_loc, float* grad_attn, int B, int Nv, int H, int D,
-                           int L, int Nq, int P, hipStream_t s, bool overwrite = false, hipStream_t side = nullptr, void* ws = nullptr,
-                           long long ws_bytes = 0, int vld = 0);
-
-extern "C" int cgg_msda_backward(const float* value, const int64_t* spatial_shapes,
-                                 const int64_t* level_start, const float* sampling_loc,
-                                 const float* attn_weight, const float* grad_out, float* grad_value,
-                                 float* grad_loc, float* grad_attn, int B, int Nv, int H, int D,
-                                 int L, int Nq, int P, cgg_stream_t stream) {
-  int rc = msda_check("cgg_msda_backward", value, sampling_loc, attn_weight, grad_out, B, Nv, H, D, L,
-                      Nq, P, CGG_F32);
-  if (rc) return rc;
-  CGG_REQUIRE(spatial_shapes && level_start && grad_value && grad_loc && grad_attn, CGG_EINVAL,
-              "cgg_msda_backward: null pointer");
-  const int DQ = D / 4;
-  CGG_REQUIRE((DQ & (DQ - 1)) == 0 && DQ <= 64, CGG_EUNSUPPORTED,
-              "cgg_msda_backward: D/4=%d must be a power of two <= 64", DQ);
-  MsdaLevels lv;
-  hipStream_t s = (hipStream_t)stream;
-  rc = msda_read_levels(spatial_shapes, level_start, L, Nv, s, &lv, "cgg_msda_backward");
-  if (rc) return rc;
-  return msda_bwd_launch(value, lv, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, s);
+  return msda_forward_impl("cgg_msda_forward_fused_vld", value_rows, nullptr, nullptr, level_hw, level_start, offs_logits, nullptr,
+                           ref_points, ld, out, B, Nv, H, D, L, Nq, P, CGG_F32, true, vld, stream, [&] {
+                             CGG_REQUIRE(vld >= H * D && vld % 32 == 0 && ld >= H * L * P * 3, CGG_EINVAL,
+                                         "cgg_msda_forward_fused_vld: vld=%d ld=%d", vld, ld);
+                             return CGG_OK;
+                           });
 }
 
 // Split backward: grad_value by the sorted-scatter kernel (msda_bwd.hip) when the pyramid is tileable (the encoder's
@@ -966,13 +881,7 @@ static int msda_bwd_launch(const float* value, const MsdaLevels& lv, const float
     const int nb = (int)((total + 255) / 256);
     if (P == 4 && cgg_aligned16(sampling_loc) && cgg_aligned16(attn_weight) && cgg_aligned16(grad_loc) && cgg_aligned16(grad_attn)) {
       // 8 x 4 pixel patches of one head per block when the pyramid allows it (see the kernel)
-      bool patch = H == 8 && D == 32 && Nq == Nv && Nq % 32 == 0;
-      long long expect = 0;
-      for (int l = 0; l < L && patch; ++l) {
-        patch = lv.start[l] == expect && lv.w[l] % 8 == 0 && lv.h[l] % 4 == 0 && lv.start[l] % 32 == 0;
-        expect += (long long)lv.h[l] * lv.w[l];
-      }
-      patch = patch && expect == Nq;
+      const bool patch = H == 8 && D == 32 && Nq == Nv && Nq % 32 == 0 && msda_levels_tile(lv, L, Nq, 8, 4, 32);
 #define CGG_G4(ACC, PATCH)                                                                                                      \
   hipLaunchKernelGGL((cgg_msda_bwd_gather4_kernel<ACC, PATCH>), dim3(nb), dim3(256), 0, s, value, lv, sampling_loc, attn_weight, \
                      grad_out, grad_loc, grad_attn, Nv, H, D, L, Nq, total, vld)
@@ -1014,45 +923,50 @@ static int msda_bwd_launch(const float* value, const MsdaLevels& lv, const float
   return CGG_OK;
 }
 
-// cgg_msda_backward with the level table from the HOST (level_hw = [h0, w0, h1, w1, ...], level_start): no device->host copy and
-// no stream synchronisation per call (the mmcv-contract entry point above reads its int64 device tensors back, once per call --
-// six stalls per training step in the encoder's backward), graph-capturable.
-static int msda_bwd_hostlevels(const float* value, const int32_t* level_hw, const int32_t* level_start, const float* sampling_loc,
-                               const float* attn_weight, const float* grad_out, float* grad_value, float* grad_loc, float* grad_attn,
-                               int B, int Nv, int H, int D, int L, int Nq, int P, int overwrite_loc_attn, cgg_stream_t stream,
-                               cgg_stream_t side_stream, void* ws = nullptr, long long ws_bytes = 0, int vld = 0) {
-  int rc = msda_check("cgg_msda_backward_hostlevels", value, sampling_loc, attn_weight, grad_out, B, Nv, H, D, L, Nq, P, CGG_F32);
+// The one backward behind cgg_msda_backward (mmcv's DEVICE level table: read back once per call, a stall -- six per training step in
+// the encoder's backward) and the three *_hostlevels entries (level_hw = [h0, w0, h1, w1, ...], level_start from the HOST: no
+// device->host copy, no stream synchronisation, graph-capturable).
+static int msda_backward_impl(const char* who, const float* value, const int64_t* dev_hw, const int64_t* dev_start, const int32_t* level_hw,
+                              const int32_t* level_start, const float* sampling_loc, const float* attn_weight, const float* grad_out,
+                              float* grad_value, float* grad_loc, float* grad_attn, int B, int Nv, int H, int D, int L, int Nq, int P,
+                              int overwrite_loc_attn, cgg_stream_t stream, cgg_stream_t side_stream, void* ws, long long ws_bytes, int vld) {
+  int rc = msda_check(who, value, sampling_loc, attn_weight, grad_out, B, Nv, H, D, L, Nq, P, CGG_F32);
   if (rc) return rc;
-  CGG_REQUIRE(level_hw && level_start && grad_value && grad_loc && grad_attn, CGG_EINVAL, "cgg_msda_backward_hostlevels: null pointer");
+  CGG_REQUIRE(((dev_hw && dev_start) || (level_hw && level_start)) && grad_value && grad_loc && grad_attn, CGG_EINVAL, "%s: null pointer", who);
   const int DQ = D / 4;
-  CGG_REQUIRE((DQ & (DQ - 1)) == 0 && DQ <= 64, CGG_EUNSUPPORTED, "cgg_msda_backward_hostlevels: D/4=%d must be a power of two <= 64", DQ);
+  CGG_REQUIRE((DQ & (DQ - 1)) == 0 && DQ <= 64, CGG_EUNSUPPORTED, "%s: D/4=%d must be a power of two <= 64", who, DQ);
   MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-    CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0 && lv.start[l] >= 0 && (long long)lv.start[l] + (long long)lv.h[l] * lv.w[l] <= Nv,
-                CGG_EINVAL, "cgg_msda_backward_hostlevels: level %d does not fit Nv=%d", l, Nv);
-  }
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = msda_entry_levels(who, dev_hw, dev_start, level_hw, level_start, L, Nv, s, &lv))) return rc;
   // overwrite_loc_attn: grad_loc / grad_attn are written, not accumulated (no zero-fill needed) -- honoured when the split
   // backward with the P == 4 gather kernel runs; *overwrite_loc_attn is only a PERMISSION, so callers that pass it must not rely
   // on accumulation and must still zero the two tensors unless cgg_msda_backward_overwrites(...) says the fast path applies
-  const bool tileable = msda_bwd_sorted_ok(lv, B, Nv, H, D, L, Nq, P);
-  const bool ow = overwrite_loc_attn && tileable && P == 4 && cgg_aligned16(sampling_loc) && cgg_aligned16(attn_weight) &&
-                  cgg_aligned16(grad_loc) && cgg_aligned16(grad_attn) && !generic_only;
+  const bool ow = overwrite_loc_attn && msda_bwd_sorted_ok(lv, B, Nv, H, D, L, Nq, P) && P == 4 && cgg_aligned16(sampling_loc) &&
+                  cgg_aligned16(attn_weight) && cgg_aligned16(grad_loc) && cgg_aligned16(grad_attn) && !generic_only;
   CGG_REQUIRE(!overwrite_loc_attn || ow, CGG_EUNSUPPORTED,
-              "cgg_msda_backward_hostlevels: overwrite_loc_attn needs the split backward (tileable pyramid, D == 32, P == 4, aligned)");
-  CGG_REQUIRE(vld == 0 || (vld >= H * D && vld % 4 == 0), CGG_EINVAL, "cgg_msda_backward_hostlevels: vld=%d", vld);
-  return msda_bwd_launch(value, lv, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P,
-                         (hipStream_t)stream, ow, (hipStream_t)side_stream, ws, ws_bytes, vld);
+              "%s: overwrite_loc_attn needs the split backward (tileable pyramid, D == 32, P == 4, aligned)", who);
+  CGG_REQUIRE(vld == 0 || (vld >= H * D && vld % 4 == 0), CGG_EINVAL, "%s: vld=%d", who, vld);
+  // (side_stream == stream or null: one stream)
+  return msda_bwd_launch(value, lv, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, s, ow,
+                         side_stream == stream ? nullptr : (hipStream_t)side_stream, ws, ws_bytes, vld);
+}
+
+extern "C" int cgg_msda_backward(const float* value, const int64_t* spatial_shapes,
+                                 const int64_t* level_start, const float* sampling_loc,
+                                 const float* attn_weight, const float* grad_out, float* grad_value,
+                                 float* grad_loc, float* grad_attn, int B, int Nv, int H, int D,
+                                 int L, int Nq, int P, cgg_stream_t stream) {
+  return msda_backward_impl("cgg_msda_backward", value, spatial_shapes, level_start, nullptr, nullptr, sampling_loc, attn_weight, grad_out,
+                            grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, 0, stream, nullptr, nullptr, 0, 0);
 }
 
 extern "C" int cgg_msda_backward_hostlevels(const float* value, const int32_t* level_hw, const int32_t* level_start,
                                             const float* sampling_loc, const float* attn_weight, const float* grad_out,
                                             float* grad_value, float* grad_loc, float* grad_attn, int B, int Nv, int H, int D, int L,
                                             int Nq, int P, int overwrite_loc_attn, cgg_stream_t stream) {
-  return msda_bwd_hostlevels(value, level_hw, level_start, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv,
-                             H, D, L, Nq, P, overwrite_loc_attn, stream, nullptr);
+  return msda_backward_impl("cgg_msda_backward_hostlevels", value, nullptr, nullptr, level_hw, level_start, sampling_loc, attn_weight,
+                            grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, overwrite_loc_attn, stream, nullptr, nullptr,
+                            0, 0);
 }
 
 // ... with the two kernels of the split backward on TWO streams: grad_value (sorted scatter) on `stream`, grad_loc / grad_attn
@@ -1062,8 +976,9 @@ extern "C" int cgg_msda_backward_hostlevels_2s(const float* value, const int32_t
                                                const float* sampling_loc, const float* attn_weight, const float* grad_out,
                                                float* grad_value, float* grad_loc, float* grad_attn, int B, int Nv, int H, int D, int L,
                                                int Nq, int P, int overwrite_loc_attn, cgg_stream_t stream, cgg_stream_t side_stream) {
-  return msda_bwd_hostlevels(value, level_hw, level_start, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv,
-                             H, D, L, Nq, P, overwrite_loc_attn, stream, side_stream == stream ? nullptr : side_stream);
+  return msda_backward_impl("cgg_msda_backward_hostlevels", value, nullptr, nullptr, level_hw, level_start, sampling_loc, attn_weight,
+                            grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, overwrite_loc_attn, stream, side_stream,
+                            nullptr, 0, 0);
 }
 
 // ... with a workspace for the TWO-PASS sorted scatter of grad_value (csrc/msda_bwd.hip): corners that leave the 4-pixel halo of
@@ -1075,19 +990,16 @@ extern "C" int cgg_msda_backward_hostlevels_ws(const float* value, int vld, cons
                                                int Nq, int P, int overwrite_loc_attn, void* ws, long long ws_bytes, cgg_stream_t stream,
                                                cgg_stream_t side_stream) {
   CGG_REQUIRE(!ws || cgg_aligned16(ws), CGG_EALIGN, "cgg_msda_backward_hostlevels_ws: workspace must be 16-B aligned");
-  return msda_bwd_hostlevels(value, level_hw, level_start, sampling_loc, attn_weight, grad_out, grad_value, grad_loc, grad_attn, B, Nv,
-                             H, D, L, Nq, P, overwrite_loc_attn, stream, side_stream == stream ? nullptr : side_stream, ws, ws_bytes, vld);
+  return msda_backward_impl("cgg_msda_backward_hostlevels", value, nullptr, nullptr, level_hw, level_start, sampling_loc, attn_weight,
+                            grad_out, grad_value, grad_loc, grad_attn, B, Nv, H, D, L, Nq, P, overwrite_loc_attn, stream, side_stream, ws,
+                            ws_bytes, vld);
 }
 
 extern "C" long long cgg_msda_backward_workspace_bytes(const int32_t* level_hw, const int32_t* level_start, int B, int Nv, int H, int D,
                                                        int L, int Nq, int P) {
   if (!level_hw || !level_start || L < 1 || L > 8 || generic_only) return 0;
   MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-  }
+  msda_levels_fill(&lv, level_hw, level_start, L);      // (unchecked: a query answers for any table, as it always has)
   return msda_bwd_two_pass_workspace_bytes(lv, B, Nv, H, D, L, Nq, P);
 }
 
@@ -1096,11 +1008,7 @@ extern "C" int cgg_msda_backward_overwrites(const int32_t* level_hw, const int32
                                             int Nq, int P) {
   if (!level_hw || !level_start || L < 1 || L > 8) return 0;
   MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-  }
+  msda_levels_fill(&lv, level_hw, level_start, L);      // (unchecked: a query answers for any table, as it always has)
   return (P == 4 && !generic_only && msda_bwd_sorted_ok(lv, B, Nv, H, D, L, Nq, P)) ? 1 : 0;
 }
 
@@ -1115,14 +1023,7 @@ static int msda_fused_bf16_impl(bool head_major, const void* value, const int32_
   CGG_REQUIRE(level_hw && level_start, CGG_EINVAL, "cgg_msda_forward_fused_bf16: null level table");
   CGG_REQUIRE(ld >= H * L * P * 3, CGG_EINVAL, "cgg_msda_forward_fused_bf16: ld too small");
   MsdaLevels lv;
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = level_start[l];
-    CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0 && lv.start[l] >= 0 &&
-                    (long long)lv.start[l] + (long long)lv.h[l] * lv.w[l] <= Nv,
-                CGG_EINVAL, "cgg_msda_forward_fused_bf16: level %d does not fit Nv=%d", l, Nv);
-  }
+  if ((rc = msda_levels_from_host("cgg_msda_forward_fused_bf16", level_hw, level_start, L, Nv, &lv))) return rc;
   const long long total = (long long)B * Nq * H * (D / 8);
   const int nblk = (int)((total + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
@@ -1347,12 +1248,8 @@ __global__ __launch_bounds__(256) void cgg_msda_prologue12_bwd_kernel(const floa
 
 static int msda_prologue_levels(MsdaLevels& lv, const int32_t* level_hw, int L, const char* who) {
   CGG_REQUIRE(level_hw && L >= 1 && L <= 8, CGG_EINVAL, "%s: bad level table (L=%d)", who, L);
-  for (int l = 0; l < L; ++l) {
-    lv.h[l] = level_hw[2 * l];
-    lv.w[l] = level_hw[2 * l + 1];
-    lv.start[l] = 0;
-    CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0, CGG_EINVAL, "%s: level %d is empty", who, l);
-  }
+  msda_levels_fill(&lv, level_hw, (const int32_t*)nullptr, L);      // (no pixel rows are read: sizes only, start = 0)
+  for (int l = 0; l < L; ++l) CGG_REQUIRE(lv.h[l] > 0 && lv.w[l] > 0, CGG_EINVAL, "%s: level %d is empty", who, l);
   return CGG_OK;
 }
 

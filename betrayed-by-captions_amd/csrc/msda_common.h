@@ -8,6 +8,46 @@ struct MsdaLevels {
   int start[8];
 };
 
+// ---- the level table, stated once (host) ----------------------------------------------------------
+// Host table (hw = [h0, w0, h1, w1, ...], start; int32 of the *_hostlevels entries, int64 read back from mmcv's device tensors) ->
+// MsdaLevels, UNCHECKED: the two geometry queries and the prologue (start == nullptr: no pixel rows, start = 0) never refused a table.
+template <typename T>
+inline void msda_levels_fill(MsdaLevels* lv, const T* hw, const T* start, int L) {
+  for (int l = 0; l < L; ++l) {
+    lv->h[l] = (int)hw[2 * l];
+    lv->w[l] = (int)hw[2 * l + 1];
+    lv->start[l] = start ? (int)start[l] : 0;
+  }
+}
+
+// ... CHECKED: every level is non-empty and lies inside the Nv value rows (64-bit on the table's own integers). The one fit rule of
+// every entry that gathers; the device-table entries have always named the level's size in the message, the host-table ones never.
+template <typename T>
+inline int msda_levels_from_host(const char* who, const T* hw, const T* start, int L, int Nv, MsdaLevels* lv) {
+  msda_levels_fill(lv, hw, start, L);
+  for (int l = 0; l < L; ++l) {
+    const long long h = hw[2 * l], w = hw[2 * l + 1], st = start[l];
+    if (h > 0 && w > 0 && st >= 0 && st + h * w <= Nv) continue;
+    if (sizeof(T) == 8) cgg_set_error("%s: level %d (%lldx%lld @%lld) does not fit Nv=%d", who, l, h, w, st, Nv);
+    else cgg_set_error("%s: level %d does not fit Nv=%d", who, l, Nv);
+    return CGG_EINVAL;
+  }
+  return CGG_OK;
+}
+
+// The gate of every lane mapping that rebuilds a query index as start[l] + tile arithmetic (the forward's 4 x 4 and 8 x 8 tiles, the
+// gather backward's 8 x 4 patches): the levels tile [0, N) in ascending order without gaps -- the fit rule above only says
+// start + h w <= Nv, and a gapped or reordered table would compute some queries twice and skip others -- and every level's w, h,
+// start are multiples of (wm, hm, sm), the tile's width, height and pixel count per block.
+inline bool msda_levels_tile(const MsdaLevels& lv, int L, int N, int wm, int hm, int sm) {
+  long long expect = 0;
+  for (int l = 0; l < L; ++l) {
+    if (lv.start[l] != expect || lv.w[l] % wm || lv.h[l] % hm || lv.start[l] % sm) return false;
+    expect += (long long)lv.h[l] * lv.w[l];
+  }
+  return expect == N;
+}
+
 __device__ __forceinline__ f32x4 cgg_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 cgg_ld4(const uint16_t* p) {
   const uint2 u = *reinterpret_cast<const uint2*>(p);

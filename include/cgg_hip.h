@@ -77,6 +77,11 @@ const char* cgg_last_error_string(void);
  * out[b,q,h*D+c] = sum_{l,p} w * bilinear_zero_pad(value_l[b,:,h,c]; x*W_l-0.5, y*H_l-0.5)
  * (grid_sample(align_corners=False, padding_mode='zeros') semantics).
  * Requires D % 4 == 0, L <= 8.
+ * The level table, whichever way it arrives (device int64 or host int32), is held to ONE rule by every entry that gathers
+ * (csrc/msda_common.h, msda_levels_from_host): H_l > 0, W_l > 0, level_start[l] >= 0, level_start[l] + H_l W_l <= Nv; anything else is
+ * CGG_EINVAL "<entry>: level <l> does not fit Nv=<Nv>". The levels need not be ascending or gapless: the lane mappings that assume it
+ * (4 x 4 / 8 x 8 tiles of the f32 stream forward, 8 x 4 patches of the gather backward) are chosen only where msda_levels_tile, next
+ * to the reader, says the levels tile [0, Nq); the two geometry queries and the prologue entries read the table unchecked.
  * ---------------------------------------------------------------------------------------------- */
 int cgg_msda_forward(const void* value, const int64_t* spatial_shapes, const int64_t* level_start,
                      const float* sampling_loc, const float* attn_weight, float* out, int B, int Nv,
